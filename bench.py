@@ -266,6 +266,28 @@ def prepare_slots(h, fp, warm, n, seed):
     return n
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def timed_outputs(chi2, q, t, X):
+    """What a caller of the timed path receives from its last LM run: the per-iteration chi2 and the estimates (solver row order).
+    Landmarks beyond the dump budget are cut to a fixed, seeded sample of rows (their indices are dumped beside them)."""
+    out = {"chi2": np.asarray(chi2, dtype=np.float64), "pose_q": q, "pose_t": t, "landmarks": X}
+    room = DUMP_MAX_BYTES - sum(a.nbytes for k, a in out.items() if k != "landmarks")
+    if X.nbytes > room:
+        keep = room // (X.itemsize * X.shape[1] + 8)
+        rows = np.sort(np.random.default_rng(0).choice(len(X), size=keep, replace=False))
+        out["landmarks"], out["landmark_rows"] = X[rows], rows.astype(np.float64)
+    return out
+
+
+def write_outputs(path, outputs):
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": path, "arrays": {k: list(a.shape) for k, a in outputs.items()}}
+
+
 def fp32_bars():
     """FP32_TOL / FP32_MIN_ITERATIONS of tests/test_gpu_configs.py, read from the file (importing it would pull pytest fixtures in)"""
     import ast
@@ -531,7 +553,12 @@ def main():
     ap.add_argument("--partition", action="store_true",
                     help="N>1: ONE graph, landmark-partitioned over the ranks with an RCCL all-reduce of [Hsc|bsc|bp] "
                          "per trial (BASELINE config 5, strong scaling) instead of one independent graph per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last LM run returned (rank 0: per-iteration chi2, pose and "
+                         "landmark estimates) as DIR/<name>.npy, so that two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.concurrent_child:
         concurrent_child(args.shape, counts=tuple(int(v) for v in args.concurrent_counts.split(",")))
         return
@@ -668,6 +695,7 @@ def main():
     c0 = counters()
     elapsed, chi2 = timed_block(args.steps)
     c1 = counters()
+    outputs = timed_outputs(chi2, *solver.state()) if args.dump_outputs and rank == 0 else None
 
     # the same block again, `--repeats` times (further perturbed starts): spread of the measurement (`value` stays the block above)
     block_ms = [timed_block(args.steps)[0] * 1e3 for _ in range(max(0, args.repeats))]
@@ -787,6 +815,8 @@ def main():
             "roofline": roof,
             "reference_kernels_on_mi355x": reference_kernels_citation() if world == 1 else None,
         }
+        if outputs is not None:
+            out["dump_outputs"] = write_outputs(args.dump_outputs, outputs)
         # the GPU side of the parity leg, then this handle goes: several live handles share the runtime's few hardware queues and
         # slow each other down (a KITTI-07-sized graph runs at half speed as the second handle of a process)
         got = None
