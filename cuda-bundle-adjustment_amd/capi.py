@@ -119,6 +119,8 @@ def load_library(precision="f64"):
         "cuba_hip_begin_run": [H],
         "cuba_hip_get_sizes": [H, C.POINTER(C.c_int)],
         "cuba_hip_evaluate_device": [H, C.c_double, C.c_int, C.POINTER(C.c_void_p)],
+        "cuba_hip_compute_covariance": [H, _dp, _dp, C.POINTER(C.c_int)],
+        "cuba_hip_get_covariance_blocks": [H, _dp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -209,6 +211,33 @@ def sparse_plan(row_ptr, col_ind, slack=-1, precision="f64"):
         out[name] = a
     h = out.pop("header")
     out.update(T=int(h[0]), nTiles=int(h[1]), nLevels=int(h[2]), slack=int(h[3]), entries=int(h[4]), nblk=int(h[5]))
+    return out
+
+
+SELINV_PLAN_ARRAYS = ("header", "stepPtr", "offRec", "colStepPtr", "cols", "gather")
+
+
+def selinv_plan(row_ptr, col_ind, slack=-1, precision="f64"):
+    """Symbolic phase of the selected inversion behind HipSolver.covariance, built on sparse_plan's factor pattern (host only, no
+    device): dict of the arrays of SelInvPlan in csrc/ba_kernels.hpp.  Step s walks level nLevels - 1 - s of the elimination tree;
+    offRec holds {tile, column, first gather entry, entries} per off-diagonal tile, gather {Sigma tile | bit 30 = stored transposed, tile
+    of L_kj} per entry."""
+    lib = load_library(precision)
+    rp = np.ascontiguousarray(row_ptr, dtype=np.int32); ci = np.ascontiguousarray(col_ind, dtype=np.int32)
+    ip = C.POINTER(C.c_int32)
+    out = {}
+    for which, name in enumerate(SELINV_PLAN_ARRAYS, start=11):
+        n = C.c_size_t()
+        rc = lib.cuba_hip_debug_sparse_plan(len(rp) - 1, rp.ctypes.data_as(ip), ci.ctypes.data_as(ip), int(slack), which, None, 0, C.byref(n))
+        if rc != 0:
+            raise CubaHipError(f"cuba_hip_debug_sparse_plan failed with status {rc}")
+        a = np.zeros(n.value, dtype=np.int32)
+        rc = lib.cuba_hip_debug_sparse_plan(len(rp) - 1, rp.ctypes.data_as(ip), ci.ctypes.data_as(ip), int(slack), which, a.ctypes.data_as(ip), n.value, C.byref(n))
+        if rc != 0:
+            raise CubaHipError(f"cuba_hip_debug_sparse_plan failed with status {rc}")
+        out[name] = a
+    h = out.pop("header")
+    out.update(nLevels=int(h[0]), nOff=int(h[1]), entries=int(h[2]), products=int(h[3]) + (int(h[4]) << 31))
     return out
 
 
@@ -423,6 +452,28 @@ class HipSolver:
         rp, ci = self.hsc_structure()
         v = self.array("hsc").reshape(len(ci), 6, 6).transpose(0, 2, 1).copy()
         return rp, ci, v
+
+    def covariance(self, landmarks=True, poses=True):
+        """Marginal covariances at the current estimate (cuba_hip_compute_covariance; g2o's computeMarginals): the inverse of the undamped
+        Gauss-Newton Hessian.  {"pose": [Pt, 6, 6] in the [omega, upsilon] tangent of the pose update, "landmark": [Lt, 3, 3] (None when
+        landmarks=False), "not_positive_definite": bool}; fixed vertices get zero blocks, a matrix that is not positive definite leaves both
+        at zero."""
+        pose = np.zeros((self.fp.Pt, 6, 6)) if poses else None
+        lm = np.zeros((self.fp.Lt, 3, 3)) if landmarks else None
+        bad = C.c_int()
+        self._ck(self.lib.cuba_hip_compute_covariance(self.h, _d(pose), _d(lm), C.byref(bad)))
+        # (column-major 6 x 6 / 3 x 3 blocks: the transpose of the row-major reading -- the blocks are symmetric up to rounding)
+        return {"pose": None if pose is None else pose.transpose(0, 2, 1).copy(),
+                "landmark": None if lm is None else lm.transpose(0, 2, 1).copy(),
+                "not_positive_definite": bool(bad.value)}
+
+    def covariance_blocks(self):
+        """values[nblk, 6, 6] ([blk][row][col]) of the marginal covariance on the reduced matrix's pattern, as hsc_structure() numbers the
+        blocks, from the last covariance() call (cuba_hip_get_covariance_blocks)"""
+        rp, ci = self.hsc_structure()
+        out = np.zeros((len(ci), 6, 6))
+        self._ck(self.lib.cuba_hip_get_covariance_blocks(self.h, _d(out)))
+        return out.transpose(0, 2, 1).copy()
 
     def time_kernels(self, reps=20):
         out = np.zeros(7)

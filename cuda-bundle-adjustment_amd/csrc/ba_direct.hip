@@ -245,6 +245,55 @@ bool sparse_chol_plan(int Pf, const int* rowptr, const int* colind, int slack, s
 	return have;
 }
 
+// Symbolic phase of the selected inversion (ba_covariance.hip runs the numeric one).  Sigma_ij for a row i of column j needs Sigma_ik for every
+// row k of column j: the rows of a column are pairwise adjacent once the column is eliminated, so (max(i, k), min(i, k)) is a tile of the
+// pattern in column min(i, k) > j, which sits on a higher level of the tree.  The gather lists are fixed and ascending in k: one writer
+// per tile, a fixed order of summation.
+size_t SelInvPlan::sigmaBytes() const { return sizeof(Scalar) * (size_t)SC_TT * (size_t)std::max(1, nTiles); }
+
+bool selinv_plan(const SparseCholPlan& p, SelInvPlan& out)
+{
+	out = SelInvPlan();
+	const int T = p.T, L = p.nLevels;
+	out.nLevels = L; out.nTiles = p.nTiles;
+	std::vector<int> level((size_t)T, 0);
+	for (int l = 0; l < L; l++)
+		for (int c = p.lvlColPtr[l]; c < p.lvlColPtr[l + 1]; c++) level[p.lvlCols[c]] = l;
+	out.stepPtr.assign((size_t)L + 1, 0); out.colStepPtr.assign((size_t)L + 1, 0);
+	out.cols.reserve(T);
+	for (int s = 0; s < L; s++)
+	{
+		const int l = L - 1 - s;
+		for (int c = p.lvlColPtr[l]; c < p.lvlColPtr[l + 1]; c++)
+		{
+			const int j = p.lvlCols[c];
+			out.cols.push_back(j);
+			const int n = p.colPtr[j + 1] - p.colPtr[j] - 1;          // |I_j|
+			out.products += 1 + n;                                     // the diagonal tile: L_jj^-T L_jj^-1 and one product per row
+			for (int t = p.colPtr[j] + 1; t < p.colPtr[j + 1]; t++)
+			{
+				const int i = p.rowIdx[t];
+				out.offRec.insert(out.offRec.end(), { t, j, (int)(out.gather.size() / 2), n });
+				for (int tk = p.colPtr[j] + 1; tk < p.colPtr[j + 1]; tk++)
+				{
+					const int k = p.rowIdx[tk];
+					int ts, tr = 0;
+					if (i == k) ts = p.colPtr[i];
+					else if (i > k) ts = find_tile(p, i, k);
+					else { ts = find_tile(p, k, i); tr = 1; }
+					if (ts < 0 || level[std::min(i, k)] <= level[j]) return false;
+					out.gather.push_back(ts | (tr << 30)); out.gather.push_back(tk);
+					if (out.gather.size() > ((size_t)1 << 30)) return false;
+				}
+				out.products += n;
+			}
+		}
+		out.stepPtr[s + 1] = (int)(out.offRec.size() / 4);
+		out.colStepPtr[s + 1] = (int)out.cols.size();
+	}
+	return true;
+}
+
 // =====================================================================================================================================
 // numeric phase (device)
 // =====================================================================================================================================
@@ -534,13 +583,18 @@ __global__ __launch_bounds__(256) void schol_extract_kernel(SparseChol d, Scalar
 	x[idx] = d.y[SC_T * (size_t)d.posOfSeg[p / SC_TP] + 6 * (p % SC_TP) + c];
 }
 
-void launch_sparse_chol_solve(const SparseChol& d, const SparseCholPlan& plan, Scalar* x, hipStream_t s)
+void launch_sparse_chol_factor(const SparseChol& d, const SparseCholPlan& plan, hipStream_t s)
 {
 	for (int l = 0; l < plan.nLevels; l++)
 	{
 		const int n = plan.lvlPtr[l + 1] - plan.lvlPtr[l];
 		if (n > 0) hipLaunchKernelGGL(schol_factor_level_kernel, dim3(n), dim3(256), 0, s, d, plan.lvlPtr[l]);
 	}
+}
+
+void launch_sparse_chol_solve(const SparseChol& d, const SparseCholPlan& plan, Scalar* x, hipStream_t s)
+{
+	launch_sparse_chol_factor(d, plan, s);
 	for (int l = plan.nLevels - 1; l >= 0; l--)
 	{
 		const int n = plan.lvlColPtr[l + 1] - plan.lvlColPtr[l];

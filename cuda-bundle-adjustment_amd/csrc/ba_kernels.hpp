@@ -306,6 +306,45 @@ struct SparseChol                 // device view
 void launch_sparse_chol_fill(const DeviceStructure& st, const DeviceSystem& sys, const SparseChol& d, hipStream_t s);
 // factorise and solve: x[0 .. 6 Pf) = A^-1 b (internal pose order)
 void launch_sparse_chol_solve(const SparseChol& d, const SparseCholPlan& plan, Scalar* x, hipStream_t s);
+// the factorisation alone (the launches of launch_sparse_chol_solve's first loop)
+void launch_sparse_chol_factor(const SparseChol& d, const SparseCholPlan& plan, hipStream_t s);
+
+// ---- marginal covariances (ba_direct.hip: symbolic phase, ba_covariance.hip: numeric phase) --------------------------------------
+// Selected inversion of the factorised reduced matrix S = L L^T on the factor's own pattern (Takahashi recurrence): for every column j,
+// the tree's levels walked from the top down,
+//     U_kj = L_kj L_jj^-1 (k in I_j, the rows of column j),   Sigma_ij = -sum_{k in I_j} Sigma_ik U_kj (i in I_j),
+//     Sigma_jj = L_jj^-T L_jj^-1 - sum_{k in I_j} U_kj^T Sigma_kj.
+// The rows of a column form a clique of the filled graph, so every Sigma_ik the sums read lies on the pattern, in a column of a higher
+// level.  The plan is built from a SparseCholPlan and changes nothing in it.
+struct SelInvPlan
+{
+	int nLevels = 0;
+	std::vector<int> stepPtr;                // [nLevels + 1] step s = level nLevels - 1 - s: its off-diagonal tiles ...
+	std::vector<int> offRec;                 // ... 4 ints each {tile (i, j), column j, first gather entry, entries}
+	std::vector<int> colStepPtr, cols;       // [nLevels + 1], [T]: the columns of step s (their diagonal tiles come second in the step)
+	std::vector<int> gather;                 // 2 ints per entry {Sigma tile (i, k) | bit 30 when it is stored as (k, i), tile (k, j)}, k ascending
+	long long products = 0;                  // tile products of one selected inversion (diagonal tiles included)
+	size_t sigmaBytes() const;               // the Sigma tile array a computation allocates (the factor's tile count)
+	int nTiles = 0;
+};
+// false: a tile the recurrence needs is missing from the pattern (cannot happen for a factor's pattern; a bug, reported by the caller)
+bool selinv_plan(const SparseCholPlan& p, SelInvPlan& out);
+
+struct SelInv                     // device view
+{
+	Scalar* sigma = nullptr;      // [nTiles][32 x 32] column-major: Sigma on the factor's pattern (diagonal tiles full, both triangles)
+	const int *offRec = nullptr, *gather = nullptr, *cols = nullptr;
+};
+// after launch_sparse_chol_factor on d: L_jj^-1 into the diagonal tiles' slots of d.tiles, U_kj into the off-diagonal slots of d.tilesT
+// (row-major), then the levels top-down into v.sigma
+void launch_selinv(const SparseChol& d, const SparseCholPlan& plan, const SelInvPlan& sp, const SelInv& v, hipStream_t s);
+// Sigma's 6 x 6 blocks: pose_cov [36 Pf] (diagonal blocks, internal order), blk_cov [36 nblk] (the blocks of the upper-triangular BSR
+// storage, through d.blkTile); either may be null
+void launch_selinv_extract(const DeviceStructure& st, const SparseChol& d, const SelInv& v, Scalar* pose_cov, Scalar* blk_cov, int Pf, hipStream_t s);
+// landmark marginals [9 Lf] (3 x 3 column-major, internal landmark order) at lambda = 0: Hll^-1 + Hll^-1 (sum_{p,q} W_p^T Sigma_pq W_q) Hll^-1,
+// from the landmark pass's Hll^-1 (sys.lm_sys) and W recomputed per edge (w_scratch: 18 E numbers)
+void launch_landmark_covariance(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const SparseChol& d, const SelInv& v,
+	Scalar* w_scratch, Scalar* lm_cov, hipStream_t s);
 
 // out3 = {chi2 total, landmark scale part, pose scale part} gathered from the result slots of the kernels enqueued before
 void launch_collect_eval(const DeviceSystem& sys, Scalar* out3, hipStream_t s);

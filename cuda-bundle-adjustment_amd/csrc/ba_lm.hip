@@ -285,16 +285,30 @@ bool cuba_hip_solver::ensureDirectPlan()
 	if (directPlanValid) return !directRefused;
 	const auto t0 = Clock::now();
 	ensureHostPattern();
-	directPlanValid = true;
 	if (!sparse_chol_plan(Pf, h_rowptr.data(), h_colind.data(), directSlack, (size_t)std::max(1, directMaxTiles), directPlan))
 	{
-		directRefused = true;
+		directPlanValid = true; directRefused = true;
 		char buf[200];
 		std::snprintf(buf, sizeof buf, "exact reduced solve unavailable: the factor of the %d-pose reduced matrix needs more than direct_max_tiles = %d tiles", Pf, directMaxTiles);
 		lastError = buf;
 		return false;
 	}
 	const SparseCholPlan& p = directPlan;
+	{
+		// (the tiles this plan adds to what the handle holds already must fit: refused like a fill beyond direct_max_tiles, not a failed allocation)
+		size_t freeB = 0, totalB = 0;
+		const size_t have = sizeof(Scalar) * (d_scTiles.size() + d_scTilesT.size());
+		if (hipMemGetInfo(&freeB, &totalB) == hipSuccess && p.tileBytes() > have && p.tileBytes() - have > freeB)
+		{
+			directPlanValid = true; directRefused = true;
+			char buf[200];
+			std::snprintf(buf, sizeof buf, "exact reduced solve unavailable: the factor of the %d-pose reduced matrix needs %.1f MB, %.1f MB of device memory are free",
+				Pf, p.tileBytes() / 1e6, freeB / 1e6);
+			lastError = buf;
+			return false;
+		}
+		(void)hipGetLastError();
+	}
 	// all index arrays in one allocation, one copy
 	std::vector<int> ints;
 	auto put = [&](const std::vector<int>& v) { const size_t o = ints.size(); ints.insert(ints.end(), v.begin(), v.end()); while (ints.size() % 4) ints.push_back(0); return o; };
@@ -310,6 +324,8 @@ bool cuba_hip_solver::ensureDirectPlan()
 	d.colPtr = base + oColPtr; d.rowIdx = base + oRowIdx; d.colOfTile = base + oColOf; d.gPtr = base + oGPtr; d.gather = base + oGather;
 	d.wgRec = base + oWgRec; d.lvlCols = base + oLvlCols; d.blkTile = base + oBlkTile; d.posOfSeg = base + oPos;
 	d.T = p.T; d.Pf = Pf; d.nTiles = p.nTiles;
+	directPlanValid = true;             // (only now: a failure above leaves the next call to try again)
+	directPlanBuilds++;
 	directPlanSeconds = std::chrono::duration<double>(Clock::now() - t0).count();
 	if (std::getenv("CUBA_HIP_DEBUG"))
 		std::fprintf(stderr, "[cuba_hip] exact reduced solve, symbolic phase: %d poses -> %d tile columns, %d tiles (%.1f MB), %d levels, %lld tile products, slack %d, %.2f ms\n",

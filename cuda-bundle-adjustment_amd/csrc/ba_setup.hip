@@ -62,6 +62,7 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 	// from here on the old graph is being replaced: a failure below (allocation, upload) leaves NO graph
 	haveGraph = false;
 	haveStructure = false;
+	covBlocksValid = false;
 	Pt = Pt_; Pf = Pf_; Lt = Lt_; Lf = Lf_; E = E_;
 	if (ranged) { partLo = ownLo; partHi = ownHi; }          // (before the sort: the internal landmark order is for whole-range handles)
 	lap(nullptr);

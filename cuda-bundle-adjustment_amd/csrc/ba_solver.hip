@@ -381,6 +381,7 @@ int cuba_hip_get_counter(cuba_hip_solver* s, const char* name, int64_t* value)
 		else if (k == "graph_uploads") *value = s->cntUploads;
 		else if (k == "value_bytes_uploaded") *value = s->cntValueBytes;
 		else if (k == "late_decision_records") *value = s->cntLateRecords;
+		else if (k == "covariance_ns") *value = (int64_t)(1e9 * s->covSeconds);
 		else throw ArgError{ "unknown counter: " + k };
 	});
 }
@@ -459,6 +460,21 @@ int cuba_hip_get_array(cuba_hip_solver* s, int which, double* out, size_t* count
 			}
 		}
 	});
+}
+
+// marginal covariances (g2o's SparseOptimizer::computeMarginals; the reference has none): ba_covariance.hip
+int cuba_hip_compute_covariance(cuba_hip_solver* s, double* pose_cov, double* landmark_cov, int* not_positive_definite)
+{
+	return guarded(s, [&] {
+		const bool ok = s->computeCovariance(pose_cov, landmark_cov);
+		if (!ok) s->lastError = "marginal covariances: non-positive pivot (the undamped reduced matrix is not positive definite)";
+		if (not_positive_definite) *not_positive_definite = ok ? 0 : 1;
+	});
+}
+
+int cuba_hip_get_covariance_blocks(cuba_hip_solver* s, double* values)
+{
+	return guarded(s, [&] { s->covarianceBlocks(values); });
 }
 
 int cuba_hip_time_kernels(cuba_hip_solver* s, int reps, double ms_per_launch[CUBA_HIP_TIMED_KERNELS])
@@ -614,24 +630,35 @@ int cuba_hip_debug_sparse_solve(int device, int n, const double* A, const double
 }
 
 // The symbolic phase alone (host only: needs no device).  which: 0 header {T, nTiles, nLevels, slack, gather entries, nblk}, 1 posOfSeg,
-// 2 colPtr, 3 rowIdx, 4 gPtr, 5 gather (4 ints per entry), 6 lvlPtr, 7 lvlTiles, 8 lvlColPtr, 9 lvlCols, 10 blkTile
+// 2 colPtr, 3 rowIdx, 4 gPtr, 5 gather (4 ints per entry), 6 lvlPtr, 7 lvlTiles, 8 lvlColPtr, 9 lvlCols, 10 blkTile;
+// the selected inversion's plan on top of it (SelInvPlan): 11 header {nLevels, off-diagonal tiles, gather entries, tile products (low,
+// high 31 bits)}, 12 stepPtr, 13 offRec (4 ints per tile), 14 colStepPtr, 15 cols, 16 gather (2 ints per entry)
 int cuba_hip_debug_sparse_plan(int n_poses, const int32_t* row_ptr, const int32_t* col_ind, int slack, int which, int32_t* out, size_t capacity, size_t* count)
 {
 	if (n_poses <= 0 || !row_ptr || !col_ind || !count) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	if (which < 0 || which > 16) return CUBA_HIP_ERR_INVALID_ARGUMENT;
 	static thread_local SparseCholPlan plan;
+	static thread_local SelInvPlan sel;
+	static thread_local bool selValid = false;
 	static thread_local std::vector<int> key;
 	std::vector<int> k(row_ptr, row_ptr + n_poses + 1);
 	k.insert(k.end(), col_ind, col_ind + row_ptr[n_poses]);
 	k.push_back(slack);
 	if (k != key)
 	{
+		key.clear(); selValid = false;
 		if (!sparse_chol_plan(n_poses, row_ptr, col_ind, slack, (size_t)1 << 22, plan)) return CUBA_HIP_ERR_RUNTIME;
 		key.swap(k);
 	}
+	if (which >= 11 && !selValid)
+	{
+		if (!selinv_plan(plan, sel)) return CUBA_HIP_ERR_RUNTIME;          // (a tile the recurrence needs is missing: a bug)
+		selValid = true;
+	}
 	const std::vector<int> header{ plan.T, plan.nTiles, plan.nLevels, plan.slack, (int)(plan.gather.size() / 4), (int)plan.blkTile.size() };
+	const std::vector<int> selHeader{ sel.nLevels, (int)(sel.offRec.size() / 4), (int)(sel.gather.size() / 2), (int)(sel.products & 0x7fffffff), (int)(sel.products >> 31) };
 	const std::vector<int>* src[] = { &header, &plan.posOfSeg, &plan.colPtr, &plan.rowIdx, &plan.gPtr, &plan.gather, &plan.lvlPtr, &plan.lvlTiles,
-		&plan.lvlColPtr, &plan.lvlCols, &plan.blkTile };
-	if (which < 0 || which > 10) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+		&plan.lvlColPtr, &plan.lvlCols, &plan.blkTile, &selHeader, &sel.stepPtr, &sel.offRec, &sel.colStepPtr, &sel.cols, &sel.gather };
 	*count = src[which]->size();
 	if (out) std::memcpy(out, src[which]->data(), sizeof(int) * std::min(capacity, src[which]->size()));
 	return CUBA_HIP_OK;

@@ -621,10 +621,25 @@ struct cuba_hip_solver
 	DevBuf<Scalar> d_scTiles, d_scTilesT, d_scY, d_scRinv;
 	DevBuf<int> d_scInts, d_scFail;
 	int64_t cntDirect = 0, cntDirectFailed = 0;
+	int64_t directPlanBuilds = 0;       // symbolic phases run so far (the covariance's plan is built on the one in force)
 	bool directUsable() const { return directFallback && !directRefused && Pf > 0; }
 	int pcgBudget(int maxIter) const;
 	bool ensureDirectPlan();
 	bool solveDirect();
+
+	// Marginal covariances (ba_covariance.hip; g2o's computeMarginals): the undamped reduced matrix at the current estimate is factorised
+	// with the exact solver's plan and buffers and inverted on the factor's pattern.  Nothing of it is visible to the LM path: it reads
+	// none of these members, and the buffers they share (hsc, bsc, lm_sys, the edge records, the factor's tiles) are rewritten by the
+	// next trial before anything reads them.  false = the matrix is not positive definite (outputs untouched).
+	SelInvPlan selPlan;
+	int64_t selPlanFor = -1;            // directPlanBuilds when selPlan was built
+	SelInv selDev;
+	DevBuf<int> d_selInts;
+	DevBuf<Scalar> d_sigma, d_covW, d_covPose, d_covBlk, d_covLm;
+	bool covBlocksValid = false;        // d_covBlk holds the cross blocks of the last computation on the current graph
+	double covSeconds = 0;              // host-side wall time of the last computation (reporting only)
+	bool computeCovariance(double* poseCov, double* lmCov);
+	void covarianceBlocks(double* out);
 
 	struct CoarseJob { cuba_hip_solver* h; int first; bool firstInvCopy; bool ownEvent; };
 	void launchCoarseJobs(std::vector<CoarseJob>& jobs, hipEvent_t common = nullptr);

@@ -164,6 +164,7 @@ public:
 	// ---- initialize: graph -> solver-order flat arrays (ref CudaBlockSolver::initialize :115-261) ----
 	void initialize() override
 	{
+		covPoseIndex_.clear(); covLmIndex_.clear();          // (marginal covariances describe the graph they were computed on)
 		const auto t0 = std::chrono::steady_clock::now();
 		static const bool dbg = std::getenv("CUBA_HIP_DEBUG") != nullptr;
 		auto tl = t0;
@@ -365,6 +366,23 @@ public:
 
 	cuba_hip_solver* handle() const { return solver_; }
 
+	// ---- marginal covariances (extension: cuba::computeCovariances) --------------------------------
+	bool computeCovariances(bool landmarks)
+	{
+		prepareOptimize();            // (the graph goes up first if initialize() changed it: the covariance is that of the current estimate)
+		covPoseIndex_.clear(); covLmIndex_.clear();
+		poseCov_.assign(36 * activePoses_.size(), 0.0);
+		lmCov_.assign(landmarks ? 9 * activeLandmarks_.size() : 0, 0.0);
+		int notPd = 0;
+		check(cuba_hip_compute_covariance(solver_, poseCov_.data(), landmarks ? lmCov_.data() : nullptr, &notPd), "cuba_hip_compute_covariance");
+		if (notPd) return false;
+		for (int i = 0; i < numFreePoses_; i++) covPoseIndex_[activePoses_[i]] = (size_t)i;
+		if (landmarks) for (int i = 0; i < numFreeLandmarks_; i++) covLmIndex_[activeLandmarks_[i]] = (size_t)i;
+		return true;
+	}
+	bool poseCovariance(const PoseVertex* v, double out[36]) const { return covBlock(covPoseIndex_, poseCov_, v, 36, out); }
+	bool landmarkCovariance(const LandmarkVertex* v, double out[9]) const { return covBlock(covLmIndex_, lmCov_, v, 9, out); }
+
 	void finishOptimize(const double* chi2, int done)
 	{
 		static const bool dbg = std::getenv("CUBA_HIP_DEBUG") != nullptr;
@@ -419,6 +437,7 @@ public:
 
 	void clear() override
 	{
+		covPoseIndex_.clear(); covLmIndex_.clear();
 		poses_.clear(); landmarks_.clear(); mono_.clear(); stereo_.clear(); stats_.clear();
 		posesDirty_ = landmarksDirty_ = edgesDirty_ = true;
 		initialized_ = false;
@@ -551,6 +570,17 @@ private:
 	bool initialized_ = false, graphDirty_ = false;
 	double initSeconds_ = 0;
 
+	template <class V>
+	static bool covBlock(const std::unordered_map<const void*, size_t>& index, const std::vector<double>& cov, const V* v, int n, double* out)
+	{
+		const auto it = index.find(v);
+		if (it == index.end()) return false;          // fixed, not part of the last computation, or nothing computed
+		std::copy(cov.begin() + (size_t)n * it->second, cov.begin() + (size_t)n * (it->second + 1), out);
+		return true;
+	}
+	std::unordered_map<const void*, size_t> covPoseIndex_, covLmIndex_;      // free vertex -> row of the last computation
+	std::vector<double> poseCov_, lmCov_;
+
 	cuba_hip_solver* solver_ = nullptr;
 	bool uploadedOnce_ = false, edgesChangedSinceUpload_ = true, valuesChangedSinceUpload_ = true;    // what cuba_hip_hint_unchanged may promise
 	int64_t uploadGeneration_ = -1;          // "graph_uploads" of the handle right after the upload those flags describe
@@ -599,6 +629,28 @@ void optimizeBatch(CudaBundleAdjustment* const* objects, int n, int niterations)
 	const int rc = cuba_hip_optimize_batch(handles.data(), n, niterations, chi2.data(), done.data(), nullptr);
 	if (rc != CUBA_HIP_OK) throw std::runtime_error(std::string("cuba_hip_optimize_batch failed: ") + cuba_hip_last_error(handles[0]));
 	for (int i = 0; i < n; i++) impl[i]->finishOptimize(chi2.data() + (size_t)i * std::max(niterations, 1), done[i]);
+}
+
+// Extension (g2o's SparseOptimizer::computeMarginals; the reference has none): marginal covariances of the free poses (6 x 6, tangent
+// [omega, upsilon] of the pose update) and, with `landmarks`, of the free landmarks (3 x 3) at the object's current estimate --
+// the inverse of the undamped Gauss-Newton Hessian (cuba_hip_compute_covariance).  false: that Hessian is not positive definite.
+bool computeCovariances(CudaBundleAdjustment* object, bool landmarks)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (!impl) throw std::runtime_error("cuba::computeCovariances: not an object of this library");
+	return impl->computeCovariances(landmarks);
+}
+
+bool poseCovariance(const CudaBundleAdjustment* object, const PoseVertex* v, double cov[36])
+{
+	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
+	return impl && impl->poseCovariance(v, cov);
+}
+
+bool landmarkCovariance(const CudaBundleAdjustment* object, const LandmarkVertex* v, double cov[9])
+{
+	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
+	return impl && impl->landmarkCovariance(v, cov);
 }
 
 }  // namespace cuba

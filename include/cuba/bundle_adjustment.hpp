@@ -75,4 +75,17 @@ public:
 // KITTI-07-sized graphs: 3.2 x one graph's throughput on one MI355X).  All objects must have been initialize()d.
 void optimizeBatch(CudaBundleAdjustment* const* objects, int n, int niterations);
 
+// Extension of this library (g2o's SparseOptimizer::computeMarginals; the reference has no counterpart): marginal covariances at the
+// object's current estimate -- the inverse of the undamped Gauss-Newton Hessian (robust weights rho' omega, fixed vertices eliminated;
+// include/cuba_hip.h, cuba_hip_compute_covariance).  Call after optimize() (or after initialize(): the graph is uploaded first).
+// computeCovariances returns false when that Hessian is not positive definite; refusals (fp32 library, a factor beyond device memory)
+// throw std::runtime_error.  The object's next optimize() runs exactly as if the call had not happened.
+//   poseCovariance      6 x 6, column-major, in the tangent [omega, upsilon] of the pose update (left-multiplicative se3 exponential)
+//   landmarkCovariance  3 x 3, column-major (only after computeCovariances(object, true))
+// Both return false for a fixed vertex, a vertex the last computation did not cover, or when nothing was computed since the last
+// initialize().
+bool computeCovariances(CudaBundleAdjustment* object, bool landmarks);
+bool poseCovariance(const CudaBundleAdjustment* object, const PoseVertex* v, double cov[36]);
+bool landmarkCovariance(const CudaBundleAdjustment* object, const LandmarkVertex* v, double cov[9]);
+
 }  // namespace cuba

@@ -319,6 +319,29 @@ int cuba_hip_get_counter(cuba_hip_solver* s, const char* name, int64_t* value);
    straight away are recorded as 0). */
 int cuba_hip_get_pcg_history(cuba_hip_solver* s, int32_t* iterations, int capacity, int* n_solves, int64_t* n_unconverged);
 
+/* ---- marginal covariances ------------------------------------------------------------------------ */
+
+/* Marginal covariances at the handle's CURRENT estimate -- the capability of g2o's SparseOptimizer::computeMarginals (Ceres:
+   Covariance); the reference has no counterpart.  The covariance is the inverse of the UNDAMPED Gauss-Newton Hessian, the matrix the LM
+   loop factorises with lambda = 0: robust weights rho'(e) omega as in constructQuadraticForm (no rho'' term), fixed vertices eliminated.
+   With S = Hpp - Hpl Hll^-1 Hlp the reduced matrix:
+     pose marginal      the 6 x 6 diagonal block of S^-1, in the tangent coordinates [omega, upsilon] of the solver's own pose update
+                        (the left-multiplicative se3 exponential of the reference's update, src/cuda_block_solver.cu:551-579);
+     landmark marginal  Hll^-1 + Hll^-1 (sum_{p,q in obs(l)} W_pl^T S^-1_pq W_ql) Hll^-1, W_pl the 6 x 3 block of Hpl;
+     cross blocks       S^-1_pq for every block (p, q) of the reduced matrix's upper-triangular pattern (cuba_hip_get_covariance_blocks);
+     fixed poses / fixed landmarks: zero blocks.
+   S is factorised with the exact reduced solver's ordering and inverted on the factor's pattern only (selected inversion): a second
+   copy of the factor's tiles in device memory.  pose_cov [36 Pt], landmark_cov [9 Lt]: column-major blocks in the caller's numbering;
+   NULL skips that output (a NULL landmark_cov skips the landmark pass).  A non-positive pivot returns CUBA_HIP_OK with
+   *not_positive_definite = 1 and the outputs untouched.  The call changes nothing the LM path sees: a later cuba_hip_optimize runs bit for
+   bit as if it had not happened.  Refusals (the handle stays usable): the fp32 library CUBA_HIP_ERR_INVALID_ARGUMENT (an fp32 inverse of a
+   bundle-adjustment Hessian is not meaningful); a landmark-partitioned handle or no graph yet CUBA_HIP_ERR_STATE; a factor beyond
+   "direct_max_tiles" or beyond free device memory CUBA_HIP_ERR_RUNTIME. */
+int cuba_hip_compute_covariance(cuba_hip_solver* s, double* pose_cov, double* landmark_cov, int* not_positive_definite);
+/* The cross blocks of the last cuba_hip_compute_covariance (g2o's computeMarginals block set), values[36 nblk], in the layout and
+   numbering of cuba_hip_get_hsc_structure.  CUBA_HIP_ERR_STATE before a successful computation and after cuba_hip_set_graph. */
+int cuba_hip_get_covariance_blocks(cuba_hip_solver* s, double* values);
+
 /* ---- introspection (parity tests) and multi-GPU plumbing ------------------------------------------ */
 
 /* Structure of the reduced system: upper-triangular BSR (replaces the accessors of
@@ -383,8 +406,10 @@ int cuba_hip_debug_sparse_solve(int device, int n, const double* A, const double
 /* The symbolic phase alone, on the host (no device needed): ordering, fill, elimination-tree levels and gather lists for the
    upper-triangular block pattern (row_ptr[n_poses + 1], col_ind; diagonal block first in every row).  which: 0 header {tile columns,
    tiles, levels, slack, gather entries, blocks}, 1 posOfSeg, 2 colPtr, 3 rowIdx, 4 gPtr, 5 gather (4 ints per entry), 6 lvlPtr,
-   7 lvlTiles, 8 lvlColPtr, 9 lvlCols, 10 blkTile (see SparseCholPlan in csrc/ba_kernels.hpp).  *count = length of the array; out may be
-   NULL to ask for it. */
+   7 lvlTiles, 8 lvlColPtr, 9 lvlCols, 10 blkTile (see SparseCholPlan in csrc/ba_kernels.hpp); the selected inversion's plan built on
+   it (cuba_hip_compute_covariance; SelInvPlan in csrc/ba_kernels.hpp): 11 header {levels, off-diagonal tiles, gather entries, tile
+   products low 31 bits, high bits}, 12 stepPtr, 13 offRec (4 ints per tile), 14 colStepPtr, 15 cols, 16 gather (2 ints per entry).
+   *count = length of the array; out may be NULL to ask for it. */
 int cuba_hip_debug_sparse_plan(int n_poses, const int32_t* row_ptr, const int32_t* col_ind, int slack, int which, int32_t* out, size_t capacity, size_t* count);
 
 /* A driver that runs the Levenberg-Marquardt loop itself through the stage calls announces the start of a run (a new lambda_0):

@@ -1,0 +1,324 @@
+"""Marginal covariances (cuba_hip_compute_covariance / HipSolver.covariance; g2o's computeMarginals) against a dense numpy inverse of
+the oracle's undamped normal equations at the library's own estimate, their reproducibility, their refusals, and the proof that a
+covariance computation leaves the LM path bit for bit as it was."""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import pytest
+
+from conftest import RK_HUBER, RK_NONE, RK_TUKEY, with_fixed
+from test_gpu_configs import dense_normal_equations, shuffled_pose_ids
+
+from cuba_amd.capi import CubaHipError, HipSolver
+from cuba_amd.graph import FlatProblem, flatten
+from cuba_amd.synth import synth_ba, synth_named
+from oracle.oracle import OracleSolver
+
+pytestmark = pytest.mark.gpu
+
+# the measured errors (the numbers DESIGN.md quotes) are written to the JSON file CUBA_COVARIANCE_RECORD names, when it is set
+_RECORD = os.environ.get("CUBA_COVARIANCE_RECORD")
+
+
+def _record(key, value):
+    if not _RECORD:
+        return
+    path = _RECORD
+    d = json.load(open(path)) if os.path.exists(path) else {}
+    d[key] = value
+    json.dump(d, open(path, "w"), indent=1, sort_keys=True)
+
+
+def small_fp(with_outlier=False):
+    fp = flatten(synth_ba(40, 600, 2400, seed=1))
+    if with_outlier:
+        # one stereo edge of a well-observed landmark 300 px off: far beyond the Tukey threshold, rho' = 0 there
+        cnt = np.bincount(fp.eL, minlength=fp.Lt)
+        e = int(np.flatnonzero((fp.eDim == 3) & (cnt[fp.eL] >= 5) & (fp.eP < fp.Pf) & (fp.eL < fp.Lf))[0])
+        fp.meas = fp.meas.copy(); fp.meas[e, 0] += 300.0
+    return fp
+
+
+def dense_covariance(h, fp, rk):
+    """inverse of the oracle's undamped full Hessian at the HIP estimate"""
+    o = OracleSolver(fp, rk)
+    o.set_state(*h.state())
+    o.compute_errors(); o.build_system()
+    H, _ = dense_normal_equations(o, fp, 0.0)
+    return np.linalg.inv(H)
+
+
+def block_errors(cov, blocks, Hi, fp, h):
+    """max over blocks of |got - want|_max / |want|_max, for pose, landmark and cross blocks"""
+    Pf, Lf = fp.Pf, fp.Lf
+    ep = max(np.abs(cov["pose"][p] - Hi[6 * p:6 * p + 6, 6 * p:6 * p + 6]).max() / np.abs(Hi[6 * p:6 * p + 6, 6 * p:6 * p + 6]).max()
+             for p in range(Pf))
+    a = 6 * Pf
+    el = max(np.abs(cov["landmark"][l] - Hi[a + 3 * l:a + 3 * l + 3, a + 3 * l:a + 3 * l + 3]).max()
+             / np.abs(Hi[a + 3 * l:a + 3 * l + 3, a + 3 * l:a + 3 * l + 3]).max() for l in range(Lf))
+    rp, ci = h.hsc_structure()
+    ec = 0.0
+    for i in range(Pf):
+        for k in range(rp[i], rp[i + 1]):
+            j = ci[k]
+            want = Hi[6 * i:6 * i + 6, 6 * j:6 * j + 6]
+            ec = max(ec, np.abs(blocks[k] - want).max() / np.abs(want).max())
+    # fixed vertices: zero blocks
+    assert not cov["pose"][Pf:].any() and not cov["landmark"][Lf:].any()
+    return ep, el, ec
+
+
+BAR = 1e-9
+
+
+def _check_small(fp, rk, label, bar=BAR, **opts):
+    h = HipSolver(fp, rk, **opts)
+    h.optimize(10)
+    cov = h.covariance(landmarks=True)
+    assert not cov["not_positive_definite"]
+    blocks = h.covariance_blocks()
+    Hi = dense_covariance(h, fp, rk)
+    ep, el, ec = block_errors(cov, blocks, Hi, fp, h)
+    _record(label, dict(pose=ep, landmark=el, cross=ec))
+    assert max(ep, el, ec) <= bar, (label, ep, el, ec)
+    return h, cov
+
+
+def test_small_graph_against_dense_inverse():
+    _check_small(small_fp(), RK_HUBER, "small_huber")
+
+
+# Tukey with the suite's thresholds (RK_TUKEY: 4 / 5 px) zeroes every edge of some landmarks of this graph: its Hll and the undamped
+# Hessian are then singular (not positive definite is the right answer there, checked on the CPU with the oracle).  Wider thresholds
+# keep the Hessian definite while the 300 px outlier still sits beyond them, at rho' = 0.
+RK_TUKEY_WIDE = ((2, 40.0), (2, 48.0))
+
+
+@pytest.mark.parametrize("rk,label", [(RK_NONE, "none"), (RK_TUKEY_WIDE, "tukey_outlier"), (RK_HUBER, "huber_outlier")])
+def test_robust_kernels(rk, label):
+    fp = small_fp(with_outlier=True)
+    h, _ = _check_small(fp, rk, "small_" + label)
+    if rk is RK_TUKEY_WIDE:
+        o = OracleSolver(fp, rk)
+        o.set_state(*h.state())
+        assert (o.chi_squares() > 48.0 ** 2).any()        # an edge at rho' = 0 took part
+
+
+def test_tukey_singular_hessian_is_reported():
+    """RK_TUKEY zeroes all edges of some landmarks after the run: a singular undamped Hessian, reported, outputs untouched"""
+    fp = small_fp()
+    h = HipSolver(fp, RK_TUKEY)
+    h.optimize(10)
+    cov = h.covariance()
+    assert cov["not_positive_definite"] and not cov["pose"].any() and not cov["landmark"].any()
+
+
+def test_fixed_vertices_shuffled_ids_and_landmark_order():
+    g = synth_ba(40, 600, 2400, seed=1)
+    _check_small(flatten(with_fixed(g, fixed_pose_rows=[3, 4, 20], fixed_lm_rows=list(range(0, 300, 7)))), RK_HUBER, "small_fixed")
+    _check_small(flatten(shuffled_pose_ids(g, seed=3)), RK_HUBER, "small_shuffled")
+    for lo in (0, 1):
+        _check_small(small_fp(), RK_HUBER, f"small_landmark_reorder_{lo}", landmark_reorder=lo)
+
+
+def test_mixed_precision_mode():
+    """under mixed_precision the LM path linearises with fp32 records; the covariance linearises in fp64 regardless (with fp32 records
+    its pose blocks were measured 1.1e-2 off in relative Frobenius norm on this graph), so the fp64 bar holds"""
+    _check_small(small_fp(), RK_HUBER, "small_mixed_precision", mixed_precision=1)
+
+
+def _dense_from_upper(rp, ci, v, Pf):
+    """symmetric dense matrix from upper-triangular BSR blocks [blk][row][col] (diagonal blocks: their upper triangle)"""
+    n = 6 * Pf
+    S = np.zeros((n, n))
+    for i in range(Pf):
+        for k in range(rp[i], rp[i + 1]):
+            j = ci[k]
+            B = v[k] if i != j else np.triu(v[k]) + np.triu(v[k], 1).T
+            S[6 * i:6 * i + 6, 6 * j:6 * j + 6] = B
+            S[6 * j:6 * j + 6, 6 * i:6 * i + 6] = B.T
+    return S
+
+
+# Against a matrix rounded independently of the library's (the oracle's reduced matrix: other summation orders), the inverse at KITTI-00
+# size differs by what the conditioning of S makes of a 1e-16 perturbation -- measured 8.7e-9 on the pose and cross blocks, 9.1e-9 on the
+# landmark sample --, so that comparison gets 5e-8.  The algorithm itself is compared with the dense inverse of the very matrix it
+# factorised (the library's own reduced matrix at lambda = 0, which the covariance call leaves in place): measured 1.0e-9, about what
+# numpy's own inverse of an 8 000 x 8 000 matrix of this conditioning carries, hence a bar of 4e-9 there.
+BAR_ORACLE_K00 = 5e-8
+BAR_OWN_K00 = 4e-9
+
+
+def test_kitti00_size_against_dense_reduced_inverse():
+    fp = flatten(synth_named("kitti00"))
+    h = HipSolver(fp, RK_HUBER)
+    h.optimize(5)
+    cov = h.covariance(landmarks=True)
+    assert not cov["not_positive_definite"]
+    blocks = h.covariance_blocks()
+    hrp, hci, hv = h.hsc()
+    Si_h = np.linalg.inv(_dense_from_upper(hrp, hci, hv, fp.Pf))
+    o = OracleSolver(fp, RK_HUBER)
+    o.set_state(*h.state())
+    o.compute_errors(); o.build_system(); o.set_lambda(0.0); o.schur()
+    rp, ci, v = o.hsc()
+    assert np.array_equal(hrp, rp) and np.array_equal(hci, ci)
+    Si_o = np.linalg.inv(_dense_from_upper(rp, ci, v, fp.Pf))
+
+    def errs(Si):
+        ep = max(np.abs(cov["pose"][p] - Si[6 * p:6 * p + 6, 6 * p:6 * p + 6]).max() / np.abs(Si[6 * p:6 * p + 6, 6 * p:6 * p + 6]).max()
+                 for p in range(fp.Pf))
+        ec = max(np.abs(blocks[k] - Si[6 * i:6 * i + 6, 6 * ci[k]:6 * ci[k] + 6]).max() / np.abs(Si[6 * i:6 * i + 6, 6 * ci[k]:6 * ci[k] + 6]).max()
+                 for i in range(fp.Pf) for k in range(rp[i], rp[i + 1]))
+        return ep, ec
+    ep_h, ec_h = errs(Si_h)
+    ep_o, ec_o = errs(Si_o)
+    # landmarks (a sample): Hll^-1 + Hll^-1 (sum W_p^T Sigma_pq W_q) Hll^-1 from the oracle's blocks and the dense reduced inverse
+    Hll = o.array("Hll").reshape(fp.Lf, 3, 3).transpose(0, 2, 1)
+    Hpl = o.array("Hpl").reshape(fp.E, 3, 6).transpose(0, 2, 1)
+    order = np.argsort(fp.eL, kind="stable")
+    starts = np.searchsorted(fp.eL[order], np.arange(fp.Lf + 1))
+    el = 0.0
+    for l in np.random.default_rng(0).choice(fp.Lf, 300, replace=False):
+        es = [e for e in order[starts[l]:starts[l + 1]] if fp.eP[e] < fp.Pf]
+        Hinv = np.linalg.inv(Hll[l])
+        M = np.zeros((3, 3))
+        for ea in es:
+            for eb in es:
+                pa, pb = fp.eP[ea], fp.eP[eb]
+                M += Hpl[ea].T @ Si_o[6 * pa:6 * pa + 6, 6 * pb:6 * pb + 6] @ Hpl[eb]
+        want = Hinv + Hinv @ M @ Hinv
+        el = max(el, np.abs(cov["landmark"][l] - want).max() / np.abs(want).max())
+    _record("kitti00", dict(pose_vs_own_matrix=ep_h, cross_vs_own_matrix=ec_h, pose_vs_oracle=ep_o, cross_vs_oracle=ec_o, landmark_sample_vs_oracle=el))
+    assert max(ep_h, ec_h) <= BAR_OWN_K00, (ep_h, ec_h)
+    assert max(ep_o, ec_o, el) <= BAR_ORACLE_K00, (ep_o, ec_o, el)
+
+
+def _run_record(h):
+    return dict(counters=h.counters(), named={k: h.counter(k) for k in NAMED}, history=h.pcg_history())
+
+
+NAMED = ("pcg_iterations", "lm_trials", "coarse_refreshes", "coarse_inline_inversions", "pcg_host_looks", "pcg_iterations_enqueued",
+         "pcg_unconverged_solves", "precond_fp32_fallbacks", "pcg_iterations_plain_launches", "host_looks", "exact_solve_fallbacks",
+         "exact_solve_failures", "graph_uploads", "value_bytes_uploaded", "late_decision_records")
+
+
+def _sequence(fp, between, **opts):
+    h = HipSolver(fp, RK_HUBER, **opts)
+    c1 = h.optimize(5)["chi2"]
+    between(h)
+    c2 = h.optimize(5)["chi2"]
+    out = dict(chi2=np.concatenate([c1, c2]), state=h.state(), edges=h.chi_squares(), rec=_run_record(h))
+    h.close()
+    return out
+
+
+def _assert_identical(a, b):
+    assert np.array_equal(a["chi2"], b["chi2"])
+    assert all(np.array_equal(x, y) for x, y in zip(a["state"], b["state"]))
+    assert np.array_equal(a["edges"], b["edges"])
+    assert a["rec"]["counters"] == b["rec"]["counters"] and a["rec"]["named"] == b["rec"]["named"]
+    assert np.array_equal(a["rec"]["history"][0], b["rec"]["history"][0]) and a["rec"]["history"][1] == b["rec"]["history"][1]
+
+
+@pytest.mark.parametrize("opts", [dict(), dict(reduced_solver=1)])
+def test_later_optimize_is_unaffected(opts):
+    fp = flatten(synth_named("kitti07"))
+    a = _sequence(fp, lambda h: h.covariance(landmarks=True), **opts)
+    b = _sequence(fp, lambda h: None, **opts)
+    _assert_identical(a, b)
+
+
+def test_repeatable_bit_for_bit():
+    fp = small_fp()
+    h = HipSolver(fp, RK_HUBER)
+    h.optimize(10)
+    c1, b1 = h.covariance(), h.covariance_blocks()
+    c2, b2 = h.covariance(), h.covariance_blocks()
+    assert np.array_equal(c1["pose"], c2["pose"]) and np.array_equal(c1["landmark"], c2["landmark"]) and np.array_equal(b1, b2)
+    poses_only = h.covariance(landmarks=False)
+    assert poses_only["landmark"] is None and np.array_equal(poses_only["pose"], c1["pose"])
+
+
+def test_refusals_leave_the_handle_usable():
+    fp = small_fp()
+    # fp32 library
+    h32 = HipSolver(fp, RK_HUBER, precision="f32")
+    with pytest.raises(CubaHipError, match="status 1"):
+        h32.covariance()
+    assert len(h32.optimize(3)["chi2"]) == 3
+    # no graph yet; no computation yet
+    h0 = HipSolver(None, RK_HUBER)
+    bad = C.c_int()
+    assert h0.lib.cuba_hip_compute_covariance(h0.h, None, None, C.byref(bad)) == 3
+    assert h0.lib.cuba_hip_get_covariance_blocks(h0.h, None) == 3
+    h = HipSolver(fp, RK_HUBER)
+    with pytest.raises(CubaHipError, match="status 3"):
+        h.covariance_blocks()
+    h.covariance(); h.covariance_blocks()
+    h.set_graph(fp)                                       # a graph change ends the validity of the blocks
+    with pytest.raises(CubaHipError, match="status 3"):
+        h.covariance_blocks()
+    # landmark-partitioned handle
+    hp = HipSolver(None, RK_HUBER)
+    hp.set_graph(fp, landmark_range=(0, fp.Lt // 2))
+    with pytest.raises(CubaHipError, match="status 3"):
+        hp.covariance()
+    # a factor beyond direct_max_tiles: refused, and the handle then optimises exactly like one that never asked
+    runs = []
+    for ask in (True, False):
+        hh = HipSolver(fp, RK_HUBER, direct_max_tiles=1)
+        if ask:
+            with pytest.raises(CubaHipError, match="status 2"):
+                hh.covariance()
+        runs.append(dict(chi2=hh.optimize(8)["chi2"], state=hh.state(), edges=hh.chi_squares(), rec=_run_record(hh)))
+        hh.close()
+    _assert_identical(runs[0], runs[1])
+
+
+def test_exactly_singular_system_is_reported():
+    """a free pose without any edge: its diagonal block of the reduced matrix is exactly zero"""
+    fp = small_fp()
+    P = fp.Pf
+    ins = lambda a: np.insert(a, P, a[0], axis=0)
+    eP = np.where(fp.eP >= P, fp.eP + 1, fp.eP).astype(np.int32)
+    sing = FlatProblem(fp.Pt + 1, fp.Pf + 1, fp.Lt, fp.Lf, ins(fp.q), ins(fp.t), ins(fp.cam), fp.Xw, eP, fp.eL, fp.eDim, fp.meas, fp.omega,
+                       ins(fp.pose_src), fp.lm_src, fp.edge_src)
+    h = HipSolver(sing, RK_HUBER)
+    cov = h.covariance()
+    assert cov["not_positive_definite"] and not cov["pose"].any() and not cov["landmark"].any()
+    with pytest.raises(CubaHipError, match="status 3"):
+        h.covariance_blocks()
+
+
+def test_cpp_sample_pose_sigmas_match_python(tmp_path):
+    """host/samples/pose_uncertainty (cuba::computeCovariances / cuba::poseCovariance) against HipSolver.covariance on the same graph"""
+    import re
+    import subprocess
+    from conftest import ROOT
+    from oracle.oracle import quat_to_rot
+    g = synth_ba(60, 1500, 6000, seed=3)
+    path = str(tmp_path / "graph.json")
+    g.to_json(path)
+    exe = os.path.join(ROOT, "cuda-bundle-adjustment_amd", "host", "samples", "pose_uncertainty")
+    out = subprocess.run([exe, path, "10", "1"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    got = {int(m[0]): np.array([float(m[1]), float(m[2]), float(m[3])])
+           for m in re.findall(r"pose (\d+) sigma (\S+) (\S+) (\S+)", out.stdout)}
+    fixed = {int(m) for m in re.findall(r"pose (\d+) fixed", out.stdout)}
+    fp = flatten(g)
+    h = HipSolver(fp, RK_HUBER)
+    h.optimize(10)
+    cov = h.covariance(landmarks=False)
+    q = h.state()[0]
+    assert len(got) == fp.Pf and len(fixed) == fp.Pt - fp.Pf
+    for p in range(fp.Pt):
+        pid = int(g.pose_ids[fp.pose_src[p]])
+        if p >= fp.Pf:
+            assert pid in fixed
+            continue
+        R = quat_to_rot(q[p])
+        want = np.sqrt(np.diag(R.T @ cov["pose"][p][3:, 3:] @ R))
+        assert np.allclose(got[pid], want, rtol=1e-6, atol=0), (pid, got[pid], want)
