@@ -136,6 +136,8 @@ def load_library(precision="f64"):
     lib.cuba_hip_debug_dense_solve.restype = C.c_int
     lib.cuba_hip_debug_sparse_solve.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int32)]
     lib.cuba_hip_debug_sparse_solve.restype = C.c_int
+    lib.cuba_hip_debug_selected_inverse.argtypes = [C.c_int, C.c_int, _dp, _dp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int32)]
+    lib.cuba_hip_debug_selected_inverse.restype = C.c_int
     lib.cuba_hip_debug_sparse_plan.argtypes = [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32),
                                                C.c_size_t, C.POINTER(C.c_size_t)]
     lib.cuba_hip_debug_sparse_plan.restype = C.c_int
@@ -187,6 +189,23 @@ def dense_solve(A, b, precision="f64", device=0, slack=-1, with_stats=False):
     if with_stats:
         return x, bool(flag.value), dict(zip(("tile_columns", "tiles", "levels", "slack"), (int(v) for v in stats)))
     return x, bool(flag.value)
+
+
+def selected_inverse(A, slack=-1, precision="f64", device=0, with_stats=False):
+    """The selected inversion behind HipSolver.covariance (csrc/ba_covariance.hip) applied to a symmetric matrix on dense_solve's block
+    pattern: test hook.  Returns (sigma, not_positive_definite[, stats]); sigma holds A^-1 on the pattern's blocks and their mirrors, as
+    the kernels extracted them (nothing symmetrised on the host), and zeros elsewhere."""
+    A = np.asfortranarray(A, dtype=np.float64)
+    sigma = np.zeros_like(A, order="F")
+    flag = C.c_int()
+    stats = (C.c_int32 * 4)()
+    rc = load_library(precision).cuba_hip_debug_selected_inverse(int(device), A.shape[0], _d(A), _d(sigma), C.byref(flag), int(slack), stats)
+    if rc != 0:
+        raise CubaHipError(f"cuba_hip_debug_selected_inverse failed with status {rc}")
+    sigma = np.array(sigma)
+    if with_stats:
+        return sigma, bool(flag.value), dict(zip(("tile_columns", "tiles", "levels", "slack"), (int(v) for v in stats)))
+    return sigma, bool(flag.value)
 
 
 SPARSE_PLAN_ARRAYS = ("header", "posOfSeg", "colPtr", "rowIdx", "gPtr", "gather", "lvlPtr", "lvlTiles", "lvlColPtr", "lvlCols", "blkTile")

@@ -333,6 +333,17 @@ void launch_landmark_covariance(const DeviceGraph& g, const DeviceStructure& st,
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // handle orchestration
 // ---------------------------------------------------------------------------------------------------------------------------------------
+void cubahip_host::upload_selinv_plan(const SelInvPlan& p, DevBuf<int>& d_ints, SelInv& view, hipStream_t s)
+{
+	std::vector<int> ints;
+	auto put = [&](const std::vector<int>& v) { const size_t o = ints.size(); ints.insert(ints.end(), v.begin(), v.end()); while (ints.size() % 4) ints.push_back(0); return o; };
+	const size_t oRec = put(p.offRec), oG = put(p.gather), oCols = put(p.cols);
+	if (ints.empty()) ints.push_back(0);
+	d_ints.upload(ints, s);
+	HIP_TRY(hipStreamSynchronize(s));
+	view.offRec = d_ints.data() + oRec; view.gather = d_ints.data() + oG; view.cols = d_ints.data() + oCols;
+}
+
 bool cuba_hip_solver::computeCovariance(double* poseCov, double* lmCov)
 {
 	if (sizeof(Scalar) != 8) throw ArgError{ "marginal covariances need the fp64 library: an fp32 inverse of a bundle-adjustment Hessian is not meaningful" };
@@ -353,13 +364,7 @@ bool cuba_hip_solver::computeCovariance(double* poseCov, double* lmCov)
 		if (selPlanFor != directPlanBuilds)
 		{
 			if (!selinv_plan(directPlan, selPlan)) throw std::logic_error("marginal covariances: a tile of the selected inversion is missing from the factor's pattern");
-			std::vector<int> ints;
-			auto put = [&](const std::vector<int>& v) { const size_t o = ints.size(); ints.insert(ints.end(), v.begin(), v.end()); while (ints.size() % 4) ints.push_back(0); return o; };
-			const size_t oRec = put(selPlan.offRec), oG = put(selPlan.gather), oCols = put(selPlan.cols);
-			if (ints.empty()) ints.push_back(0);
-			d_selInts.upload(ints, stream);
-			sync();
-			selDev.offRec = d_selInts.data() + oRec; selDev.gather = d_selInts.data() + oG; selDev.cols = d_selInts.data() + oCols;
+			upload_selinv_plan(selPlan, d_selInts, selDev, stream);
 			selPlanFor = directPlanBuilds;
 		}
 		const size_t sigmaCount = (size_t)SC_TT * std::max(1, directPlan.nTiles);

@@ -550,6 +550,64 @@ int cuba_hip_get_sizes(cuba_hip_solver* s, int sizes[5])
 	});
 }
 
+}  // extern "C"
+
+namespace
+{
+// What the debug hooks of the exact solver build from a dense matrix: the reduced system as the library would hold it -- the 6 x 6 blocks
+// on or above the diagonal that are not identically zero (the diagonal ones always), one block per (row, column) -- its plan, and the
+// device views the fill and the factorisation read.
+struct DebugSystem
+{
+	SparseCholPlan plan;
+	std::vector<int> blkrow, colind;
+	DevBuf<Scalar> dBlocks, dB, dTiles, dTilesT, dY, dRinv;
+	DevBuf<int> dRow, dCol, dFail, dColPtr, dRowIdx, dColOf, dGPtr, dGather, dLvlTiles, dLvlCols, dBlkTile, dPos;
+	SparseChol d;
+	DeviceStructure st;
+	DeviceSystem sys;
+};
+
+// false: the factor needs more than 2^22 tiles
+bool debug_system(int n, const double* A, const double* b, int slack, int32_t stats[4], DebugSystem& q)
+{
+	const int P = n / 6;
+	std::vector<Scalar> blocks; std::vector<int> rowptr(1, 0);
+	for (int bi = 0; bi < P; bi++)
+	{
+		for (int bj = bi; bj < P; bj++)
+		{
+			bool any = bi == bj;
+			for (int c = 0; c < 6 && !any; c++) for (int r = 0; r < 6; r++) any = any || A[(size_t)(6 * bj + c) * n + 6 * bi + r] != 0.0;
+			if (!any) continue;
+			q.blkrow.push_back(bi); q.colind.push_back(bj);
+			for (int c = 0; c < 6; c++) for (int r = 0; r < 6; r++) blocks.push_back((Scalar)A[(size_t)(6 * bj + c) * n + 6 * bi + r]);
+		}
+		rowptr.push_back((int)q.colind.size());
+	}
+	SparseCholPlan& plan = q.plan;
+	if (!sparse_chol_plan(P, rowptr.data(), q.colind.data(), slack, (size_t)1 << 22, plan)) return false;
+	if (stats) { stats[0] = plan.T; stats[1] = plan.nTiles; stats[2] = plan.nLevels; stats[3] = plan.slack; }
+	std::vector<Scalar> hb(b, b + n);
+	q.dBlocks.upload(blocks, nullptr); q.dB.upload(hb, nullptr); q.dRow.upload(q.blkrow, nullptr); q.dCol.upload(q.colind, nullptr);
+	q.dColPtr.upload(plan.colPtr, nullptr); q.dRowIdx.upload(plan.rowIdx, nullptr); q.dColOf.upload(plan.colOfTile, nullptr); q.dGPtr.upload(plan.gPtr, nullptr);
+	q.dGather.upload(plan.gather, nullptr); q.dLvlTiles.upload(plan.wgRec, nullptr); q.dLvlCols.upload(plan.lvlCols, nullptr);
+	q.dBlkTile.upload(plan.blkTile, nullptr); q.dPos.upload(plan.posOfSeg, nullptr);
+	q.dTiles.resize((size_t)SC_TT * ((size_t)plan.nTiles + 1)); q.dTilesT.resize((size_t)SC_TT * plan.nTiles);
+	q.dY.resize((size_t)SC_T * plan.T); q.dRinv.resize((size_t)SC_T * plan.T); q.dFail.resize(1);
+	SparseChol& d = q.d;
+	d.tiles = q.dTiles.data(); d.tilesT = q.dTilesT.data(); d.y = q.dY.data(); d.rinv = q.dRinv.data(); d.fail = q.dFail.data();
+	d.colPtr = q.dColPtr.data(); d.rowIdx = q.dRowIdx.data(); d.colOfTile = q.dColOf.data(); d.gPtr = q.dGPtr.data(); d.gather = q.dGather.data();
+	d.wgRec = q.dLvlTiles.data(); d.lvlCols = q.dLvlCols.data(); d.blkTile = q.dBlkTile.data(); d.posOfSeg = q.dPos.data();
+	d.T = plan.T; d.Pf = P; d.nTiles = plan.nTiles;
+	q.st.nblk = (int)q.blkrow.size(); q.st.hsc_blkrow = q.dRow.data(); q.st.hsc_colind = q.dCol.data();
+	q.sys.hsc = q.dBlocks.data(); q.sys.bsc = q.dB.data();
+	return true;
+}
+}  // namespace
+
+extern "C" {
+
 int cuba_hip_debug_dense_inverse(int device, int n, const double* A, double* Ainv)
 {
 	if (n <= 0 || !A || !Ainv) return CUBA_HIP_ERR_INVALID_ARGUMENT;
@@ -581,52 +639,85 @@ int cuba_hip_debug_sparse_solve(int device, int n, const double* A, const double
 	if (hipSetDevice(device) != hipSuccess) return CUBA_HIP_ERR_NO_DEVICE;
 	try
 	{
-		// the matrix as the reduced system would hold it: the 6 x 6 blocks on or above the diagonal that are not identically zero (the
-		// diagonal ones always), one block per (row, column)
-		const int P = n / 6;
-		std::vector<Scalar> blocks; std::vector<int> blkrow, colind, rowptr(1, 0);
-		for (int bi = 0; bi < P; bi++)
-		{
-			for (int bj = bi; bj < P; bj++)
-			{
-				bool any = bi == bj;
-				for (int c = 0; c < 6 && !any; c++) for (int r = 0; r < 6; r++) any = any || A[(size_t)(6 * bj + c) * n + 6 * bi + r] != 0.0;
-				if (!any) continue;
-				blkrow.push_back(bi); colind.push_back(bj);
-				for (int c = 0; c < 6; c++) for (int r = 0; r < 6; r++) blocks.push_back((Scalar)A[(size_t)(6 * bj + c) * n + 6 * bi + r]);
-			}
-			rowptr.push_back((int)colind.size());
-		}
-		SparseCholPlan plan;
-		if (!sparse_chol_plan(P, rowptr.data(), colind.data(), slack, (size_t)1 << 22, plan)) return CUBA_HIP_ERR_RUNTIME;
-		if (stats) { stats[0] = plan.T; stats[1] = plan.nTiles; stats[2] = plan.nLevels; stats[3] = plan.slack; }
-		std::vector<Scalar> hb(b, b + n);
-		DevBuf<Scalar> dBlocks, dB, dTiles, dTilesT, dY, dRinv, dX; DevBuf<int> dRow, dCol, dFail;
-		dBlocks.upload(blocks, nullptr); dB.upload(hb, nullptr); dRow.upload(blkrow, nullptr); dCol.upload(colind, nullptr);
-		DevBuf<int> dColPtr, dRowIdx, dColOf, dGPtr, dGather, dLvlTiles, dLvlCols, dBlkTile, dPos;
-		dColPtr.upload(plan.colPtr, nullptr); dRowIdx.upload(plan.rowIdx, nullptr); dColOf.upload(plan.colOfTile, nullptr); dGPtr.upload(plan.gPtr, nullptr);
-		dGather.upload(plan.gather, nullptr); dLvlTiles.upload(plan.wgRec, nullptr); dLvlCols.upload(plan.lvlCols, nullptr);
-		dBlkTile.upload(plan.blkTile, nullptr); dPos.upload(plan.posOfSeg, nullptr);
-		dTiles.resize((size_t)SC_TT * ((size_t)plan.nTiles + 1)); dTilesT.resize((size_t)SC_TT * plan.nTiles);
-		dY.resize((size_t)SC_T * plan.T); dRinv.resize((size_t)SC_T * plan.T); dFail.resize(1); dX.resize(n);
-		SparseChol d;
-		d.tiles = dTiles.data(); d.tilesT = dTilesT.data(); d.y = dY.data(); d.rinv = dRinv.data(); d.fail = dFail.data();
-		d.colPtr = dColPtr.data(); d.rowIdx = dRowIdx.data(); d.colOfTile = dColOf.data(); d.gPtr = dGPtr.data(); d.gather = dGather.data();
-		d.wgRec = dLvlTiles.data(); d.lvlCols = dLvlCols.data(); d.blkTile = dBlkTile.data(); d.posOfSeg = dPos.data();
-		d.T = plan.T; d.Pf = P; d.nTiles = plan.nTiles;
-		DeviceStructure st; DeviceSystem sys;
-		st.nblk = (int)blkrow.size(); st.hsc_blkrow = dRow.data(); st.hsc_colind = dCol.data();
-		sys.hsc = dBlocks.data(); sys.bsc = dB.data();
-		launch_sparse_chol_fill(st, sys, d, nullptr);
-		launch_sparse_chol_solve(d, plan, dX.data(), nullptr);
+		DebugSystem q;
+		if (!debug_system(n, A, b, slack, stats, q)) return CUBA_HIP_ERR_RUNTIME;
+		DevBuf<Scalar> dX; dX.resize(n);
+		launch_sparse_chol_fill(q.st, q.sys, q.d, nullptr);
+		launch_sparse_chol_solve(q.d, q.plan, dX.data(), nullptr);
 		std::vector<Scalar> hx(n); int flag = 0;
 		HIP_TRY(hipMemcpy(hx.data(), dX.data(), sizeof(Scalar) * n, hipMemcpyDeviceToHost));
-		HIP_TRY(hipMemcpy(&flag, dFail.data(), sizeof(int), hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(&flag, q.dFail.data(), sizeof(int), hipMemcpyDeviceToHost));
 		for (int i = 0; i < n; i++) x[i] = (double)hx[i];
 		if (not_positive_definite) *not_positive_definite = flag;
 		return CUBA_HIP_OK;
 	}
 	catch (const HipError&) { return CUBA_HIP_ERR_RUNTIME; }
+	catch (const std::exception&) { return CUBA_HIP_ERR_RUNTIME; }
+	catch (...) { return CUBA_HIP_ERR_RUNTIME; }
+}
+
+int cuba_hip_debug_selected_inverse(int device, int n, const double* A, double* sigma, int* not_positive_definite, int slack, int32_t stats[4])
+{
+	if (n <= 0 || n % 6 != 0 || !A || !sigma) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	if (sizeof(Scalar) != 8) return CUBA_HIP_ERR_INVALID_ARGUMENT;          // (as cuba_hip_compute_covariance in the fp32 library)
+	if (hipSetDevice(device) != hipSuccess) return CUBA_HIP_ERR_NO_DEVICE;
+	try
+	{
+		const size_t nn = (size_t)n * n;
+		std::fill(sigma, sigma + nn, 0.0);
+		if (not_positive_definite) *not_positive_definite = 0;
+		const int P = n / 6;
+		const std::vector<double> zeros(n, 0.0);
+		DebugSystem q;
+		if (!debug_system(n, A, zeros.data(), slack, stats, q)) return CUBA_HIP_ERR_RUNTIME;
+		// cuba_hip_solver::computeCovariance's calls, in its order
+		launch_sparse_chol_fill(q.st, q.sys, q.d, nullptr);
+		launch_sparse_chol_factor(q.d, q.plan, nullptr);
+		int flag = 0;
+		HIP_TRY(hipMemcpy(&flag, q.dFail.data(), sizeof(int), hipMemcpyDeviceToHost));
+		if (flag)
+		{
+			if (not_positive_definite) *not_positive_definite = 1;
+			return CUBA_HIP_OK;
+		}
+		SelInvPlan sp;
+		if (!selinv_plan(q.plan, sp)) return CUBA_HIP_ERR_RUNTIME;
+		DevBuf<int> dSelInts; DevBuf<Scalar> dSigma, dPose, dBlk;
+		SelInv v;
+		upload_selinv_plan(sp, dSelInts, v, nullptr);
+		// (all-ones bytes, a NaN: a tile, block or element the kernels should have written and did not shows up in the output)
+		dSigma.resize((size_t)SC_TT * std::max(1, q.plan.nTiles)); dPose.resize((size_t)36 * P); dBlk.resize((size_t)36 * q.st.nblk);
+		HIP_TRY(hipMemset(dSigma.data(), 0xff, sizeof(Scalar) * dSigma.size()));
+		HIP_TRY(hipMemset(dPose.data(), 0xff, sizeof(Scalar) * dPose.size()));
+		HIP_TRY(hipMemset(dBlk.data(), 0xff, sizeof(Scalar) * dBlk.size()));
+		v.sigma = dSigma.data();
+		launch_selinv(q.d, q.plan, sp, v, nullptr);
+		launch_selinv_extract(q.st, q.d, v, dPose.data(), dBlk.data(), P, nullptr);
+		std::vector<Scalar> hp(dPose.size()), hb(dBlk.size());
+		HIP_TRY(hipMemcpy(hp.data(), dPose.data(), sizeof(Scalar) * hp.size(), hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(hb.data(), dBlk.data(), sizeof(Scalar) * hb.size(), hipMemcpyDeviceToHost));
+		// scattered as extracted (6 x 6 column-major blocks): the off-diagonal blocks of the pattern and their transposes, then the pose
+		// blocks on the diagonal -- nothing symmetrised here, so a diagonal block shows the kernels' own symmetry
+		for (int b = 0; b < q.st.nblk; b++)
+		{
+			const int bi = q.blkrow[b], bj = q.colind[b];
+			if (bi == bj) continue;
+			for (int c = 0; c < 6; c++)
+				for (int r = 0; r < 6; r++)
+				{
+					const double val = (double)hb[36 * (size_t)b + 6 * c + r];
+					sigma[(size_t)(6 * bj + c) * n + 6 * bi + r] = val;
+					sigma[(size_t)(6 * bi + r) * n + 6 * bj + c] = val;
+				}
+		}
+		for (int p = 0; p < P; p++)
+			for (int c = 0; c < 6; c++)
+				for (int r = 0; r < 6; r++) sigma[(size_t)(6 * p + c) * n + 6 * p + r] = (double)hp[36 * (size_t)p + 6 * c + r];
+		return CUBA_HIP_OK;
+	}
+	catch (const HipError&) { return CUBA_HIP_ERR_RUNTIME; }
+	catch (const std::exception&) { return CUBA_HIP_ERR_RUNTIME; }
+	catch (...) { return CUBA_HIP_ERR_RUNTIME; }
 }
 
 // The symbolic phase alone (host only: needs no device).  which: 0 header {T, nTiles, nLevels, slack, gather entries, nblk}, 1 posOfSeg,
@@ -637,31 +728,45 @@ int cuba_hip_debug_sparse_plan(int n_poses, const int32_t* row_ptr, const int32_
 {
 	if (n_poses <= 0 || !row_ptr || !col_ind || !count) return CUBA_HIP_ERR_INVALID_ARGUMENT;
 	if (which < 0 || which > 16) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	// the patterns the library itself hands to sparse_chol_plan (Hsc's h_rowptr / h_colind), and nothing else: rows that start at 0 and
+	// never shrink, each led by its own diagonal block, columns strictly increasing and below n_poses (sparse_chol_plan indexes by them)
+	if (row_ptr[0] != 0) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	for (int i = 0; i < n_poses; i++)
+	{
+		if (row_ptr[i + 1] <= row_ptr[i] || col_ind[row_ptr[i]] != i) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+		for (int k = row_ptr[i] + 1; k < row_ptr[i + 1]; k++)
+			if (col_ind[k] <= col_ind[k - 1] || col_ind[k] >= n_poses) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	}
 	static thread_local SparseCholPlan plan;
 	static thread_local SelInvPlan sel;
 	static thread_local bool selValid = false;
 	static thread_local std::vector<int> key;
-	std::vector<int> k(row_ptr, row_ptr + n_poses + 1);
-	k.insert(k.end(), col_ind, col_ind + row_ptr[n_poses]);
-	k.push_back(slack);
-	if (k != key)
+	try
 	{
-		key.clear(); selValid = false;
-		if (!sparse_chol_plan(n_poses, row_ptr, col_ind, slack, (size_t)1 << 22, plan)) return CUBA_HIP_ERR_RUNTIME;
-		key.swap(k);
+		std::vector<int> k(row_ptr, row_ptr + n_poses + 1);
+		k.insert(k.end(), col_ind, col_ind + row_ptr[n_poses]);
+		k.push_back(slack);
+		if (k != key)
+		{
+			key.clear(); selValid = false;
+			if (!sparse_chol_plan(n_poses, row_ptr, col_ind, slack, (size_t)1 << 22, plan)) return CUBA_HIP_ERR_RUNTIME;
+			key.swap(k);
+		}
+		if (which >= 11 && !selValid)
+		{
+			if (!selinv_plan(plan, sel)) return CUBA_HIP_ERR_RUNTIME;          // (a tile the recurrence needs is missing: a bug)
+			selValid = true;
+		}
+		const std::vector<int> header{ plan.T, plan.nTiles, plan.nLevels, plan.slack, (int)(plan.gather.size() / 4), (int)plan.blkTile.size() };
+		const std::vector<int> selHeader{ sel.nLevels, (int)(sel.offRec.size() / 4), (int)(sel.gather.size() / 2), (int)(sel.products & 0x7fffffff), (int)(sel.products >> 31) };
+		const std::vector<int>* src[] = { &header, &plan.posOfSeg, &plan.colPtr, &plan.rowIdx, &plan.gPtr, &plan.gather, &plan.lvlPtr, &plan.lvlTiles,
+			&plan.lvlColPtr, &plan.lvlCols, &plan.blkTile, &selHeader, &sel.stepPtr, &sel.offRec, &sel.colStepPtr, &sel.cols, &sel.gather };
+		*count = src[which]->size();
+		if (out) std::memcpy(out, src[which]->data(), sizeof(int) * std::min(capacity, src[which]->size()));
+		return CUBA_HIP_OK;
 	}
-	if (which >= 11 && !selValid)
-	{
-		if (!selinv_plan(plan, sel)) return CUBA_HIP_ERR_RUNTIME;          // (a tile the recurrence needs is missing: a bug)
-		selValid = true;
-	}
-	const std::vector<int> header{ plan.T, plan.nTiles, plan.nLevels, plan.slack, (int)(plan.gather.size() / 4), (int)plan.blkTile.size() };
-	const std::vector<int> selHeader{ sel.nLevels, (int)(sel.offRec.size() / 4), (int)(sel.gather.size() / 2), (int)(sel.products & 0x7fffffff), (int)(sel.products >> 31) };
-	const std::vector<int>* src[] = { &header, &plan.posOfSeg, &plan.colPtr, &plan.rowIdx, &plan.gPtr, &plan.gather, &plan.lvlPtr, &plan.lvlTiles,
-		&plan.lvlColPtr, &plan.lvlCols, &plan.blkTile, &selHeader, &sel.stepPtr, &sel.offRec, &sel.colStepPtr, &sel.cols, &sel.gather };
-	*count = src[which]->size();
-	if (out) std::memcpy(out, src[which]->data(), sizeof(int) * std::min(capacity, src[which]->size()));
-	return CUBA_HIP_OK;
+	catch (const std::exception&) { key.clear(); selValid = false; return CUBA_HIP_ERR_RUNTIME; }
+	catch (...) { key.clear(); selValid = false; return CUBA_HIP_ERR_RUNTIME; }
 }
 
 int cuba_hip_begin_run(cuba_hip_solver* s)

@@ -115,6 +115,10 @@ extern std::atomic<int> g_liveHandles;
 
 constexpr int CUBA_HIP_BATCH_MAX = 64;       // graphs per cuba_hip_optimize_batch call
 
+// The selected inversion's work lists (offRec, gather, cols: each starting on a 16-byte boundary for the kernels' int4 / int2 loads) into
+// `ints`, and their device addresses into `view` (ba_covariance.hip; the covariance and cuba_hip_debug_selected_inverse).  Waits for s.
+void upload_selinv_plan(const SelInvPlan& p, DevBuf<int>& ints, SelInv& view, hipStream_t s);
+
 }  // namespace cubahip_host
 using namespace cubahip_host;
 

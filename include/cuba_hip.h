@@ -403,13 +403,21 @@ int cuba_hip_debug_dense_inverse(int device, int n, const double* A, double* Ain
    No solver handle involved.  cuba_hip_debug_dense_solve = the same with slack -1 and no statistics. */
 int cuba_hip_debug_dense_solve(int device, int n, const double* A, const double* b, double* x, int* not_positive_definite);
 int cuba_hip_debug_sparse_solve(int device, int n, const double* A, const double* b, double* x, int* not_positive_definite, int slack, int32_t stats[4]);
+/* Test hook for the selected inversion behind cuba_hip_compute_covariance (csrc/ba_covariance.hip), on the matrix and block pattern
+   cuba_hip_debug_sparse_solve takes: fill, factorisation, fail flag, selected inversion and extraction, the calls of the covariance in its
+   order.  sigma: n x n column-major, A^-1 on every block of the pattern and its mirror (the diagonal blocks as the pose extraction
+   delivers them, the off-diagonal ones as the block extraction does, with their transposes), zero elsewhere.  A matrix that is not
+   positive definite: CUBA_HIP_OK, *not_positive_definite = 1, sigma all zero.  The fp32 library: CUBA_HIP_ERR_INVALID_ARGUMENT.
+   stats (optional) as above.  No solver handle involved. */
+int cuba_hip_debug_selected_inverse(int device, int n, const double* A, double* sigma, int* not_positive_definite, int slack, int32_t stats[4]);
 /* The symbolic phase alone, on the host (no device needed): ordering, fill, elimination-tree levels and gather lists for the
    upper-triangular block pattern (row_ptr[n_poses + 1], col_ind; diagonal block first in every row).  which: 0 header {tile columns,
    tiles, levels, slack, gather entries, blocks}, 1 posOfSeg, 2 colPtr, 3 rowIdx, 4 gPtr, 5 gather (4 ints per entry), 6 lvlPtr,
    7 lvlTiles, 8 lvlColPtr, 9 lvlCols, 10 blkTile (see SparseCholPlan in csrc/ba_kernels.hpp); the selected inversion's plan built on
    it (cuba_hip_compute_covariance; SelInvPlan in csrc/ba_kernels.hpp): 11 header {levels, off-diagonal tiles, gather entries, tile
    products low 31 bits, high bits}, 12 stepPtr, 13 offRec (4 ints per tile), 14 colStepPtr, 15 cols, 16 gather (2 ints per entry).
-   *count = length of the array; out may be NULL to ask for it. */
+   *count = length of the array; out may be NULL to ask for it.  A malformed pattern (row_ptr[0] != 0, a row without its diagonal block
+   first, columns not strictly increasing or not below n_poses) is CUBA_HIP_ERR_INVALID_ARGUMENT. */
 int cuba_hip_debug_sparse_plan(int n_poses, const int32_t* row_ptr, const int32_t* col_ind, int slack, int which, int32_t* out, size_t capacity, size_t* count);
 
 /* A driver that runs the Levenberg-Marquardt loop itself through the stage calls announces the start of a run (a new lambda_0):

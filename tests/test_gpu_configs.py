@@ -428,12 +428,9 @@ def dense_normal_equations(o, fp, lam):
     return H, b
 
 
-def test_duplicate_observations_of_one_pose(solvers):
-    """Two observations of one landmark by the SAME pose (a monocular and a stereo edge): the diagonal-block branch of
-    the block pass (a == b).  Checked against a dense solve of the full normal equations -- the mathematically
-    complete Schur complement (T + T^T on the diagonal block; the reference and hence the oracle's literal restatement
-    add only T there, DESIGN.md section 5)."""
-    HipSolver, OracleSolver = solvers
+def graph_with_duplicate_observations():
+    """the 40-pose graph with 80 stereo edges observed again as monocular ones and 40 monocular edges duplicated: 120 second
+    observations of a landmark by the same pose"""
     g = copy.deepcopy(synth_ba(40, 600, 2400, seed=1))
     rng = np.random.default_rng(2)
     pick_s = rng.choice(len(g.stereo_vp), 80, replace=False)        # stereo edges observed again as monocular ones
@@ -444,6 +441,16 @@ def test_duplicate_observations_of_one_pose(solvers):
     g.mono_vp = np.concatenate([g.mono_vp, g.mono_vp[pick_m]]); g.mono_vl = np.concatenate([g.mono_vl, g.mono_vl[pick_m]])
     g.mono_meas = np.concatenate([g.mono_meas, g.mono_meas[pick_m] + rng.normal(0, 0.5, (40, 2))])
     g.mono_info = np.concatenate([g.mono_info, g.mono_info[pick_m]])
+    return g
+
+
+def test_duplicate_observations_of_one_pose(solvers):
+    """Two observations of one landmark by the SAME pose (a monocular and a stereo edge): the diagonal-block branch of
+    the block pass (a == b).  Checked against a dense solve of the full normal equations -- the mathematically
+    complete Schur complement (T + T^T on the diagonal block; the reference and hence the oracle's literal restatement
+    add only T there, DESIGN.md section 5)."""
+    HipSolver, OracleSolver = solvers
+    g = graph_with_duplicate_observations()
     fp = flatten(g)
     key = fp.eP.astype(np.int64) * fp.Lt + fp.eL
     assert len(np.unique(key)) == fp.E - 120

@@ -100,3 +100,15 @@ def test_capi_fails_loudly_without_gpu():
     from cuba_amd.capi import CubaHipError, HipSolver
     with pytest.raises(CubaHipError):
         HipSolver()
+
+
+def test_selected_inverse_hook_checks_its_arguments_without_a_device():
+    """cuba_hip_debug_selected_inverse rejects an order that is not a positive multiple of 6 and null matrices before it touches a device"""
+    from cuba_amd import capi
+    lib = capi.load_library("f64")
+    A = np.eye(12)
+    out = np.zeros((12, 12))
+    flag = ctypes.c_int()
+    for n, a, s in ((7, A, out), (0, A, out), (-6, A, out), (12, None, out), (12, A, None)):
+        assert lib.cuba_hip_debug_selected_inverse(0, n, capi._d(a), capi._d(s), ctypes.byref(flag), -1, None) == 1, (n, a is None, s is None)
+    assert not out.any()

@@ -87,3 +87,46 @@ def test_dense_pattern_fills_every_tile():
     row_ptr, col_ind = band_pattern(60, 60)
     plan = sparse_plan(row_ptr, col_ind)
     assert plan["nTiles"] == 12 * 13 // 2                            # dense: every tile on or below the diagonal
+
+
+def _malformed_patterns():
+    """(name, row_ptr, col_ind) of patterns the library never builds: each would index outside the plan's arrays"""
+    rp, ci = band_pattern(12, 2)
+    out = []
+    r = rp.copy(); r[0] = 1
+    out.append(("row_ptr_starts_at_1", r, ci))
+    r = rp.copy(); r[5] = r[4] - 1
+    out.append(("row_ptr_decreases", r, ci))
+    c = ci.copy(); c[rp[3] + 1], c[rp[3] + 2] = c[rp[3] + 2], c[rp[3] + 1]
+    out.append(("columns_not_increasing", rp, c))
+    c = ci.copy(); c[rp[3] + 2] = c[rp[3] + 1]
+    out.append(("column_repeated", rp, c))
+    r = rp.copy(); r[4:] -= 1; c = np.delete(ci, rp[3])                      # row 3 loses its diagonal block
+    out.append(("diagonal_missing", r, c))
+    c = ci.copy(); c[rp[6]] = 5                                               # row 6 led by a lower-triangle block
+    out.append(("lower_triangle_entry", rp, c))
+    c = ci.copy(); c[rp[11] - 1] = 12                                         # (the last block of row 10: 10, 11, 12)
+    out.append(("column_beyond_n_poses", rp, c))
+    c = ci.copy(); c[rp[10] - 1] = 1 << 20                                    # (the last block of row 9)
+    out.append(("column_far_beyond_n_poses", rp, c))
+    c = ci.copy(); c[rp[2] + 1] = -7
+    out.append(("negative_column", rp, c))
+    return out
+
+
+def test_malformed_patterns_are_refused():
+    """cuba_hip_debug_sparse_plan validates its pattern before anything is built (a column outside [0, n_poses) would write outside the
+    ordering's adjacency bitmap); the plan cache of the hook stays keyed to the last good pattern."""
+    from cuba_amd.capi import CubaHipError, selinv_plan
+    rp, ci = CASES["band_loop_closure"]()
+    before, sel_before = sparse_plan(rp, ci, slack=4), selinv_plan(rp, ci, slack=4)
+    for name, r, c in _malformed_patterns():
+        with pytest.raises(CubaHipError, match="status 1"):
+            sparse_plan(r, c)
+        with pytest.raises(CubaHipError, match="status 1"):
+            selinv_plan(r, c, slack=4)
+    after, sel_after = sparse_plan(rp, ci, slack=4), selinv_plan(rp, ci, slack=4)
+    for a, b in ((before, after), (sel_before, sel_after)):
+        assert a.keys() == b.keys()
+        for k in a:
+            assert np.array_equal(a[k], b[k]), k
