@@ -121,6 +121,7 @@ def load_library(precision="f64"):
         "cuba_hip_evaluate_device": [H, C.c_double, C.c_int, C.POINTER(C.c_void_p)],
         "cuba_hip_compute_covariance": [H, _dp, _dp, C.POINTER(C.c_int)],
         "cuba_hip_get_covariance_blocks": [H, _dp],
+        "cuba_hip_compute_covariance_pairs": [H, C.c_int, _ip, _ip, _ip, _ip, _dp, C.POINTER(C.c_int)],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -141,6 +142,12 @@ def load_library(precision="f64"):
     lib.cuba_hip_debug_sparse_plan.argtypes = [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32),
                                                C.c_size_t, C.POINTER(C.c_size_t)]
     lib.cuba_hip_debug_sparse_plan.restype = C.c_int
+    lib.cuba_hip_debug_inverse_blocks.argtypes = [C.c_int, C.c_int, _dp, C.c_int, _ip, _ip, _dp, C.POINTER(C.c_int), C.c_int,
+                                                  C.POINTER(C.c_int32)]
+    lib.cuba_hip_debug_inverse_blocks.restype = C.c_int
+    lib.cuba_hip_debug_pair_plan.argtypes = [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, _ip, _ip, C.c_int,
+                                             C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.cuba_hip_debug_pair_plan.restype = C.c_int
     lib.cuba_hip_last_error.argtypes = [H]
     lib.cuba_hip_last_error.restype = C.c_char_p
     lib.cuba_hip_version.restype = C.c_char_p
@@ -206,6 +213,55 @@ def selected_inverse(A, slack=-1, precision="f64", device=0, with_stats=False):
     if with_stats:
         return sigma, bool(flag.value), dict(zip(("tile_columns", "tiles", "levels", "slack"), (int(v) for v in stats)))
     return sigma, bool(flag.value)
+
+
+def inverse_blocks(A, pairs, slack=-1, precision="f64", device=0, with_stats=False):
+    """The kernels behind HipSolver.covariance_pairs applied to a symmetric matrix on dense_solve's block pattern: test hook.  pairs: (i, j)
+    6 x 6 block indices, on or off the pattern.  Returns (blocks [n, 6, 6] = A^-1[6i:6i+6, 6j:6j+6], not_positive_definite[, stats])."""
+    A = np.asfortranarray(A, dtype=np.float64)
+    pr = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+    bi, bj = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+    out = np.zeros((len(pr), 36))
+    flag = C.c_int()
+    stats = (C.c_int32 * 4)()
+    rc = load_library(precision).cuba_hip_debug_inverse_blocks(int(device), A.shape[0], _d(A), len(pr), bi.ctypes.data_as(_ip),
+                                                               bj.ctypes.data_as(_ip), _d(out), C.byref(flag), int(slack), stats)
+    if rc != 0:
+        raise CubaHipError(f"cuba_hip_debug_inverse_blocks failed with status {rc}")
+    blocks = out.reshape(-1, 6, 6).transpose(0, 2, 1).copy()
+    if with_stats:
+        return blocks, bool(flag.value), dict(zip(("tile_columns", "tiles", "levels", "slack"), (int(v) for v in stats)))
+    return blocks, bool(flag.value)
+
+
+PAIR_PLAN_ARRAYS = ("header", "pairs", "fwdPtr", "fwdCols", "bwdPtr", "bwdCols", "slotPtr", "slotCols", "fLvlPtr", "fRec", "fGather",
+                    "bLvlPtr", "bRec", "bGather")
+
+
+def pair_plan(row_ptr, col_ind, pairs, slack=-1, precision="f64"):
+    """Symbolic phase of the pair solve behind HipSolver.covariance_pairs for pose pairs (i = left, j = right) on an upper-triangular
+    block pattern (host only, no device): dict of the arrays of PairPlan in csrc/ba_kernels.hpp, all blocks in one chunk.  "pairs" holds
+    {block, column, 0, 0} per pair; fRec / bRec {slot, tile column, first gather entry, entries}; fGather / bGather {tile, slot}."""
+    lib = load_library(precision)
+    rp = np.ascontiguousarray(row_ptr, dtype=np.int32); ci = np.ascontiguousarray(col_ind, dtype=np.int32)
+    pr = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+    bi, bj = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+    ip = C.POINTER(C.c_int32)
+    out = {}
+    for which, name in enumerate(PAIR_PLAN_ARRAYS):
+        n = C.c_size_t()
+        args = (len(rp) - 1, rp.ctypes.data_as(ip), ci.ctypes.data_as(ip), int(slack), len(pr), bi.ctypes.data_as(_ip), bj.ctypes.data_as(_ip), which)
+        rc = lib.cuba_hip_debug_pair_plan(*args, None, 0, C.byref(n))
+        if rc != 0:
+            raise CubaHipError(f"cuba_hip_debug_pair_plan failed with status {rc}")
+        a = np.zeros(n.value, dtype=np.int32)
+        rc = lib.cuba_hip_debug_pair_plan(*args, a.ctypes.data_as(ip), n.value, C.byref(n))
+        if rc != 0:
+            raise CubaHipError(f"cuba_hip_debug_pair_plan failed with status {rc}")
+        out[name] = a
+    h = out.pop("header")
+    out.update(blocks=int(h[0]), slots=int(h[1]), fRecords=int(h[2]), fEntries=int(h[3]), bRecords=int(h[4]), bEntries=int(h[5]))
+    return out
 
 
 SPARSE_PLAN_ARRAYS = ("header", "posOfSeg", "colPtr", "rowIdx", "gPtr", "gather", "lvlPtr", "lvlTiles", "lvlColPtr", "lvlCols", "blkTile")
@@ -493,6 +549,28 @@ class HipSolver:
         out = np.zeros((len(ci), 6, 6))
         self._ck(self.lib.cuba_hip_get_covariance_blocks(self.h, _d(out)))
         return out.transpose(0, 2, 1).copy()
+
+    VERTEX_KINDS = {"pose": 0, "landmark": 1}
+
+    def covariance_pairs(self, pairs):
+        """Covariance blocks of arbitrary vertex pairs (cuba_hip_compute_covariance_pairs): pairs = [(kind_a, i, kind_b, j), ...] with kinds
+        "pose" / "landmark" and indices in the caller's numbering.  Returns ([array (dim_a, dim_b) per pair, [row][col], rows from a and
+        columns from b], not_positive_definite); fixed vertices give zero blocks."""
+        n = len(pairs)
+        ka = np.zeros(max(n, 1), dtype=np.int32); ia = np.zeros_like(ka); kb = np.zeros_like(ka); ib = np.zeros_like(ka)
+        for k, (a_kind, a, b_kind, b) in enumerate(pairs):
+            ka[k] = self.VERTEX_KINDS.get(a_kind, -1) if isinstance(a_kind, str) else int(a_kind)
+            kb[k] = self.VERTEX_KINDS.get(b_kind, -1) if isinstance(b_kind, str) else int(b_kind)
+            ia[k], ib[k] = int(a), int(b)
+        out = np.zeros((max(n, 1), 36))
+        bad = C.c_int()
+        self._ck(self.lib.cuba_hip_compute_covariance_pairs(self.h, n, ka.ctypes.data_as(_ip), ia.ctypes.data_as(_ip), kb.ctypes.data_as(_ip),
+                                                            ib.ctypes.data_as(_ip), _d(out), C.byref(bad)))
+        blocks = []
+        for k in range(n):
+            da, db = (6 if ka[k] == 0 else 3), (6 if kb[k] == 0 else 3)
+            blocks.append(out[k, :da * db].reshape(db, da).T.copy())
+        return blocks, bool(bad.value)
 
     def time_kernels(self, reps=20):
         out = np.zeros(7)

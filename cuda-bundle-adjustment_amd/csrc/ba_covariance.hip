@@ -171,6 +171,11 @@ void launch_selinv(const SparseChol& d, const SparseCholPlan& plan, const SelInv
 	(void)plan;
 }
 
+void launch_diag_inverse(const SparseChol& d, hipStream_t s)
+{
+	if (d.T > 0) hipLaunchKernelGGL(selinv_diag_inverse_kernel, dim3(d.T), dim3(64), 0, s, d);
+}
+
 // element (r, c) of Sigma's 6 x 6 block (pa, pb) of free poses (internal order) whose tile is known: the addressing of
 // schol_fill_blocks_kernel (tile (row position, column position), column-major)
 __device__ __forceinline__ Scalar sigma_elem(const Scalar* __restrict__ tile, int tr, int li, int lj)
@@ -224,6 +229,11 @@ __global__ __launch_bounds__(256) void edge_w_kernel(DeviceGraph g, Scalar* __re
 			const Scalar v = le.lin.JP[0][r] * le.lin.JL[0][c] + le.lin.JP[1][r] * le.lin.JL[1][c] + le.lin.JP[2][r] * le.lin.JL[2][c];
 			w[c * 6 + r] = on ? le.wr * v : Scalar(0);
 		}
+}
+
+void launch_edge_w(const DeviceGraph& g, Scalar* W, hipStream_t s)
+{
+	if (g.E > 0) hipLaunchKernelGGL(edge_w_kernel, dim3((g.E + 255) / 256), dim3(256), 0, s, g, W);
 }
 
 // the tile of Sigma that holds block (ka, kb) of tile positions (ka != kb): (max, min) in column min's sorted row list

@@ -346,6 +346,51 @@ void launch_selinv_extract(const DeviceStructure& st, const SparseChol& d, const
 void launch_landmark_covariance(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const SparseChol& d, const SelInv& v,
 	Scalar* w_scratch, Scalar* lm_cov, hipStream_t s);
 
+// L_jj^-1 into the diagonal tiles' slots of d.tiles (the first launch of launch_selinv; the rest of the factor is left as it is)
+void launch_diag_inverse(const SparseChol& d, hipStream_t s);
+// W = the 6 x 3 Hpl block of every edge at the current estimate (18 E numbers, column-major; zero for an edge to a fixed vertex)
+void launch_edge_w(const DeviceGraph& g, Scalar* W, hipStream_t s);
+
+// ---- marginal covariances of arbitrary pairs (ba_covariance_pairs.hip) ------------------------------------------------------------
+// X_b = S^-1 C_b for 32-column blocks of right-hand sides (the poses of one segment, or ten landmarks' W columns), solved only on the tree
+// columns a block touches: the FORWARD set (ancestors of the segments C_b touches) and the BACKWARD set (ancestors of the segments the
+// pairs' left sides read).  Both are unions of root-ward chains (parent = first off-diagonal row of a column), hence closed under the rows
+// of a column.  A request is packed once; its blocks run in chunks that fit the workspace.
+struct PairRequest                // host, internal numbering (pose kind 0, landmark kind 1)
+{
+	int nBlocks = 0;
+	std::vector<int> rhsPtr, rhsPos;         // [nBlocks + 1]: tile columns (positions) the block's right-hand side touches, ascending
+	std::vector<int> leftPtr, leftPos;       // [nBlocks + 1]: tile columns its pairs' extraction reads, ascending
+	std::vector<int> poseRec;                // 4 ints per right pose {block, column in the block, 0, 0}, by block
+	std::vector<int> lmRec;                  // 4 ints per right landmark {landmark, block, column, 0}, by block
+	std::vector<int> pairRec;                // 8 ints per computed pair {kind a, a, block, column of b, kind b, b, output index, 0}
+};
+// pairs with a negative index (a fixed vertex) are left out; lmPtr / ePose: the landmark-major edge lists (only read for landmarks)
+void pair_pack(const SparseCholPlan& p, int n, const int* kindA, const int* idxA, const int* kindB, const int* idxB,
+	const std::vector<int>& lmPtr, const std::vector<int>& ePose, PairRequest& rq);
+struct PairPlan                   // host: blocks [b0, b1) of a request (one chunk)
+{
+	int b0 = 0, b1 = 0, nLevels = 0, T = 0;
+	std::vector<int> fwdPtr, fwdCols;        // per block of the chunk: the forward set, ascending
+	std::vector<int> bwdPtr, bwdCols;        // per block: the backward set, ascending
+	std::vector<int> slotPtr, slotCols;      // per block: its workspace tiles (the union of both sets, ascending), numbered across the chunk
+	std::vector<int> slotOf;                 // [(b1 - b0) T] slot of (block, tile column), -1 outside the block's sets
+	std::vector<int> fLvlPtr, fRec;          // forward work by level ascending; 4 ints per record {slot, column j, first gather entry, entries}
+	std::vector<int> fGather;                // 2 ints per entry {tile (j, k), slot of k}: k in the forward set, ascending
+	std::vector<int> bLvlPtr, bRec;          // backward work, step s = level nLevels - 1 - s; records as above
+	std::vector<int> bGather;                // 2 ints per entry {tile (i, j), slot of i}: every row i of column j, ascending
+	size_t slots() const { return slotCols.size(); }
+};
+size_t pair_block_slots(const SparseCholPlan& p, const PairRequest& rq, int b);
+// false: a row of a column is missing from the backward set (cannot happen for a factor's pattern; a bug, reported by the caller)
+bool pair_plan(const SparseCholPlan& p, const PairRequest& rq, int b0, int b1, PairPlan& out);
+struct PairDev                    // device view of one chunk
+{
+	Scalar* X = nullptr;          // [slots][32 x 32] column-major: C -> Y -> X
+	const int *fRec = nullptr, *fGather = nullptr, *bRec = nullptr, *bGather = nullptr, *slotOf = nullptr, *rhsPos = nullptr;
+	int T = 0;
+};
+
 // out3 = {chi2 total, landmark scale part, pose scale part} gathered from the result slots of the kernels enqueued before
 void launch_collect_eval(const DeviceSystem& sys, Scalar* out3, hipStream_t s);
 

@@ -141,6 +141,11 @@ int cuba_hip_set_option(cuba_hip_solver* s, const char* key, double value)
 		}
 		else if (k == "pcg_aggregate") { s->pcgAggregate = (int)value; s->haveStructure = false; }
 		else if (k == "coarse_linear") { s->coarseLinear = value != 0; s->haveStructure = false; }
+		else if (k == "covariance_workspace_mb")
+		{
+			if (value < 0 || value > (double)(1 << 30)) throw ArgError{ "covariance_workspace_mb must lie in 0 .. 2^30 (0 = automatic)" };
+			s->covWorkspaceMb = value;
+		}
 		else if (k == "landmark_reorder") s->lmReorder = value != 0;         // (takes effect with the next cuba_hip_set_graph)
 		else if (k == "reduction_chunks")
 		{
@@ -382,6 +387,8 @@ int cuba_hip_get_counter(cuba_hip_solver* s, const char* name, int64_t* value)
 		else if (k == "value_bytes_uploaded") *value = s->cntValueBytes;
 		else if (k == "late_decision_records") *value = s->cntLateRecords;
 		else if (k == "covariance_ns") *value = (int64_t)(1e9 * s->covSeconds);
+		else if (k == "covariance_pairs_ns") *value = (int64_t)(1e9 * s->covPairsSeconds);
+		else if (k == "covariance_pairs_chunks") *value = s->covPairChunks;
 		else throw ArgError{ "unknown counter: " + k };
 	});
 }
@@ -475,6 +482,16 @@ int cuba_hip_compute_covariance(cuba_hip_solver* s, double* pose_cov, double* la
 int cuba_hip_get_covariance_blocks(cuba_hip_solver* s, double* values)
 {
 	return guarded(s, [&] { s->covarianceBlocks(values); });
+}
+
+int cuba_hip_compute_covariance_pairs(cuba_hip_solver* s, int n, const int32_t* kind_a, const int32_t* index_a, const int32_t* kind_b,
+	const int32_t* index_b, double* out, int* not_positive_definite)
+{
+	return guarded(s, [&] {
+		const bool ok = s->computeCovariancePairs(n, kind_a, index_a, kind_b, index_b, out);
+		if (!ok) s->lastError = "covariance pairs: non-positive pivot (the undamped reduced matrix is not positive definite)";
+		if (not_positive_definite) *not_positive_definite = ok ? 0 : 1;
+	});
 }
 
 int cuba_hip_time_kernels(cuba_hip_solver* s, int reps, double ms_per_launch[CUBA_HIP_TIMED_KERNELS])
@@ -720,6 +737,119 @@ int cuba_hip_debug_selected_inverse(int device, int n, const double* A, double* 
 	catch (...) { return CUBA_HIP_ERR_RUNTIME; }
 }
 
+}  // extern "C"
+
+namespace
+{
+// the patterns the library itself hands to sparse_chol_plan (Hsc's h_rowptr / h_colind), and nothing else: rows that start at 0 and
+// never shrink, each led by its own diagonal block, columns strictly increasing and below n_poses (sparse_chol_plan indexes by them)
+bool pattern_ok(int n_poses, const int32_t* row_ptr, const int32_t* col_ind)
+{
+	if (row_ptr[0] != 0) return false;
+	for (int i = 0; i < n_poses; i++)
+	{
+		if (row_ptr[i + 1] <= row_ptr[i] || col_ind[row_ptr[i]] != i) return false;
+		for (int k = row_ptr[i] + 1; k < row_ptr[i + 1]; k++)
+			if (col_ind[k] <= col_ind[k - 1] || col_ind[k] >= n_poses) return false;
+	}
+	return true;
+}
+
+// pose pairs (block_i = left, block_j = right) of a debug hook, packed as the handle packs a request of free poses
+void debug_pack(const SparseCholPlan& plan, int n_pairs, const int32_t* block_i, const int32_t* block_j, PairRequest& rq)
+{
+	const std::vector<int> zeros((size_t)std::max(n_pairs, 1), 0), none;
+	pair_pack(plan, n_pairs, zeros.data(), block_i, zeros.data(), block_j, none, none, rq);
+}
+}  // namespace
+
+extern "C" {
+
+int cuba_hip_debug_inverse_blocks(int device, int n, const double* A, int n_pairs, const int32_t* block_i, const int32_t* block_j, double* out,
+	int* not_positive_definite, int slack, int32_t stats[4])
+{
+	if (n <= 0 || n % 6 != 0 || !A || n_pairs < 0 || (n_pairs > 0 && (!block_i || !block_j || !out))) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	if (sizeof(Scalar) != 8) return CUBA_HIP_ERR_INVALID_ARGUMENT;          // (as cuba_hip_compute_covariance_pairs in the fp32 library)
+	const int P = n / 6;
+	for (int k = 0; k < n_pairs; k++)
+		if (block_i[k] < 0 || block_i[k] >= P || block_j[k] < 0 || block_j[k] >= P) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	if (hipSetDevice(device) != hipSuccess) return CUBA_HIP_ERR_NO_DEVICE;
+	try
+	{
+		std::fill(out, out + (size_t)36 * n_pairs, 0.0);
+		if (not_positive_definite) *not_positive_definite = 0;
+		const std::vector<double> zeros(n, 0.0);
+		DebugSystem q;
+		if (!debug_system(n, A, zeros.data(), slack, stats, q)) return CUBA_HIP_ERR_RUNTIME;
+		// cuba_hip_solver::computeCovariancePairs' calls, in its order
+		launch_sparse_chol_fill(q.st, q.sys, q.d, nullptr);
+		launch_sparse_chol_factor(q.d, q.plan, nullptr);
+		int flag = 0;
+		HIP_TRY(hipMemcpy(&flag, q.dFail.data(), sizeof(int), hipMemcpyDeviceToHost));
+		if (flag)
+		{
+			if (not_positive_definite) *not_positive_definite = 1;
+			return CUBA_HIP_OK;
+		}
+		PairRequest rq;
+		debug_pack(q.plan, n_pairs, block_i, block_j, rq);
+		size_t freeB = 0, totalB = 0;
+		HIP_TRY(hipMemGetInfo(&freeB, &totalB));
+		PairWork w;
+		DevBuf<Scalar> dOut;
+		dOut.resize((size_t)36 * std::max(n_pairs, 1));
+		// (all-ones bytes, a NaN: an output the kernels should have written and did not shows up)
+		HIP_TRY(hipMemset(dOut.data(), 0xff, sizeof(Scalar) * dOut.size()));
+		const int chunks = run_covariance_pairs(q.d, q.plan, DeviceGraph(), DeviceSystem(), nullptr, rq, freeB / 2, w, dOut.data(), nullptr);
+		(void)chunks;
+		std::vector<Scalar> h((size_t)36 * n_pairs);
+		if (n_pairs) HIP_TRY(hipMemcpy(h.data(), dOut.data(), sizeof(Scalar) * h.size(), hipMemcpyDeviceToHost));
+		HIP_TRY(hipDeviceSynchronize());
+		for (size_t i = 0; i < h.size(); i++) out[i] = (double)h[i];
+		return CUBA_HIP_OK;
+	}
+	catch (const HipError&) { return CUBA_HIP_ERR_RUNTIME; }
+	catch (const std::exception&) { return CUBA_HIP_ERR_RUNTIME; }
+	catch (...) { return CUBA_HIP_ERR_RUNTIME; }
+}
+
+// The pair solve's symbolic phase alone (host only), all blocks in one chunk.  which: 0 header {blocks, slots, forward records, forward
+// gather entries, backward records, backward gather entries}, 1 pairs {block, column, 0, 0}, 2 fwdPtr, 3 fwdCols, 4 bwdPtr, 5 bwdCols,
+// 6 slotPtr, 7 slotCols, 8 fLvlPtr, 9 fRec, 10 fGather, 11 bLvlPtr, 12 bRec, 13 bGather
+int cuba_hip_debug_pair_plan(int n_poses, const int32_t* row_ptr, const int32_t* col_ind, int slack, int n_pairs, const int32_t* block_i,
+	const int32_t* block_j, int which, int32_t* out, size_t capacity, size_t* count)
+{
+	if (n_poses <= 0 || !row_ptr || !col_ind || !count || n_pairs < 0 || (n_pairs > 0 && (!block_i || !block_j))) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	if (which < 0 || which > 13) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	if (!pattern_ok(n_poses, row_ptr, col_ind)) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	for (int k = 0; k < n_pairs; k++)
+		if (block_i[k] < 0 || block_i[k] >= n_poses || block_j[k] < 0 || block_j[k] >= n_poses) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	try
+	{
+		SparseCholPlan plan;
+		if (!sparse_chol_plan(n_poses, row_ptr, col_ind, slack, (size_t)1 << 22, plan)) return CUBA_HIP_ERR_RUNTIME;
+		PairRequest rq;
+		debug_pack(plan, n_pairs, block_i, block_j, rq);
+		PairPlan pl;
+		if (!pair_plan(plan, rq, 0, rq.nBlocks, pl)) return CUBA_HIP_ERR_RUNTIME;
+		std::vector<int> pairs((size_t)4 * n_pairs, 0);
+		for (size_t r = 0; r < rq.pairRec.size(); r += 8)
+		{
+			const int k = rq.pairRec[r + 6];
+			pairs[4 * (size_t)k] = rq.pairRec[r + 2]; pairs[4 * (size_t)k + 1] = rq.pairRec[r + 3];
+		}
+		const std::vector<int> header{ rq.nBlocks, (int)pl.slots(), (int)(pl.fRec.size() / 4), (int)(pl.fGather.size() / 2), (int)(pl.bRec.size() / 4),
+			(int)(pl.bGather.size() / 2) };
+		const std::vector<int>* src[] = { &header, &pairs, &pl.fwdPtr, &pl.fwdCols, &pl.bwdPtr, &pl.bwdCols, &pl.slotPtr, &pl.slotCols,
+			&pl.fLvlPtr, &pl.fRec, &pl.fGather, &pl.bLvlPtr, &pl.bRec, &pl.bGather };
+		*count = src[which]->size();
+		if (out) std::memcpy(out, src[which]->data(), sizeof(int) * std::min(capacity, src[which]->size()));
+		return CUBA_HIP_OK;
+	}
+	catch (const std::exception&) { return CUBA_HIP_ERR_RUNTIME; }
+	catch (...) { return CUBA_HIP_ERR_RUNTIME; }
+}
+
 // The symbolic phase alone (host only: needs no device).  which: 0 header {T, nTiles, nLevels, slack, gather entries, nblk}, 1 posOfSeg,
 // 2 colPtr, 3 rowIdx, 4 gPtr, 5 gather (4 ints per entry), 6 lvlPtr, 7 lvlTiles, 8 lvlColPtr, 9 lvlCols, 10 blkTile;
 // the selected inversion's plan on top of it (SelInvPlan): 11 header {nLevels, off-diagonal tiles, gather entries, tile products (low,
@@ -728,15 +858,7 @@ int cuba_hip_debug_sparse_plan(int n_poses, const int32_t* row_ptr, const int32_
 {
 	if (n_poses <= 0 || !row_ptr || !col_ind || !count) return CUBA_HIP_ERR_INVALID_ARGUMENT;
 	if (which < 0 || which > 16) return CUBA_HIP_ERR_INVALID_ARGUMENT;
-	// the patterns the library itself hands to sparse_chol_plan (Hsc's h_rowptr / h_colind), and nothing else: rows that start at 0 and
-	// never shrink, each led by its own diagonal block, columns strictly increasing and below n_poses (sparse_chol_plan indexes by them)
-	if (row_ptr[0] != 0) return CUBA_HIP_ERR_INVALID_ARGUMENT;
-	for (int i = 0; i < n_poses; i++)
-	{
-		if (row_ptr[i + 1] <= row_ptr[i] || col_ind[row_ptr[i]] != i) return CUBA_HIP_ERR_INVALID_ARGUMENT;
-		for (int k = row_ptr[i] + 1; k < row_ptr[i + 1]; k++)
-			if (col_ind[k] <= col_ind[k - 1] || col_ind[k] >= n_poses) return CUBA_HIP_ERR_INVALID_ARGUMENT;
-	}
+	if (!pattern_ok(n_poses, row_ptr, col_ind)) return CUBA_HIP_ERR_INVALID_ARGUMENT;
 	static thread_local SparseCholPlan plan;
 	static thread_local SelInvPlan sel;
 	static thread_local bool selValid = false;

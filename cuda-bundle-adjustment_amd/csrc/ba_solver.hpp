@@ -119,6 +119,14 @@ constexpr int CUBA_HIP_BATCH_MAX = 64;       // graphs per cuba_hip_optimize_bat
 // `ints`, and their device addresses into `view` (ba_covariance.hip; the covariance and cuba_hip_debug_selected_inverse).  Waits for s.
 void upload_selinv_plan(const SelInvPlan& p, DevBuf<int>& ints, SelInv& view, hipStream_t s);
 
+// Workspace of cuba_hip_compute_covariance_pairs (and its debug hook): a chunk's tiles and work lists.
+struct PairWork { DevBuf<Scalar> X; DevBuf<int> ints; };
+// runs the request chunk by chunk (ba_covariance_pairs.hip) after launch_sparse_chol_factor on d: L_jj^-1, right-hand sides, forward and
+// backward levels, extraction into out[36 r] for the r-th pair record (its output index field); W: Hpl blocks per edge (landmark pairs only).
+// Throws std::runtime_error when one block's tiles exceed budgetBytes.  Returns the number of chunks; the work is left in the stream.
+int run_covariance_pairs(const SparseChol& d, const SparseCholPlan& plan, const DeviceGraph& g, const DeviceSystem& sys, const Scalar* W,
+	const PairRequest& rq, size_t budgetBytes, PairWork& w, Scalar* out, hipStream_t s);
+
 }  // namespace cubahip_host
 using namespace cubahip_host;
 
@@ -644,6 +652,14 @@ struct cuba_hip_solver
 	double covSeconds = 0;              // host-side wall time of the last computation (reporting only)
 	bool computeCovariance(double* poseCov, double* lmCov);
 	void covarianceBlocks(double* out);
+	// Covariance blocks of arbitrary pose / landmark pairs (ba_covariance_pairs.hip): self-contained (linearisation at lambda = 0, fill,
+	// factorisation, then triangular solves restricted to the tree paths the request touches).  false: not positive definite, out untouched.
+	double covWorkspaceMb = 0;          // option "covariance_workspace_mb": cap of one chunk's workspace (MiB, fractions allowed), 0 = half the free device memory
+	double covPairsSeconds = 0;         // host-side wall time of the last call (reporting only)
+	int covPairChunks = 0;              // chunks the last call ran in
+	PairWork covPairWork;
+	DevBuf<Scalar> d_pairOut;
+	bool computeCovariancePairs(int n, const int32_t* kindA, const int32_t* indexA, const int32_t* kindB, const int32_t* indexB, double* out);
 
 	struct CoarseJob { cuba_hip_solver* h; int first; bool firstInvCopy; bool ownEvent; };
 	void launchCoarseJobs(std::vector<CoarseJob>& jobs, hipEvent_t common = nullptr);

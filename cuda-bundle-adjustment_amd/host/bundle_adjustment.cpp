@@ -380,6 +380,42 @@ public:
 		if (landmarks) for (int i = 0; i < numFreeLandmarks_; i++) covLmIndex_[activeLandmarks_[i]] = (size_t)i;
 		return true;
 	}
+	bool computeCrossCovariances(const std::vector<CovariancePair>& pairs, std::vector<std::array<double, 36>>& out)
+	{
+		prepareOptimize();            // (as computeCovariances: the estimate on the device is the current one)
+		std::map<const PoseVertex*, int> poseIdx;
+		std::map<const LandmarkVertex*, int> lmIdx;
+		for (size_t i = 0; i < activePoses_.size(); i++) poseIdx[activePoses_[i]] = (int)i;
+		for (size_t i = 0; i < activeLandmarks_.size(); i++) lmIdx[activeLandmarks_[i]] = (int)i;
+		const size_t n = pairs.size();
+		std::vector<int32_t> kind[2], index[2];
+		for (int s = 0; s < 2; s++) { kind[s].resize(std::max<size_t>(n, 1)); index[s].resize(std::max<size_t>(n, 1)); }
+		for (size_t k = 0; k < n; k++)
+			for (int s = 0; s < 2; s++)
+			{
+				const CovarianceVertex& v = s ? pairs[k].second : pairs[k].first;
+				if (v.pose)
+				{
+					const auto it = poseIdx.find(v.pose);
+					if (it == poseIdx.end()) throw std::invalid_argument("cuba::computeCrossCovariances: a pose vertex of pair " + std::to_string(k) + " is not part of the graph");
+					kind[s][k] = CUBA_HIP_VERTEX_POSE; index[s][k] = it->second;
+				}
+				else
+				{
+					const auto it = v.landmark ? lmIdx.find(v.landmark) : lmIdx.end();
+					if (it == lmIdx.end()) throw std::invalid_argument("cuba::computeCrossCovariances: a landmark vertex of pair " + std::to_string(k) + " is not part of the graph");
+					kind[s][k] = CUBA_HIP_VERTEX_LANDMARK; index[s][k] = it->second;
+				}
+			}
+		std::vector<double> blocks(36 * std::max<size_t>(n, 1), 0.0);
+		int notPd = 0;
+		check(cuba_hip_compute_covariance_pairs(solver_, (int)n, kind[0].data(), index[0].data(), kind[1].data(), index[1].data(), blocks.data(), &notPd),
+			"cuba_hip_compute_covariance_pairs");
+		if (notPd) return false;
+		out.resize(n);
+		for (size_t k = 0; k < n; k++) std::copy(blocks.begin() + 36 * k, blocks.begin() + 36 * (k + 1), out[k].begin());
+		return true;
+	}
 	bool poseCovariance(const PoseVertex* v, double out[36]) const { return covBlock(covPoseIndex_, poseCov_, v, 36, out); }
 	bool landmarkCovariance(const LandmarkVertex* v, double out[9]) const { return covBlock(covLmIndex_, lmCov_, v, 9, out); }
 
@@ -639,6 +675,13 @@ bool computeCovariances(CudaBundleAdjustment* object, bool landmarks)
 	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
 	if (!impl) throw std::runtime_error("cuba::computeCovariances: not an object of this library");
 	return impl->computeCovariances(landmarks);
+}
+
+bool computeCrossCovariances(CudaBundleAdjustment* object, const std::vector<CovariancePair>& pairs, std::vector<std::array<double, 36>>& out)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (!impl) throw std::runtime_error("cuba::computeCrossCovariances: not an object of this library");
+	return impl->computeCrossCovariances(pairs, out);
 }
 
 bool poseCovariance(const CudaBundleAdjustment* object, const PoseVertex* v, double cov[36])

@@ -15,7 +15,10 @@
 // initialize()/optimize() instead of being printed and ignored (ref src/macro.h:22-27).
 #pragma once
 
+#include <array>
 #include <cstddef>
+#include <utility>
+#include <vector>
 
 #include "ba_types.hpp"
 
@@ -87,5 +90,22 @@ void optimizeBatch(CudaBundleAdjustment* const* objects, int n, int niterations)
 bool computeCovariances(CudaBundleAdjustment* object, bool landmarks);
 bool poseCovariance(const CudaBundleAdjustment* object, const PoseVertex* v, double cov[36]);
 bool landmarkCovariance(const CudaBundleAdjustment* object, const LandmarkVertex* v, double cov[9]);
+
+// Covariance blocks of arbitrary vertex pairs (include/cuba_hip.h, cuba_hip_compute_covariance_pairs): any two vertices, co-visible or
+// not -- the drift of the last pose against the first, loop-closure gates, pose-landmark and landmark-landmark cross terms.  A
+// CovarianceVertex names a PoseVertex or a LandmarkVertex of the object; out[k] receives pair k's dim(a) x dim(b) block of the same
+// inverse as computeCovariances (6 for a pose, 3 for a landmark; rows from a, columns from b, column-major with leading dimension
+// dim(a), the rest zero; zero for a fixed vertex).  Self-contained (no earlier computeCovariances needed).  Returns false, out
+// untouched, when the Hessian is not positive definite; a vertex that is not part of the object throws std::invalid_argument, other
+// refusals (fp32 library, a factor beyond device memory) throw std::runtime_error.  The object's next optimize() is unaffected.
+struct CovarianceVertex
+{
+	const PoseVertex* pose = nullptr;
+	const LandmarkVertex* landmark = nullptr;
+	CovarianceVertex(const PoseVertex* v) : pose(v) {}
+	CovarianceVertex(const LandmarkVertex* v) : landmark(v) {}
+};
+using CovariancePair = std::pair<CovarianceVertex, CovarianceVertex>;
+bool computeCrossCovariances(CudaBundleAdjustment* object, const std::vector<CovariancePair>& pairs, std::vector<std::array<double, 36>>& out);
 
 }  // namespace cuba

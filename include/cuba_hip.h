@@ -44,6 +44,8 @@ typedef enum cuba_hip_status
 /* robust kernel kinds / edge types: include/cuda_bundle_adjustment_types.h:143-148,213-218 */
 enum { CUBA_HIP_ROBUST_NONE = 0, CUBA_HIP_ROBUST_HUBER = 1, CUBA_HIP_ROBUST_TUKEY = 2 };
 enum { CUBA_HIP_EDGE_MONOCULAR = 0, CUBA_HIP_EDGE_STEREO = 1 };
+/* vertex kinds of cuba_hip_compute_covariance_pairs */
+enum { CUBA_HIP_VERTEX_POSE = 0, CUBA_HIP_VERTEX_LANDMARK = 1 };
 
 /* profile buckets, same order and meaning as CudaBlockSolver::ProfileItem (src/cuda_bundle_adjustment.cpp:77-88).
    Bucket 5 ("symbolic decomposition") holds the reduced-system structure analysis, bucket 6
@@ -341,6 +343,23 @@ int cuba_hip_compute_covariance(cuba_hip_solver* s, double* pose_cov, double* la
 /* The cross blocks of the last cuba_hip_compute_covariance (g2o's computeMarginals block set), values[36 nblk], in the layout and
    numbering of cuba_hip_get_hsc_structure.  CUBA_HIP_ERR_STATE before a successful computation and after cuba_hip_set_graph. */
 int cuba_hip_get_covariance_blocks(cuba_hip_solver* s, double* values);
+/* Covariance blocks of ARBITRARY vertex pairs (g2o's computeMarginals with any block list): pair k is (kind_a[k], index_a[k]) against
+   (kind_b[k], index_b[k]), kinds CUBA_HIP_VERTEX_POSE / CUBA_HIP_VERTEX_LANDMARK, indices in the caller's numbering; any two vertices, not
+   only co-visible ones (the drift of the last pose against the first, loop-closure gating, pose-landmark and landmark-landmark terms).
+   out[36 n]: pair k's dim(a) x dim(b) block of the inverse of the undamped Hessian (the matrix cuba_hip_compute_covariance inverts), rows
+   from a, columns from b, column-major with leading dimension dim(a) (6 for a pose, 3 for a landmark); the rest of the 36 numbers is zero.
+   A fixed vertex on either side gives a zero block.  The call is self-contained: it linearises at lambda = 0, factorises the reduced
+   matrix S with the exact solver's plan and solves S X = C for the right-hand sides of the right vertices, on the elimination-tree paths
+   the request touches only; it needs no earlier cuba_hip_compute_covariance.  The side with fewer distinct vertices
+   is solved for (pose 0 against every pose: one right-hand-side block) and the blocks are transposed back.  Right-hand sides go in chunks
+   sized against free device memory (option "covariance_workspace_mb" caps a chunk; 0 = automatic); a workspace above 64 MiB is freed at
+   the end of the call.  A non-positive pivot returns CUBA_HIP_OK
+   with *not_positive_definite = 1 and out untouched.  A later cuba_hip_optimize runs bit for bit as if the call had not happened.
+   Refusals (the handle stays usable): those of cuba_hip_compute_covariance, a chunk of one block that does not fit
+   CUBA_HIP_ERR_RUNTIME, and a bad kind or an index out of range CUBA_HIP_ERR_INVALID_ARGUMENT (checked before any device work).
+   Counters "covariance_pairs_ns": the last call's time, "covariance_pairs_chunks": the chunks it ran in. */
+int cuba_hip_compute_covariance_pairs(cuba_hip_solver* s, int n, const int32_t* kind_a, const int32_t* index_a, const int32_t* kind_b,
+	const int32_t* index_b, double* out, int* not_positive_definite);
 
 /* ---- introspection (parity tests) and multi-GPU plumbing ------------------------------------------ */
 
@@ -419,6 +438,20 @@ int cuba_hip_debug_selected_inverse(int device, int n, const double* A, double* 
    *count = length of the array; out may be NULL to ask for it.  A malformed pattern (row_ptr[0] != 0, a row without its diagonal block
    first, columns not strictly increasing or not below n_poses) is CUBA_HIP_ERR_INVALID_ARGUMENT. */
 int cuba_hip_debug_sparse_plan(int n_poses, const int32_t* row_ptr, const int32_t* col_ind, int slack, int which, int32_t* out, size_t capacity, size_t* count);
+/* Test hook for cuba_hip_compute_covariance_pairs' kernels on a given matrix (as cuba_hip_debug_selected_inverse): pair k is the 6 x 6
+   block (block_i[k], block_j[k]) of A^-1, column-major into out[36 k], whether or not it lies on the pattern.  Fill, factorisation, fail
+   flag, then the pair calls of the handle with every block index read as a free pose.  A matrix that is not positive definite:
+   CUBA_HIP_OK, *not_positive_definite = 1, out all zero.  stats (optional) as above.  No solver handle involved. */
+int cuba_hip_debug_inverse_blocks(int device, int n, const double* A, int n_pairs, const int32_t* block_i, const int32_t* block_j, double* out,
+	int* not_positive_definite, int slack, int32_t stats[4]);
+/* The pair solve's symbolic phase alone, on the host (no device needed), for the pattern of cuba_hip_debug_sparse_plan and the pose pairs
+   (block_i[k], block_j[k]) as cuba_hip_debug_inverse_blocks packs them, all blocks in one chunk.  which: 0 header {blocks, slots, forward
+   records, forward gather entries, backward records, backward gather entries}, 1 pairs (4 ints per pair {block, column of j, 0, 0}),
+   2 fwdPtr, 3 fwdCols, 4 bwdPtr, 5 bwdCols, 6 slotPtr, 7 slotCols, 8 fLvlPtr, 9 fRec (4 ints {slot, column, first entry, entries}),
+   10 fGather (2 ints {tile, slot}), 11 bLvlPtr, 12 bRec, 13 bGather (PairPlan in csrc/ba_kernels.hpp).  Malformed patterns as for
+   cuba_hip_debug_sparse_plan, and block indices outside [0, n_poses), are CUBA_HIP_ERR_INVALID_ARGUMENT. */
+int cuba_hip_debug_pair_plan(int n_poses, const int32_t* row_ptr, const int32_t* col_ind, int slack, int n_pairs, const int32_t* block_i,
+	const int32_t* block_j, int which, int32_t* out, size_t capacity, size_t* count);
 
 /* A driver that runs the Levenberg-Marquardt loop itself through the stage calls announces the start of a run (a new lambda_0):
    the coarse inverse of the two-level preconditioner and the iteration-count predictions of the previous run are dropped, as
