@@ -148,6 +148,8 @@ def load_library(precision="f64"):
     lib.cuba_hip_debug_pair_plan.argtypes = [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, _ip, _ip, C.c_int,
                                              C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)]
     lib.cuba_hip_debug_pair_plan.restype = C.c_int
+    lib.cuba_hip_debug_pcg_config.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.cuba_hip_debug_pcg_config.restype = C.c_int
     lib.cuba_hip_last_error.argtypes = [H]
     lib.cuba_hip_last_error.restype = C.c_char_p
     lib.cuba_hip_version.restype = C.c_char_p
@@ -506,6 +508,19 @@ class HipSolver:
         it = np.zeros(max(n.value, 1), dtype=np.int32)
         self._ck(self.lib.cuba_hip_get_pcg_history(self.h, it.ctypes.data_as(_ip), n.value, C.byref(n), C.byref(bad)))
         return it[:n.value], int(bad.value)
+
+    def pcg_config(self):
+        """The PCG configuration in force (cuba_hip_debug_pcg_config): a dict of agg, cl, nc, spmv_rows, upper, ell_m, ell_over,
+        coarse_fp32, rows_ept, and pose_order (the caller's index of every free pose in the solver's internal order)."""
+        cfg = (C.c_int32 * 9)()
+        n = C.c_size_t()
+        self._ck(self.lib.cuba_hip_debug_pcg_config(self.h, cfg, None, 0, C.byref(n)))
+        order = np.zeros(max(n.value, 1), dtype=np.int32)
+        self._ck(self.lib.cuba_hip_debug_pcg_config(self.h, cfg, order.ctypes.data_as(_ip), n.value, C.byref(n)))
+        keys = ("agg", "cl", "nc", "spmv_rows", "upper", "ell_m", "ell_over", "coarse_fp32", "rows_ept")
+        out = {k: int(v) for k, v in zip(keys, cfg)}
+        out["pose_order"] = order[:n.value]
+        return out
 
     def array(self, name):
         n = C.c_size_t()

@@ -201,6 +201,7 @@ void launch_pcg2_fused(const DeviceGraph& g, const DeviceSystem& sys, int k, int
 // one iteration of the upper-triangle form (sys.upper): which = 1 SpMV | 2 row updates | 4 preconditioner (7 = all three, in this order)
 int spmv_upper_grid(int Pf);      // workgroups of the upper-triangle SpMV (= its p.Ap partials)
 int pcg_rows_max_aggregate();     // largest aggregate (poses) the row-update launch of the upper-triangle iteration handles
+int pcg_rows_entries_per_thread(const DeviceSystem& sys);   // row entries per thread of that launch for sys.agg: 2, 4 or 8
 void launch_build_lowpos(const DeviceGraph& g, const DeviceStructure& st, int* lowpos, hipStream_t s);
 void launch_pcg_upper_iteration(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, int k, int maxIter, Scalar tol2, hipStream_t s, int which = 7);
 // what the last node of an iteration graph does, as a launch: advance the iteration offset by n, run the stop test on the residual the

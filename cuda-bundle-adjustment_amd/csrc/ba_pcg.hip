@@ -1197,10 +1197,15 @@ __global__ __launch_bounds__(ROWS_T) void pcg_rows_kernel(DeviceGraph g, DeviceS
 }
 
 typedef void (*PcgRowsKernel)(DeviceGraph, DeviceStructure, DeviceSystem, int, int, Scalar);
-static PcgRowsKernel pcg_rows_kernel_for(const DeviceSystem& sys)
+int pcg_rows_entries_per_thread(const DeviceSystem& sys)
 {
 	const int entries = 6 * sys.agg;
-	return entries <= 2 * ROWS_T ? pcg_rows_kernel<2> : entries <= 4 * ROWS_T ? pcg_rows_kernel<4> : pcg_rows_kernel<8>;
+	return entries <= 2 * ROWS_T ? 2 : entries <= 4 * ROWS_T ? 4 : 8;
+}
+static PcgRowsKernel pcg_rows_kernel_for(const DeviceSystem& sys)
+{
+	const int ept = pcg_rows_entries_per_thread(sys);
+	return ept == 2 ? pcg_rows_kernel<2> : ept == 4 ? pcg_rows_kernel<4> : pcg_rows_kernel<8>;
 }
 int pcg_rows_max_aggregate() { return ROWS_MAX_AGG; }
 
@@ -1239,14 +1244,15 @@ static bool spmv_wants_occupancy(const DeviceGraph& g) { return 2 * (long long)g
 int spmv_rows_for(int Pf)
 {
 	return 2 * (long long)Pf > 3 * 1024 ? 4 : 2;
-}                            // (the 4-row workgroup needs the 128-VGPR instantiation)
+}
 // large graphs (4 rows per workgroup): one wave per block row; small ones: two waves per row, 2 rows per workgroup
 // (measured: S2M 17.0 -> 15.6 us, G4M 28.5 -> 25.0 us with the row-per-wave kernel; at KITTI-00 size 7.1 vs 5.9 us)
+// (a graph with 2 rows per workgroup never wants the 128-VGPR occupancy instantiation: spmv_rows_for and spmv_wants_occupancy are the
+// same test, so only the batched launch, whose row count spans several graphs, uses pcg_spmv_batch_kernel<2, 4>)
 static bool spmv_row_per_wave(const DeviceSystem& sys) { return sys.spmv_rows >= 4; }
-static void* spmv_kernel_for(const DeviceGraph& g, const DeviceSystem& sys)
+static void* spmv_kernel_for(const DeviceGraph&, const DeviceSystem& sys)
 {
-	if (sys.spmv_rows == 4) return (void*)pcg_spmv_row_kernel<4>;
-	return spmv_wants_occupancy(g) ? (void*)pcg_spmv_kernel<2, 4> : (void*)pcg_spmv_kernel<2, 1>;
+	return sys.spmv_rows == 4 ? (void*)pcg_spmv_row_kernel<4> : (void*)pcg_spmv_kernel<2, 1>;
 }
 static dim3 spmv_block_for(const DeviceSystem& sys) { return dim3((spmv_row_per_wave(sys) ? 64 : 128) * sys.spmv_rows); }
 

@@ -891,6 +891,22 @@ int cuba_hip_debug_sparse_plan(int n_poses, const int32_t* row_ptr, const int32_
 	catch (...) { key.clear(); selValid = false; return CUBA_HIP_ERR_RUNTIME; }
 }
 
+// The PCG configuration in force (read-only): {agg, cl, nc, spmv_rows, upper, ell_m, ell_over, coarse inverse stored in fp32, row entries
+// per thread of the upper-triangle row update (0 when that iteration is off)}, and the internal order of the free poses
+int cuba_hip_debug_pcg_config(cuba_hip_solver* s, int32_t cfg[9], int32_t* pose_order, size_t capacity, size_t* count)
+{
+	return guarded(s, [&] {
+		if (!cfg) throw ArgError{ "null output" };
+		s->need();
+		const DeviceSystem& y = s->sys;
+		const int32_t v[9] = { y.agg, y.cl, y.nc, y.spmv_rows, y.upper, s->st.ell_m, s->st.ell_over, y.acinv32 != nullptr ? 1 : 0,
+			y.upper ? pcg_rows_entries_per_thread(y) : 0 };
+		std::memcpy(cfg, v, sizeof v);
+		if (count) *count = s->poseOldOfNew.size();
+		if (pose_order) std::memcpy(pose_order, s->poseOldOfNew.data(), sizeof(int32_t) * std::min(capacity, s->poseOldOfNew.size()));
+	});
+}
+
 int cuba_hip_begin_run(cuba_hip_solver* s)
 {
 	return guarded(s, [&] { s->need(); s->coarseValid = false; s->startRunHistory(); });

@@ -453,6 +453,15 @@ int cuba_hip_debug_inverse_blocks(int device, int n, const double* A, int n_pair
 int cuba_hip_debug_pair_plan(int n_poses, const int32_t* row_ptr, const int32_t* col_ind, int slack, int n_pairs, const int32_t* block_i,
 	const int32_t* block_j, int which, int32_t* out, size_t capacity, size_t* count);
 
+/* Test hook, read-only: the PCG configuration in force after the option rules (aggregate widening, constant coarse functions, the
+   block-Jacobi fallback, the automatic upper-triangle rule, the fp64 repeat of a solve that broke down with the fp32-stored coarse inverse).
+   cfg = {pcg_aggregate (0 = block-Jacobi only), coarse functions per aggregate and pose component (1 or 2), aggregates, block rows per SpMV
+   workgroup (2 or 4), upper-triangle iteration (0 / 1), fixed-width row levels (20 entries each), some row wider than those (0 / 1),
+   coarse inverse stored in fp32 (0 / 1), row entries per thread of the upper-triangle row update (2, 4, 8; 0 when that iteration is
+   off)}.  pose_order[i] = the caller's index of the i-th free pose in the solver's internal order (aggregates are runs of consecutive
+   internal indices); *count = Pf, pose_order may be NULL. */
+int cuba_hip_debug_pcg_config(cuba_hip_solver* s, int32_t cfg[9], int32_t* pose_order, size_t capacity, size_t* count);
+
 /* A driver that runs the Levenberg-Marquardt loop itself through the stage calls announces the start of a run (a new lambda_0):
    the coarse inverse of the two-level preconditioner and the iteration-count predictions of the previous run are dropped, as
    cuba_hip_optimize does at its start; a hand-over to the exact reduced solve that an earlier run made (option "direct_fallback")

@@ -484,10 +484,8 @@ def test_duplicate_observations_of_one_pose(solvers):
     assert len(chi2) == 6 and np.all(np.diff(chi2) < 0)
 
 
-def test_block_rows_wider_than_the_fixed_width_rows(solvers):
-    """One pose co-visible with more than 60 others: its block row leaves the fixed-width part of the SpMV
-    (DeviceStructure::ell_over).  PCG solution vs the oracle's exact Cholesky, and the LM trajectory."""
-    HipSolver, OracleSolver = solvers
+def hub_graph():
+    """synth_ba(150, ...) plus far landmarks that make pose 75 co-visible with more than 60 others"""
     from scipy.spatial.transform import Rotation
     g = copy.deepcopy(synth_ba(150, 3000, 12000, seed=8))
     rng = np.random.default_rng(3)
@@ -513,7 +511,14 @@ def test_block_rows_wider_than_the_fixed_width_rows(solvers):
     g.mono_vp = np.concatenate([g.mono_vp, np.full(len(pick), hub)]); g.mono_vl = np.concatenate([g.mono_vl, g.lm_ids[pick]])
     g.mono_meas = np.concatenate([g.mono_meas, np.stack([u, v], 1) + rng.normal(0, 1, (len(pick), 2))])
     g.mono_info = np.concatenate([g.mono_info, np.ones(len(pick))])
-    fp = flatten(g)
+    return g
+
+
+def test_block_rows_wider_than_the_fixed_width_rows(solvers):
+    """One pose co-visible with more than 60 others: its block row leaves the fixed-width part of the SpMV
+    (DeviceStructure::ell_over).  PCG solution vs the oracle's exact Cholesky, and the LM trajectory."""
+    HipSolver, OracleSolver = solvers
+    fp = flatten(hub_graph())
     o = OracleSolver(fp, RK_HUBER); o.compute_errors(); o.build_system()
     lam = 1e-6 * o.max_diagonal()
     o.set_lambda(lam); assert o.solve()
