@@ -29,6 +29,12 @@ Next to `value` the line carries
                  PCG iterations, chi2 max-rel-diff against the oracle (live for kitti07, the committed
                  tests/golden/baseline_shapes_chi2.json for all).
 
+A plain run prints the headline only: it sets up, takes the warm-up iteration and the --warmup steps, times the --steps steps, writes
+--dump-outputs if asked and prints the line (`value`, `ms_per_step` and the counters of the timed region).  Everything else named here
+-- the parity check against the committed oracle trajectories (`rank_parity`), `repeats`, `value_replay`, `heuristics_off`, `roofline`,
+`exact_solve`, `shapes`, `float32`, `concurrent`, `cpu_baseline`, `contract_wall`, the citation of the reference's kernels and, for N > 1,
+the `partitioned` leg -- runs only with --full.
+
 N = 1 : BASELINE.json configs[1] -- ba_kitti_00 shape (1332 poses / 133383 landmarks / 561116 edges,
         synthetic stand-in, seed 0), fp64, Huber kernels as in samples/sample_comparison_with_g2o.cpp:195-200.
 N > 1 : configs[3] -- one independent KITTI-00-sized graph per GPU (seeds 100+rank), no data-path
@@ -543,13 +549,17 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--shape", default="kitti00")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the C++-API leg (the reference's sample protocol)")
-    ap.add_argument("--no-shapes", action="store_true", help="skip the kitti07 / s2m / g4m legs (N = 1 only)")
-    ap.add_argument("--repeats", type=int, default=5, help="further timed blocks of --steps steps for the median / min / max")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline: parity against the committed oracle trajectories, repeats, "
+                         "replay and heuristics-off protocols, roofline, exact solve, other shapes, fp32, concurrent handles, CPU "
+                         "baseline, the C++-API wall and (N > 1) the landmark-partitioned leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the oracle parity leg")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: skip the C++-API leg (the reference's sample protocol)")
+    ap.add_argument("--no-shapes", action="store_true", help="with --full: skip the kitti07 / s2m / g4m legs (N = 1 only)")
+    ap.add_argument("--repeats", type=int, default=5, help="with --full: further timed blocks of --steps steps for the median / min / max")
     ap.add_argument("--concurrent-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--concurrent-counts", default="2,4", help=argparse.SUPPRESS)
-    ap.add_argument("--no-concurrent", action="store_true", help="skip the concurrent-handles leg (N = 1 only)")
+    ap.add_argument("--no-concurrent", action="store_true", help="with --full: skip the concurrent-handles leg (N = 1 only)")
     ap.add_argument("--partition", action="store_true",
                     help="N>1: ONE graph, landmark-partitioned over the ranks with an RCCL all-reduce of [Hsc|bsc|bp] "
                          "per trial (BASELINE config 5, strong scaling) instead of one independent graph per GPU")
@@ -630,18 +640,21 @@ def main():
         except (OSError, KeyError):
             pass
         return None
-    parity = {"rank": rank, "seed": seed, "chi2_max_rel_diff_vs_golden": None}
-    gold = golden_chi2()
-    got0 = optimize(LM_RUN)
-    if gold is not None and len(gold) == len(got0):
-        parity["chi2_max_rel_diff_vs_golden"] = float(np.max(np.abs(got0 - np.array(gold)) / np.array(gold)))
-    parity["chi2_last"] = float(got0[-1]) if len(got0) else None
-    solver.set_state(fp.q, fp.t, fp.Xw)
+    parity = None
+    if args.full:
+        parity = {"rank": rank, "seed": seed, "chi2_max_rel_diff_vs_golden": None}
+        gold = golden_chi2()
+        got0 = optimize(LM_RUN)
+        if gold is not None and len(gold) == len(got0):
+            parity["chi2_max_rel_diff_vs_golden"] = float(np.max(np.abs(got0 - np.array(gold)) / np.array(gold)))
+        parity["chi2_last"] = float(got0[-1]) if len(got0) else None
+        solver.set_state(fp.q, fp.t, fp.Xw)
     # the reference protocol's warm-up: one LM iteration from the initial guess moves the estimates; the timed runs of
     # optimize(10) start from there (sample_comparison_with_g2o.cpp:303-307) -- each from its own perturbation of that estimate
     optimize(1)
     q0, t0, X0 = solver.state()
-    total_runs = (args.warmup + LM_RUN - 1) // LM_RUN + (1 + max(0, args.repeats)) * ((args.steps + LM_RUN - 1) // LM_RUN)
+    repeats = max(0, args.repeats) if args.full else 0
+    total_runs = (args.warmup + LM_RUN - 1) // LM_RUN + (1 + repeats) * ((args.steps + LM_RUN - 1) // LM_RUN)
     nslots = prepare_slots(solver, fp, (q0, t0, X0), max(2, min(48, total_runs)), seed=1000 + rank)
     next_slot = [0]
 
@@ -697,38 +710,39 @@ def main():
     c1 = counters()
     outputs = timed_outputs(chi2, *solver.state()) if args.dump_outputs and rank == 0 else None
 
-    # the same block again, `--repeats` times (further perturbed starts): spread of the measurement (`value` stays the block above)
-    block_ms = [timed_block(args.steps)[0] * 1e3 for _ in range(max(0, args.repeats))]
+    if args.full:
+        # the same block again, `--repeats` times (further perturbed starts): spread of the measurement (`value` stays the block above)
+        block_ms = [timed_block(args.steps)[0] * 1e3 for _ in range(repeats)]
 
-    # ---- the protocol of rounds 1-3 beside it (every run from the SAME estimate), and both protocols with the three replay-exact
-    # heuristics switched off: what they are worth, in the driver's line
-    run_steps(LM_RUN, replay=True)
-    replay_s, _ = timed_block(args.steps, replay=True)
-    for k in HEURISTICS:
-        solver.set_option(k, 0)
-    run_steps(LM_RUN)
-    hoff_s, _ = timed_block(args.steps)
-    run_steps(LM_RUN, replay=True)
-    hoff_replay_s, _ = timed_block(args.steps, replay=True)
-    for k in HEURISTICS:
-        solver.set_option(k, 1)
-    rank_parity = [parity]
-    if dist is not None:
-        rank_parity = [None] * world
-        dist.all_gather_object(rank_parity, parity)
+        # ---- the protocol of rounds 1-3 beside it (every run from the SAME estimate), and both protocols with the three replay-exact
+        # heuristics switched off: what they are worth, in the driver's line
+        run_steps(LM_RUN, replay=True)
+        replay_s, _ = timed_block(args.steps, replay=True)
+        for k in HEURISTICS:
+            solver.set_option(k, 0)
+        run_steps(LM_RUN)
+        hoff_s, _ = timed_block(args.steps)
+        run_steps(LM_RUN, replay=True)
+        hoff_replay_s, _ = timed_block(args.steps, replay=True)
+        for k in HEURISTICS:
+            solver.set_option(k, 1)
+        rank_parity = [parity]
+        if dist is not None:
+            rank_parity = [None] * world
+            dist.all_gather_object(rank_parity, parity)
 
     pcg_iters = c1["pcg_iterations"] - c0["pcg_iterations"]
     trials = c1["lm_trials"] - c0["lm_trials"]
     E = fp.E
     graphs = 1 if partitioned else world
     value = E * args.steps * graphs / elapsed
+    nblk = c1["hsc_blocks"]
 
     out = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline leg: per-kernel device time from HIP events on the solver's stream ------------
         solver.set_state(q0, t0, X0)
         kt = solver.time_kernels(reps=20)
-        nblk = c1["hsc_blocks"]
         nc = 0 if kt["coarse_setup"] == 0 else c1["coarse_dim"] / 6.0        # algorithmic_bytes() takes the coarse dimension / 6
         alg = algorithmic_bytes(fp, nblk, nc, upper=kt.get("pcg_precond", 0) > 0 and kt.get("coarse_setup", 0) > 0)
         launches = {"residual_chi2": trials + args.steps, "linearize_schur": trials, "pcg_spmv": pcg_iters,
@@ -780,6 +794,7 @@ def main():
                 "traffic_source": os.path.basename(pmc_path) if traffic else None, "rocprof_source": ev["stats_file"],
                 "traffic_stale": traffic_stale, "kernel_source_sha16": source_sha16(),
                 "kernels": kernels, "path": path}
+    if rank == 0:
         out = {
             "metric": "edges/sec (edge-iterations/s = E x LM iterations / wall, graph resident in HBM, every timed 10-iteration run from its own "
                       "perturbed start) + 10-iter LM wall-clock (contract_wall: initialize()+optimize(10) after warm-up, C++ API) on KITTI-00-shaped "
@@ -804,19 +819,23 @@ def main():
             "final_chi2": float(chi2[-1]),
             "protocol": {"timed_runs": "each optimize(%d) from its own seeded perturbation of the warm state" % LM_RUN, **PERTURB,
                          "distinct_starts": nslots},
-            "value_replay": E * args.steps * graphs / replay_s, "ms_per_step_replay": replay_s * 1e3 / args.steps,
-            "heuristics_off": {"options": {k: 0 for k in HEURISTICS}, "value": E * args.steps * graphs / hoff_s,
-                               "ms_per_step": hoff_s * 1e3 / args.steps, "value_replay": E * args.steps * graphs / hoff_replay_s,
-                               "ms_per_step_replay": hoff_replay_s * 1e3 / args.steps},
-            "rank_parity": rank_parity,
-            "repeats": ({"blocks": len(block_ms), "steps_per_block": args.steps, "ms_per_step_median": float(np.median(block_ms)) / args.steps,
-                         "ms_per_step_min": min(block_ms) / args.steps, "ms_per_step_max": max(block_ms) / args.steps,
-                         "value_median": E * args.steps * graphs / (float(np.median(block_ms)) * 1e-3)} if block_ms else None),
-            "roofline": roof,
-            "reference_kernels_on_mi355x": reference_kernels_citation() if world == 1 else None,
         }
+        if args.full:
+            out.update({
+                "value_replay": E * args.steps * graphs / replay_s, "ms_per_step_replay": replay_s * 1e3 / args.steps,
+                "heuristics_off": {"options": {k: 0 for k in HEURISTICS}, "value": E * args.steps * graphs / hoff_s,
+                                   "ms_per_step": hoff_s * 1e3 / args.steps, "value_replay": E * args.steps * graphs / hoff_replay_s,
+                                   "ms_per_step_replay": hoff_replay_s * 1e3 / args.steps},
+                "rank_parity": rank_parity,
+                "repeats": ({"blocks": len(block_ms), "steps_per_block": args.steps, "ms_per_step_median": float(np.median(block_ms)) / args.steps,
+                             "ms_per_step_min": min(block_ms) / args.steps, "ms_per_step_max": max(block_ms) / args.steps,
+                             "value_median": E * args.steps * graphs / (float(np.median(block_ms)) * 1e-3)} if block_ms else None),
+                "roofline": roof,
+                "reference_kernels_on_mi355x": reference_kernels_citation() if world == 1 else None,
+            })
         if outputs is not None:
             out["dump_outputs"] = write_outputs(args.dump_outputs, outputs)
+    if rank == 0 and args.full:
         # the GPU side of the parity leg, then this handle goes: several live handles share the runtime's few hardware queues and
         # slow each other down (a KITTI-07-sized graph runs at half speed as the second handle of a process)
         got = None
@@ -878,7 +897,7 @@ def main():
     # over the ranks by the native driver with RCCL all-reduces -- and report it inside the same line as `partitioned`.  It is the
     # first place a multi-rank RCCL communicator of this library runs, so it is fenced: a watchdog on every rank prints the line
     # without it and exits if the leg has not finished in time; any exception just drops the object.
-    if world > 1 and not partitioned and os.environ.get("CUBA_BENCH_PARTITION_LEG", "1") != "0":
+    if args.full and world > 1 and not partitioned and os.environ.get("CUBA_BENCH_PARTITION_LEG", "1") != "0":
         import threading
         solver.close()                 # (one live handle per process: see above)
 

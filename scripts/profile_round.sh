@@ -27,8 +27,8 @@ for shp in s2m g4m; do
   rm -rf $out/${tag}_${shp}_pmc_FETCH_SIZE $out/${tag}_${shp}_pmc_WRITE_SIZE $out/${tag}_${shp}_stats      # (raw counter dumps of the large shapes: hundreds of MB)
 done
 cp $out/${tag}_kitti00_kernel_stats.csv profiles/
-python bench.py --steps 50 --warmup 10 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python bench.py --steps 50 --warmup 10 --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 # the same command under the tracer (main leg only): its per-kernel averages must agree with the line's HIP-event times
-(cd /tmp && run rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_bench_stats -- python $root/bench.py --steps 50 --warmup 10 --no-shapes --no-end-to-end > $out/${tag}_bench_stats.log 2>&1)
+(cd "$TMPDIR" && run rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_bench_stats -- python $root/bench.py --steps 50 --warmup 10 --full --no-shapes --no-end-to-end > $out/${tag}_bench_stats.log 2>&1)
 f=$(find $out/${tag}_bench_stats -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp "$f" $out/${tag}_bench_py_kernel_stats.csv
 tail -c 600 $out/${tag}_bench.json
