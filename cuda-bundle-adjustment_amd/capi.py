@@ -122,6 +122,8 @@ def load_library(precision="f64"):
         "cuba_hip_compute_covariance": [H, _dp, _dp, C.POINTER(C.c_int)],
         "cuba_hip_get_covariance_blocks": [H, _dp],
         "cuba_hip_compute_covariance_pairs": [H, C.c_int, _ip, _ip, _ip, _ip, _dp, C.POINTER(C.c_int)],
+        "cuba_hip_set_pose_priors": [H, C.c_int, _ip, _dp, _dp, _dp],
+        "cuba_hip_prior_chi_squares": [H, _dp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -382,6 +384,7 @@ class HipSolver:
         landmark_range = (begin, end): cuba_hip_set_graph_partition -- the upload of one rank of a landmark partition, which sends the
         measurements and information of its own landmarks' edges only."""
         self.fp = fp
+        self._n_priors = 0              # (every upload clears the pose priors)
         q, t, cam, Xw = (np.ascontiguousarray(a, dtype=np.float64) for a in (fp.q, fp.t, fp.cam, fp.Xw))
         eP = np.ascontiguousarray(fp.eP, dtype=np.int32)
         eL = np.ascontiguousarray(fp.eL, dtype=np.int32)
@@ -476,6 +479,24 @@ class HipSolver:
         out = np.zeros(self.fp.E)
         self._ck(self.lib.cuba_hip_chi_squares(self.h, _d(out)))
         return out
+
+    def set_pose_priors(self, pose, q, t, info):
+        """SE(3) pose priors (cuba_hip_set_pose_priors), replacing the handle's set: pose[n] in the solver numbering, q[n, 4] (x, y, z, w),
+        t[n, 3], info[n, 6, 6] in the [omega, upsilon] order of the pose update (symmetric).  An empty pose list clears the set."""
+        pose = np.ascontiguousarray(pose, dtype=np.int32).reshape(-1)
+        n = len(pose)
+        q = np.ascontiguousarray(q, dtype=np.float64).reshape(n, 4)
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(n, 3)
+        # (column-major 6 x 6 blocks: the transpose of the row-major reading)
+        info = np.ascontiguousarray(np.asarray(info, dtype=np.float64).reshape(n, 6, 6).transpose(0, 2, 1))
+        self._ck(self.lib.cuba_hip_set_pose_priors(self.h, n, pose.ctypes.data_as(_ip), _d(q), _d(t), _d(info)))
+        self._n_priors = n
+
+    def prior_chi_squares(self):
+        """r^T Omega r of every prior at the current estimate, in the order they were given (0 for priors on fixed poses)"""
+        out = np.zeros(max(getattr(self, "_n_priors", 0), 1))
+        self._ck(self.lib.cuba_hip_prior_chi_squares(self.h, _d(out)))
+        return out[:getattr(self, "_n_priors", 0)]
 
     def chi_squares_two_step(self):
         """cuba_hip_chi_squares_begin / _end (the C++ layer does its write-back between the two)"""

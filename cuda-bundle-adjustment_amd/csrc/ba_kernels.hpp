@@ -1,4 +1,4 @@
-// ba_kernels.hpp -- launch interface of the gfx950 kernels (implemented in ba_edge.hip, ba_linearize.hip, ba_pcg.hip, ba_coarse.hip).
+// ba_kernels.hpp -- launch interface of the gfx950 kernels (implemented in ba_edge.hip, ba_linearize.hip, ba_pcg.hip, ba_coarse.hip, ba_prior.hip).
 //
 // Device data model (all SoA, fp64 + int32):
 //   poses      q[4*Pt] t[3*Pt] cam[5*Pt]          free poses [0,Pf) first, fixed after
@@ -136,9 +136,29 @@ struct DeviceSystem
 	int* lowpos = nullptr;     // [nblk] position of every off-diagonal block in that order (launch_build_lowpos)
 };
 
+// SE(3) pose priors (ba_prior.hip): r^T Omega r, r = log(T Tbar^-1) in the [omega, upsilon] tangent of the pose update.  Sorted by
+// internal pose (stable: a pose's priors are contiguous and in the caller's order); priors on fixed poses come last and are ignored.
+struct DevicePriors
+{
+	int n = 0;                     // priors
+	int nPoses = 0;                // free poses with priors
+	const int* pose_ptr = nullptr; // [nPoses + 1] range of every such pose in the sorted list
+	const int* pose_id = nullptr;  // [nPoses] its internal pose index
+	const int* pose = nullptr;     // [n] internal pose of every prior (>= Pf: a fixed pose)
+	const Scalar *qbar = nullptr, *tbar = nullptr;   // [4 n] unit quaternions, [3 n]
+	const Scalar* info = nullptr;  // [36 n] column-major
+	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 on fixed poses)
+};
+// J^T Omega J into the diagonal blocks of hsc (upper triangle), -J^T Omega r into bp and (mode 1) bsc, J = J_l(r)^-1: behind the Schur pass
+void launch_prior_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DevicePriors& pr, int mode, hipStream_t s);
+// per-prior chi2 into pr.chi, per-workgroup partial sums into parts[0 .. prior_chi2_parts(&pr))
+void launch_prior_chi2(const DeviceGraph& g, const DevicePriors& pr, Scalar* parts, hipStream_t s);
+int prior_chi2_parts(const DevicePriors* pr);     // 0 for no priors (pr null or empty), at most 64
+
 // residual / robust chi2 over all edges -> sys.slots[0..NSLOT) (must be zeroed by the caller).
 // per_edge (optional, sorted edge order): non-robust omega*|r|^2.
-void launch_residual_chi2(const DeviceGraph& g, Scalar* parts, Scalar* slots, Scalar* per_edge, hipStream_t st);
+// pr (optional): the priors' chi2 partials follow the edges' and are summed with them (the objective F of the LM loop)
+void launch_residual_chi2(const DeviceGraph& g, Scalar* parts, Scalar* slots, Scalar* per_edge, hipStream_t st, const DevicePriors* pr = nullptr);
 
 // mode 0: assemble only (Hpp -> diagonal blocks of hsc, bp, Hll/bl -> lm_sys, max diagonal of Hll)
 // mode 1: full linearise + Schur reduction with damping lambda (hsc, bsc, bp, inv(Hll+lambda)/bl -> lm_sys)
@@ -165,9 +185,10 @@ void launch_pose_scale(const DeviceGraph& g, const DeviceSystem& sys, Scalar lam
 // [q | t | Xw] made before the trial: the pass reads the pre-update estimate from it while it writes the updated one), then the sums
 // + report.  trial_tail_parts(): numbers of partial-sum scratch (sys.parts) it needs.
 struct LmDevice;
+// pr (optional): the priors' chi2 at the updated poses, a launch between the edge pass and the sums; its partials join the edges' chi2 partials
 void launch_trial_tail_fused(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, Scalar lambda, const Scalar* old, hipStream_t s,
-	const LmDevice* decide = nullptr);
-size_t trial_tail_parts(const DeviceGraph& g, const DeviceStructure& st);
+	const LmDevice* decide = nullptr, const DevicePriors* pr = nullptr);
+size_t trial_tail_parts(const DeviceGraph& g, const DeviceStructure& st, int priorParts = 0);
 // Device-resident LM decision (control flow of CudaBundleAdjustmentImpl::optimize, /root/reference/src/cuda_bundle_adjustment.cpp:816-851):
 // state = {F, lambda, nu, halt, trials, accepted (last trial), rejections in a row, max rejections} in device memory, lam = the damping as
 // the kernels read it (sys.lam_dev), ring = device-mapped host records, LM_REC numbers per trial {Fhat, denominator, rho, next lambda,

@@ -494,6 +494,20 @@ int cuba_hip_compute_covariance_pairs(cuba_hip_solver* s, int n, const int32_t* 
 	});
 }
 
+int cuba_hip_set_pose_priors(cuba_hip_solver* s, int n, const int32_t* pose, const double* q, const double* t, const double* info)
+{
+	return guarded(s, [&] { s->setPosePriors(n, pose, q, t, info); });
+}
+
+int cuba_hip_prior_chi_squares(cuba_hip_solver* s, double* chi2_per_prior)
+{
+	return guarded(s, [&] {
+		if (!s->haveGraph) throw StateError{ "set_graph must be called first" };
+		if (!s->h_priorPose.empty() && !chi2_per_prior) throw ArgError{ "null output" };
+		s->priorChiSquares(chi2_per_prior);
+	});
+}
+
 int cuba_hip_time_kernels(cuba_hip_solver* s, int reps, double ms_per_launch[CUBA_HIP_TIMED_KERNELS])
 {
 	return guarded(s, [&] {
@@ -517,6 +531,7 @@ int cuba_hip_set_partition(cuba_hip_solver* s, int landmark_begin, int landmark_
 			return;
 		}
 		if (landmark_begin < 0 || landmark_end > s->Lt || landmark_begin > landmark_end) throw ArgError{ "bad landmark range" };
+		if (!s->h_priorPose.empty()) throw StateError{ "a landmark partition is not available on a handle with pose priors" };
 		if (s->partHi >= 0 && landmark_begin == s->partLo && landmark_end == s->partHi) return;      // (cuba_hip_set_graph_partition set it already)
 		s->partLo = landmark_begin; s->partHi = landmark_end;
 		s->haveStructure = false;
@@ -923,7 +938,7 @@ int cuba_hip_evaluate_device(cuba_hip_solver* s, double lambda, int with_scale, 
 		s->need();
 		if (!device_scalars3) throw ArgError{ "null output" };
 		s->d_eval.resize(4);
-		launch_residual_chi2(s->g, s->d_parts.data(), s->slotsDev, nullptr, s->stream);
+		launch_residual_chi2(s->g, s->d_parts.data(), s->slotsDev, nullptr, s->stream, s->priors());
 		if (with_scale) launch_pose_scale(s->g, s->sys, lambda, s->slotsDev + 3 * NSLOT, s->stream);
 		launch_collect_eval(s->sys, s->d_eval.data(), s->stream);
 		*device_scalars3 = s->d_eval.data();

@@ -566,7 +566,27 @@ struct cuba_hip_solver
 
 	void ensureHostPattern();
 
-	void need() { if (!haveGraph) throw StateError{ "set_graph must be called first" }; buildStructure(); finishValues(); g.rk[0] = rk[0]; g.rk[1] = rk[1]; st.mixed = mixedPrecision ? 1 : 0; }
+	void need()
+	{
+		if (!haveGraph) throw StateError{ "set_graph must be called first" };
+		buildStructure(); finishValues(); g.rk[0] = rk[0]; g.rk[1] = rk[1]; st.mixed = mixedPrecision ? 1 : 0;
+		if (!h_priorPose.empty() && !priorsUploaded) uploadPriors();
+	}
+
+	// SE(3) pose priors (ba_prior.hip; cuba_hip_set_pose_priors): the caller's set in its own numbering (quaternions normalised,
+	// information symmetrised), and its device copy in the internal pose order -- made by need() once the pose order is known, again
+	// whenever that order changes.  No priors: nothing of it is launched, and every launch and kernel argument is as without this feature.
+	std::vector<int> h_priorPose; std::vector<double> h_priorQ, h_priorT, h_priorInfo;
+	std::vector<int> h_priorOrder;       // sorted position -> caller's prior index
+	bool priorsUploaded = false;
+	DevBuf<int> d_priorInts; DevBuf<Scalar> d_priorVals, d_priorChi;
+	DevicePriors pri;
+	const DevicePriors* priors() const { return h_priorPose.empty() ? nullptr : &pri; }
+	int priorParts() const { return prior_chi2_parts(priors()); }
+	void setPosePriors(int n, const int32_t* pose, const double* q, const double* t, const double* info);
+	void clearPosePriors() { h_priorPose.clear(); h_priorQ.clear(); h_priorT.clear(); h_priorInfo.clear(); h_priorOrder.clear(); priorsUploaded = false; pri = DevicePriors(); }
+	void uploadPriors();
+	void priorChiSquares(double* out);
 
 	double readSlots(int which)
 	{

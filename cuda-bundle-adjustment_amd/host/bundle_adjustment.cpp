@@ -126,6 +126,7 @@ public:
 		if (it == poses_.end()) return;
 		const std::vector<BaseEdge*> incident(it->second->edges.begin(), it->second->edges.end());
 		for (BaseEdge* e : incident) removeEdge(e);
+		priors_.erase(std::remove_if(priors_.begin(), priors_.end(), [&](const PosePrior* p) { return p->vertex == it->second; }), priors_.end());
 		poses_.erase(it);
 		posesDirty_ = true;
 	}
@@ -165,6 +166,7 @@ public:
 	void initialize() override
 	{
 		covPoseIndex_.clear(); covLmIndex_.clear();          // (marginal covariances describe the graph they were computed on)
+		priorsDirty_ = true;                                 // (the priors as they stand now go to the device with the next solve)
 		const auto t0 = std::chrono::steady_clock::now();
 		static const bool dbg = std::getenv("CUBA_HIP_DEBUG") != nullptr;
 		auto tl = t0;
@@ -348,10 +350,52 @@ public:
 			check(cuba_hip_build_structure(solver_), "cuba_hip_build_structure");
 			check(cuba_hip_set_graph_end(solver_), "cuba_hip_set_graph_end");
 			graphDirty_ = false;
+			priorsDirty_ = true;          // (an upload clears the handle's priors)
 			uploadedOnce_ = true; edgesChangedSinceUpload_ = valuesChangedSinceUpload_ = false;       // from here on the device holds exactly these edges and values
 			(void)cuba_hip_get_counter(solver_, "graph_uploads", &uploadGeneration_);
 		}
 		lap("create + set_graph");
+		uploadPriors();
+	}
+
+	// ---- pose priors (extension: cuba::addPosePrior) ------------------------------------------------
+	void addPosePrior(PosePrior* p)
+	{
+		if (!p || !p->vertex) throw std::invalid_argument("cuba::addPosePrior: a prior needs a pose vertex");
+		if (std::find(priors_.begin(), priors_.end(), p) == priors_.end()) priors_.push_back(p);
+	}
+	void removePosePrior(PosePrior* p) { priors_.erase(std::remove(priors_.begin(), priors_.end(), p), priors_.end()); }
+	double priorChiSquared(const PosePrior* p) const
+	{
+		const auto it = priorChi_.find(p);
+		return it == priorChi_.end() ? 0.0 : it->second;
+	}
+	// (only when priors exist -- or existed at the last initialize(), which then clears them on the device)
+	void uploadPriors()
+	{
+		if (!priorsDirty_) return;
+		priorsDirty_ = false;
+		priorChi_.clear();
+		uploadedPriors_.clear();
+		if (priors_.empty() && !priorsOnDevice_) return;
+		std::map<const PoseVertex*, int> poseIdx;
+		for (size_t i = 0; i < activePoses_.size(); i++) poseIdx[activePoses_[i]] = (int)i;
+		const size_t n = priors_.size();
+		std::vector<int32_t> pose(n);
+		std::vector<double> q(4 * n), t(3 * n), info(36 * n);
+		for (size_t k = 0; k < n; k++)
+		{
+			const PosePrior* p = priors_[k];
+			const auto it = poseIdx.find(p->vertex);
+			if (it == poseIdx.end()) throw std::invalid_argument("cuba::addPosePrior: the vertex of a prior is not part of the graph");
+			pose[k] = it->second;
+			for (int i = 0; i < 4; i++) q[4 * k + i] = p->q.coeffs().data()[i];
+			for (int i = 0; i < 3; i++) t[3 * k + i] = p->t.data()[i];
+			std::copy(p->information.begin(), p->information.end(), info.begin() + 36 * k);
+		}
+		check(cuba_hip_set_pose_priors(solver_, (int)n, pose.data(), q.data(), t.data(), info.data()), "cuba_hip_set_pose_priors");
+		priorsOnDevice_ = n > 0;
+		uploadedPriors_ = priors_;
 	}
 
 	// (optimize() in three steps, so that cuba::optimizeBatch can run the middle one for several objects at once)
@@ -430,6 +474,12 @@ public:
 			tl = now;
 		};
 		for (int i = 0; i < done; i++) stats_.push_back({ i, chi2[i] });
+		if (!uploadedPriors_.empty())
+		{
+			std::vector<double> pc(uploadedPriors_.size());
+			check(cuba_hip_prior_chi_squares(solver_, pc.data()), "cuba_hip_prior_chi_squares");
+			for (size_t k = 0; k < pc.size(); k++) priorChi_[uploadedPriors_[k]] = pc[k];
+		}
 
 		// finalize (ref :512-526): estimates back into the caller's vertices
 		check(cuba_hip_get_solution(solver_, q_.data(), t_.data(), Xw_.data()), "cuba_hip_get_solution");
@@ -475,6 +525,7 @@ public:
 	{
 		covPoseIndex_.clear(); covLmIndex_.clear();
 		poses_.clear(); landmarks_.clear(); mono_.clear(); stereo_.clear(); stats_.clear();
+		priors_.clear(); priorChi_.clear();
 		posesDirty_ = landmarksDirty_ = edgesDirty_ = true;
 		initialized_ = false;
 	}
@@ -597,6 +648,9 @@ private:
 
 	// flattened problem (solver order)
 	std::vector<PoseVertex*> activePoses_;
+	std::vector<PosePrior*> priors_, uploadedPriors_;     // in the caller's order; the set the last initialize() handed to the device
+	bool priorsOnDevice_ = false, priorsDirty_ = false;
+	std::map<const PosePrior*, double> priorChi_;
 	std::vector<LandmarkVertex*> activeLandmarks_;
 	std::vector<BaseEdge*> activeEdges_;
 	int numFreePoses_ = 0, numFreeLandmarks_ = 0;
@@ -694,6 +748,26 @@ bool landmarkCovariance(const CudaBundleAdjustment* object, const LandmarkVertex
 {
 	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
 	return impl && impl->landmarkCovariance(v, cov);
+}
+
+// Extension (g2o's unary pose edges): SE(3) pose priors, effective at the next initialize() (cuba_hip_set_pose_priors)
+void addPosePrior(CudaBundleAdjustment* object, PosePrior* prior)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (!impl) throw std::runtime_error("cuba::addPosePrior: not an object of this library");
+	impl->addPosePrior(prior);
+}
+
+void removePosePrior(CudaBundleAdjustment* object, PosePrior* prior)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (impl) impl->removePosePrior(prior);
+}
+
+double priorChiSquared(const CudaBundleAdjustment* object, const PosePrior* prior)
+{
+	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
+	return impl ? impl->priorChiSquared(prior) : 0.0;
 }
 
 }  // namespace cuba

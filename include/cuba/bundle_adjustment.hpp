@@ -108,4 +108,21 @@ struct CovarianceVertex
 using CovariancePair = std::pair<CovarianceVertex, CovarianceVertex>;
 bool computeCrossCovariances(CudaBundleAdjustment* object, const std::vector<CovariancePair>& pairs, std::vector<std::array<double, 36>>& out);
 
+// Extension (g2o's unary pose edges; include/cuba_hip.h, cuba_hip_set_pose_priors): an SE(3) prior on one pose vertex -- prior pose (q, t),
+// world -> camera like the vertex, and a symmetric 6 x 6 information matrix, column-major, in the tangent [omega, upsilon] of the pose
+// update (poseCovariance's tangent: the inverse of one window's marginal is a prior of the next).  Objective term r^T Omega r with
+// r = log(T Tbar^-1), no robust kernel.  The caller owns the PosePrior, as it owns edges; additions, removals and changes take effect
+// at the next initialize().  removePoseVertex and clear() drop the priors of the vertex / all priors.  priorChiSquared: r^T Omega r at
+// the estimate of the last optimize() (0 before one, and for a prior on a fixed vertex).
+struct PosePrior
+{
+	PoseVertex* vertex = nullptr;
+	PoseVertex::Rotation q;
+	PoseVertex::Translation t;
+	std::array<double, 36> information{};
+};
+void addPosePrior(CudaBundleAdjustment* object, PosePrior* prior);
+void removePosePrior(CudaBundleAdjustment* object, PosePrior* prior);
+double priorChiSquared(const CudaBundleAdjustment* object, const PosePrior* prior);
+
 }  // namespace cuba

@@ -361,6 +361,30 @@ int cuba_hip_get_covariance_blocks(cuba_hip_solver* s, double* values);
 int cuba_hip_compute_covariance_pairs(cuba_hip_solver* s, int n, const int32_t* kind_a, const int32_t* index_a, const int32_t* kind_b,
 	const int32_t* index_b, double* out, int* not_positive_definite);
 
+/* ---- SE(3) pose priors (g2o's unary pose edges; the reference has no counterpart) --------------------------------------------------
+   A prior names pose `pose` (the caller's solver numbering, 0 <= pose < Pt), a prior pose Tbar = (q, t) (world -> camera, quaternion
+   (x, y, z, w), normalised by the library) and a 6 x 6 information matrix Omega (symmetric, column-major, in the [omega, upsilon] order of
+   the pose update T <- exp(d) T -- the tangent cuba_hip_compute_covariance reports in, so that Sigma^-1 of one window is a prior of the next).
+     residual     r = log(T Tbar^-1) = [w ; V(w)^-1 (t - R Rbar^T tbar)], w = log(R Rbar^T)
+     objective    r^T Omega r, no robust kernel; the LM objective F (cuba_hip_optimize's chi2, cuba_hip_compute_errors, the gain ratio) is the
+                  robust edge sum plus the prior sum
+     linearised   with J = J_l(r)^-1, the inverse left Jacobian of SE(3): Hpp += J^T Omega J, bp += -J^T Omega r (the convention
+                  (H + lambda I) x = b of the rest of the ABI); in the reduced system the same terms land in the pose's diagonal block and in
+                  bsc, and the maximum diagonal of lambda_0 = tau max diag(H) includes them.
+   Several priors on one pose are summed in the caller's order; priors on fixed poses are accepted and ignored (chi2 0).  Every solve
+   path honours them: the device-decision loop, the host loop (option "profile", graphs without free landmarks), both PCG forms, the exact
+   solver, the fp32 library, mixed precision, the covariances (a prior makes a graph without a fixed pose invertible).
+   cuba_hip_set_pose_priors replaces the whole set (n = 0 clears it): q[4 n], t[3 n], info[36 n].  Valid any time after cuba_hip_set_graph,
+   which clears the set.  Non-finite values, an information matrix that is not symmetric (beyond 1e-9 of its largest entry; within it the
+   two triangles are averaged) or a pose out of range: CUBA_HIP_ERR_INVALID_ARGUMENT, the handle unchanged.  Refused with
+   CUBA_HIP_ERR_STATE: a landmark-partitioned handle (and cuba_hip_set_partition on a handle with priors, hence the multi-GPU driver) and a
+   graph without edges.  Setting priors drops the run-to-run memories of option "heuristics" as a new graph does.  A handle with priors
+   takes part in cuba_hip_optimize_batch through the path that batches the PCG iterations only (results stay bit-identical to solo runs).
+   cuba_hip_prior_chi_squares: r^T Omega r of every prior at the current estimate, in the caller's order (to gate bad GPS or relocalisation
+   priors, as cuba_hip_chi_squares serves for edges). */
+int cuba_hip_set_pose_priors(cuba_hip_solver* s, int n, const int32_t* pose, const double* q, const double* t, const double* info);
+int cuba_hip_prior_chi_squares(cuba_hip_solver* s, double* chi2_per_prior);
+
 /* ---- introspection (parity tests) and multi-GPU plumbing ------------------------------------------ */
 
 /* Structure of the reduced system: upper-triangular BSR (replaces the accessors of
