@@ -124,6 +124,8 @@ def load_library(precision="f64"):
         "cuba_hip_compute_covariance_pairs": [H, C.c_int, _ip, _ip, _ip, _ip, _dp, C.POINTER(C.c_int)],
         "cuba_hip_set_pose_priors": [H, C.c_int, _ip, _dp, _dp, _dp],
         "cuba_hip_prior_chi_squares": [H, _dp],
+        "cuba_hip_set_relative_pose_edges": [H, C.c_int, _ip, _ip, _dp, _dp, _dp],
+        "cuba_hip_relative_pose_chi_squares": [H, _dp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -385,6 +387,7 @@ class HipSolver:
         measurements and information of its own landmarks' edges only."""
         self.fp = fp
         self._n_priors = 0              # (every upload clears the pose priors)
+        self._n_rel = 0                 # (and the relative-pose edges)
         q, t, cam, Xw = (np.ascontiguousarray(a, dtype=np.float64) for a in (fp.q, fp.t, fp.cam, fp.Xw))
         eP = np.ascontiguousarray(fp.eP, dtype=np.int32)
         eL = np.ascontiguousarray(fp.eL, dtype=np.int32)
@@ -491,6 +494,29 @@ class HipSolver:
         info = np.ascontiguousarray(np.asarray(info, dtype=np.float64).reshape(n, 6, 6).transpose(0, 2, 1))
         self._ck(self.lib.cuba_hip_set_pose_priors(self.h, n, pose.ctypes.data_as(_ip), _d(q), _d(t), _d(info)))
         self._n_priors = n
+
+    def set_relative_pose_edges(self, pose_i, pose_j, q, t, info):
+        """SE(3) relative-pose edges (cuba_hip_set_relative_pose_edges), replacing the handle's set: pose_i[n], pose_j[n] in the solver
+        numbering, the measured T_j T_i^-1 as q[n, 4] (x, y, z, w) and t[n, 3], info[n, 6, 6] symmetric in [omega, upsilon] order;
+        n = 0 clears."""
+        pose_i = np.ascontiguousarray(pose_i, dtype=np.int32).reshape(-1)
+        pose_j = np.ascontiguousarray(pose_j, dtype=np.int32).reshape(-1)
+        n = int(pose_i.size)
+        q = np.ascontiguousarray(q, dtype=np.float64).reshape(n, 4)
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(n, 3)
+        # (symmetric matrices: row- and column-major agree up to the symmetrisation the library applies)
+        info = np.ascontiguousarray(np.asarray(info, dtype=np.float64).reshape(n, 6, 6).transpose(0, 2, 1))
+        if pose_j.size != n:
+            raise ValueError("pose_i and pose_j differ in length")
+        self._ck(self.lib.cuba_hip_set_relative_pose_edges(self.h, n, pose_i.ctypes.data_as(_ip), pose_j.ctypes.data_as(_ip), _d(q), _d(t), _d(info)))
+        self._n_rel = n
+
+    def relative_pose_chi_squares(self):
+        """r^T Omega r of every relative-pose edge at the current estimate, in the order they were given (0 with both ends fixed)"""
+        n = getattr(self, "_n_rel", 0)
+        out = np.zeros(max(n, 1))
+        self._ck(self.lib.cuba_hip_relative_pose_chi_squares(self.h, _d(out)))
+        return out[:n]
 
     def prior_chi_squares(self):
         """r^T Omega r of every prior at the current estimate, in the order they were given (0 for priors on fixed poses)"""

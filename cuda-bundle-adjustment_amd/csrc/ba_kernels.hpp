@@ -1,4 +1,4 @@
-// ba_kernels.hpp -- launch interface of the gfx950 kernels (implemented in ba_edge.hip, ba_linearize.hip, ba_pcg.hip, ba_coarse.hip, ba_prior.hip).
+// ba_kernels.hpp -- launch interface of the gfx950 kernels (implemented in ba_edge.hip, ba_linearize.hip, ba_pcg.hip, ba_coarse.hip, ba_prior.hip, ba_relpose.hip).
 //
 // Device data model (all SoA, fp64 + int32):
 //   poses      q[4*Pt] t[3*Pt] cam[5*Pt]          free poses [0,Pf) first, fixed after
@@ -155,10 +155,40 @@ void launch_prior_linearize(const DeviceGraph& g, const DeviceStructure& st, con
 void launch_prior_chi2(const DeviceGraph& g, const DevicePriors& pr, Scalar* parts, hipStream_t s);
 int prior_chi2_parts(const DevicePriors* pr);     // 0 for no priors (pr null or empty), at most 64
 
+// SE(3) relative-pose edges (ba_relpose.hip): r^T Omega r, r = log(T_j T_i^-1 Zbar^-1), between two poses.  Sorted: the edges between two
+// free poses first, stable by the block (min, max) of the internal pose pair (a block's edges contiguous, in the caller's order), then the
+// edges with one fixed end (they act on the free end only), then those with two (ignored).
+constexpr int REL_REC = 90;        // numbers of an edge's linearisation record (layout: ba_relpose.hip)
+struct DeviceRelPoses
+{
+	int n = 0;                     // edges
+	int nActive = 0;               // the first nActive have a free end
+	int nBlocks = 0;               // off-diagonal blocks of hsc with such edges
+	int nPoses = 0;                // free poses with such edges
+	const int *pose_i = nullptr, *pose_j = nullptr;   // [n] internal poses of every edge (>= Pf: a fixed pose)
+	const int* blk_ptr = nullptr;  // [nBlocks + 1] range of every such block in the sorted list
+	const int* blk_id = nullptr;   // [nBlocks] its block of hsc
+	const int* pose_ptr = nullptr; // [nPoses + 1] range of every such pose in pose_item
+	const int* pose_id = nullptr;  // [nPoses] its internal pose index
+	const int* pose_item = nullptr;// the pose's edges in the caller's order: 2 * sorted edge + (0: the pose is the edge's i, 1: its j)
+	const Scalar *q = nullptr, *t = nullptr;          // [4 n] unit quaternions, [3 n]: the measurements Zbar
+	const Scalar* info = nullptr;  // [36 n] column-major
+	Scalar* rec = nullptr;         // [REL_REC n] linearisation records, number-major (number el of edge k at el n + k)
+	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 with both ends fixed)
+};
+// two launches behind the Schur pass and the priors': per-edge records, then their sums into hsc (diagonal blocks: upper triangle; mode 1: the
+// off-diagonal blocks of the pairs, stored whole where a block has no Schur products), bp and (mode 1) bsc
+void launch_relpose_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DeviceRelPoses& rp, int mode, hipStream_t s);
+// per-edge chi2 into rp.chi, per-workgroup partial sums into parts[0 .. relpose_chi2_parts(&rp))
+void launch_relpose_chi2(const DeviceGraph& g, const DeviceRelPoses& rp, Scalar* parts, hipStream_t s);
+int relpose_chi2_parts(const DeviceRelPoses* rp);     // 0 for no edges (rp null or empty), at most 64
+
 // residual / robust chi2 over all edges -> sys.slots[0..NSLOT) (must be zeroed by the caller).
 // per_edge (optional, sorted edge order): non-robust omega*|r|^2.
-// pr (optional): the priors' chi2 partials follow the edges' and are summed with them (the objective F of the LM loop)
-void launch_residual_chi2(const DeviceGraph& g, Scalar* parts, Scalar* slots, Scalar* per_edge, hipStream_t st, const DevicePriors* pr = nullptr);
+// pr, rp (optional): the priors' and then the relative-pose edges' chi2 partials follow the edges' and are summed with them (the objective F
+// of the LM loop)
+void launch_residual_chi2(const DeviceGraph& g, Scalar* parts, Scalar* slots, Scalar* per_edge, hipStream_t st, const DevicePriors* pr = nullptr,
+	const DeviceRelPoses* rp = nullptr);
 
 // mode 0: assemble only (Hpp -> diagonal blocks of hsc, bp, Hll/bl -> lm_sys, max diagonal of Hll)
 // mode 1: full linearise + Schur reduction with damping lambda (hsc, bsc, bp, inv(Hll+lambda)/bl -> lm_sys)
@@ -185,10 +215,11 @@ void launch_pose_scale(const DeviceGraph& g, const DeviceSystem& sys, Scalar lam
 // [q | t | Xw] made before the trial: the pass reads the pre-update estimate from it while it writes the updated one), then the sums
 // + report.  trial_tail_parts(): numbers of partial-sum scratch (sys.parts) it needs.
 struct LmDevice;
-// pr (optional): the priors' chi2 at the updated poses, a launch between the edge pass and the sums; its partials join the edges' chi2 partials
+// pr, rp (optional): the priors' / relative-pose edges' chi2 at the updated poses, launches between the edge pass and the sums; their partials join
+// the edges' chi2 partials
 void launch_trial_tail_fused(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, Scalar lambda, const Scalar* old, hipStream_t s,
-	const LmDevice* decide = nullptr, const DevicePriors* pr = nullptr);
-size_t trial_tail_parts(const DeviceGraph& g, const DeviceStructure& st, int priorParts = 0);
+	const LmDevice* decide = nullptr, const DevicePriors* pr = nullptr, const DeviceRelPoses* rp = nullptr);
+size_t trial_tail_parts(const DeviceGraph& g, const DeviceStructure& st, int priorParts = 0);      // priorParts: the priors' + the relative-pose edges' partials
 // Device-resident LM decision (control flow of CudaBundleAdjustmentImpl::optimize, /root/reference/src/cuda_bundle_adjustment.cpp:816-851):
 // state = {F, lambda, nu, halt, trials, accepted (last trial), rejections in a row, max rejections} in device memory, lam = the damping as
 // the kernels read it (sys.lam_dev), ring = device-mapped host records, LM_REC numbers per trial {Fhat, denominator, rho, next lambda,

@@ -32,6 +32,7 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 	if ((Pt_ && (!q || !t || !cam)) || (Lt_ && !Xw) || (E_ && (!ep || !el || !edim || !meas || !omega))) throw ArgError{ "null array" };
 	const auto t0 = Clock::now();
 	clearPosePriors();            // (priors name poses of the previous graph)
+	clearRelativePoseEdges();     // (so do relative-pose edges; need() rebuilds a kept structure unless the same pairs come back)
 	static const bool noCache = std::getenv("CUBA_HIP_NO_STRUCTURE_CACHE") != nullptr;   // A/B knob for set-up timings
 	const bool sameCounts = !noCache && !ranged && haveStructure && partHi < 0 && Pt == Pt_ && Pf == Pf_ && Lt == Lt_ && Lf == Lf_ && E == E_;
 	// the very same index arrays as in the previous call (re-initialisation of an unchanged graph): the sort, the
@@ -334,11 +335,16 @@ void cuba_hip_solver::buildStructure()
 	std::vector<long long> peWeight(peAllPtr.begin(), peAllPtr.end());
 	// row i of the pattern collects, for every landmark pose i sees, the poses after it in that landmark's edge list:
 	// each row is produced by one thread into its own segment (no atomics)
+	// (the pose pairs of the relative-pose edges: off-diagonal seeds, sorted by (row, column))
+	h_relSeeds = relSeedKeys();
+	std::vector<int> relRowPtr(Pf + 1, 0);
+	for (uint64_t k : h_relSeeds) relRowPtr[(size_t)(k >> 32) + 1]++;
+	for (int i = 0; i < Pf; i++) relRowPtr[i + 1] += relRowPtr[i];
 	std::vector<long long> rowStart(Pf + 1, 0);
 	{
 		std::vector<long long> cnt(Pf, 1);                   // the diagonal block always exists
 		parallelRows(Pf, peWeight, [&](int i) {
-			long long c = 1;
+			long long c = 1 + (relRowPtr[i + 1] - relRowPtr[i]);
 			for (int x = peAllPtr[i]; x < peAllPtr[i + 1]; x++)
 			{
 				const int e = peAll[x], l = slm[e];
@@ -356,6 +362,7 @@ void cuba_hip_solver::buildStructure()
 	parallelRows(Pf, rowStart, [&](int i) {
 		long long slot = rowStart[i];
 		ent[slot++] = PatternEntry{ (uint64_t)i << 32, -1, -1 };                    // id 0 = diagonal seed, sorts first
+		for (int x = relRowPtr[i]; x < relRowPtr[i + 1]; x++) ent[slot++] = PatternEntry{ (uint64_t)(uint32_t)h_relSeeds[x] << 32, -1, -1 };
 		for (int x = peAllPtr[i]; x < peAllPtr[i + 1]; x++)
 		{
 			const int e = peAll[x], l = slm[e];
@@ -786,6 +793,7 @@ void cuba_hip_solver::publishStructure(int nblk, int nWaves, int nBig, int nOd, 
 	sys.acinv32 = fp32Inverse() && agg > 0 ? d_coarse32[0].data() : nullptr;
 	cutReductionParts();
 	haveStructure = true;
+	structRelPairs = h_relPairs; cntStructureBuilds++;
 }
 
 // Landmark partitions: cut the reduced matrix at block rows into at most `redChunks` ranges of about equal size and group the block list
@@ -1098,7 +1106,10 @@ void cuba_hip_solver::buildStructureDevice()
 	sync();
 	lap("structure (device): pairs, pose lists, wave counts");
 	if (Lf == 0) npairs = 0;
-	if (npairs >= (1LL << 31) - Pf) throw ArgError{ "graph too dense: more than 2^31 Schur block products" };
+	// the pose pairs of the relative-pose edges: off-diagonal seeds of the pattern, in the internal pose order in force
+	h_relSeeds = relSeedKeys();
+	const int nRelSeeds = (int)h_relSeeds.size(), nSeeds = Pf + nRelSeeds;
+	if (npairs >= (1LL << 31) - nSeeds) throw ArgError{ "graph too dense: more than 2^31 Schur block products" };
 	nmul = npairs + nFreeEdges;
 	const int nWaves = hc[topo::CNT_NWAVES], nBig = hc[topo::CNT_NBIG];
 	d_waveLm.resize((size_t)2 * nWaves); d_bigLm.resize(nBig);
@@ -1110,10 +1121,12 @@ void cuba_hip_solver::buildStructureDevice()
 		topo::launch_segment_subrange(d_pePtr.data(), Pf, d_peEdge.data(), g.e_begin, g.e_end, d_peBeg.data(), d_peEnd.data(), stream);
 	}
 	// 4. pattern entries (diagonal seeds + one per product), sorted by (row, column); head flags; block index of every entry
-	const size_t nEnt = (size_t)Pf + (size_t)npairs;
+	const size_t nEnt = (size_t)nSeeds + (size_t)npairs;
+	if (nRelSeeds) d_relSeeds.upload(h_relSeeds, stream);
 	d_k64a.resize(nEnt); d_k64b.resize(nEnt); d_v64a.resize(nEnt); d_v64b.resize(nEnt);
 	sortTemp(nEnt);
-	topo::launch_pattern_entries(d_lmptr.data(), d_epose.data(), d_elm.data(), d_lmNfree.data(), d_lmPairBase.data(), E, Lf, Pf, d_k64a.data(), d_v64a.data(), stream);
+	topo::launch_pattern_entries(d_lmptr.data(), d_epose.data(), d_elm.data(), d_lmNfree.data(), d_lmPairBase.data(), E, Lf, Pf, d_k64a.data(), d_v64a.data(),
+		nRelSeeds ? d_relSeeds.data() : nullptr, nRelSeeds, stream);
 	HIP_TRY(topo::sort_u64_u64(d_topoTemp.data(), d_topoTemp.size(), d_k64a.data(), d_k64b.data(), d_v64a.data(), d_v64b.data(), nEnt, 32 + bitsFor(Pf), stream));
 	d_tmpI0.resize(std::max(nEnt, (size_t)E)); d_tmpI1.resize(std::max(nEnt, (size_t)E));
 	topo::launch_entry_heads(d_k64b.data(), nEnt, d_tmpI0.data(), stream);
@@ -1122,6 +1135,13 @@ void cuba_hip_solver::buildStructureDevice()
 	{
 		HIP_TRY(topo::inclusive_scan_i32(d_topoTemp.data(), d_topoTemp.size(), d_tmpI0.data(), d_tmpI1.data(), nEnt, stream));
 		// ---- synchronisation 2: number of blocks ------------------------------------------------------------------
+		// (off-diagonal seeds: the product positions need the number of seeds before every entry)
+		if (nRelSeeds)
+		{
+			d_relSeedFlag.resize(nEnt); d_relSeedScan.resize(nEnt);
+			topo::launch_seed_flags(d_v64b.data(), nEnt, d_relSeedFlag.data(), stream);
+			HIP_TRY(topo::inclusive_scan_i32(d_topoTemp.data(), d_topoTemp.size(), d_relSeedFlag.data(), d_relSeedScan.data(), nEnt, stream));
+		}
 		nblk = readBack(d_tmpI1.data() + (nEnt - 1));
 	}
 	lap("structure (device): entries sorted, blocks counted");
@@ -1129,7 +1149,8 @@ void cuba_hip_solver::buildStructureDevice()
 	d_colind.resize(nblk); d_blkrow.resize(nblk); d_prodPtr.resize((size_t)nblk + 1); d_prodEa.resize((size_t)npairs); d_prodEb.resize((size_t)npairs);
 	d_rowptr.resize((size_t)Pf + 1);
 	if (nblk == 0) { d_prodPtr.zero(stream); d_rowptr.zero(stream); }
-	topo::launch_blocks_from_entries(d_k64b.data(), d_v64b.data(), d_tmpI1.data(), nEnt, Pf, d_colind.data(), d_blkrow.data(), d_prodPtr.data(),
+	topo::launch_blocks_from_entries(d_k64b.data(), d_v64b.data(), d_tmpI1.data(), nEnt, nSeeds, nRelSeeds ? d_relSeedScan.data() : nullptr,
+		d_colind.data(), d_blkrow.data(), d_prodPtr.data(),
 		d_prodEa.data(), d_prodEb.data(), stream);
 	topo::launch_segment_ptr(d_blkrow.data(), nblk, Pf, d_rowptr.data(), stream);
 	// (the tile order of the Schur block pass -- a host computation over the block list -- needs only what exists from here on: its

@@ -384,6 +384,7 @@ int cuba_hip_get_counter(cuba_hip_solver* s, const char* name, int64_t* value)
 		else if (k == "exact_solve_fallbacks") *value = s->cntDirect;
 		else if (k == "exact_solve_failures") *value = s->cntDirectFailed;
 		else if (k == "graph_uploads") *value = s->cntUploads;
+		else if (k == "structure_builds") *value = s->cntStructureBuilds;
 		else if (k == "value_bytes_uploaded") *value = s->cntValueBytes;
 		else if (k == "late_decision_records") *value = s->cntLateRecords;
 		else if (k == "covariance_ns") *value = (int64_t)(1e9 * s->covSeconds);
@@ -508,6 +509,20 @@ int cuba_hip_prior_chi_squares(cuba_hip_solver* s, double* chi2_per_prior)
 	});
 }
 
+int cuba_hip_set_relative_pose_edges(cuba_hip_solver* s, int n, const int32_t* pose_i, const int32_t* pose_j, const double* q, const double* t, const double* info)
+{
+	return guarded(s, [&] { s->setRelativePoseEdges(n, pose_i, pose_j, q, t, info); });
+}
+
+int cuba_hip_relative_pose_chi_squares(cuba_hip_solver* s, double* chi2_per_edge)
+{
+	return guarded(s, [&] {
+		if (!s->haveGraph) throw StateError{ "set_graph must be called first" };
+		if (!s->h_relI.empty() && !chi2_per_edge) throw ArgError{ "null output" };
+		s->relativePoseChiSquares(chi2_per_edge);
+	});
+}
+
 int cuba_hip_time_kernels(cuba_hip_solver* s, int reps, double ms_per_launch[CUBA_HIP_TIMED_KERNELS])
 {
 	return guarded(s, [&] {
@@ -532,6 +547,7 @@ int cuba_hip_set_partition(cuba_hip_solver* s, int landmark_begin, int landmark_
 		}
 		if (landmark_begin < 0 || landmark_end > s->Lt || landmark_begin > landmark_end) throw ArgError{ "bad landmark range" };
 		if (!s->h_priorPose.empty()) throw StateError{ "a landmark partition is not available on a handle with pose priors" };
+		if (!s->h_relI.empty()) throw StateError{ "a landmark partition is not available on a handle with relative-pose edges" };
 		if (s->partHi >= 0 && landmark_begin == s->partLo && landmark_end == s->partHi) return;      // (cuba_hip_set_graph_partition set it already)
 		s->partLo = landmark_begin; s->partHi = landmark_end;
 		s->haveStructure = false;
@@ -938,7 +954,7 @@ int cuba_hip_evaluate_device(cuba_hip_solver* s, double lambda, int with_scale, 
 		s->need();
 		if (!device_scalars3) throw ArgError{ "null output" };
 		s->d_eval.resize(4);
-		launch_residual_chi2(s->g, s->d_parts.data(), s->slotsDev, nullptr, s->stream, s->priors());
+		launch_residual_chi2(s->g, s->d_parts.data(), s->slotsDev, nullptr, s->stream, s->priors(), s->relPoses());
 		if (with_scale) launch_pose_scale(s->g, s->sys, lambda, s->slotsDev + 3 * NSLOT, s->stream);
 		launch_collect_eval(s->sys, s->d_eval.data(), s->stream);
 		*device_scalars3 = s->d_eval.data();

@@ -569,8 +569,10 @@ struct cuba_hip_solver
 	void need()
 	{
 		if (!haveGraph) throw StateError{ "set_graph must be called first" };
+		if (haveStructure && h_relPairs != structRelPairs) haveStructure = false;      // (the relative-pose pairs are part of the topology)
 		buildStructure(); finishValues(); g.rk[0] = rk[0]; g.rk[1] = rk[1]; st.mixed = mixedPrecision ? 1 : 0;
 		if (!h_priorPose.empty() && !priorsUploaded) uploadPriors();
+		if (!h_relI.empty() && (!relUploaded || relStructure != cntStructureBuilds)) uploadRelativePoseEdges();
 	}
 
 	// SE(3) pose priors (ba_prior.hip; cuba_hip_set_pose_priors): the caller's set in its own numbering (quaternions normalised,
@@ -587,6 +589,29 @@ struct cuba_hip_solver
 	void clearPosePriors() { h_priorPose.clear(); h_priorQ.clear(); h_priorT.clear(); h_priorInfo.clear(); h_priorOrder.clear(); priorsUploaded = false; pri = DevicePriors(); }
 	void uploadPriors();
 	void priorChiSquares(double* out);
+
+	// SE(3) relative-pose edges (ba_relpose.hip; cuba_hip_set_relative_pose_edges): the caller's set in its own numbering, the distinct
+	// free-free pairs among them (sorted keys i << 32 | j, i < j, caller's numbering) and the pairs the current structure was seeded with:
+	// every such pair owns a block of the reduced matrix, so need() rebuilds the structure exactly when the two sets differ.  The device
+	// copy (internal pose order, blocks looked up in the pattern) is renewed with every structure.  No such edges: nothing of it is launched,
+	// no extra seed enters the pattern build, and every launch and kernel argument is as without this feature.
+	std::vector<int> h_relI, h_relJ; std::vector<double> h_relQ, h_relT, h_relInfo;
+	std::vector<uint64_t> h_relPairs, structRelPairs;
+	std::vector<int> h_relOrder;         // sorted position -> caller's edge index
+	bool relUploaded = false;
+	int64_t relStructure = -1;           // cntStructureBuilds at the upload
+	int64_t cntStructureBuilds = 0;      // structures published on this handle (never reset)
+	std::vector<uint64_t> h_relSeeds;    // the pairs as the last pattern build took them
+	DevBuf<int> d_relInts, d_relSeedFlag, d_relSeedScan; DevBuf<uint64_t> d_relSeeds; DevBuf<Scalar> d_relVals, d_relRec, d_relChi;
+	DeviceRelPoses rel;
+	const DeviceRelPoses* relPoses() const { return h_relI.empty() ? nullptr : &rel; }
+	int extraChiParts() const { return priorParts() + relpose_chi2_parts(relPoses()); }      // chi2 partials that follow the reprojection edges'
+	void setRelativePoseEdges(int n, const int32_t* pi, const int32_t* pj, const double* q, const double* t, const double* info);
+	void clearRelativePoseEdges() { h_relI.clear(); h_relJ.clear(); h_relQ.clear(); h_relT.clear(); h_relInfo.clear(); h_relPairs.clear(); h_relOrder.clear(); relUploaded = false; rel = DeviceRelPoses(); }
+	void uploadRelativePoseEdges();
+	void relativePoseChiSquares(double* out);
+	// the pairs as (row, column) keys of the pattern in the internal pose order, sorted
+	std::vector<uint64_t> relSeedKeys() const;
 
 	double readSlots(int which)
 	{

@@ -141,23 +141,38 @@ __global__ __launch_bounds__(T) void copy_u32_int_kernel(const uint32_t* in, int
 	if (i < n) out[i] = (int)in[i];
 }
 
-__global__ __launch_bounds__(T) void pattern_entries_kernel(const int* lm_ptr, const int* e_pose, const int* e_lm, const int* nfree, const long long* pairBase,
-	int E, int Lf, int Pf, uint64_t* keys, uint64_t* vals)
+// nSeeds = Pf + the off-diagonal seeds (the pose pairs of the relative-pose edges, extraSeeds; none: nSeeds = Pf, extraSeeds unused)
+__device__ __forceinline__ void pattern_entries_body(const int* lm_ptr, const int* e_pose, const int* e_lm, const int* nfree, const long long* pairBase,
+	int E, int Lf, int Pf, uint64_t* keys, uint64_t* vals, const uint64_t* extraSeeds, int nSeeds)
 {
 	const int i = blockIdx.x * T + threadIdx.x;
 	if (i < Pf) { keys[i] = ((uint64_t)i << 32) | (uint32_t)i; vals[i] = 0; }       // diagonal seeds: every free pose owns its diagonal block
+	else if (i < nSeeds) { keys[i] = extraSeeds[i - Pf]; vals[i] = 0; }              // off-diagonal seeds
 	if (i >= E) return;
 	const int l = e_lm[i];
 	if (l >= Lf) return;
 	const int b0 = lm_ptr[l], a = i - b0, n = nfree[l];
 	if (a >= n) return;                                                            // edge of a fixed pose
 	const uint64_t pa = (uint64_t)(uint32_t)(e_pose[i] & ~STEREO_BIT);
-	size_t out = (size_t)Pf + (size_t)pairBase[l] + (size_t)a * (n - 1) - (size_t)a * (a - 1) / 2;     // id of product (a, a + 1)
+	size_t out = (size_t)nSeeds + (size_t)pairBase[l] + (size_t)a * (n - 1) - (size_t)a * (a - 1) / 2;     // id of product (a, a + 1)
 	for (int c = a + 1; c < n; c++, out++)
 	{
 		keys[out] = (pa << 32) | (uint32_t)(e_pose[b0 + c] & ~STEREO_BIT);
 		vals[out] = ((uint64_t)(uint32_t)(i + 1) << 32) | (uint32_t)(b0 + c + 1);
 	}
+}
+
+__global__ __launch_bounds__(T) void pattern_entries_kernel(const int* lm_ptr, const int* e_pose, const int* e_lm, const int* nfree, const long long* pairBase,
+	int E, int Lf, int Pf, uint64_t* keys, uint64_t* vals)
+{
+	pattern_entries_body(lm_ptr, e_pose, e_lm, nfree, pairBase, E, Lf, Pf, keys, vals, nullptr, Pf);
+}
+
+// the same with the pose pairs of the relative-pose edges as further seeds
+__global__ __launch_bounds__(T) void pattern_entries_seeded_kernel(const int* lm_ptr, const int* e_pose, const int* e_lm, const int* nfree, const long long* pairBase,
+	int E, int Lf, int Pf, uint64_t* keys, uint64_t* vals, const uint64_t* extraSeeds, int nSeeds)
+{
+	pattern_entries_body(lm_ptr, e_pose, e_lm, nfree, pairBase, E, Lf, Pf, keys, vals, extraSeeds, nSeeds);
 }
 
 __global__ __launch_bounds__(T) void entry_heads_kernel(const uint64_t* keys, size_t n, int* head)
@@ -166,8 +181,14 @@ __global__ __launch_bounds__(T) void entry_heads_kernel(const uint64_t* keys, si
 	if (j < n) head[j] = (j == 0 || keys[j] != keys[j - 1]) ? 1 : 0;
 }
 
-__global__ __launch_bounds__(T) void blocks_from_entries_kernel(const uint64_t* keys, const uint64_t* vals, const int* blkOfEntry, size_t n, int Pf,
-	int* colind, int* blkrow, int* prod_ptr, int* prod_ea, int* prod_eb)
+__global__ __launch_bounds__(T) void seed_flags_kernel(const uint64_t* vals, size_t n, int* flag)
+{
+	const size_t j = (size_t)blockIdx.x * T + threadIdx.x;
+	if (j < n) flag[j] = vals[j] == 0 ? 1 : 0;
+}
+
+__device__ __forceinline__ void blocks_from_entries_body(const uint64_t* keys, const uint64_t* vals, const int* blkOfEntry, size_t n, int nSeeds,
+	const int* seedScan, int* colind, int* blkrow, int* prod_ptr, int* prod_ea, int* prod_eb)
 {
 	const size_t j = (size_t)blockIdx.x * T + threadIdx.x;
 	if (j >= n) return;
@@ -176,9 +197,11 @@ __global__ __launch_bounds__(T) void blocks_from_entries_kernel(const uint64_t* 
 	const int b = blkOfEntry[j] - 1;
 	const bool head = j == 0 || keys[j - 1] != key;
 	const bool seed = val == 0;
-	// seeds: one per row, first entry of its row (stable sort, seeds first in the input) => row + 1 seeds up to and
-	// including a non-seed entry of that row, row seeds before the seed of that row
-	const long long ppos = (long long)j - row - 1;
+	// ppos = j - (seeds up to and including entry j): the products before a product, one less than the products before a seed.
+	// Diagonal seeds only (seedScan null): one per row, first entry of its row (stable sort, seeds first in the input) => row + 1 seeds
+	// up to and including a non-seed entry of that row, row seeds before the seed of that row.  With the off-diagonal seeds of
+	// relative-pose pairs the count comes from a scan of the seed flags.
+	const long long ppos = seedScan ? (long long)j - seedScan[j] : (long long)j - row - 1;
 	if (head)
 	{
 		colind[b] = col; blkrow[b] = row;
@@ -189,7 +212,20 @@ __global__ __launch_bounds__(T) void blocks_from_entries_kernel(const uint64_t* 
 		prod_ea[ppos] = (int)(val >> 32) - 1;
 		prod_eb[ppos] = (int)(uint32_t)val - 1;
 	}
-	if (j == n - 1) prod_ptr[b + 1] = (int)(n - (size_t)Pf);
+	if (j == n - 1) prod_ptr[b + 1] = (int)(n - (size_t)nSeeds);
+}
+
+__global__ __launch_bounds__(T) void blocks_from_entries_kernel(const uint64_t* keys, const uint64_t* vals, const int* blkOfEntry, size_t n, int Pf,
+	int* colind, int* blkrow, int* prod_ptr, int* prod_ea, int* prod_eb)
+{
+	blocks_from_entries_body(keys, vals, blkOfEntry, n, Pf, nullptr, colind, blkrow, prod_ptr, prod_ea, prod_eb);
+}
+
+// the same with off-diagonal seeds among the entries (seedScan: inclusive scan of the seed flags)
+__global__ __launch_bounds__(T) void blocks_from_entries_seeded_kernel(const uint64_t* keys, const uint64_t* vals, const int* blkOfEntry, size_t n, int nSeeds,
+	const int* seedScan, int* colind, int* blkrow, int* prod_ptr, int* prod_ea, int* prod_eb)
+{
+	blocks_from_entries_body(keys, vals, blkOfEntry, n, nSeeds, seedScan, colind, blkrow, prod_ptr, prod_ea, prod_eb);
 }
 
 // For every segment s of a list (items ptr[s] .. ptr[s + 1], their values ascending): the sub-range whose values lie in [vlo, vhi).
@@ -462,10 +498,18 @@ void launch_copy_u32_to_int(const uint32_t* in, int* out, int n, hipStream_t s)
 }
 
 void launch_pattern_entries(const int* lm_ptr, const int* e_pose, const int* e_lm, const int* nfree, const long long* pairBase, int E, int Lf, int Pf,
-	uint64_t* keys, uint64_t* vals, hipStream_t s)
+	uint64_t* keys, uint64_t* vals, const uint64_t* extraSeeds, int nExtra, hipStream_t s)
 {
-	const size_t n = (size_t)(E > Pf ? E : Pf);
-	if (n > 0) hipLaunchKernelGGL(pattern_entries_kernel, grid_for(n), dim3(T), 0, s, lm_ptr, e_pose, e_lm, nfree, pairBase, E, Lf, Pf, keys, vals);
+	const int nSeeds = Pf + nExtra;
+	const size_t n = (size_t)(E > nSeeds ? E : nSeeds);
+	if (n == 0) return;
+	if (nExtra == 0) hipLaunchKernelGGL(pattern_entries_kernel, grid_for(n), dim3(T), 0, s, lm_ptr, e_pose, e_lm, nfree, pairBase, E, Lf, Pf, keys, vals);
+	else hipLaunchKernelGGL(pattern_entries_seeded_kernel, grid_for(n), dim3(T), 0, s, lm_ptr, e_pose, e_lm, nfree, pairBase, E, Lf, Pf, keys, vals, extraSeeds, nSeeds);
+}
+
+void launch_seed_flags(const uint64_t* vals, size_t n, int* flag, hipStream_t s)
+{
+	if (n > 0) hipLaunchKernelGGL(seed_flags_kernel, grid_for(n), dim3(T), 0, s, vals, n, flag);
 }
 
 namespace
@@ -538,10 +582,12 @@ void launch_entry_heads(const uint64_t* keys, size_t n, int* head, hipStream_t s
 	if (n > 0) hipLaunchKernelGGL(entry_heads_kernel, grid_for(n), dim3(T), 0, s, keys, n, head);
 }
 
-void launch_blocks_from_entries(const uint64_t* keys, const uint64_t* vals, const int* blkOfEntry, size_t n, int Pf, int* colind, int* blkrow, int* prod_ptr,
-	int* prod_ea, int* prod_eb, hipStream_t s)
+void launch_blocks_from_entries(const uint64_t* keys, const uint64_t* vals, const int* blkOfEntry, size_t n, int nSeeds, const int* seedScan, int* colind,
+	int* blkrow, int* prod_ptr, int* prod_ea, int* prod_eb, hipStream_t s)
 {
-	if (n > 0) hipLaunchKernelGGL(blocks_from_entries_kernel, grid_for(n), dim3(T), 0, s, keys, vals, blkOfEntry, n, Pf, colind, blkrow, prod_ptr, prod_ea, prod_eb);
+	if (n == 0) return;
+	if (!seedScan) hipLaunchKernelGGL(blocks_from_entries_kernel, grid_for(n), dim3(T), 0, s, keys, vals, blkOfEntry, n, nSeeds, colind, blkrow, prod_ptr, prod_ea, prod_eb);
+	else hipLaunchKernelGGL(blocks_from_entries_seeded_kernel, grid_for(n), dim3(T), 0, s, keys, vals, blkOfEntry, n, nSeeds, seedScan, colind, blkrow, prod_ptr, prod_ea, prod_eb);
 }
 
 void launch_segment_subrange(const int* ptr, int nseg, const int* vals, int vlo, int vhi, int* beg, int* end, hipStream_t s)

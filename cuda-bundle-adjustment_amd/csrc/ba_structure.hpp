@@ -55,11 +55,15 @@ void launch_copy_u32_to_int(const uint32_t* in, int* out, int n, hipStream_t s);
 void launch_gather_int(const int* idx, const int* src, size_t n, int* dst, hipStream_t s);     // dst[i] = src[idx[i]]
 // pattern entries: Pf diagonal seeds first, then every pair (a < c) of free-pose edges of every free landmark in
 // product-id order: key = row << 32 | column, value = (edge a + 1) << 32 | (edge c + 1), 0 for a seed
+// extraSeeds[nExtra] (optional): keys of further, off-diagonal seeds -- the pose pairs of the relative-pose edges --, placed behind the
+// diagonal ones
 void launch_pattern_entries(const int* lm_ptr, const int* e_pose, const int* e_lm, const int* nfree, const long long* pairBase,
-	int E, int Lf, int Pf, uint64_t* keys, uint64_t* vals, hipStream_t s);
+	int E, int Lf, int Pf, uint64_t* keys, uint64_t* vals, const uint64_t* extraSeeds, int nExtra, hipStream_t s);
+void launch_seed_flags(const uint64_t* vals, size_t n, int* flag, hipStream_t s);      // 1 for a seed entry
 void launch_entry_heads(const uint64_t* keys, size_t n, int* head, hipStream_t s);
 // blocks and product lists from the sorted entries (blkOfEntry = inclusive scan of the head flags)
-void launch_blocks_from_entries(const uint64_t* keys, const uint64_t* vals, const int* blkOfEntry, size_t n, int Pf,
+// seedScan: inclusive scan of the seed flags of the sorted entries, or null when the nSeeds seeds are the diagonal ones only
+void launch_blocks_from_entries(const uint64_t* keys, const uint64_t* vals, const int* blkOfEntry, size_t n, int nSeeds, const int* seedScan,
 	int* colind, int* blkrow, int* prod_ptr, int* prod_ea, int* prod_eb, hipStream_t s);
 // blocks with products, longest list first (stable): sort keys + values; counters[CNT_NOD] = their number
 // counters[CNT_FARBLOCKS] = number of blocks more than farOffset block columns off the diagonal (pose order check)

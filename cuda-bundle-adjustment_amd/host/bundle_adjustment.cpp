@@ -127,6 +127,7 @@ public:
 		const std::vector<BaseEdge*> incident(it->second->edges.begin(), it->second->edges.end());
 		for (BaseEdge* e : incident) removeEdge(e);
 		priors_.erase(std::remove_if(priors_.begin(), priors_.end(), [&](const PosePrior* p) { return p->vertex == it->second; }), priors_.end());
+		relEdges_.erase(std::remove_if(relEdges_.begin(), relEdges_.end(), [&](const RelativePoseEdge* e) { return e->vertexI == it->second || e->vertexJ == it->second; }), relEdges_.end());
 		poses_.erase(it);
 		posesDirty_ = true;
 	}
@@ -167,6 +168,7 @@ public:
 	{
 		covPoseIndex_.clear(); covLmIndex_.clear();          // (marginal covariances describe the graph they were computed on)
 		priorsDirty_ = true;                                 // (the priors as they stand now go to the device with the next solve)
+		relDirty_ = true;                                    // (so do the relative-pose edges)
 		const auto t0 = std::chrono::steady_clock::now();
 		static const bool dbg = std::getenv("CUBA_HIP_DEBUG") != nullptr;
 		auto tl = t0;
@@ -347,6 +349,10 @@ public:
 				static_cast<int>(activeLandmarks_.size()), numFreeLandmarks_, q_.data(), t_.data(), cam_.data(), Xw_.data(),
 				static_cast<int>(activeEdges_.size()), edgePose_.data(), edgeLandmark_.data(), edgeDim_.data(), meas_.data(), omega_.data()),
 				"cuba_hip_set_graph_begin");
+			// (an upload clears the handle's relative-pose edges; their pose pairs are part of the block pattern, so they go up before the
+			// structure analysis: an unchanged pair set then keeps the structure of the previous initialize())
+			relOnDevice_ = false; relDirty_ = true;
+			uploadRelativePoseEdges();
 			check(cuba_hip_build_structure(solver_), "cuba_hip_build_structure");
 			check(cuba_hip_set_graph_end(solver_), "cuba_hip_set_graph_end");
 			graphDirty_ = false;
@@ -356,6 +362,47 @@ public:
 		}
 		lap("create + set_graph");
 		uploadPriors();
+		uploadRelativePoseEdges();
+	}
+
+	// ---- relative-pose edges (extension: cuba::addRelativePoseEdge) ----------------------------------
+	void addRelativePoseEdge(RelativePoseEdge* e)
+	{
+		if (!e || !e->vertexI || !e->vertexJ || e->vertexI == e->vertexJ) throw std::invalid_argument("cuba::addRelativePoseEdge: an edge needs two different pose vertices");
+		if (std::find(relEdges_.begin(), relEdges_.end(), e) == relEdges_.end()) relEdges_.push_back(e);
+	}
+	void removeRelativePoseEdge(RelativePoseEdge* e) { relEdges_.erase(std::remove(relEdges_.begin(), relEdges_.end(), e), relEdges_.end()); }
+	double relativePoseChiSquared(const RelativePoseEdge* e) const
+	{
+		const auto it = relChi_.find(e);
+		return it == relChi_.end() ? 0.0 : it->second;
+	}
+	// (only when such edges exist -- or existed at the last initialize(), which then clears them on the device)
+	void uploadRelativePoseEdges()
+	{
+		if (!relDirty_) return;
+		relDirty_ = false;
+		relChi_.clear();
+		uploadedRel_.clear();
+		if (relEdges_.empty() && !relOnDevice_) return;
+		std::map<const PoseVertex*, int> poseIdx;
+		for (size_t i = 0; i < activePoses_.size(); i++) poseIdx[activePoses_[i]] = (int)i;
+		const size_t n = relEdges_.size();
+		std::vector<int32_t> pi(n), pj(n);
+		std::vector<double> q(4 * n), t(3 * n), info(36 * n);
+		for (size_t k = 0; k < n; k++)
+		{
+			const RelativePoseEdge* e = relEdges_[k];
+			const auto a = poseIdx.find(e->vertexI), b = poseIdx.find(e->vertexJ);
+			if (a == poseIdx.end() || b == poseIdx.end()) throw std::invalid_argument("cuba::addRelativePoseEdge: a vertex of a relative-pose edge is not part of the graph");
+			pi[k] = a->second; pj[k] = b->second;
+			for (int i = 0; i < 4; i++) q[4 * k + i] = e->q.coeffs().data()[i];
+			for (int i = 0; i < 3; i++) t[3 * k + i] = e->t.data()[i];
+			std::copy(e->information.begin(), e->information.end(), info.begin() + 36 * k);
+		}
+		check(cuba_hip_set_relative_pose_edges(solver_, (int)n, pi.data(), pj.data(), q.data(), t.data(), info.data()), "cuba_hip_set_relative_pose_edges");
+		relOnDevice_ = n > 0;
+		uploadedRel_ = relEdges_;
 	}
 
 	// ---- pose priors (extension: cuba::addPosePrior) ------------------------------------------------
@@ -480,6 +527,12 @@ public:
 			check(cuba_hip_prior_chi_squares(solver_, pc.data()), "cuba_hip_prior_chi_squares");
 			for (size_t k = 0; k < pc.size(); k++) priorChi_[uploadedPriors_[k]] = pc[k];
 		}
+		if (!uploadedRel_.empty())
+		{
+			std::vector<double> rc(uploadedRel_.size());
+			check(cuba_hip_relative_pose_chi_squares(solver_, rc.data()), "cuba_hip_relative_pose_chi_squares");
+			for (size_t k = 0; k < rc.size(); k++) relChi_[uploadedRel_[k]] = rc[k];
+		}
 
 		// finalize (ref :512-526): estimates back into the caller's vertices
 		check(cuba_hip_get_solution(solver_, q_.data(), t_.data(), Xw_.data()), "cuba_hip_get_solution");
@@ -526,6 +579,7 @@ public:
 		covPoseIndex_.clear(); covLmIndex_.clear();
 		poses_.clear(); landmarks_.clear(); mono_.clear(); stereo_.clear(); stats_.clear();
 		priors_.clear(); priorChi_.clear();
+		relEdges_.clear(); relChi_.clear();
 		posesDirty_ = landmarksDirty_ = edgesDirty_ = true;
 		initialized_ = false;
 	}
@@ -651,6 +705,9 @@ private:
 	std::vector<PosePrior*> priors_, uploadedPriors_;     // in the caller's order; the set the last initialize() handed to the device
 	bool priorsOnDevice_ = false, priorsDirty_ = false;
 	std::map<const PosePrior*, double> priorChi_;
+	std::vector<RelativePoseEdge*> relEdges_, uploadedRel_;   // as priors_ / uploadedPriors_
+	bool relOnDevice_ = false, relDirty_ = false;
+	std::map<const RelativePoseEdge*, double> relChi_;
 	std::vector<LandmarkVertex*> activeLandmarks_;
 	std::vector<BaseEdge*> activeEdges_;
 	int numFreePoses_ = 0, numFreeLandmarks_ = 0;
@@ -768,6 +825,26 @@ double priorChiSquared(const CudaBundleAdjustment* object, const PosePrior* prio
 {
 	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
 	return impl ? impl->priorChiSquared(prior) : 0.0;
+}
+
+// Extension (g2o's binary SE(3) edge): relative-pose edges, effective at the next initialize() (cuba_hip_set_relative_pose_edges)
+void addRelativePoseEdge(CudaBundleAdjustment* object, RelativePoseEdge* edge)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (!impl) throw std::runtime_error("cuba::addRelativePoseEdge: not an object of this library");
+	impl->addRelativePoseEdge(edge);
+}
+
+void removeRelativePoseEdge(CudaBundleAdjustment* object, RelativePoseEdge* edge)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (impl) impl->removeRelativePoseEdge(edge);
+}
+
+double relativePoseChiSquared(const CudaBundleAdjustment* object, const RelativePoseEdge* edge)
+{
+	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
+	return impl ? impl->relativePoseChiSquared(edge) : 0.0;
 }
 
 }  // namespace cuba

@@ -125,4 +125,23 @@ void addPosePrior(CudaBundleAdjustment* object, PosePrior* prior);
 void removePosePrior(CudaBundleAdjustment* object, PosePrior* prior);
 double priorChiSquared(const CudaBundleAdjustment* object, const PosePrior* prior);
 
+// Extension (g2o's binary SE(3) edge; include/cuba_hip.h, cuba_hip_set_relative_pose_edges): a relative-pose edge between two different
+// pose vertices -- odometry, IMU pre-integration, loop closures.  (q, t) is the measured relative pose T_j T_i^-1 of the world -> camera
+// poses of `vertexI` and `vertexJ` (it maps camera-i coordinates to camera-j coordinates); `information` is symmetric 6 x 6, column-major,
+// in the tangent [omega, upsilon] of the pose update.  Objective term r^T Omega r with r = log(T_j T_i^-1 Zbar^-1), no robust kernel.
+// Ownership and lifetime as for PosePrior: the caller owns the edge; additions, removals and changes take effect at the next
+// initialize(); both vertices must be part of the graph then.  removePoseVertex drops the vertex's relative-pose edges, clear() all.
+// relativePoseChiSquared: r^T Omega r at the estimate of the last optimize() (0 before one, and for an edge between two fixed vertices).
+struct RelativePoseEdge
+{
+	PoseVertex* vertexI = nullptr;
+	PoseVertex* vertexJ = nullptr;
+	PoseVertex::Rotation q;
+	PoseVertex::Translation t;
+	std::array<double, 36> information{};
+};
+void addRelativePoseEdge(CudaBundleAdjustment* object, RelativePoseEdge* edge);
+void removeRelativePoseEdge(CudaBundleAdjustment* object, RelativePoseEdge* edge);
+double relativePoseChiSquared(const CudaBundleAdjustment* object, const RelativePoseEdge* edge);
+
 }  // namespace cuba

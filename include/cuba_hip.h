@@ -385,6 +385,38 @@ int cuba_hip_compute_covariance_pairs(cuba_hip_solver* s, int n, const int32_t* 
 int cuba_hip_set_pose_priors(cuba_hip_solver* s, int n, const int32_t* pose, const double* q, const double* t, const double* info);
 int cuba_hip_prior_chi_squares(cuba_hip_solver* s, double* chi2_per_prior);
 
+/* ---- SE(3) relative-pose edges (g2o's binary SE(3) edge: odometry, loop closures; the reference has no counterpart) ------------------
+   An edge names two DIFFERENT poses i, j (the caller's solver numbering, 0 <= i, j < Pt), a measured relative pose Zbar = (q, t) of
+   T_j T_i^-1 (world -> camera poses, so Zbar maps camera-i coordinates to camera-j coordinates; quaternion (x, y, z, w), normalised by the
+   library) and a 6 x 6 information matrix Omega (symmetric, column-major, [omega, upsilon] order of the pose update T <- exp(d) T, the
+   tangent cuba_hip_compute_covariance reports in).
+     residual     r = log(T_j T_i^-1 Zbar^-1)
+     objective    r^T Omega r, no robust kernel; the LM objective F (cuba_hip_optimize's chi2, cuba_hip_compute_errors, the gain ratio) is the
+                  robust edge sum plus the prior sum plus the relative-pose sum
+     linearised   exactly under the solver's update: with M = T_j T_i^-1 = [R_M | t_M] and Ad(M) = [[R_M, 0], [[t_M]x R_M, R_M]],
+                  J_j = dr/dd_j = J_l(r)^-1 and J_i = dr/dd_i = -J_l(r)^-1 Ad(M).  Hpp_ii += J_i^T Omega J_i, Hpp_jj += J_j^T Omega J_j,
+                  Hpp_ij += J_i^T Omega J_j, bp_i += -J_i^T Omega r, bp_j += -J_j^T Omega r; the same terms in the reduced system (Hsc, bsc);
+                  the maximum diagonal of lambda_0 includes them.
+   Unlike a prior, an edge between two free poses owns an off-diagonal block of the reduced system: the set of distinct free-free pairs is
+   part of the topology.  The structure is rebuilt (lazily, at the next call that needs it) exactly when that set differs from the one the
+   current structure was built with -- new values on the same pairs, or cuba_hip_set_graph on an unchanged topology followed by the same
+   pairs, keep it; cuba_hip_get_counter "structure_builds" counts the builds.
+   With one end fixed the edge acts on the free end only (it equals a prior Zbar T_i on pose j); with both fixed it is accepted and
+   ignored (chi2 0).  Several edges on one pair are summed in the caller's order.  A free pose held by relative-pose edges alone is legal.
+   Every solve path honours the edges: the device-decision loop, the host loop, both PCG forms, the exact solver, the fp32 library, mixed
+   precision, the covariances (a pair is a block of Hsc, so cuba_hip_get_covariance_blocks reports it).
+   cuba_hip_set_relative_pose_edges replaces the whole set (n = 0 clears it): pose_i[n], pose_j[n], q[4 n], t[3 n], info[36 n].  Valid any
+   time after cuba_hip_set_graph, which clears the set.  i == j, an index out of range, non-finite values or an information matrix that is
+   not symmetric (beyond 1e-9 of its largest entry; within it the two triangles are averaged): CUBA_HIP_ERR_INVALID_ARGUMENT, the handle
+   unchanged.  Refused with CUBA_HIP_ERR_STATE, the handle staying usable: a landmark-partitioned handle (and cuba_hip_set_partition on a
+   handle with such edges, hence the multi-GPU driver) and a graph without reprojection edges.  Setting the edges drops the run-to-run
+   memories of option "heuristics" as a new graph does.  A handle with such edges takes part in cuba_hip_optimize_batch through the path
+   that batches the PCG iterations only (results stay bit-identical to solo runs).
+   cuba_hip_relative_pose_chi_squares: r^T Omega r of every edge at the current estimate, in the caller's order (to gate loop closures). */
+int cuba_hip_set_relative_pose_edges(cuba_hip_solver* s, int n, const int32_t* pose_i, const int32_t* pose_j, const double* q, const double* t,
+	const double* info);
+int cuba_hip_relative_pose_chi_squares(cuba_hip_solver* s, double* chi2_per_edge);
+
 /* ---- introspection (parity tests) and multi-GPU plumbing ------------------------------------------ */
 
 /* Structure of the reduced system: upper-triangular BSR (replaces the accessors of
