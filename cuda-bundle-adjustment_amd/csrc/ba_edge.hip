@@ -46,16 +46,14 @@ __global__ __launch_bounds__(256) void residual_chi2_kernel(DeviceGraph g, Scala
 	residual_chi2_body(g, parts, per_edge, blockIdx.x, gridDim.x);
 }
 
-void launch_residual_chi2(const DeviceGraph& g, Scalar* parts, Scalar* slots, Scalar* per_edge, hipStream_t st, const DevicePriors* pr, const DeviceRelPoses* rp)
+void launch_residual_chi2(const DeviceGraph& g, Scalar* parts, Scalar* slots, Scalar* per_edge, hipStream_t st, const DevicePoseFactors* pf)
 {
 	const int n = g.e_end - g.e_begin;
 	const int grid = n > 0 ? min((n + 255) / 256, 2048) : 0;
 	if (grid > 0) hipLaunchKernelGGL(residual_chi2_kernel, dim3(grid), dim3(256), 0, st, g, parts, per_edge);
-	const int nPr = prior_chi2_parts(pr);
-	if (nPr > 0) launch_prior_chi2(g, *pr, parts + grid, st);
-	const int nRp = relpose_chi2_parts(rp);
-	if (nRp > 0) launch_relpose_chi2(g, *rp, parts + grid + nPr, st);
-	launch_reduce_parts(parts, grid + nPr + nRp, slots, st);
+	const int nPf = pose_factor_chi2_parts(pf);
+	if (nPf > 0) launch_pose_factor_chi2(g, *pf, parts + grid, st);
+	launch_reduce_parts(parts, grid + nPf, slots, st);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -624,31 +622,29 @@ __global__ __launch_bounds__(256) void big_trial_tail_kernel(DeviceGraph g, Devi
 	if (threadIdx.x == 0) chiParts[blockIdx.x] = (rsh[0] + rsh[1]) + (rsh[2] + rsh[3]);
 }
 
-size_t trial_tail_parts(const DeviceGraph& g, const DeviceStructure& st, int priorParts)
+size_t trial_tail_parts(const DeviceGraph& g, const DeviceStructure& st, int factorParts)
 {
 	const size_t a = (size_t)(st.nWaves + LIN_BLOCK / WAVE - 1) / (LIN_BLOCK / WAVE) + st.nBig;
 	const size_t nA = (a + 63) / 64 * 64;
-	return nA + (a + priorParts + 63) / 64 * 64 + 4 * 256 + 64;
+	return nA + (a + factorParts + 63) / 64 * 64 + 4 * 256 + 64;
 }
 
 void launch_trial_tail_fused(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, Scalar lambda, const Scalar* old, hipStream_t s,
-	const LmDevice* decide, const DevicePriors* pr, const DeviceRelPoses* rp)
+	const LmDevice* decide, const DevicePoseFactors* pf)
 {
 	const int nLm = (st.nWaves + LIN_BLOCK / WAVE - 1) / (LIN_BLOCK / WAVE);
 	const int nA = nLm + st.nBig;
-	const int nRp = relpose_chi2_parts(rp);
-	const int nPr = prior_chi2_parts(pr) + nRp;      // (all the partials that follow the edges')
+	const int nPf = pose_factor_chi2_parts(pf);      // (the partials that follow the edges')
 	Scalar* scParts = sys.parts;
 	Scalar* chiParts = sys.parts + (size_t)(nA + 63) / 64 * 64;
-	Scalar* scaleParts = chiParts + (size_t)(nA + nPr + 63) / 64 * 64;
+	Scalar* scaleParts = chiParts + (size_t)(nA + nPf + 63) / 64 * 64;
 	const int poseBlocks = (g.Pf + LIN_BLOCK - 1) / LIN_BLOCK;
 	const int nScale = g.Pf > 0 ? min((g.Pf * 6 + 255) / 256, 256) : 0;
 	if (nLm + poseBlocks + nScale > 0)
 		hipLaunchKernelGGL(trial_tail_kernel, dim3(nLm + poseBlocks + nScale), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, old, scParts, chiParts, nLm, poseBlocks, scaleParts, nScale);
 	if (st.nBig > 0) hipLaunchKernelGGL(big_trial_tail_kernel, dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, old, scParts + nLm, chiParts + nLm);
-	if (nPr > nRp) launch_prior_chi2(g, *pr, chiParts + nA, s);          // (at the poses the edge pass has just updated)
-	if (nRp > 0) launch_relpose_chi2(g, *rp, chiParts + nA + (nPr - nRp), s);
-	hipLaunchKernelGGL(reduce_report_kernel, dim3(1), dim3(1024), 0, s, sys, scParts, nA, sys.slots + NSLOT, chiParts, nA + nPr, sys.slots, scaleParts, 4 * nScale, sys.slots + 3 * NSLOT,
+	if (nPf > 0) launch_pose_factor_chi2(g, *pf, chiParts + nA, s);          // (at the poses the edge pass has just updated)
+	hipLaunchKernelGGL(reduce_report_kernel, dim3(1), dim3(1024), 0, s, sys, scParts, nA, sys.slots + NSLOT, chiParts, nA + nPf, sys.slots, scaleParts, 4 * nScale, sys.slots + 3 * NSLOT,
 		decide ? decide->state : (double*)nullptr, decide ? decide->lam : (Scalar*)nullptr, decide ? decide->ring : (double*)nullptr);
 }
 

@@ -1,4 +1,4 @@
-// ba_kernels.hpp -- launch interface of the gfx950 kernels (implemented in ba_edge.hip, ba_linearize.hip, ba_pcg.hip, ba_coarse.hip, ba_prior.hip, ba_relpose.hip).
+// ba_kernels.hpp -- launch interface of the gfx950 kernels (implemented in ba_edge.hip, ba_linearize.hip, ba_pcg.hip, ba_coarse.hip, ba_posefactor.hip).
 //
 // Device data model (all SoA, fp64 + int32):
 //   poses      q[4*Pt] t[3*Pt] cam[5*Pt]          free poses [0,Pf) first, fixed after
@@ -136,7 +136,7 @@ struct DeviceSystem
 	int* lowpos = nullptr;     // [nblk] position of every off-diagonal block in that order (launch_build_lowpos)
 };
 
-// SE(3) pose priors (ba_prior.hip): r^T Omega r, r = log(T Tbar^-1) in the [omega, upsilon] tangent of the pose update.  Sorted by
+// SE(3) pose priors (ba_posefactor.hip): r^T Omega r, r = log(T Tbar^-1) in the [omega, upsilon] tangent of the pose update.  Sorted by
 // internal pose (stable: a pose's priors are contiguous and in the caller's order); priors on fixed poses come last and are ignored.
 struct DevicePriors
 {
@@ -149,16 +149,11 @@ struct DevicePriors
 	const Scalar* info = nullptr;  // [36 n] column-major
 	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 on fixed poses)
 };
-// J^T Omega J into the diagonal blocks of hsc (upper triangle), -J^T Omega r into bp and (mode 1) bsc, J = J_l(r)^-1: behind the Schur pass
-void launch_prior_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DevicePriors& pr, int mode, hipStream_t s);
-// per-prior chi2 into pr.chi, per-workgroup partial sums into parts[0 .. prior_chi2_parts(&pr))
-void launch_prior_chi2(const DeviceGraph& g, const DevicePriors& pr, Scalar* parts, hipStream_t s);
-int prior_chi2_parts(const DevicePriors* pr);     // 0 for no priors (pr null or empty), at most 64
 
-// SE(3) relative-pose edges (ba_relpose.hip): r^T Omega r, r = log(T_j T_i^-1 Zbar^-1), between two poses.  Sorted: the edges between two
+// SE(3) relative-pose edges (ba_posefactor.hip): r^T Omega r, r = log(T_j T_i^-1 Zbar^-1), between two poses.  Sorted: the edges between two
 // free poses first, stable by the block (min, max) of the internal pose pair (a block's edges contiguous, in the caller's order), then the
 // edges with one fixed end (they act on the free end only), then those with two (ignored).
-constexpr int REL_REC = 90;        // numbers of an edge's linearisation record (layout: ba_relpose.hip)
+constexpr int REL_REC = 90;        // numbers of an edge's linearisation record (layout: ba_posefactor.hip)
 struct DeviceRelPoses
 {
 	int n = 0;                     // edges
@@ -176,19 +171,22 @@ struct DeviceRelPoses
 	Scalar* rec = nullptr;         // [REL_REC n] linearisation records, number-major (number el of edge k at el n + k)
 	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 with both ends fixed)
 };
-// two launches behind the Schur pass and the priors': per-edge records, then their sums into hsc (diagonal blocks: upper triangle; mode 1: the
-// off-diagonal blocks of the pairs, stored whole where a block has no Schur products), bp and (mode 1) bsc
-void launch_relpose_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DeviceRelPoses& rp, int mode, hipStream_t s);
-// per-edge chi2 into rp.chi, per-workgroup partial sums into parts[0 .. relpose_chi2_parts(&rp))
-void launch_relpose_chi2(const DeviceGraph& g, const DeviceRelPoses& rp, Scalar* parts, hipStream_t s);
-int relpose_chi2_parts(const DeviceRelPoses* rp);     // 0 for no edges (rp null or empty), at most 64
+
+// The pose factors of a handle: what the rest of the library sees of the two kinds (a kind without factors: n = 0, nothing of it is launched).
+struct DevicePoseFactors { DevicePriors priors; DeviceRelPoses rel; };
+// behind the Schur pass, the priors first: J^T Omega J into the diagonal blocks of hsc (upper triangle), -J^T Omega r into bp and (mode 1)
+// bsc, J = J_l(r)^-1; then the edges in two launches: per-edge records, then their sums into hsc (diagonal blocks: upper triangle; mode 1:
+// the off-diagonal blocks of the pairs, stored whole where a block has no Schur products), bp and (mode 1) bsc
+void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DevicePoseFactors& pf, int mode, hipStream_t s);
+// per-factor chi2 into priors.chi / rel.chi, per-workgroup partial sums into parts[0 .. pose_factor_chi2_parts(&pf)): the priors' first, the
+// edges' behind them
+void launch_pose_factor_chi2(const DeviceGraph& g, const DevicePoseFactors& pf, Scalar* parts, hipStream_t s);
+int pose_factor_chi2_parts(const DevicePoseFactors* pf);     // 0 for no factors (pf null), at most 64 per kind
 
 // residual / robust chi2 over all edges -> sys.slots[0..NSLOT) (must be zeroed by the caller).
 // per_edge (optional, sorted edge order): non-robust omega*|r|^2.
-// pr, rp (optional): the priors' and then the relative-pose edges' chi2 partials follow the edges' and are summed with them (the objective F
-// of the LM loop)
-void launch_residual_chi2(const DeviceGraph& g, Scalar* parts, Scalar* slots, Scalar* per_edge, hipStream_t st, const DevicePriors* pr = nullptr,
-	const DeviceRelPoses* rp = nullptr);
+// pf (optional): the pose factors' chi2 partials follow the edges' and are summed with them (the objective F of the LM loop)
+void launch_residual_chi2(const DeviceGraph& g, Scalar* parts, Scalar* slots, Scalar* per_edge, hipStream_t st, const DevicePoseFactors* pf = nullptr);
 
 // mode 0: assemble only (Hpp -> diagonal blocks of hsc, bp, Hll/bl -> lm_sys, max diagonal of Hll)
 // mode 1: full linearise + Schur reduction with damping lambda (hsc, bsc, bp, inv(Hll+lambda)/bl -> lm_sys)
@@ -215,11 +213,11 @@ void launch_pose_scale(const DeviceGraph& g, const DeviceSystem& sys, Scalar lam
 // [q | t | Xw] made before the trial: the pass reads the pre-update estimate from it while it writes the updated one), then the sums
 // + report.  trial_tail_parts(): numbers of partial-sum scratch (sys.parts) it needs.
 struct LmDevice;
-// pr, rp (optional): the priors' / relative-pose edges' chi2 at the updated poses, launches between the edge pass and the sums; their partials join
-// the edges' chi2 partials
+// pf (optional): the pose factors' chi2 at the updated poses, launches between the edge pass and the sums; their partials join the edges'
+// chi2 partials
 void launch_trial_tail_fused(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, Scalar lambda, const Scalar* old, hipStream_t s,
-	const LmDevice* decide = nullptr, const DevicePriors* pr = nullptr, const DeviceRelPoses* rp = nullptr);
-size_t trial_tail_parts(const DeviceGraph& g, const DeviceStructure& st, int priorParts = 0);      // priorParts: the priors' + the relative-pose edges' partials
+	const LmDevice* decide = nullptr, const DevicePoseFactors* pf = nullptr);
+size_t trial_tail_parts(const DeviceGraph& g, const DeviceStructure& st, int factorParts = 0);      // factorParts: pose_factor_chi2_parts()
 // Device-resident LM decision (control flow of CudaBundleAdjustmentImpl::optimize, /root/reference/src/cuda_bundle_adjustment.cpp:816-851):
 // state = {F, lambda, nu, halt, trials, accepted (last trial), rejections in a row, max rejections} in device memory, lam = the damping as
 // the kernels read it (sys.lam_dev), ring = device-mapped host records, LM_REC numbers per trial {Fhat, denominator, rho, next lambda,

@@ -143,7 +143,7 @@ double cuba_hip_solver::computeErrors()
 {
 	need();
 	StageTimer tm(this, 2);
-	launch_residual_chi2(g, d_parts.data(), slotsDev, nullptr, stream, priors(), relPoses());   // its second stage writes all NSLOT entries of the slot group
+	launch_residual_chi2(g, d_parts.data(), slotsDev, nullptr, stream, poseFactors());   // its second stage writes all NSLOT entries of the slot group
 	return readSlots(0);
 }
 
@@ -155,8 +155,7 @@ void cuba_hip_solver::linearize(int mode, double lam, bool withBackup)
 	if (parts && !partsByCaller)
 		for (size_t c = 1; c < redParts.size(); c++) launch_block_pass(g, st, sys, redParts[c].od, stream);
 	// (a launch of its own: the Schur pass's block part may still update a diagonal block its pose part stored)
-	if (priors()) launch_prior_linearize(g, st, sys, pri, mode, stream);
-	if (relPoses()) launch_relpose_linearize(g, st, sys, rel, mode, stream);
+	if (poseFactors()) launch_pose_factor_linearize(g, st, sys, pf, mode, stream);
 }
 
 void cuba_hip_solver::schurPart(int part, size_t ranges[4])
@@ -753,7 +752,7 @@ bool cuba_hip_solver::lmAfterSolveHost(LmRun& r)
 bool cuba_hip_solver::lmAfterSolve(LmRun& r, bool ok)
 {
 	if (!lmAfterSolveHost(r)) return false;
-	if (ok) launch_trial_tail_fused(g, st, sys, (Scalar)-1, d_backup.data(), stream, &r.lm, priors(), relPoses());
+	if (ok) launch_trial_tail_fused(g, st, sys, (Scalar)-1, d_backup.data(), stream, &r.lm, poseFactors());
 	else launch_lm_decide_failed(sys, r.lm, stream);
 	noteReport();
 	launch_restore_if_rejected(d_state.data(), d_backup.data(), d_state.size(), r.lm, stream);
@@ -785,12 +784,12 @@ int cuba_hip_solver::optimizeDeviceDecision(int niter, double* chi2Out)
 // every launch of a trial batched (one stream for all graphs): the standard launch sequence only
 bool cuba_hip_solver::fullyBatchable() const
 {
-	return batchable() && st.nBig == 0 && st.nDiagProd == 0 && st.nOd > 0 && st.nWaves > 0 && redParts.empty() && h_priorPose.empty() && h_relI.empty();
+	return batchable() && st.nBig == 0 && st.nDiagProd == 0 && st.nOd > 0 && st.nWaves > 0 && redParts.empty() && !poseFactors();
 }
 
 bool cuba_hip_solver::batchable() const
 {
-	return !profile && partHi < 0 && Pf > 0 && Lf > 0 && E > 0 && trial_tail_parts(g, st, extraChiParts()) <= d_parts.size() && batch_kernel_class(g, sys) >= 0;
+	return !profile && partHi < 0 && Pf > 0 && Lf > 0 && E > 0 && trial_tail_parts(g, st, poseFactorParts()) <= d_parts.size() && batch_kernel_class(g, sys) >= 0;
 }
 
 // The overlapped coarse inversions a batch's handles decided on in this trial (solveBegin, `regular` schedule), enqueued together on
@@ -1128,7 +1127,7 @@ int cuba_hip_solver::optimize(int niter, double* chi2Out)
 	lap("optimize: structure ready");
 	// the default: the decision of every trial on the device, the trial's tail fused into one pass over the edges.  The host loop below
 	// serves the profiled run (every stage synchronises), landmark partitions (the sums need the other ranks) and the degenerate graphs.
-	if (!profile && partHi < 0 && Pf > 0 && Lf > 0 && E > 0 && trial_tail_parts(g, st, extraChiParts()) <= d_parts.size())
+	if (!profile && partHi < 0 && Pf > 0 && Lf > 0 && E > 0 && trial_tail_parts(g, st, poseFactorParts()) <= d_parts.size())
 		return optimizeDeviceDecision(niter, chi2Out);
 	coarseValid = false;          // a new LM run starts from a new lambda_0: never reuse the coarse inverse across runs
 	startRunHistory();
@@ -1186,7 +1185,7 @@ int cuba_hip_solver::optimize(int niter, double* chi2Out)
 
 void cuba_hip_solver::enqueueEvaluate(double lam, bool withScale)
 {
-	launch_residual_chi2(g, d_parts.data(), slotsDev, nullptr, stream, priors(), relPoses());
+	launch_residual_chi2(g, d_parts.data(), slotsDev, nullptr, stream, poseFactors());
 	if (withScale) launch_pose_scale(g, sys, lam, slotsDev + 3 * NSLOT, stream);
 	launch_pcg_report(sys, stream); noteReport();       // ticket behind the results (which the kernels wrote into the mapped host block)
 }

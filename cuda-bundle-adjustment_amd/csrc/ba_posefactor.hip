@@ -1,0 +1,640 @@
+// ba_posefactor.hip -- the pose factors: terms r^T Omega r of the objective on the SE(3) poses alone, r in the [omega, upsilon] tangent of
+// the solver's left-multiplicative update T <- exp(d) T (pose_exp_update), Omega a full symmetric 6 x 6 information.  Two kinds:
+//
+//   pose priors (cuba_hip_set_pose_priors): unary, r = log(T Tbar^-1), linearised with the exact derivative dr/dd =
+//     J_l(r)^-1.  A prior touches the diagonal 6 x 6 block of its pose in the reduced matrix and the pose's entries of bp / bsc only.
+//   relative-pose edges (cuba_hip_set_relative_pose_edges; section 7d): binary, r = log(T_j T_i^-1 Zbar^-1), dr/dd_j = J_l(r)^-1 and
+//     dr/dd_i = -J_l(r)^-1 Ad(T_j T_i^-1).  Such an edge owns an off-diagonal block of the reduced matrix: the set of free-free pairs seeds
+//     the block pattern (ba_setup.hip), and a pair that no landmark connects gets a block without Schur products, which only the kernels
+//     below write.
+//
+// The two kinds keep kernels of their own (a prior is not run as a one-ended edge: its sums would be taken in another order); they share the
+// device helpers below, the host-side validation, packing, upload and read-back, and one interface (ba_kernels.hpp: DevicePoseFactors).
+//
+//   prior_linearize_kernel     lane = free pose with priors: its priors in the caller's order, J^T Omega J / J^T Omega r summed in
+//                              registers, then added to the pose's diagonal block (upper triangle), bp and (mode 1) bsc -- one writer per
+//                              block, a launch of its own behind the Schur pass (which may still update a diagonal block the pose pass stored)
+//   relpose_linearize_kernel   lane = edge: r, J_i, J_j and the edge's record {J_i^T Omega J_i, J_j^T Omega J_j (upper triangles),
+//                              the cross term laid out as the block (min, max) of the internal pose pair stores it, J_i^T Omega r,
+//                              J_j^T Omega r}
+//   relpose_gather_kernel      lane = one number of the reduced system: an entry of an off-diagonal block with relative edges (the sum of
+//                              its edges' cross terms, added to what the Schur pass stored, or stored whole when the block has no products),
+//                              or an entry of a pose's diagonal block (upper triangle) / of bp and (mode 1) bsc, summed over the pose's
+//                              edges in the caller's order -- one writer per number, fixed order, no atomics; behind the Schur pass and the
+//                              priors' launch
+//   prior_chi2_kernel,         lane = factor: r^T Omega r at the current estimate into the per-factor output and into per-workgroup partials
+//   relpose_chi2_kernel        that the caller sums together with the reprojection edges' partials (fixed order, no atomics)
+//
+// Host side: the caller's two sets (validated, kept in the caller's numbering), the edges' pair set (part of the topology) and the upload
+// of either set in the internal pose order.
+#include "ba_solver.hpp"
+#include "ba_device.hpp"
+#include "ba_se3.hpp"
+
+namespace cubahip
+{
+
+constexpr int PRIOR_LIN_BLOCK = 64;
+constexpr int REL_LIN_BLOCK = 64;
+constexpr int REL_GATHER_BLOCK = 256;
+constexpr int CHI_BLOCK = 256;
+constexpr int CHI_MAX_GROUPS = 64;     // a chi2 launch's partials (a grid-stride loop beyond): they join the reprojection edges' partials
+// record of an edge: [0, 21) J_i^T Omega J_i, [21, 42) J_j^T Omega J_j (upper triangles, entry c (c + 1) / 2 + r), [42, 78) the cross block
+// (column-major, rows = the pose of smaller internal index), [78, 84) J_i^T Omega r, [84, 90) J_j^T Omega r
+constexpr int REL_HII = 0, REL_HJJ = 21, REL_HX = 42, REL_GI = 78, REL_GJ = 84;
+static_assert(REL_GJ + 6 == REL_REC, "record layout");
+constexpr int REL_POSE_NUMBERS = 27;        // 21 entries of a diagonal block + 6 of bp / bsc
+
+// ---- shared device helpers --------------------------------------------------------------------------------------------------------
+
+// pose `ip` of a [4 n] quaternion / [3 n] translation pair of arrays (the estimates, or a set's measurements)
+__device__ __forceinline__ void load_pose(const Scalar* qs, const Scalar* ts, int ip, Scalar q[4], Scalar t[3])
+{
+#pragma unroll
+	for (int i = 0; i < 4; i++) q[i] = qs[4 * (size_t)ip + i];
+#pragma unroll
+	for (int i = 0; i < 3; i++) t[i] = ts[3 * (size_t)ip + i];
+}
+
+// Omega r (Omega column-major) and r^T Omega r
+__device__ __forceinline__ Scalar info_times(const Scalar* O, const Scalar r[6], Scalar Or[6])
+{
+#pragma unroll
+	for (int i = 0; i < 6; i++) Or[i] = 0;
+#pragma unroll
+	for (int c = 0; c < 6; c++)
+#pragma unroll
+		for (int i = 0; i < 6; i++) Or[i] += O[6 * c + i] * r[c];
+	Scalar chi = 0;
+#pragma unroll
+	for (int i = 0; i < 6; i++) chi += r[i] * Or[i];
+	return chi;
+}
+
+// J = [[A, 0], [B, A]], or its negative
+__device__ __forceinline__ void se3_jacobian(const Scalar A[3][3], const Scalar B[3][3], Scalar J[6][6], bool negative = false)
+{
+#pragma unroll
+	for (int a = 0; a < 3; a++)
+#pragma unroll
+		for (int b = 0; b < 3; b++)
+		{
+			const Scalar x = negative ? -A[a][b] : A[a][b], y = negative ? -B[a][b] : B[a][b];
+			J[a][b] = x; J[a][3 + b] = 0; J[3 + a][b] = y; J[3 + a][3 + b] = x;
+		}
+}
+
+// the lanes' chi2 sums of a CHI_BLOCK workgroup -> its partial
+__device__ __forceinline__ void chi2_partial(Scalar acc, Scalar* __restrict__ parts)
+{
+	acc = wave_sum(acc);
+	__shared__ Scalar part[CHI_BLOCK / WAVE];
+	if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+	__syncthreads();
+	if (threadIdx.x == 0) parts[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
+}
+
+// workgroups (= partials) of a chi2 launch over n factors
+static int chi2_parts(int n) { return n > 0 ? std::min((n + CHI_BLOCK - 1) / CHI_BLOCK, CHI_MAX_GROUPS) : 0; }
+
+// ---- pose priors ------------------------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(PRIOR_LIN_BLOCK) void prior_linearize_kernel(DeviceGraph g, DeviceStructure st, DeviceSystem sys, DevicePriors pr, int mode)
+{
+	const int i = blockIdx.x * PRIOR_LIN_BLOCK + threadIdx.x;
+	if (i >= pr.nPoses) return;
+	const int ip = pr.pose_id[i];
+	Scalar q[4], t[3];
+	load_pose(g.q, g.t, ip, q, t);
+	Scalar H[21], gv[6];
+#pragma unroll
+	for (int k = 0; k < 21; k++) H[k] = 0;
+#pragma unroll
+	for (int k = 0; k < 6; k++) gv[k] = 0;
+	const int k1 = pr.pose_ptr[i + 1];
+	for (int k = pr.pose_ptr[i]; k < k1; k++)
+	{
+		Scalar qb[4], tb[3], r[6], A[3][3], B[3][3], J[6][6];
+		load_pose(pr.qbar, pr.tbar, k, qb, tb);
+		prior_residual(q, t, qb, tb, r, A);
+		prior_jacobian_b(r, A, B);
+		se3_jacobian(A, B, J);
+		const Scalar* O = pr.info + 36 * (size_t)k;
+		// H += J^T (Omega J), column by column (upper triangle, acc[c (c + 1) / 2 + r] as the pose pass stores it)
+#pragma unroll
+		for (int c = 0; c < 6; c++)
+		{
+			Scalar oj[6];
+#pragma unroll
+			for (int a = 0; a < 6; a++) oj[a] = 0;
+#pragma unroll
+			for (int m = 0; m < 6; m++)
+#pragma unroll
+				for (int a = 0; a < 6; a++) oj[a] += O[6 * m + a] * J[m][c];
+#pragma unroll
+			for (int rr = 0; rr <= c; rr++)
+			{
+				Scalar s = 0;
+#pragma unroll
+				for (int a = 0; a < 6; a++) s += J[a][rr] * oj[a];
+				H[c * (c + 1) / 2 + rr] += s;
+			}
+		}
+		Scalar Or[6];
+		(void)info_times(O, r, Or);
+#pragma unroll
+		for (int c = 0; c < 6; c++)
+		{
+			Scalar s = 0;
+#pragma unroll
+			for (int a = 0; a < 6; a++) s += J[a][c] * Or[a];
+			gv[c] += s;
+		}
+	}
+	Scalar* blk = sys.hsc + 36 * (size_t)st.hsc_rowptr[ip];
+#pragma unroll
+	for (int c = 0; c < 6; c++)
+	{
+#pragma unroll
+		for (int rr = 0; rr <= c; rr++) blk[c * 6 + rr] += H[c * (c + 1) / 2 + rr];
+		sys.bp[6 * (size_t)ip + c] -= gv[c];
+		if (mode == 1) sys.bsc[6 * (size_t)ip + c] -= gv[c];
+	}
+}
+
+__global__ __launch_bounds__(CHI_BLOCK) void prior_chi2_kernel(DeviceGraph g, DevicePriors pr, Scalar* __restrict__ parts)
+{
+	Scalar acc = 0;
+	for (int k = blockIdx.x * CHI_BLOCK + threadIdx.x; k < pr.n; k += gridDim.x * CHI_BLOCK)
+	{
+		const int ip = pr.pose[k];
+		Scalar chi = 0;
+		if (ip < g.Pf)
+		{
+			Scalar q[4], t[3], qb[4], tb[3], r[6], A[3][3], Or[6];
+			load_pose(g.q, g.t, ip, q, t);
+			load_pose(pr.qbar, pr.tbar, k, qb, tb);
+			prior_residual(q, t, qb, tb, r, A);
+			chi = info_times(pr.info + 36 * (size_t)k, r, Or);
+		}
+		pr.chi[k] = chi;
+		acc += chi;
+	}
+	chi2_partial(acc, parts);
+}
+
+// ---- relative-pose edges ----------------------------------------------------------------------------------------------------------
+
+// number `el` of the record of edge k: the records are stored number-major (all edges' number 0, then number 1, ...), so that the lanes of
+// the linearisation -- consecutive edges -- store to consecutive addresses
+__device__ __forceinline__ Scalar& rel_rec(const DeviceRelPoses& rp, int k, int el) { return rp.rec[(size_t)el * rp.n + k]; }
+
+// Hamilton product of (x, y, z, w) quaternions
+__device__ __forceinline__ void quat_mul(const Scalar a[4], const Scalar b[4], Scalar o[4])
+{
+	o[0] = a[3] * b[0] + b[3] * a[0] + (a[1] * b[2] - a[2] * b[1]);
+	o[1] = a[3] * b[1] + b[3] * a[1] + (a[2] * b[0] - a[0] * b[2]);
+	o[2] = a[3] * b[2] + b[3] * a[2] + (a[0] * b[1] - a[1] * b[0]);
+	o[3] = a[3] * b[3] - (a[0] * b[0] + a[1] * b[1] + a[2] * b[2]);
+}
+
+struct RelEnds { Scalar qi[4], ti[3], qj[4], tj[3]; };
+
+__device__ __forceinline__ void load_rel_ends(const DeviceGraph& g, const DeviceRelPoses& rp, int k, RelEnds& e)
+{
+	load_pose(g.q, g.t, rp.pose_i[k], e.qi, e.ti);
+	load_pose(g.q, g.t, rp.pose_j[k], e.qj, e.tj);
+}
+
+// r = log(T_j T_i^-1 Zbar^-1) = log(T_j (Zbar T_i)^-1): the priors' residual of pose j against Zbar T_i; A = J_w^-1
+__device__ __forceinline__ void rel_residual(const RelEnds& e, const DeviceRelPoses& rp, int k, Scalar r[6], Scalar A[3][3])
+{
+	Scalar qz[4], tz[3], qb[4], tb[3];
+	load_pose(rp.q, rp.t, k, qz, tz);
+	quat_mul(qz, e.qi, qb);
+	quat_rotate(qz, e.ti, tb);
+	tb[0] += tz[0]; tb[1] += tz[1]; tb[2] += tz[2];
+	prior_residual(e.qj, e.tj, qb, tb, r, A);
+}
+
+__global__ __launch_bounds__(REL_LIN_BLOCK) void relpose_linearize_kernel(DeviceGraph g, DeviceRelPoses rp)
+{
+	const int k = blockIdx.x * REL_LIN_BLOCK + threadIdx.x;
+	if (k >= rp.nActive) return;
+	RelEnds e;
+	load_rel_ends(g, rp, k, e);
+	Scalar r[6], A[3][3], B[3][3];
+	rel_residual(e, rp, k, r, A);
+	prior_jacobian_b(r, A, B);
+	// M = T_j T_i^-1 = [R_M | t_M]
+	Scalar qc[4] = { -e.qi[0], -e.qi[1], -e.qi[2], e.qi[3] }, qm[4], tM[3];
+	quat_mul(e.qj, qc, qm);
+	const Scalar inv = 1 / sqrt(qm[0] * qm[0] + qm[1] * qm[1] + qm[2] * qm[2] + qm[3] * qm[3]);
+#pragma unroll
+	for (int x = 0; x < 4; x++) qm[x] *= inv;
+	const Rot3 RM = quat_to_rot(qm[0], qm[1], qm[2], qm[3]);
+	quat_rotate(qm, e.ti, tM);
+	tM[0] = e.tj[0] - tM[0]; tM[1] = e.tj[1] - tM[1]; tM[2] = e.tj[2] - tM[2];
+	// J_j = [[A, 0], [B, A]],  J_i = -J_j Ad(M) = [[X, 0], [Y, X]],  X = -A R_M,  Y = -(B R_M + A [t_M]x R_M)
+	Scalar TM[3][3], TR[3][3], X[3][3], Y[3][3], BR[3][3], ATR[3][3];
+	hat3(tM, TM);
+	mul3(TM, RM.m, TR);
+	mul3(A, RM.m, X);
+	mul3(B, RM.m, BR);
+	mul3(A, TR, ATR);
+#pragma unroll
+	for (int a = 0; a < 3; a++)
+#pragma unroll
+		for (int b = 0; b < 3; b++) Y[a][b] = BR[a][b] + ATR[a][b];
+	Scalar Ji[6][6], Jj[6][6];
+	se3_jacobian(A, B, Jj);
+	se3_jacobian(X, Y, Ji, true);
+	const Scalar* O = rp.info + 36 * (size_t)k;
+	// the cross term J_i^T Omega J_j is the block (i, j); the block pattern stores (min, max) of the internal indices: transposed if i > j
+	const bool flip = rp.pose_i[k] > rp.pose_j[k];
+#pragma unroll
+	for (int c = 0; c < 6; c++)
+	{
+		Scalar oi[6], oj[6];
+#pragma unroll
+		for (int a = 0; a < 6; a++) { oi[a] = 0; oj[a] = 0; }
+#pragma unroll
+		for (int m = 0; m < 6; m++)
+#pragma unroll
+			for (int a = 0; a < 6; a++) { oi[a] += O[6 * m + a] * Ji[m][c]; oj[a] += O[6 * m + a] * Jj[m][c]; }
+#pragma unroll
+		for (int rr = 0; rr < 6; rr++)
+		{
+			Scalar sii = 0, sjj = 0, sx = 0;
+#pragma unroll
+			for (int a = 0; a < 6; a++) { sii += Ji[a][rr] * oi[a]; sjj += Jj[a][rr] * oj[a]; sx += Ji[a][rr] * oj[a]; }
+			if (rr <= c) { rel_rec(rp, k, REL_HII + c * (c + 1) / 2 + rr) = sii; rel_rec(rp, k, REL_HJJ + c * (c + 1) / 2 + rr) = sjj; }
+			rel_rec(rp, k, REL_HX + (flip ? rr * 6 + c : c * 6 + rr)) = sx;
+		}
+	}
+	Scalar Or[6];
+	(void)info_times(O, r, Or);
+#pragma unroll
+	for (int c = 0; c < 6; c++)
+	{
+		Scalar si = 0, sj = 0;
+#pragma unroll
+		for (int a = 0; a < 6; a++) { si += Ji[a][c] * Or[a]; sj += Jj[a][c] * Or[a]; }
+		rel_rec(rp, k, REL_GI + c) = si; rel_rec(rp, k, REL_GJ + c) = sj;
+	}
+}
+
+__global__ __launch_bounds__(REL_GATHER_BLOCK) void relpose_gather_kernel(DeviceStructure st, DeviceSystem sys, DeviceRelPoses rp, int mode)
+{
+	const int x = blockIdx.x * REL_GATHER_BLOCK + threadIdx.x;
+	const int nBlkNumbers = mode == 1 ? 36 * rp.nBlocks : 0;
+	if (x < nBlkNumbers)
+	{
+		const int b = x / 36, el = x - 36 * b;
+		const int blk = rp.blk_id[b];
+		Scalar s = 0;
+		const int k1 = rp.blk_ptr[b + 1];
+		for (int k = rp.blk_ptr[b]; k < k1; k++) s += rel_rec(rp, k, REL_HX + el);
+		Scalar* dst = sys.hsc + 36 * (size_t)blk + el;
+		// (a block with products was stored by the Schur pass of this linearisation; one without has no other writer)
+		*dst = st.prod_end[blk] > st.prod_beg[blk] ? *dst + s : s;
+		return;
+	}
+	const int y = x - nBlkNumbers;
+	const int p = y / REL_POSE_NUMBERS, el = y - REL_POSE_NUMBERS * p;
+	if (p >= rp.nPoses) return;
+	const int ip = rp.pose_id[p];
+	Scalar s = 0;
+	const int k1 = rp.pose_ptr[p + 1];
+	for (int k = rp.pose_ptr[p]; k < k1; k++)
+	{
+		const int item = rp.pose_item[k], side = item & 1;
+		s += rel_rec(rp, item >> 1, el < 21 ? (side ? REL_HJJ : REL_HII) + el : (side ? REL_GJ : REL_GI) + (el - 21));
+	}
+	if (el < 21)
+	{
+		// packed upper-triangle index -> (r, c)
+		int c = 0;
+		while ((c + 1) * (c + 2) / 2 <= el) c++;
+		const int rr = el - c * (c + 1) / 2;
+		sys.hsc[36 * (size_t)st.hsc_rowptr[ip] + c * 6 + rr] += s;
+	}
+	else
+	{
+		sys.bp[6 * (size_t)ip + (el - 21)] -= s;
+		if (mode == 1) sys.bsc[6 * (size_t)ip + (el - 21)] -= s;
+	}
+}
+
+__global__ __launch_bounds__(CHI_BLOCK) void relpose_chi2_kernel(DeviceGraph g, DeviceRelPoses rp, Scalar* __restrict__ parts)
+{
+	Scalar acc = 0;
+	for (int k = blockIdx.x * CHI_BLOCK + threadIdx.x; k < rp.n; k += gridDim.x * CHI_BLOCK)
+	{
+		Scalar chi = 0;
+		if (k < rp.nActive)
+		{
+			RelEnds e;
+			load_rel_ends(g, rp, k, e);
+			Scalar r[6], A[3][3], Or[6];
+			rel_residual(e, rp, k, r, A);
+			chi = info_times(rp.info + 36 * (size_t)k, r, Or);
+		}
+		rp.chi[k] = chi;
+		acc += chi;
+	}
+	chi2_partial(acc, parts);
+}
+
+// ---- launches ---------------------------------------------------------------------------------------------------------------------
+
+static void launch_prior_chi2(const DeviceGraph& g, const DevicePriors& pr, Scalar* parts, hipStream_t s)
+{
+	const int grid = chi2_parts(pr.n);
+	if (grid > 0) hipLaunchKernelGGL(prior_chi2_kernel, dim3(grid), dim3(CHI_BLOCK), 0, s, g, pr, parts);
+}
+
+static void launch_relpose_chi2(const DeviceGraph& g, const DeviceRelPoses& rp, Scalar* parts, hipStream_t s)
+{
+	const int grid = chi2_parts(rp.n);
+	if (grid > 0) hipLaunchKernelGGL(relpose_chi2_kernel, dim3(grid), dim3(CHI_BLOCK), 0, s, g, rp, parts);
+}
+
+int pose_factor_chi2_parts(const DevicePoseFactors* pf) { return pf ? chi2_parts(pf->priors.n) + chi2_parts(pf->rel.n) : 0; }
+
+void launch_pose_factor_chi2(const DeviceGraph& g, const DevicePoseFactors& pf, Scalar* parts, hipStream_t s)
+{
+	launch_prior_chi2(g, pf.priors, parts, s);
+	launch_relpose_chi2(g, pf.rel, parts + chi2_parts(pf.priors.n), s);
+}
+
+void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DevicePoseFactors& pf, int mode, hipStream_t s)
+{
+	const DevicePriors& pr = pf.priors;
+	if (pr.nPoses > 0) hipLaunchKernelGGL(prior_linearize_kernel, dim3((pr.nPoses + PRIOR_LIN_BLOCK - 1) / PRIOR_LIN_BLOCK), dim3(PRIOR_LIN_BLOCK), 0, s, g, st, sys, pr, mode);
+	const DeviceRelPoses& rp = pf.rel;
+	if (rp.nActive <= 0) return;
+	hipLaunchKernelGGL(relpose_linearize_kernel, dim3((rp.nActive + REL_LIN_BLOCK - 1) / REL_LIN_BLOCK), dim3(REL_LIN_BLOCK), 0, s, g, rp);
+	const size_t numbers = (mode == 1 ? (size_t)36 * rp.nBlocks : 0) + (size_t)REL_POSE_NUMBERS * rp.nPoses;
+	hipLaunchKernelGGL(relpose_gather_kernel, dim3((unsigned)((numbers + REL_GATHER_BLOCK - 1) / REL_GATHER_BLOCK)), dim3(REL_GATHER_BLOCK), 0, s, st, sys, rp, mode);
+}
+
+}  // namespace cubahip
+
+// ---- host side --------------------------------------------------------------------------------------------------------------------
+
+// the q | t | information of factor k of a caller's set into `v` (sized by the caller): finite, the quaternion normalised, the information
+// symmetric and symmetrised.  `what`, `kind`: how the messages name the factor's measurement ("prior" / "relative") and its kind
+static void take_factor_values(PoseFactorValues& v, int k, const double* q, const double* t, const double* info, const std::string& what, const std::string& kind)
+{
+	double nq = 0;
+	for (int i = 0; i < 4; i++) { if (!std::isfinite(q[4 * (size_t)k + i])) throw ArgError{ "non-finite " + what + " rotation" }; nq += q[4 * (size_t)k + i] * q[4 * (size_t)k + i]; }
+	nq = std::sqrt(nq);
+	if (!(nq > 0) || !std::isfinite(nq)) throw ArgError{ kind + " quaternion of zero norm" };
+	for (int i = 0; i < 4; i++) v.q[4 * (size_t)k + i] = q[4 * (size_t)k + i] / nq;
+	for (int i = 0; i < 3; i++) { if (!std::isfinite(t[3 * (size_t)k + i])) throw ArgError{ "non-finite " + what + " translation" }; v.t[3 * (size_t)k + i] = t[3 * (size_t)k + i]; }
+	const double* O = info + 36 * (size_t)k;
+	double m = 0;
+	for (int i = 0; i < 36; i++) { if (!std::isfinite(O[i])) throw ArgError{ "non-finite " + kind + " information" }; m = std::max(m, std::fabs(O[i])); }
+	for (int c = 0; c < 6; c++)
+		for (int r = 0; r < c; r++)
+			if (std::fabs(O[6 * c + r] - O[6 * r + c]) > 1e-9 * m) throw ArgError{ kind + " information is not symmetric" };
+	// (symmetrised: within the tolerance above the two triangles may differ by rounding; the kernels read both)
+	for (int c = 0; c < 6; c++)
+		for (int r = 0; r < 6; r++) v.info[36 * (size_t)k + 6 * c + r] = r == c ? O[6 * c + r] : 0.5 * (O[6 * c + r] + O[6 * r + c]);
+}
+
+static PoseFactorValues sized_factor_values(int n, bool binary)
+{
+	PoseFactorValues v;
+	v.pi.resize((size_t)n); v.pj.resize(binary ? (size_t)n : 0); v.q.resize((size_t)4 * n); v.t.resize((size_t)3 * n); v.info.resize((size_t)36 * n);
+	return v;
+}
+
+// a validated set replaces the handle's: its device copy is due, and the run-to-run memories that the values of the system feed go, as a
+// new graph drops them (a run after a change of the factors depends on the state and the factors only)
+static void adopt_factor_values(cuba_hip_solver& s, PoseFactorSet& set, PoseFactorValues&& v)
+{
+	set.v = std::move(v);
+	set.uploaded = false;
+	s.firstInvValid = false; s.firstInvPending = false; s.prevRunIters.clear(); s.runIters.clear(); s.firstSolveIters = 0;
+}
+
+void cuba_hip_solver::setPosePriors(int n, const int32_t* pose, const double* q, const double* t, const double* info)
+{
+	if (!haveGraph) throw StateError{ "set_graph must be called first" };
+	if (n < 0) throw ArgError{ "negative prior count" };
+	if (n > 0 && (partHi >= 0 || valuesPartial)) throw StateError{ "pose priors are not available on a landmark-partitioned handle" };
+	if (n > 0 && E == 0) throw StateError{ "pose priors need a graph with edges" };
+	if (n > 0 && (!pose || !q || !t || !info)) throw ArgError{ "null prior array" };
+	PoseFactorValues v = sized_factor_values(n, false);
+	for (int k = 0; k < n; k++)
+	{
+		if (pose[k] < 0 || pose[k] >= Pt) throw ArgError{ "prior pose index out of range" };
+		v.pi[k] = pose[k];
+		take_factor_values(v, k, q, t, info, "prior", "prior");
+	}
+	adopt_factor_values(*this, priorSet, std::move(v));
+	pf.priors = DevicePriors();
+}
+
+void cuba_hip_solver::setRelativePoseEdges(int n, const int32_t* pi, const int32_t* pj, const double* q, const double* t, const double* info)
+{
+	if (!haveGraph) throw StateError{ "set_graph must be called first" };
+	if (n < 0) throw ArgError{ "negative relative-pose edge count" };
+	if (n > 0 && (partHi >= 0 || valuesPartial)) throw StateError{ "relative-pose edges are not available on a landmark-partitioned handle" };
+	if (n > 0 && E == 0) throw StateError{ "relative-pose edges need a graph with reprojection edges" };
+	if (n > 0 && (!pi || !pj || !q || !t || !info)) throw ArgError{ "null relative-pose edge array" };
+	PoseFactorValues v = sized_factor_values(n, true);
+	for (int k = 0; k < n; k++)
+	{
+		if (pi[k] < 0 || pi[k] >= Pt || pj[k] < 0 || pj[k] >= Pt) throw ArgError{ "relative-pose edge: pose index out of range" };
+		if (pi[k] == pj[k]) throw ArgError{ "relative-pose edge between a pose and itself" };
+		v.pi[k] = pi[k]; v.pj[k] = pj[k];
+		take_factor_values(v, k, q, t, info, "relative", "relative-pose");
+	}
+	// the distinct free-free pairs (caller's numbering, smaller index first): part of the topology -- need() rebuilds the structure when
+	// they differ from the pairs the current one was seeded with
+	std::vector<uint64_t> pairs;
+	for (int k = 0; k < n; k++)
+		if (v.pi[k] < Pf && v.pj[k] < Pf) pairs.push_back(((uint64_t)(uint32_t)std::min(v.pi[k], v.pj[k]) << 32) | (uint32_t)std::max(v.pi[k], v.pj[k]));
+	std::sort(pairs.begin(), pairs.end());
+	pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+	h_relPairs.swap(pairs);
+	adopt_factor_values(*this, relSet, std::move(v));
+	pf.rel = DeviceRelPoses();
+	covBlocksValid = false;          // (the covariance blocks describe the edge set -- and the block pattern -- they were computed on)
+}
+
+std::vector<uint64_t> cuba_hip_solver::relSeedKeys() const
+{
+	std::vector<uint64_t> keys(h_relPairs.size());
+	for (size_t x = 0; x < keys.size(); x++)
+	{
+		int a = (int)(h_relPairs[x] >> 32), b = (int)(uint32_t)h_relPairs[x];
+		if (reorderActive) { a = poseNewOfOld[a]; b = poseNewOfOld[b]; }
+		keys[x] = ((uint64_t)(uint32_t)std::min(a, b) << 32) | (uint32_t)std::max(a, b);
+	}
+	std::sort(keys.begin(), keys.end());
+	return keys;
+}
+
+// set.order: the caller's factors stable by `key` (factors of equal key stay in the caller's order)
+static void sort_factors(PoseFactorSet& set, const std::vector<uint64_t>& key)
+{
+	set.order.resize(key.size());
+	std::iota(set.order.begin(), set.order.end(), 0);
+	std::stable_sort(set.order.begin(), set.order.end(), [&](int a, int b) { return key[a] < key[b]; });
+}
+
+// a set's index arrays (`ints`, laid out by the caller) and its values q | t | information in the sorted order -> device; the device
+// pointers of the values and of the per-factor chi2 come back through q, t, info, chi
+static void upload_factor_arrays(cuba_hip_solver& s, PoseFactorSet& set, const std::vector<int>& ints, const Scalar*& q, const Scalar*& t, const Scalar*& info, Scalar*& chi)
+{
+	const size_t n = set.order.size();
+	std::vector<Scalar> vals(43 * n);
+	Scalar* vq = vals.data(); Scalar* vt = vq + 4 * n; Scalar* vi = vt + 3 * n;
+	for (size_t p = 0; p < n; p++)
+	{
+		const size_t k = (size_t)set.order[p];
+		for (int i = 0; i < 4; i++) vq[4 * p + i] = (Scalar)set.v.q[4 * k + i];
+		for (int i = 0; i < 3; i++) vt[3 * p + i] = (Scalar)set.v.t[3 * k + i];
+		for (int i = 0; i < 36; i++) vi[36 * p + i] = (Scalar)set.v.info[36 * k + i];
+	}
+	set.d_ints.upload(ints, s.stream);
+	set.d_vals.upload(vals, s.stream);
+	set.d_chi.resize(std::max(n, (size_t)1));
+	q = set.d_vals.data(); t = q + 4 * n; info = t + 3 * n;
+	chi = set.d_chi.data();
+	s.sync();          // (the staging vectors go out of scope)
+	set.uploaded = true;
+}
+
+static std::vector<int> concat(std::initializer_list<const std::vector<int>*> parts)
+{
+	std::vector<int> out;
+	for (const std::vector<int>* p : parts) out.insert(out.end(), p->begin(), p->end());
+	return out;
+}
+
+// the caller's priors -> device, in the internal pose order (stable by internal pose: every pose's priors contiguous, in the caller's order)
+static void upload_priors(cuba_hip_solver& s)
+{
+	PoseFactorSet& set = s.priorSet;
+	const int n = set.n(), Pf = s.Pf;
+	std::vector<uint64_t> internal((size_t)n);
+	for (int k = 0; k < n; k++) internal[k] = (uint64_t)s.internalPose(set.v.pi[k]);
+	sort_factors(set, internal);
+	std::vector<int> ptr, ids, poses((size_t)n);
+	for (int p = 0; p < n; p++)
+	{
+		poses[p] = (int)internal[set.order[p]];
+		if (poses[p] < Pf && (ids.empty() || ids.back() != poses[p])) { ids.push_back(poses[p]); ptr.push_back(p); }
+	}
+	int nFree = 0;
+	while (nFree < n && poses[nFree] < Pf) nFree++;
+	ptr.push_back(nFree);
+	const int np = (int)ids.size();
+	DevicePriors pr;
+	upload_factor_arrays(s, set, concat({ &ptr, &ids, &poses }), pr.qbar, pr.tbar, pr.info, pr.chi);
+	pr.n = n; pr.nPoses = np;
+	pr.pose_ptr = set.d_ints.data(); pr.pose_id = pr.pose_ptr + (np + 1); pr.pose = pr.pose_id + np;
+	s.pf.priors = pr;
+}
+
+// the caller's edges -> device, in the internal pose order: free-free edges first, stable by the block (min, max) of the internal pair -- a
+// block's edges contiguous and in the caller's order --, then the edges with one fixed end, then (inactive) those with two
+static void upload_relative_pose_edges(cuba_hip_solver& s)
+{
+	PoseFactorSet& set = s.relSet;
+	const int n = set.n(), Pf = s.Pf;
+	std::vector<int> a((size_t)n), b((size_t)n);
+	std::vector<uint64_t> key((size_t)n);
+	for (int k = 0; k < n; k++)
+	{
+		a[k] = s.internalPose(set.v.pi[k]); b[k] = s.internalPose(set.v.pj[k]);
+		const int nFixed = (a[k] >= Pf) + (b[k] >= Pf);
+		key[k] = nFixed == 0 ? (((uint64_t)(uint32_t)std::min(a[k], b[k]) << 32) | (uint32_t)std::max(a[k], b[k])) : (~0ull - (uint64_t)(2 - nFixed));
+	}
+	sort_factors(set, key);
+	std::vector<int> posOf((size_t)n);
+	for (int p = 0; p < n; p++) posOf[set.order[p]] = p;
+	s.ensureHostPattern();
+	std::vector<int> si((size_t)n), sj((size_t)n), blkPtr, blkId;
+	int nActive = 0;
+	for (int p = 0; p < n; p++)
+	{
+		const int k = set.order[p];
+		si[p] = a[k]; sj[p] = b[k];
+		if (a[k] < Pf || b[k] < Pf) nActive = p + 1;
+		if (a[k] < Pf && b[k] < Pf && (p == 0 || key[k] != key[set.order[p - 1]]))
+		{
+			const int row = std::min(a[k], b[k]), col = std::max(a[k], b[k]);
+			const int* c0 = s.h_colind.data() + s.h_rowptr[row]; const int* c1 = s.h_colind.data() + s.h_rowptr[row + 1];
+			const int* it = std::lower_bound(c0, c1, col);
+			if (it == c1 || *it != col) throw StateError{ "relative-pose edge without its block in the pattern" };
+			blkPtr.push_back(p); blkId.push_back((int)(it - s.h_colind.data()));
+		}
+	}
+	int nFreeFree = 0;
+	while (nFreeFree < n && si[nFreeFree] < Pf && sj[nFreeFree] < Pf) nFreeFree++;
+	blkPtr.push_back(nFreeFree);
+	// per free pose: its edges in the caller's order (item = 2 * sorted position + end: 0 = the pose is i, 1 = j)
+	std::vector<std::pair<int, int>> items;
+	for (int k = 0; k < n; k++)
+	{
+		if (a[k] < Pf) items.emplace_back(a[k], 2 * posOf[k]);
+		if (b[k] < Pf) items.emplace_back(b[k], 2 * posOf[k] + 1);
+	}
+	std::stable_sort(items.begin(), items.end(), [](const std::pair<int, int>& x, const std::pair<int, int>& y) { return x.first < y.first; });
+	std::vector<int> posePtr, poseId, poseItem;
+	for (size_t x = 0; x < items.size(); x++)
+	{
+		if (x == 0 || items[x].first != items[x - 1].first) { posePtr.push_back((int)x); poseId.push_back(items[x].first); }
+		poseItem.push_back(items[x].second);
+	}
+	posePtr.push_back((int)items.size());
+	const int nb = (int)blkId.size(), np = (int)poseId.size();
+	DeviceRelPoses rp;
+	upload_factor_arrays(s, set, concat({ &si, &sj, &blkPtr, &blkId, &posePtr, &poseId, &poseItem }), rp.q, rp.t, rp.info, rp.chi);
+	s.d_relRec.resize((size_t)cubahip::REL_REC * std::max(n, 1));
+	rp.n = n; rp.nActive = nActive; rp.nBlocks = nb; rp.nPoses = np;
+	rp.pose_i = set.d_ints.data(); rp.pose_j = rp.pose_i + n;
+	rp.blk_ptr = rp.pose_j + n; rp.blk_id = rp.blk_ptr + (nb + 1);
+	rp.pose_ptr = rp.blk_id + nb; rp.pose_id = rp.pose_ptr + (np + 1); rp.pose_item = rp.pose_id + np;
+	rp.rec = s.d_relRec.data();
+	s.pf.rel = rp;
+	s.relStructure = s.cntStructureBuilds;
+}
+
+// (the priors depend on the pose order only -- a change of it marks them --, the edges' blocks on the structure)
+void cuba_hip_solver::uploadPoseFactors()
+{
+	if (priorSet.n() > 0 && !priorSet.uploaded) upload_priors(*this);
+	if (relSet.n() > 0 && (!relSet.uploaded || relStructure != cntStructureBuilds)) upload_relative_pose_edges(*this);
+}
+
+// the per-factor chi2 of the chi2 launch just issued (sorted order on the device) -> the caller's order
+static void read_factor_chi2(cuba_hip_solver& s, const PoseFactorSet& set, const Scalar* chi, double* out)
+{
+	const size_t n = set.order.size();
+	std::vector<double> sorted(n);
+	s.downloadAsDouble(chi, sorted.data(), n);
+	for (size_t p = 0; p < n; p++) out[set.order[p]] = sorted[p];
+}
+
+void cuba_hip_solver::priorChiSquares(double* out)
+{
+	need();
+	if (priorSet.n() == 0) return;
+	launch_prior_chi2(g, pf.priors, d_parts.data(), stream);
+	read_factor_chi2(*this, priorSet, pf.priors.chi, out);
+}
+
+void cuba_hip_solver::relativePoseChiSquares(double* out)
+{
+	need();
+	if (relSet.n() == 0) return;
+	launch_relpose_chi2(g, pf.rel, d_parts.data(), stream);
+	read_factor_chi2(*this, relSet, pf.rel.chi, out);
+}

@@ -31,8 +31,7 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 	if (sizeof(Scalar) == 4 && Lt_ >= (1 << 23)) throw ArgError{ "fp32 build: at most 2^23 - 1 landmarks" };
 	if ((Pt_ && (!q || !t || !cam)) || (Lt_ && !Xw) || (E_ && (!ep || !el || !edim || !meas || !omega))) throw ArgError{ "null array" };
 	const auto t0 = Clock::now();
-	clearPosePriors();            // (priors name poses of the previous graph)
-	clearRelativePoseEdges();     // (so do relative-pose edges; need() rebuilds a kept structure unless the same pairs come back)
+	clearPoseFactors();           // (they name poses of the previous graph; need() rebuilds a kept structure unless the same pairs come back)
 	static const bool noCache = std::getenv("CUBA_HIP_NO_STRUCTURE_CACHE") != nullptr;   // A/B knob for set-up timings
 	const bool sameCounts = !noCache && !ranged && haveStructure && partHi < 0 && Pt == Pt_ && Pf == Pf_ && Lt == Lt_ && Lf == Lf_ && E == E_;
 	// the very same index arrays as in the previous call (re-initialisation of an unchanged graph): the sort, the
@@ -904,7 +903,7 @@ void cuba_hip_solver::resetPoseOrder()
 {
 	if (reorderActive) dropSnapshots();          // (they hold rows in the order that ends here)
 	reorderActive = false;
-	priorsUploaded = false;
+	priorSet.uploaded = false;
 	poseNewOfOld.resize(Pf); poseOldOfNew.resize(Pf);
 	for (int i = 0; i < Pf; i++) poseNewOfOld[i] = poseOldOfNew[i] = i;
 }
@@ -999,7 +998,7 @@ void cuba_hip_solver::applyPoseOrder(const std::vector<int>& newOfOld)
 	permutePoseArray(state.data(), 4, false); permutePoseArray(state.data() + 4 * (size_t)Pt, 3, false); permutePoseArray(camv.data(), 5, false);
 	poseNewOfOld = newOfOld;
 	reorderActive = false;
-	priorsUploaded = false;
+	priorSet.uploaded = false;
 	for (int i = 0; i < Pf; i++) { poseOldOfNew[newOfOld[i]] = i; if (newOfOld[i] != i) reorderActive = true; }
 	permuteStateRows(state, camv);
 	d_state.upload(state, stream); d_cam.upload(camv, stream);

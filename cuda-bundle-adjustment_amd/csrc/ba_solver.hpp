@@ -130,6 +130,17 @@ int run_covariance_pairs(const SparseChol& d, const SparseCholPlan& plan, const 
 }  // namespace cubahip_host
 using namespace cubahip_host;
 
+// one kind of pose factor (pose priors, relative-pose edges) as a handle keeps it: cuba_hip_solver, ba_posefactor.hip
+struct PoseFactorValues { std::vector<int> pi, pj; std::vector<double> q, t, info; };      // [n] poses (pj: edges only), [4 n], [3 n], [36 n]
+struct PoseFactorSet
+{
+	PoseFactorValues v;
+	std::vector<int> order;          // sorted position -> caller's index (set by the upload)
+	bool uploaded = false;
+	DevBuf<int> d_ints; DevBuf<Scalar> d_vals, d_chi;
+	int n() const { return (int)v.pi.size(); }
+};
+
 struct cuba_hip_solver;
 int cuba_hip_optimize_batch_impl(cuba_hip_solver** hs, int n, int niter, double* chi2, int* nDone);
 
@@ -571,45 +582,37 @@ struct cuba_hip_solver
 		if (!haveGraph) throw StateError{ "set_graph must be called first" };
 		if (haveStructure && h_relPairs != structRelPairs) haveStructure = false;      // (the relative-pose pairs are part of the topology)
 		buildStructure(); finishValues(); g.rk[0] = rk[0]; g.rk[1] = rk[1]; st.mixed = mixedPrecision ? 1 : 0;
-		if (!h_priorPose.empty() && !priorsUploaded) uploadPriors();
-		if (!h_relI.empty() && (!relUploaded || relStructure != cntStructureBuilds)) uploadRelativePoseEdges();
+		uploadPoseFactors();
 	}
 
-	// SE(3) pose priors (ba_prior.hip; cuba_hip_set_pose_priors): the caller's set in its own numbering (quaternions normalised,
-	// information symmetrised), and its device copy in the internal pose order -- made by need() once the pose order is known, again
-	// whenever that order changes.  No priors: nothing of it is launched, and every launch and kernel argument is as without this feature.
-	std::vector<int> h_priorPose; std::vector<double> h_priorQ, h_priorT, h_priorInfo;
-	std::vector<int> h_priorOrder;       // sorted position -> caller's prior index
-	bool priorsUploaded = false;
-	DevBuf<int> d_priorInts; DevBuf<Scalar> d_priorVals, d_priorChi;
-	DevicePriors pri;
-	const DevicePriors* priors() const { return h_priorPose.empty() ? nullptr : &pri; }
-	int priorParts() const { return prior_chi2_parts(priors()); }
+	// The pose factors (ba_posefactor.hip): SE(3) pose priors (cuba_hip_set_pose_priors) and relative-pose edges
+	// (cuba_hip_set_relative_pose_edges).  Either set is kept as the caller gave it, in its own numbering (quaternions normalised,
+	// information symmetrised), with a device copy in the internal pose order that need() makes: the priors' once the pose order is known and
+	// again whenever that order changes; the edges' (their blocks are looked up in the pattern) with every structure.  No factors:
+	// poseFactors() is null, nothing of it is launched, no extra seed enters the pattern build, and every launch and kernel argument is as
+	// without this feature.
+	PoseFactorSet priorSet, relSet;
+	DevicePoseFactors pf;
+	const DevicePoseFactors* poseFactors() const { return priorSet.n() + relSet.n() > 0 ? &pf : nullptr; }
+	int poseFactorParts() const { return pose_factor_chi2_parts(poseFactors()); }      // chi2 partials that follow the reprojection edges'
+	void clearPoseFactors()
+	{
+		for (PoseFactorSet* set : { &priorSet, &relSet }) { set->v = PoseFactorValues(); set->order.clear(); set->uploaded = false; }
+		h_relPairs.clear(); pf = DevicePoseFactors();
+	}
+	void uploadPoseFactors();
+	int internalPose(int p) const { return p < Pf && reorderActive ? poseNewOfOld[p] : p; }      // of a pose in the caller's numbering
 	void setPosePriors(int n, const int32_t* pose, const double* q, const double* t, const double* info);
-	void clearPosePriors() { h_priorPose.clear(); h_priorQ.clear(); h_priorT.clear(); h_priorInfo.clear(); h_priorOrder.clear(); priorsUploaded = false; pri = DevicePriors(); }
-	void uploadPriors();
 	void priorChiSquares(double* out);
-
-	// SE(3) relative-pose edges (ba_relpose.hip; cuba_hip_set_relative_pose_edges): the caller's set in its own numbering, the distinct
-	// free-free pairs among them (sorted keys i << 32 | j, i < j, caller's numbering) and the pairs the current structure was seeded with:
-	// every such pair owns a block of the reduced matrix, so need() rebuilds the structure exactly when the two sets differ.  The device
-	// copy (internal pose order, blocks looked up in the pattern) is renewed with every structure.  No such edges: nothing of it is launched,
-	// no extra seed enters the pattern build, and every launch and kernel argument is as without this feature.
-	std::vector<int> h_relI, h_relJ; std::vector<double> h_relQ, h_relT, h_relInfo;
+	void setRelativePoseEdges(int n, const int32_t* pi, const int32_t* pj, const double* q, const double* t, const double* info);
+	void relativePoseChiSquares(double* out);
+	// the edges' distinct free-free pairs (sorted keys i << 32 | j, i < j, caller's numbering) and the pairs the current structure was seeded
+	// with: every such pair owns a block of the reduced matrix, so need() rebuilds the structure exactly when the two sets differ
 	std::vector<uint64_t> h_relPairs, structRelPairs;
-	std::vector<int> h_relOrder;         // sorted position -> caller's edge index
-	bool relUploaded = false;
-	int64_t relStructure = -1;           // cntStructureBuilds at the upload
+	int64_t relStructure = -1;           // cntStructureBuilds at the edges' upload
 	int64_t cntStructureBuilds = 0;      // structures published on this handle (never reset)
 	std::vector<uint64_t> h_relSeeds;    // the pairs as the last pattern build took them
-	DevBuf<int> d_relInts, d_relSeedFlag, d_relSeedScan; DevBuf<uint64_t> d_relSeeds; DevBuf<Scalar> d_relVals, d_relRec, d_relChi;
-	DeviceRelPoses rel;
-	const DeviceRelPoses* relPoses() const { return h_relI.empty() ? nullptr : &rel; }
-	int extraChiParts() const { return priorParts() + relpose_chi2_parts(relPoses()); }      // chi2 partials that follow the reprojection edges'
-	void setRelativePoseEdges(int n, const int32_t* pi, const int32_t* pj, const double* q, const double* t, const double* info);
-	void clearRelativePoseEdges() { h_relI.clear(); h_relJ.clear(); h_relQ.clear(); h_relT.clear(); h_relInfo.clear(); h_relPairs.clear(); h_relOrder.clear(); relUploaded = false; rel = DeviceRelPoses(); }
-	void uploadRelativePoseEdges();
-	void relativePoseChiSquares(double* out);
+	DevBuf<int> d_relSeedFlag, d_relSeedScan; DevBuf<uint64_t> d_relSeeds; DevBuf<Scalar> d_relRec;
 	// the pairs as (row, column) keys of the pattern in the internal pose order, sorted
 	std::vector<uint64_t> relSeedKeys() const;
 

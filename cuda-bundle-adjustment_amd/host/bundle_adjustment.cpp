@@ -169,6 +169,7 @@ public:
 		covPoseIndex_.clear(); covLmIndex_.clear();          // (marginal covariances describe the graph they were computed on)
 		priorsDirty_ = true;                                 // (the priors as they stand now go to the device with the next solve)
 		relDirty_ = true;                                    // (so do the relative-pose edges)
+		poseIdx_.clear();                                    // (the factors' pose index: rebuilt below from the poses active now)
 		const auto t0 = std::chrono::steady_clock::now();
 		static const bool dbg = std::getenv("CUBA_HIP_DEBUG") != nullptr;
 		auto tl = t0;
@@ -365,7 +366,32 @@ public:
 		uploadRelativePoseEdges();
 	}
 
-	// ---- relative-pose edges (extension: cuba::addRelativePoseEdge) ----------------------------------
+	// ---- pose factors (extensions: cuba::addPosePrior, cuba::addRelativePoseEdge) --------------------
+	// index of a factor's vertex among the active poses (the map is built with the first factor of an initialize()); `refusal`: the message
+	// for a vertex that is not part of the graph
+	int32_t factorPose(const PoseVertex* v, const char* refusal)
+	{
+		if (poseIdx_.empty())
+			for (size_t i = 0; i < activePoses_.size(); i++) poseIdx_[activePoses_[i]] = (int32_t)i;
+		const auto it = poseIdx_.find(v);
+		if (it == poseIdx_.end()) throw std::invalid_argument(refusal);
+		return it->second;
+	}
+	// q | t | information of a set of factors as the C ABI takes them
+	struct FactorArrays { std::vector<double> q, t, info; };
+	template <class F> static FactorArrays packFactors(const std::vector<F*>& factors)
+	{
+		const size_t n = factors.size();
+		FactorArrays a{ std::vector<double>(4 * n), std::vector<double>(3 * n), std::vector<double>(36 * n) };
+		for (size_t k = 0; k < n; k++)
+		{
+			for (int i = 0; i < 4; i++) a.q[4 * k + i] = factors[k]->q.coeffs().data()[i];
+			for (int i = 0; i < 3; i++) a.t[3 * k + i] = factors[k]->t.data()[i];
+			std::copy(factors[k]->information.begin(), factors[k]->information.end(), a.info.begin() + 36 * k);
+		}
+		return a;
+	}
+
 	void addRelativePoseEdge(RelativePoseEdge* e)
 	{
 		if (!e || !e->vertexI || !e->vertexJ || e->vertexI == e->vertexJ) throw std::invalid_argument("cuba::addRelativePoseEdge: an edge needs two different pose vertices");
@@ -385,27 +411,16 @@ public:
 		relChi_.clear();
 		uploadedRel_.clear();
 		if (relEdges_.empty() && !relOnDevice_) return;
-		std::map<const PoseVertex*, int> poseIdx;
-		for (size_t i = 0; i < activePoses_.size(); i++) poseIdx[activePoses_[i]] = (int)i;
 		const size_t n = relEdges_.size();
 		std::vector<int32_t> pi(n), pj(n);
-		std::vector<double> q(4 * n), t(3 * n), info(36 * n);
-		for (size_t k = 0; k < n; k++)
-		{
-			const RelativePoseEdge* e = relEdges_[k];
-			const auto a = poseIdx.find(e->vertexI), b = poseIdx.find(e->vertexJ);
-			if (a == poseIdx.end() || b == poseIdx.end()) throw std::invalid_argument("cuba::addRelativePoseEdge: a vertex of a relative-pose edge is not part of the graph");
-			pi[k] = a->second; pj[k] = b->second;
-			for (int i = 0; i < 4; i++) q[4 * k + i] = e->q.coeffs().data()[i];
-			for (int i = 0; i < 3; i++) t[3 * k + i] = e->t.data()[i];
-			std::copy(e->information.begin(), e->information.end(), info.begin() + 36 * k);
-		}
-		check(cuba_hip_set_relative_pose_edges(solver_, (int)n, pi.data(), pj.data(), q.data(), t.data(), info.data()), "cuba_hip_set_relative_pose_edges");
+		const char* refusal = "cuba::addRelativePoseEdge: a vertex of a relative-pose edge is not part of the graph";
+		for (size_t k = 0; k < n; k++) { pi[k] = factorPose(relEdges_[k]->vertexI, refusal); pj[k] = factorPose(relEdges_[k]->vertexJ, refusal); }
+		const FactorArrays a = packFactors(relEdges_);
+		check(cuba_hip_set_relative_pose_edges(solver_, (int)n, pi.data(), pj.data(), a.q.data(), a.t.data(), a.info.data()), "cuba_hip_set_relative_pose_edges");
 		relOnDevice_ = n > 0;
 		uploadedRel_ = relEdges_;
 	}
 
-	// ---- pose priors (extension: cuba::addPosePrior) ------------------------------------------------
 	void addPosePrior(PosePrior* p)
 	{
 		if (!p || !p->vertex) throw std::invalid_argument("cuba::addPosePrior: a prior needs a pose vertex");
@@ -425,22 +440,11 @@ public:
 		priorChi_.clear();
 		uploadedPriors_.clear();
 		if (priors_.empty() && !priorsOnDevice_) return;
-		std::map<const PoseVertex*, int> poseIdx;
-		for (size_t i = 0; i < activePoses_.size(); i++) poseIdx[activePoses_[i]] = (int)i;
 		const size_t n = priors_.size();
 		std::vector<int32_t> pose(n);
-		std::vector<double> q(4 * n), t(3 * n), info(36 * n);
-		for (size_t k = 0; k < n; k++)
-		{
-			const PosePrior* p = priors_[k];
-			const auto it = poseIdx.find(p->vertex);
-			if (it == poseIdx.end()) throw std::invalid_argument("cuba::addPosePrior: the vertex of a prior is not part of the graph");
-			pose[k] = it->second;
-			for (int i = 0; i < 4; i++) q[4 * k + i] = p->q.coeffs().data()[i];
-			for (int i = 0; i < 3; i++) t[3 * k + i] = p->t.data()[i];
-			std::copy(p->information.begin(), p->information.end(), info.begin() + 36 * k);
-		}
-		check(cuba_hip_set_pose_priors(solver_, (int)n, pose.data(), q.data(), t.data(), info.data()), "cuba_hip_set_pose_priors");
+		for (size_t k = 0; k < n; k++) pose[k] = factorPose(priors_[k]->vertex, "cuba::addPosePrior: the vertex of a prior is not part of the graph");
+		const FactorArrays a = packFactors(priors_);
+		check(cuba_hip_set_pose_priors(solver_, (int)n, pose.data(), a.q.data(), a.t.data(), a.info.data()), "cuba_hip_set_pose_priors");
 		priorsOnDevice_ = n > 0;
 		uploadedPriors_ = priors_;
 	}
@@ -708,6 +712,7 @@ private:
 	std::vector<RelativePoseEdge*> relEdges_, uploadedRel_;   // as priors_ / uploadedPriors_
 	bool relOnDevice_ = false, relDirty_ = false;
 	std::map<const RelativePoseEdge*, double> relChi_;
+	std::map<const PoseVertex*, int32_t> poseIdx_;            // active pose -> solver index, for the factors of this initialize()
 	std::vector<LandmarkVertex*> activeLandmarks_;
 	std::vector<BaseEdge*> activeEdges_;
 	int numFreePoses_ = 0, numFreeLandmarks_ = 0;
