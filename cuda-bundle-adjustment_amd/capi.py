@@ -126,6 +126,7 @@ def load_library(precision="f64"):
         "cuba_hip_prior_chi_squares": [H, _dp],
         "cuba_hip_set_relative_pose_edges": [H, C.c_int, _ip, _ip, _dp, _dp, _dp],
         "cuba_hip_relative_pose_chi_squares": [H, _dp],
+        "cuba_hip_set_pose_factor_robust_kernels": [H, C.c_int, C.c_int, _ip, _dp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -510,6 +511,21 @@ class HipSolver:
             raise ValueError("pose_i and pose_j differ in length")
         self._ck(self.lib.cuba_hip_set_relative_pose_edges(self.h, n, pose_i.ctypes.data_as(_ip), pose_j.ctypes.data_as(_ip), _d(q), _d(t), _d(info)))
         self._n_rel = n
+
+    def set_pose_factor_robust_kernels(self, factor_type, kind, delta):
+        """Robust kernels of the current pose priors (factor_type 0) or relative-pose edges (1), cuba_hip_set_pose_factor_robust_kernels:
+        kind[n] (0 none, 1 Huber, 2 Tukey, 3 Cauchy) and delta[n] in the order the set was given; scalars broadcast to the set's size.
+        Empty arrays clear the kernels of that type."""
+        n = getattr(self, "_n_priors", 0) if factor_type == 0 else getattr(self, "_n_rel", 0)
+        if np.ndim(kind) == 0:
+            kind = np.full(n, kind)
+        if np.ndim(delta) == 0:
+            delta = np.full(n, delta)
+        kind = np.ascontiguousarray(kind, dtype=np.int32).reshape(-1)
+        delta = np.ascontiguousarray(delta, dtype=np.float64).reshape(-1)
+        if kind.size != delta.size:
+            raise ValueError("kind and delta differ in length")
+        self._ck(self.lib.cuba_hip_set_pose_factor_robust_kernels(self.h, int(factor_type), int(kind.size), kind.ctypes.data_as(_ip), _d(delta)))
 
     def relative_pose_chi_squares(self):
         """r^T Omega r of every relative-pose edge at the current estimate, in the order they were given (0 with both ends fixed)"""

@@ -136,7 +136,12 @@ struct DeviceSystem
 	int* lowpos = nullptr;     // [nblk] position of every off-diagonal block in that order (launch_build_lowpos)
 };
 
-// SE(3) pose priors (ba_posefactor.hip): r^T Omega r, r = log(T Tbar^-1) in the [omega, upsilon] tangent of the pose update.  Sorted by
+// robust kernel of a pose factor (cuba_hip_set_pose_factor_robust_kernels): with e = r^T Omega r the objective term is rho(e) and the
+// linearisation takes w Omega, w = rho'(e), for Omega.  Kinds 1 and 2 are robust_rho / robust_weight (ba_math.hpp); Cauchy, rho =
+// delta^2 log1p(e / delta^2), exists for the pose factors only (helpers in ba_posefactor.hip).
+enum { POSE_FACTOR_KERNEL_NONE = 0, POSE_FACTOR_KERNEL_HUBER = 1, POSE_FACTOR_KERNEL_TUKEY = 2, POSE_FACTOR_KERNEL_CAUCHY = 3 };
+
+// SE(3) pose priors (ba_posefactor.hip): rho(r^T Omega r), r = log(T Tbar^-1) in the [omega, upsilon] tangent of the pose update.  Sorted by
 // internal pose (stable: a pose's priors are contiguous and in the caller's order); priors on fixed poses come last and are ignored.
 struct DevicePriors
 {
@@ -148,9 +153,11 @@ struct DevicePriors
 	const Scalar *qbar = nullptr, *tbar = nullptr;   // [4 n] unit quaternions, [3 n]
 	const Scalar* info = nullptr;  // [36 n] column-major
 	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 on fixed poses)
+	const int* rk_kind = nullptr;  // [n] robust kernel of every prior, sorted as the values; null: no prior has one (the kernels' ROBUST = false)
+	const Scalar* rk_delta = nullptr;   // [n]
 };
 
-// SE(3) relative-pose edges (ba_posefactor.hip): r^T Omega r, r = log(T_j T_i^-1 Zbar^-1), between two poses.  Sorted: the edges between two
+// SE(3) relative-pose edges (ba_posefactor.hip): rho(r^T Omega r), r = log(T_j T_i^-1 Zbar^-1), between two poses.  Sorted: the edges between two
 // free poses first, stable by the block (min, max) of the internal pose pair (a block's edges contiguous, in the caller's order), then the
 // edges with one fixed end (they act on the free end only), then those with two (ignored).
 constexpr int REL_REC = 90;        // numbers of an edge's linearisation record (layout: ba_posefactor.hip)
@@ -170,15 +177,17 @@ struct DeviceRelPoses
 	const Scalar* info = nullptr;  // [36 n] column-major
 	Scalar* rec = nullptr;         // [REL_REC n] linearisation records, number-major (number el of edge k at el n + k)
 	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 with both ends fixed)
+	const int* rk_kind = nullptr;  // [n] robust kernel of every edge, sorted as the values; null: no edge has one (the kernels' ROBUST = false)
+	const Scalar* rk_delta = nullptr;   // [n]
 };
 
 // The pose factors of a handle: what the rest of the library sees of the two kinds (a kind without factors: n = 0, nothing of it is launched).
 struct DevicePoseFactors { DevicePriors priors; DeviceRelPoses rel; };
-// behind the Schur pass, the priors first: J^T Omega J into the diagonal blocks of hsc (upper triangle), -J^T Omega r into bp and (mode 1)
+// behind the Schur pass, the priors first (Omega: w Omega of a factor with a robust kernel): J^T Omega J into the diagonal blocks of hsc (upper triangle), -J^T Omega r into bp and (mode 1)
 // bsc, J = J_l(r)^-1; then the edges in two launches: per-edge records, then their sums into hsc (diagonal blocks: upper triangle; mode 1:
 // the off-diagonal blocks of the pairs, stored whole where a block has no Schur products), bp and (mode 1) bsc
 void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DevicePoseFactors& pf, int mode, hipStream_t s);
-// per-factor chi2 into priors.chi / rel.chi, per-workgroup partial sums into parts[0 .. pose_factor_chi2_parts(&pf)): the priors' first, the
+// per-factor chi2 (the plain r^T Omega r) into priors.chi / rel.chi, per-workgroup partial sums of rho(chi2) into parts[0 .. pose_factor_chi2_parts(&pf)): the priors' first, the
 // edges' behind them
 void launch_pose_factor_chi2(const DeviceGraph& g, const DevicePoseFactors& pf, Scalar* parts, hipStream_t s);
 int pose_factor_chi2_parts(const DevicePoseFactors* pf);     // 0 for no factors (pf null), at most 64 per kind

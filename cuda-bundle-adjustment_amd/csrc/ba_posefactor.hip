@@ -1,4 +1,4 @@
-// ba_posefactor.hip -- the pose factors: terms r^T Omega r of the objective on the SE(3) poses alone, r in the [omega, upsilon] tangent of
+// ba_posefactor.hip -- the pose factors: terms rho(r^T Omega r) of the objective on the SE(3) poses alone, r in the [omega, upsilon] tangent of
 // the solver's left-multiplicative update T <- exp(d) T (pose_exp_update), Omega a full symmetric 6 x 6 information.  Two kinds:
 //
 //   pose priors (cuba_hip_set_pose_priors): unary, r = log(T Tbar^-1), linearised with the exact derivative dr/dd =
@@ -7,6 +7,11 @@
 //     dr/dd_i = -J_l(r)^-1 Ad(T_j T_i^-1).  Such an edge owns an off-diagonal block of the reduced matrix: the set of free-free pairs seeds
 //     the block pattern (ba_setup.hip), and a pair that no landmark connects gets a block without Schur products, which only the kernels
 //     below write.
+//
+// A factor may carry a robust kernel (cuba_hip_set_pose_factor_robust_kernels; section 7e): with e = r^T Omega r its term is rho(e) and its
+// linearisation takes w Omega, w = rho'(e), for Omega (no second-order term, as the reprojection edges).  The four kernels that see a
+// residual are templates on ROBUST; a set without kernels has null kind / delta arrays and runs the `false` instantiations, which hold
+// nothing of this.
 //
 // The two kinds keep kernels of their own (a prior is not run as a one-ended edge: its sums would be taken in another order); they share the
 // device helpers below, the host-side validation, packing, upload and read-back, and one interface (ba_kernels.hpp: DevicePoseFactors).
@@ -22,8 +27,8 @@
 //                              or an entry of a pose's diagonal block (upper triangle) / of bp and (mode 1) bsc, summed over the pose's
 //                              edges in the caller's order -- one writer per number, fixed order, no atomics; behind the Schur pass and the
 //                              priors' launch
-//   prior_chi2_kernel,         lane = factor: r^T Omega r at the current estimate into the per-factor output and into per-workgroup partials
-//   relpose_chi2_kernel        that the caller sums together with the reprojection edges' partials (fixed order, no atomics)
+//   prior_chi2_kernel,         lane = factor: r^T Omega r at the current estimate into the per-factor output and (rho of it) into per-workgroup
+//   relpose_chi2_kernel        partials that the caller sums together with the reprojection edges' partials (fixed order, no atomics)
 //
 // Host side: the caller's two sets (validated, kept in the caller's numbering), the edges' pair set (part of the topology) and the upload
 // of either set in the internal pose order.
@@ -84,6 +89,19 @@ __device__ __forceinline__ void se3_jacobian(const Scalar A[3][3], const Scalar 
 		}
 }
 
+// rho(e) and rho'(e) of a factor's robust kernel: Huber and Tukey as the reprojection edges have them, and Cauchy
+__device__ __forceinline__ Scalar factor_rho(int kind, Scalar delta, Scalar e)
+{
+	if (kind == POSE_FACTOR_KERNEL_CAUCHY) { const Scalar d2 = delta * delta; return d2 * log1p(e / d2); }
+	return robust_rho(kind, delta, e);
+}
+
+__device__ __forceinline__ Scalar factor_weight(int kind, Scalar delta, Scalar e)
+{
+	if (kind == POSE_FACTOR_KERNEL_CAUCHY) return 1 / (1 + e / (delta * delta));
+	return robust_weight(kind, delta, e);
+}
+
 // the lanes' chi2 sums of a CHI_BLOCK workgroup -> its partial
 __device__ __forceinline__ void chi2_partial(Scalar acc, Scalar* __restrict__ parts)
 {
@@ -99,6 +117,7 @@ static int chi2_parts(int n) { return n > 0 ? std::min((n + CHI_BLOCK - 1) / CHI
 
 // ---- pose priors ------------------------------------------------------------------------------------------------------------------
 
+template <bool ROBUST>
 __global__ __launch_bounds__(PRIOR_LIN_BLOCK) void prior_linearize_kernel(DeviceGraph g, DeviceStructure st, DeviceSystem sys, DevicePriors pr, int mode)
 {
 	const int i = blockIdx.x * PRIOR_LIN_BLOCK + threadIdx.x;
@@ -120,6 +139,13 @@ __global__ __launch_bounds__(PRIOR_LIN_BLOCK) void prior_linearize_kernel(Device
 		prior_jacobian_b(r, A, B);
 		se3_jacobian(A, B, J);
 		const Scalar* O = pr.info + 36 * (size_t)k;
+		Scalar Or[6];
+		Scalar w = 1;
+		if constexpr (ROBUST)
+		{
+			const Scalar e = info_times(O, r, Or);
+			w = factor_weight(pr.rk_kind[k], pr.rk_delta[k], e);
+		}
 		// H += J^T (Omega J), column by column (upper triangle, acc[c (c + 1) / 2 + r] as the pose pass stores it)
 #pragma unroll
 		for (int c = 0; c < 6; c++)
@@ -137,18 +163,19 @@ __global__ __launch_bounds__(PRIOR_LIN_BLOCK) void prior_linearize_kernel(Device
 				Scalar s = 0;
 #pragma unroll
 				for (int a = 0; a < 6; a++) s += J[a][rr] * oj[a];
-				H[c * (c + 1) / 2 + rr] += s;
+				if constexpr (ROBUST) H[c * (c + 1) / 2 + rr] += w * s;
+				else H[c * (c + 1) / 2 + rr] += s;
 			}
 		}
-		Scalar Or[6];
-		(void)info_times(O, r, Or);
+		if constexpr (!ROBUST) (void)info_times(O, r, Or);
 #pragma unroll
 		for (int c = 0; c < 6; c++)
 		{
 			Scalar s = 0;
 #pragma unroll
 			for (int a = 0; a < 6; a++) s += J[a][c] * Or[a];
-			gv[c] += s;
+			if constexpr (ROBUST) gv[c] += w * s;
+			else gv[c] += s;
 		}
 	}
 	Scalar* blk = sys.hsc + 36 * (size_t)st.hsc_rowptr[ip];
@@ -162,6 +189,7 @@ __global__ __launch_bounds__(PRIOR_LIN_BLOCK) void prior_linearize_kernel(Device
 	}
 }
 
+template <bool ROBUST>
 __global__ __launch_bounds__(CHI_BLOCK) void prior_chi2_kernel(DeviceGraph g, DevicePriors pr, Scalar* __restrict__ parts)
 {
 	Scalar acc = 0;
@@ -178,7 +206,8 @@ __global__ __launch_bounds__(CHI_BLOCK) void prior_chi2_kernel(DeviceGraph g, De
 			chi = info_times(pr.info + 36 * (size_t)k, r, Or);
 		}
 		pr.chi[k] = chi;
-		acc += chi;
+		if constexpr (ROBUST) acc += factor_rho(pr.rk_kind[k], pr.rk_delta[k], chi);
+		else acc += chi;
 	}
 	chi2_partial(acc, parts);
 }
@@ -217,6 +246,7 @@ __device__ __forceinline__ void rel_residual(const RelEnds& e, const DeviceRelPo
 	prior_residual(e.qj, e.tj, qb, tb, r, A);
 }
 
+template <bool ROBUST>
 __global__ __launch_bounds__(REL_LIN_BLOCK) void relpose_linearize_kernel(DeviceGraph g, DeviceRelPoses rp)
 {
 	const int k = blockIdx.x * REL_LIN_BLOCK + threadIdx.x;
@@ -250,6 +280,13 @@ __global__ __launch_bounds__(REL_LIN_BLOCK) void relpose_linearize_kernel(Device
 	se3_jacobian(A, B, Jj);
 	se3_jacobian(X, Y, Ji, true);
 	const Scalar* O = rp.info + 36 * (size_t)k;
+	Scalar Or[6];
+	Scalar w = 1;
+	if constexpr (ROBUST)
+	{
+		const Scalar e = info_times(O, r, Or);
+		w = factor_weight(rp.rk_kind[k], rp.rk_delta[k], e);
+	}
 	// the cross term J_i^T Omega J_j is the block (i, j); the block pattern stores (min, max) of the internal indices: transposed if i > j
 	const bool flip = rp.pose_i[k] > rp.pose_j[k];
 #pragma unroll
@@ -268,18 +305,19 @@ __global__ __launch_bounds__(REL_LIN_BLOCK) void relpose_linearize_kernel(Device
 			Scalar sii = 0, sjj = 0, sx = 0;
 #pragma unroll
 			for (int a = 0; a < 6; a++) { sii += Ji[a][rr] * oi[a]; sjj += Jj[a][rr] * oj[a]; sx += Ji[a][rr] * oj[a]; }
+			if constexpr (ROBUST) { sii *= w; sjj *= w; sx *= w; }
 			if (rr <= c) { rel_rec(rp, k, REL_HII + c * (c + 1) / 2 + rr) = sii; rel_rec(rp, k, REL_HJJ + c * (c + 1) / 2 + rr) = sjj; }
 			rel_rec(rp, k, REL_HX + (flip ? rr * 6 + c : c * 6 + rr)) = sx;
 		}
 	}
-	Scalar Or[6];
-	(void)info_times(O, r, Or);
+	if constexpr (!ROBUST) (void)info_times(O, r, Or);
 #pragma unroll
 	for (int c = 0; c < 6; c++)
 	{
 		Scalar si = 0, sj = 0;
 #pragma unroll
 		for (int a = 0; a < 6; a++) { si += Ji[a][c] * Or[a]; sj += Jj[a][c] * Or[a]; }
+		if constexpr (ROBUST) { si *= w; sj *= w; }
 		rel_rec(rp, k, REL_GI + c) = si; rel_rec(rp, k, REL_GJ + c) = sj;
 	}
 }
@@ -326,6 +364,7 @@ __global__ __launch_bounds__(REL_GATHER_BLOCK) void relpose_gather_kernel(Device
 	}
 }
 
+template <bool ROBUST>
 __global__ __launch_bounds__(CHI_BLOCK) void relpose_chi2_kernel(DeviceGraph g, DeviceRelPoses rp, Scalar* __restrict__ parts)
 {
 	Scalar acc = 0;
@@ -341,7 +380,8 @@ __global__ __launch_bounds__(CHI_BLOCK) void relpose_chi2_kernel(DeviceGraph g, 
 			chi = info_times(rp.info + 36 * (size_t)k, r, Or);
 		}
 		rp.chi[k] = chi;
-		acc += chi;
+		if constexpr (ROBUST) acc += factor_rho(rp.rk_kind[k], rp.rk_delta[k], chi);
+		else acc += chi;
 	}
 	chi2_partial(acc, parts);
 }
@@ -351,13 +391,17 @@ __global__ __launch_bounds__(CHI_BLOCK) void relpose_chi2_kernel(DeviceGraph g, 
 static void launch_prior_chi2(const DeviceGraph& g, const DevicePriors& pr, Scalar* parts, hipStream_t s)
 {
 	const int grid = chi2_parts(pr.n);
-	if (grid > 0) hipLaunchKernelGGL(prior_chi2_kernel, dim3(grid), dim3(CHI_BLOCK), 0, s, g, pr, parts);
+	if (grid <= 0) return;
+	if (pr.rk_kind) hipLaunchKernelGGL(prior_chi2_kernel<true>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, pr, parts);
+	else hipLaunchKernelGGL(prior_chi2_kernel<false>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, pr, parts);
 }
 
 static void launch_relpose_chi2(const DeviceGraph& g, const DeviceRelPoses& rp, Scalar* parts, hipStream_t s)
 {
 	const int grid = chi2_parts(rp.n);
-	if (grid > 0) hipLaunchKernelGGL(relpose_chi2_kernel, dim3(grid), dim3(CHI_BLOCK), 0, s, g, rp, parts);
+	if (grid <= 0) return;
+	if (rp.rk_kind) hipLaunchKernelGGL(relpose_chi2_kernel<true>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, rp, parts);
+	else hipLaunchKernelGGL(relpose_chi2_kernel<false>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, rp, parts);
 }
 
 int pose_factor_chi2_parts(const DevicePoseFactors* pf) { return pf ? chi2_parts(pf->priors.n) + chi2_parts(pf->rel.n) : 0; }
@@ -371,10 +415,17 @@ void launch_pose_factor_chi2(const DeviceGraph& g, const DevicePoseFactors& pf, 
 void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DevicePoseFactors& pf, int mode, hipStream_t s)
 {
 	const DevicePriors& pr = pf.priors;
-	if (pr.nPoses > 0) hipLaunchKernelGGL(prior_linearize_kernel, dim3((pr.nPoses + PRIOR_LIN_BLOCK - 1) / PRIOR_LIN_BLOCK), dim3(PRIOR_LIN_BLOCK), 0, s, g, st, sys, pr, mode);
+	if (pr.nPoses > 0)
+	{
+		const dim3 grid((pr.nPoses + PRIOR_LIN_BLOCK - 1) / PRIOR_LIN_BLOCK);
+		if (pr.rk_kind) hipLaunchKernelGGL(prior_linearize_kernel<true>, grid, dim3(PRIOR_LIN_BLOCK), 0, s, g, st, sys, pr, mode);
+		else hipLaunchKernelGGL(prior_linearize_kernel<false>, grid, dim3(PRIOR_LIN_BLOCK), 0, s, g, st, sys, pr, mode);
+	}
 	const DeviceRelPoses& rp = pf.rel;
 	if (rp.nActive <= 0) return;
-	hipLaunchKernelGGL(relpose_linearize_kernel, dim3((rp.nActive + REL_LIN_BLOCK - 1) / REL_LIN_BLOCK), dim3(REL_LIN_BLOCK), 0, s, g, rp);
+	const dim3 linGrid((rp.nActive + REL_LIN_BLOCK - 1) / REL_LIN_BLOCK);
+	if (rp.rk_kind) hipLaunchKernelGGL(relpose_linearize_kernel<true>, linGrid, dim3(REL_LIN_BLOCK), 0, s, g, rp);
+	else hipLaunchKernelGGL(relpose_linearize_kernel<false>, linGrid, dim3(REL_LIN_BLOCK), 0, s, g, rp);
 	const size_t numbers = (mode == 1 ? (size_t)36 * rp.nBlocks : 0) + (size_t)REL_POSE_NUMBERS * rp.nPoses;
 	hipLaunchKernelGGL(relpose_gather_kernel, dim3((unsigned)((numbers + REL_GATHER_BLOCK - 1) / REL_GATHER_BLOCK)), dim3(REL_GATHER_BLOCK), 0, s, st, sys, rp, mode);
 }
@@ -413,11 +464,18 @@ static PoseFactorValues sized_factor_values(int n, bool binary)
 
 // a validated set replaces the handle's: its device copy is due, and the run-to-run memories that the values of the system feed go, as a
 // new graph drops them (a run after a change of the factors depends on the state and the factors only)
+static void forget_factor_memories(cuba_hip_solver& s, PoseFactorSet& set)
+{
+	set.uploaded = false;
+	s.firstInvValid = false; s.firstInvPending = false; s.prevRunIters.clear(); s.runIters.clear(); s.firstSolveIters = 0;
+}
+
+// (the replaced set is a new set: the robust kernels of the previous one go with it)
 static void adopt_factor_values(cuba_hip_solver& s, PoseFactorSet& set, PoseFactorValues&& v)
 {
 	set.v = std::move(v);
-	set.uploaded = false;
-	s.firstInvValid = false; s.firstInvPending = false; s.prevRunIters.clear(); s.runIters.clear(); s.firstSolveIters = 0;
+	set.kind.clear(); set.delta.clear();
+	forget_factor_memories(s, set);
 }
 
 void cuba_hip_solver::setPosePriors(int n, const int32_t* pose, const double* q, const double* t, const double* info)
@@ -466,6 +524,31 @@ void cuba_hip_solver::setRelativePoseEdges(int n, const int32_t* pi, const int32
 	covBlocksValid = false;          // (the covariance blocks describe the edge set -- and the block pattern -- they were computed on)
 }
 
+// kernels of the current set of one type, in the caller's order; n = 0 (or kinds all 0) clears them.  The values of the system change, its
+// structure does not: the device copy of the set is due again, nothing else
+void cuba_hip_solver::setPoseFactorRobustKernels(int factorType, int n, const int32_t* kind, const double* delta)
+{
+	if (!haveGraph) throw StateError{ "set_graph must be called first" };
+	if (factorType < 0 || factorType > 1) throw ArgError{ "bad pose-factor type" };
+	PoseFactorSet& set = factorType == 0 ? priorSet : relSet;
+	if (n != 0 && n != set.n()) throw ArgError{ "robust kernels: the count differs from the set's" };
+	if (n > 0 && (!kind || !delta)) throw ArgError{ "null robust-kernel array" };
+	bool any = false;
+	for (int k = 0; k < n; k++)
+	{
+		if (kind[k] < cubahip::POSE_FACTOR_KERNEL_NONE || kind[k] > cubahip::POSE_FACTOR_KERNEL_CAUCHY) throw ArgError{ "bad pose-factor robust kernel" };
+		if (!std::isfinite(delta[k])) throw ArgError{ "non-finite robust-kernel delta" };
+		if (kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE && !(delta[k] > 0)) throw ArgError{ "robust-kernel delta must be positive" };
+		any = any || kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE;
+	}
+	if (any) { set.kind.assign(kind, kind + n); set.delta.assign(delta, delta + n); }
+	else { set.kind.clear(); set.delta.clear(); }
+	forget_factor_memories(*this, set);
+	(factorType == 0 ? pf.priors.rk_kind : pf.rel.rk_kind) = nullptr;
+	(factorType == 0 ? pf.priors.rk_delta : pf.rel.rk_delta) = nullptr;
+	covBlocksValid = false;
+}
+
 std::vector<uint64_t> cuba_hip_solver::relSeedKeys() const
 {
 	std::vector<uint64_t> keys(h_relPairs.size());
@@ -488,11 +571,15 @@ static void sort_factors(PoseFactorSet& set, const std::vector<uint64_t>& key)
 }
 
 // a set's index arrays (`ints`, laid out by the caller) and its values q | t | information in the sorted order -> device; the device
-// pointers of the values and of the per-factor chi2 come back through q, t, info, chi
-static void upload_factor_arrays(cuba_hip_solver& s, PoseFactorSet& set, const std::vector<int>& ints, const Scalar*& q, const Scalar*& t, const Scalar*& info, Scalar*& chi)
+// pointers of the values and of the per-factor chi2 come back through q, t, info, chi.  A set with robust kernels: their kinds follow the
+// index arrays, their deltas the values, by the same permutation (rk_kind, rk_delta; null without)
+static void upload_factor_arrays(cuba_hip_solver& s, PoseFactorSet& set, std::vector<int> ints, const Scalar*& q, const Scalar*& t, const Scalar*& info, Scalar*& chi,
+	const int*& rk_kind, const Scalar*& rk_delta)
 {
 	const size_t n = set.order.size();
-	std::vector<Scalar> vals(43 * n);
+	const bool robust = !set.kind.empty();
+	const size_t nInts = ints.size();
+	std::vector<Scalar> vals((robust ? 44 : 43) * n);
 	Scalar* vq = vals.data(); Scalar* vt = vq + 4 * n; Scalar* vi = vt + 3 * n;
 	for (size_t p = 0; p < n; p++)
 	{
@@ -500,12 +587,14 @@ static void upload_factor_arrays(cuba_hip_solver& s, PoseFactorSet& set, const s
 		for (int i = 0; i < 4; i++) vq[4 * p + i] = (Scalar)set.v.q[4 * k + i];
 		for (int i = 0; i < 3; i++) vt[3 * p + i] = (Scalar)set.v.t[3 * k + i];
 		for (int i = 0; i < 36; i++) vi[36 * p + i] = (Scalar)set.v.info[36 * k + i];
+		if (robust) { ints.push_back(set.kind[k]); vi[36 * n + p] = (Scalar)set.delta[k]; }
 	}
 	set.d_ints.upload(ints, s.stream);
 	set.d_vals.upload(vals, s.stream);
 	set.d_chi.resize(std::max(n, (size_t)1));
 	q = set.d_vals.data(); t = q + 4 * n; info = t + 3 * n;
 	chi = set.d_chi.data();
+	rk_kind = robust ? set.d_ints.data() + nInts : nullptr; rk_delta = robust ? info + 36 * n : nullptr;
 	s.sync();          // (the staging vectors go out of scope)
 	set.uploaded = true;
 }
@@ -536,7 +625,7 @@ static void upload_priors(cuba_hip_solver& s)
 	ptr.push_back(nFree);
 	const int np = (int)ids.size();
 	DevicePriors pr;
-	upload_factor_arrays(s, set, concat({ &ptr, &ids, &poses }), pr.qbar, pr.tbar, pr.info, pr.chi);
+	upload_factor_arrays(s, set, concat({ &ptr, &ids, &poses }), pr.qbar, pr.tbar, pr.info, pr.chi, pr.rk_kind, pr.rk_delta);
 	pr.n = n; pr.nPoses = np;
 	pr.pose_ptr = set.d_ints.data(); pr.pose_id = pr.pose_ptr + (np + 1); pr.pose = pr.pose_id + np;
 	s.pf.priors = pr;
@@ -596,7 +685,7 @@ static void upload_relative_pose_edges(cuba_hip_solver& s)
 	posePtr.push_back((int)items.size());
 	const int nb = (int)blkId.size(), np = (int)poseId.size();
 	DeviceRelPoses rp;
-	upload_factor_arrays(s, set, concat({ &si, &sj, &blkPtr, &blkId, &posePtr, &poseId, &poseItem }), rp.q, rp.t, rp.info, rp.chi);
+	upload_factor_arrays(s, set, concat({ &si, &sj, &blkPtr, &blkId, &posePtr, &poseId, &poseItem }), rp.q, rp.t, rp.info, rp.chi, rp.rk_kind, rp.rk_delta);
 	s.d_relRec.resize((size_t)cubahip::REL_REC * std::max(n, 1));
 	rp.n = n; rp.nActive = nActive; rp.nBlocks = nb; rp.nPoses = np;
 	rp.pose_i = set.d_ints.data(); rp.pose_j = rp.pose_i + n;

@@ -514,6 +514,11 @@ int cuba_hip_set_relative_pose_edges(cuba_hip_solver* s, int n, const int32_t* p
 	return guarded(s, [&] { s->setRelativePoseEdges(n, pose_i, pose_j, q, t, info); });
 }
 
+int cuba_hip_set_pose_factor_robust_kernels(cuba_hip_solver* s, int factor_type, int n, const int32_t* kind, const double* delta)
+{
+	return guarded(s, [&] { s->setPoseFactorRobustKernels(factor_type, n, kind, delta); });
+}
+
 int cuba_hip_relative_pose_chi_squares(cuba_hip_solver* s, double* chi2_per_edge)
 {
 	return guarded(s, [&] {

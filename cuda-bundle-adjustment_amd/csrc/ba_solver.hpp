@@ -135,6 +135,7 @@ struct PoseFactorValues { std::vector<int> pi, pj; std::vector<double> q, t, inf
 struct PoseFactorSet
 {
 	PoseFactorValues v;
+	std::vector<int> kind; std::vector<double> delta;      // [n] robust kernels in the caller's numbering; empty: no factor has one
 	std::vector<int> order;          // sorted position -> caller's index (set by the upload)
 	bool uploaded = false;
 	DevBuf<int> d_ints; DevBuf<Scalar> d_vals, d_chi;
@@ -588,7 +589,8 @@ struct cuba_hip_solver
 	// The pose factors (ba_posefactor.hip): SE(3) pose priors (cuba_hip_set_pose_priors) and relative-pose edges
 	// (cuba_hip_set_relative_pose_edges).  Either set is kept as the caller gave it, in its own numbering (quaternions normalised,
 	// information symmetrised), with a device copy in the internal pose order that need() makes: the priors' once the pose order is known and
-	// again whenever that order changes; the edges' (their blocks are looked up in the pattern) with every structure.  No factors:
+	// again whenever that order changes; the edges' (their blocks are looked up in the pattern) with every structure; either again after
+	// cuba_hip_set_pose_factor_robust_kernels, whose kinds and deltas travel with the values.  No factors:
 	// poseFactors() is null, nothing of it is launched, no extra seed enters the pattern build, and every launch and kernel argument is as
 	// without this feature.
 	PoseFactorSet priorSet, relSet;
@@ -597,7 +599,7 @@ struct cuba_hip_solver
 	int poseFactorParts() const { return pose_factor_chi2_parts(poseFactors()); }      // chi2 partials that follow the reprojection edges'
 	void clearPoseFactors()
 	{
-		for (PoseFactorSet* set : { &priorSet, &relSet }) { set->v = PoseFactorValues(); set->order.clear(); set->uploaded = false; }
+		for (PoseFactorSet* set : { &priorSet, &relSet }) { set->v = PoseFactorValues(); set->kind.clear(); set->delta.clear(); set->order.clear(); set->uploaded = false; }
 		h_relPairs.clear(); pf = DevicePoseFactors();
 	}
 	void uploadPoseFactors();
@@ -606,6 +608,7 @@ struct cuba_hip_solver
 	void priorChiSquares(double* out);
 	void setRelativePoseEdges(int n, const int32_t* pi, const int32_t* pj, const double* q, const double* t, const double* info);
 	void relativePoseChiSquares(double* out);
+	void setPoseFactorRobustKernels(int factorType, int n, const int32_t* kind, const double* delta);
 	// the edges' distinct free-free pairs (sorted keys i << 32 | j, i < j, caller's numbering) and the pairs the current structure was seeded
 	// with: every such pair owns a block of the reduced matrix, so need() rebuilds the structure exactly when the two sets differ
 	std::vector<uint64_t> h_relPairs, structRelPairs;

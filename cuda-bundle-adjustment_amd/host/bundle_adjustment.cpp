@@ -391,6 +391,20 @@ public:
 		}
 		return a;
 	}
+	// the factors' robust kernels follow the set they belong to (a set without any: nothing is sent, the handle has none after the upload)
+	template <class F> void uploadFactorKernels(int factorType, const std::vector<F*>& factors)
+	{
+		const size_t n = factors.size();
+		std::vector<int32_t> kind(n);
+		std::vector<double> delta(n);
+		bool any = false;
+		for (size_t k = 0; k < n; k++)
+		{
+			kind[k] = static_cast<int32_t>(factors[k]->kernel); delta[k] = factors[k]->delta;
+			any = any || factors[k]->kernel != PoseFactorKernel::NONE;
+		}
+		if (any) check(cuba_hip_set_pose_factor_robust_kernels(solver_, factorType, (int)n, kind.data(), delta.data()), "cuba_hip_set_pose_factor_robust_kernels");
+	}
 
 	void addRelativePoseEdge(RelativePoseEdge* e)
 	{
@@ -417,6 +431,7 @@ public:
 		for (size_t k = 0; k < n; k++) { pi[k] = factorPose(relEdges_[k]->vertexI, refusal); pj[k] = factorPose(relEdges_[k]->vertexJ, refusal); }
 		const FactorArrays a = packFactors(relEdges_);
 		check(cuba_hip_set_relative_pose_edges(solver_, (int)n, pi.data(), pj.data(), a.q.data(), a.t.data(), a.info.data()), "cuba_hip_set_relative_pose_edges");
+		uploadFactorKernels(1, relEdges_);
 		relOnDevice_ = n > 0;
 		uploadedRel_ = relEdges_;
 	}
@@ -445,6 +460,7 @@ public:
 		for (size_t k = 0; k < n; k++) pose[k] = factorPose(priors_[k]->vertex, "cuba::addPosePrior: the vertex of a prior is not part of the graph");
 		const FactorArrays a = packFactors(priors_);
 		check(cuba_hip_set_pose_priors(solver_, (int)n, pose.data(), a.q.data(), a.t.data(), a.info.data()), "cuba_hip_set_pose_priors");
+		uploadFactorKernels(0, priors_);
 		priorsOnDevice_ = n > 0;
 		uploadedPriors_ = priors_;
 	}

@@ -108,18 +108,26 @@ struct CovarianceVertex
 using CovariancePair = std::pair<CovarianceVertex, CovarianceVertex>;
 bool computeCrossCovariances(CudaBundleAdjustment* object, const std::vector<CovariancePair>& pairs, std::vector<std::array<double, 36>>& out);
 
+// Robust kernel of a pose factor (PosePrior, RelativePoseEdge; include/cuba_hip.h, cuba_hip_set_pose_factor_robust_kernels): with
+// e = r^T Omega r the objective term becomes rho(e) and the linearisation takes rho'(e) Omega for Omega.  HUBER and TUKEY are the kernels of
+// the reprojection edges; CAUCHY, rho = delta^2 log1p(e / delta^2), exists for the pose factors only -- the usual choice on loop closures,
+// since its weight never reaches zero.  (RobustKernelType mirrors the reference's type and knows no Cauchy.)
+enum class PoseFactorKernel { NONE = 0, HUBER = 1, TUKEY = 2, CAUCHY = 3 };
+
 // Extension (g2o's unary pose edges; include/cuba_hip.h, cuba_hip_set_pose_priors): an SE(3) prior on one pose vertex -- prior pose (q, t),
 // world -> camera like the vertex, and a symmetric 6 x 6 information matrix, column-major, in the tangent [omega, upsilon] of the pose
 // update (poseCovariance's tangent: the inverse of one window's marginal is a prior of the next).  Objective term r^T Omega r with
-// r = log(T Tbar^-1), no robust kernel.  The caller owns the PosePrior, as it owns edges; additions, removals and changes take effect
+// r = log(T Tbar^-1), or rho(r^T Omega r) when `kernel` is set (`delta` > 0 then).  The caller owns the PosePrior, as it owns edges; additions, removals and changes take effect
 // at the next initialize().  removePoseVertex and clear() drop the priors of the vertex / all priors.  priorChiSquared: r^T Omega r at
-// the estimate of the last optimize() (0 before one, and for a prior on a fixed vertex).
+// the estimate of the last optimize() (0 before one, and for a prior on a fixed vertex) -- the plain value under a kernel too.
 struct PosePrior
 {
 	PoseVertex* vertex = nullptr;
 	PoseVertex::Rotation q;
 	PoseVertex::Translation t;
 	std::array<double, 36> information{};
+	PoseFactorKernel kernel = PoseFactorKernel::NONE;
+	double delta = 0;
 };
 void addPosePrior(CudaBundleAdjustment* object, PosePrior* prior);
 void removePosePrior(CudaBundleAdjustment* object, PosePrior* prior);
@@ -128,7 +136,8 @@ double priorChiSquared(const CudaBundleAdjustment* object, const PosePrior* prio
 // Extension (g2o's binary SE(3) edge; include/cuba_hip.h, cuba_hip_set_relative_pose_edges): a relative-pose edge between two different
 // pose vertices -- odometry, IMU pre-integration, loop closures.  (q, t) is the measured relative pose T_j T_i^-1 of the world -> camera
 // poses of `vertexI` and `vertexJ` (it maps camera-i coordinates to camera-j coordinates); `information` is symmetric 6 x 6, column-major,
-// in the tangent [omega, upsilon] of the pose update.  Objective term r^T Omega r with r = log(T_j T_i^-1 Zbar^-1), no robust kernel.
+// in the tangent [omega, upsilon] of the pose update.  Objective term r^T Omega r with r = log(T_j T_i^-1 Zbar^-1), or
+// rho(r^T Omega r) when `kernel` is set (`delta` > 0 then): a false loop closure under CAUCHY or TUKEY no longer bends the trajectory.
 // Ownership and lifetime as for PosePrior: the caller owns the edge; additions, removals and changes take effect at the next
 // initialize(); both vertices must be part of the graph then.  removePoseVertex drops the vertex's relative-pose edges, clear() all.
 // relativePoseChiSquared: r^T Omega r at the estimate of the last optimize() (0 before one, and for an edge between two fixed vertices).
@@ -139,6 +148,8 @@ struct RelativePoseEdge
 	PoseVertex::Rotation q;
 	PoseVertex::Translation t;
 	std::array<double, 36> information{};
+	PoseFactorKernel kernel = PoseFactorKernel::NONE;
+	double delta = 0;
 };
 void addRelativePoseEdge(CudaBundleAdjustment* object, RelativePoseEdge* edge);
 void removeRelativePoseEdge(CudaBundleAdjustment* object, RelativePoseEdge* edge);

@@ -366,8 +366,8 @@ int cuba_hip_compute_covariance_pairs(cuba_hip_solver* s, int n, const int32_t* 
    (x, y, z, w), normalised by the library) and a 6 x 6 information matrix Omega (symmetric, column-major, in the [omega, upsilon] order of
    the pose update T <- exp(d) T -- the tangent cuba_hip_compute_covariance reports in, so that Sigma^-1 of one window is a prior of the next).
      residual     r = log(T Tbar^-1) = [w ; V(w)^-1 (t - R Rbar^T tbar)], w = log(R Rbar^T)
-     objective    r^T Omega r, no robust kernel; the LM objective F (cuba_hip_optimize's chi2, cuba_hip_compute_errors, the gain ratio) is the
-                  robust edge sum plus the prior sum
+     objective    r^T Omega r, or rho(r^T Omega r) under a robust kernel (cuba_hip_set_pose_factor_robust_kernels below); the LM objective F
+                  (cuba_hip_optimize's chi2, cuba_hip_compute_errors, the gain ratio) is the robust edge sum plus the prior sum
      linearised   with J = J_l(r)^-1, the inverse left Jacobian of SE(3): Hpp += J^T Omega J, bp += -J^T Omega r (the convention
                   (H + lambda I) x = b of the rest of the ABI); in the reduced system the same terms land in the pose's diagonal block and in
                   bsc, and the maximum diagonal of lambda_0 = tau max diag(H) includes them.
@@ -391,8 +391,9 @@ int cuba_hip_prior_chi_squares(cuba_hip_solver* s, double* chi2_per_prior);
    library) and a 6 x 6 information matrix Omega (symmetric, column-major, [omega, upsilon] order of the pose update T <- exp(d) T, the
    tangent cuba_hip_compute_covariance reports in).
      residual     r = log(T_j T_i^-1 Zbar^-1)
-     objective    r^T Omega r, no robust kernel; the LM objective F (cuba_hip_optimize's chi2, cuba_hip_compute_errors, the gain ratio) is the
-                  robust edge sum plus the prior sum plus the relative-pose sum
+     objective    r^T Omega r, or rho(r^T Omega r) under a robust kernel (cuba_hip_set_pose_factor_robust_kernels below); the LM objective F
+                  (cuba_hip_optimize's chi2, cuba_hip_compute_errors, the gain ratio) is the robust edge sum plus the prior sum plus the
+                  relative-pose sum
      linearised   exactly under the solver's update: with M = T_j T_i^-1 = [R_M | t_M] and Ad(M) = [[R_M, 0], [[t_M]x R_M, R_M]],
                   J_j = dr/dd_j = J_l(r)^-1 and J_i = dr/dd_i = -J_l(r)^-1 Ad(M).  Hpp_ii += J_i^T Omega J_i, Hpp_jj += J_j^T Omega J_j,
                   Hpp_ij += J_i^T Omega J_j, bp_i += -J_i^T Omega r, bp_j += -J_j^T Omega r; the same terms in the reduced system (Hsc, bsc);
@@ -416,6 +417,31 @@ int cuba_hip_prior_chi_squares(cuba_hip_solver* s, double* chi2_per_prior);
 int cuba_hip_set_relative_pose_edges(cuba_hip_solver* s, int n, const int32_t* pose_i, const int32_t* pose_j, const double* q, const double* t,
 	const double* info);
 int cuba_hip_relative_pose_chi_squares(cuba_hip_solver* s, double* chi2_per_edge);
+
+/* ---- robust kernels on the pose factors (g2o's setRobustKernel on those edges) -------------------------------------------------------
+   Every pose prior (factor_type 0) and every relative-pose edge (factor_type 1) may carry a kernel (kind, delta) of its own.  With
+   e = r^T Omega r, residual and Omega as above:
+     objective    rho(e) in place of e: in the LM objective F, cuba_hip_compute_errors and the gain ratio
+     linearised   with w Omega in place of Omega, w = rho'(e), in every term of the factor (J^T Omega J, the cross block, J^T Omega r into bp /
+                  bsc); no second-order term -- the convention of the reprojection edges' kernels, and g2o's.  lambda_0 sees the weighted terms.
+     kind 0  none     rho = e                                                               w = 1
+          1  Huber    rho = e (e <= delta^2), 2 delta sqrt(e) - delta^2 beyond              w = 1, delta / sqrt(e)
+          2  Tukey    rho = delta^2 / 3 (1 - (1 - e / delta^2)^3), delta^2 / 3 beyond       w = (1 - e / delta^2)^2, 0
+          3  Cauchy   rho = delta^2 log1p(e / delta^2)                                      w = 1 / (1 + e / delta^2)
+   (Cauchy exists for the pose factors only: cuba_hip_set_robust_kernel refuses kind 3.)
+   kind[n], delta[n] are in the caller's order of the CURRENT set of that type; n is that set's count, or 0, which clears the kernels of the
+   type.  The kernels belong to the set: cuba_hip_set_pose_priors / cuba_hip_set_relative_pose_edges (the replaced set is a new set) and
+   cuba_hip_set_graph drop them.  Setting kernels never rebuilds the structure ("structure_builds" stays); it drops the run-to-run memories
+   of option "heuristics" and invalidates cached covariance blocks, as a change of the factors' values does.  A handle that never sets a
+   kernel (or sets kinds all 0) runs exactly the code and computes exactly the bits of a library without this entry point.
+   Every solve path honours the kernels (those listed above, cuba_hip_optimize_batch included).  The covariance entry points report the
+   inverse of the WEIGHTED Hessian at the current estimate: a factor that Tukey has given weight 0 contributes nothing, so a graph that
+   depended on it for its gauge reports not_positive_definite.
+   cuba_hip_prior_chi_squares / cuba_hip_relative_pose_chi_squares keep returning the plain r^T Omega r (what a caller gates on; w follows).
+   CUBA_HIP_ERR_INVALID_ARGUMENT, the handle unchanged: n neither 0 nor the set's count, factor_type outside {0, 1}, a kind outside 0..3, a
+   non-finite delta, delta <= 0 on a kind != 0. */
+int cuba_hip_set_pose_factor_robust_kernels(cuba_hip_solver* s, int factor_type /* 0 priors, 1 relative-pose edges */, int n, const int32_t* kind,
+	const double* delta);
 
 /* ---- introspection (parity tests) and multi-GPU plumbing ------------------------------------------ */
 

@@ -2,12 +2,15 @@
 
     python scripts/relative_pose_times.py [--shape kitti00] [--iters 10] [--reps 10] [--closures 20] [--out file.json]
 
-Three variants of one shape, each on a handle of its own: (a) no relative-pose edges, (b) odometry edges on every consecutive pose pair,
-(c) (b) plus `closures` long-range loop closures between poses that share no landmark.  The measurements are the relative poses of the
-start, a few centimetres / tenths of a degree off.  Per repeat the variants run in turn (every run starts from the same estimate, restored
+Four variants of one shape, each on a handle of its own: (a) no relative-pose edges, (b) odometry edges on every consecutive pose pair,
+(c) (b) plus `closures` long-range loop closures between poses that share no landmark, (d) (c) with robust kernels
+(set_pose_factor_robust_kernels): Huber on every odometry edge, Cauchy on the closures, delta^2 = 12.592.  The measurements are the
+relative poses of the start, a few centimetres / tenths of a degree off.  Per repeat the variants run in turn (every run starts from the same estimate, restored
 with set_state) and the wall time of optimize(iters) is taken; the script reports medians, minima and the spread per variant, the ratio of
 each variant's median to (a)'s, and -- to tell the cost of the launches from that of the graph -- the PCG iterations and the blocks of the
-reduced matrix of each variant."""
+reduced matrix of each variant.  (d) is timed in a second round against (c) alone, after (b)'s handle is closed -- at most three handles
+(streams) are alive at a time, as in the first round: a fourth one slows every variant down -- and reported with its ratio to (c) of
+that round."""
 import argparse
 import json
 import os
@@ -51,6 +54,23 @@ def edges_on(fp, pairs, seed=0):
     return (np.array([p[0] for p in pairs], dtype=np.int32), np.array([p[1] for p in pairs], dtype=np.int32), np.array(qz), np.array(tz), info)
 
 
+def run_rounds(a, handles, start, times, info):
+    """reps + 1 rounds over the handles in turn, every run from `start`; round 0 is the warm-up (structure, allocations, coarse inverse
+    memory)"""
+    for rep in range(a.reps + 1):
+        for name, h in handles.items():
+            h.set_state(*start)
+            before = h.counters()["pcg_iterations"]
+            t0 = time.perf_counter()
+            c = h.optimize(a.iters)["chi2"]
+            dt = time.perf_counter() - t0
+            if rep > 0:
+                times[name].append(dt)
+            cnt = h.counters()
+            info[name] = dict(final_chi2=float(c[-1]), pcg_iterations=cnt["pcg_iterations"] - before, hsc_blocks=cnt["hsc_blocks"],
+                              exact_solves=h.counter("exact_solve_fallbacks"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", default="kitti00")
@@ -82,24 +102,26 @@ def main():
     start = plain.state()
     times = {name: [] for name in variants}
     info = {}
-    for rep in range(a.reps + 1):                 # (repeat 0 is the warm-up: structure, allocations, coarse inverse memory)
-        for name, h in handles.items():
-            h.set_state(*start)
-            before = h.counters()["pcg_iterations"]
-            t0 = time.perf_counter()
-            c = h.optimize(a.iters)["chi2"]
-            dt = time.perf_counter() - t0
-            if rep > 0:
-                times[name].append(dt)
-            cnt = h.counters()
-            info[name] = dict(final_chi2=float(c[-1]), pcg_iterations=cnt["pcg_iterations"] - before, hsc_blocks=cnt["hsc_blocks"],
-                              exact_solves=h.counter("exact_solve_fallbacks"))
+    run_rounds(a, handles, start, times, info)
+    # second round: (d) against (c)
+    handles.pop("odometry").close()
+    variants["robust"] = variants["odometry_and_closures"]
+    robust = HipSolver(fp, RK_HUBER)
+    robust.set_relative_pose_edges(*variants["robust"])
+    robust.set_pose_factor_robust_kernels(1, [1] * len(odometry) + [3] * len(closures), float(np.sqrt(12.592)))
+    second = {"odometry_and_closures": handles["odometry_and_closures"], "robust": robust}
+    times2 = {name: [] for name in second}
+    run_rounds(a, second, start, times2, info)
+    times["robust"] = times2["robust"]
+    handles["robust"] = robust
     base = float(np.median(times["none"]))
     out = dict(shape=a.shape, poses=fp.Pf, landmarks=fp.Lf, edges=fp.E, iterations=a.iters, reps=a.reps)
     for name in variants:
         ts = 1e3 * np.array(times[name])
         out[name] = dict(ms_median=float(np.median(ts)), ms_min=float(ts.min()), ms_max=float(ts.max()), ratio_to_none=float(np.median(ts)) / (1e3 * base),
                          relative_pose_edges=0 if variants[name] is None else len(variants[name][0]), **info[name])
+    out["robust"]["ratio_to_odometry_and_closures"] = float(np.median(times2["robust"]) / np.median(times2["odometry_and_closures"]))
+    out["robust"]["odometry_and_closures_ms_median_same_round"] = 1e3 * float(np.median(times2["odometry_and_closures"]))
     print(json.dumps(out), flush=True)
     if a.out:
         json.dump(out, open(a.out, "w"), indent=1)
