@@ -266,7 +266,7 @@ __device__ __forceinline__ void lm_decide(double* st, Scalar* lamOut, double* ri
 }
 
 __device__ __forceinline__ void reduce_report_body(const DeviceSystem& sys, const Scalar* pA, int nA, Scalar* oA, const Scalar* pB, int nB, Scalar* oB,
-	const Scalar* pC, int nC, Scalar* oC, double* lmState, Scalar* lmLam, double* lmRing)
+	const Scalar* pC, int nC, Scalar* oC, double* lmState, Scalar* lmLam, double* lmRing, int publish)
 {
 	__shared__ Scalar sh[3][16];
 	// the three sums side by side: thread shares first, then one barrier for all of them (each is added exactly as
@@ -281,6 +281,9 @@ __device__ __forceinline__ void reduce_report_body(const DeviceSystem& sys, cons
 		store_slot_group(oA, tA); store_slot_group(oB, tB); store_slot_group(oC, tC);
 		if (lmState && threadIdx.x == 0) lm_decide(lmState, lmLam, lmRing, 1, (double)tA, (double)tB, (double)tC);
 	}
+	// publish = 0 (a decision of the device-decided run that the host does not wait for): the record and the slots are plain stores into
+	// the coherent mapped blocks, no ticket; the ticket of the next reduced solve's report, written by a later kernel, covers them
+	if (!publish) return;
 	__threadfence_system();          // every writer's results before the ticket
 	asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // (and landed: see publish_report)
 	__syncthreads();
@@ -289,9 +292,9 @@ __device__ __forceinline__ void reduce_report_body(const DeviceSystem& sys, cons
 
 
 __global__ __launch_bounds__(1024) void reduce_report_kernel(DeviceSystem sys, const Scalar* pA, int nA, Scalar* oA, const Scalar* pB, int nB, Scalar* oB,
-	const Scalar* pC, int nC, Scalar* oC, double* lmState, Scalar* lmLam, double* lmRing)
+	const Scalar* pC, int nC, Scalar* oC, double* lmState, Scalar* lmLam, double* lmRing, int publish)
 {
-	reduce_report_body(sys, pA, nA, oA, pB, nB, oB, pC, nC, oC, lmState, lmLam, lmRing);
+	reduce_report_body(sys, pA, nA, oA, pB, nB, oB, pC, nC, oC, lmState, lmLam, lmRing, publish);
 }
 
 __global__ __launch_bounds__(1024) void reduce_report_batch_kernel(const BatchEntry* __restrict__ tab)
@@ -299,7 +302,7 @@ __global__ __launch_bounds__(1024) void reduce_report_batch_kernel(const BatchEn
 	const BatchEntry& e = tab[blockIdx.x];
 	const BatchTrial& t = e.t;
 	if (!t.reportOn) return;
-	reduce_report_body(e.sys, t.scParts, t.nA, e.sys.slots + NSLOT, t.chiParts, t.nA, e.sys.slots, t.scaleParts, 4 * t.nScale, e.sys.slots + 3 * NSLOT, t.lmState, t.lmLam, t.lmRing);
+	reduce_report_body(e.sys, t.scParts, t.nA, e.sys.slots + NSLOT, t.chiParts, t.nA, e.sys.slots, t.scaleParts, 4 * t.nScale, e.sys.slots + 3 * NSLOT, t.lmState, t.lmLam, t.lmRing, 1);
 }
 
 __global__ __launch_bounds__(256) void landmark_scale_kernel(DeviceGraph g, DeviceSystem sys, Scalar lambda, Scalar* parts)
@@ -630,7 +633,7 @@ size_t trial_tail_parts(const DeviceGraph& g, const DeviceStructure& st, int fac
 }
 
 void launch_trial_tail_fused(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, Scalar lambda, const Scalar* old, hipStream_t s,
-	const LmDevice* decide, const DevicePoseFactors* pf)
+	const LmDevice* decide, const DevicePoseFactors* pf, int publish)
 {
 	const int nLm = (st.nWaves + LIN_BLOCK / WAVE - 1) / (LIN_BLOCK / WAVE);
 	const int nA = nLm + st.nBig;
@@ -645,7 +648,7 @@ void launch_trial_tail_fused(const DeviceGraph& g, const DeviceStructure& st, co
 	if (st.nBig > 0) hipLaunchKernelGGL(big_trial_tail_kernel, dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, old, scParts + nLm, chiParts + nLm);
 	if (nPf > 0) launch_pose_factor_chi2(g, *pf, chiParts + nA, s);          // (at the poses the edge pass has just updated)
 	hipLaunchKernelGGL(reduce_report_kernel, dim3(1), dim3(1024), 0, s, sys, scParts, nA, sys.slots + NSLOT, chiParts, nA + nPf, sys.slots, scaleParts, 4 * nScale, sys.slots + 3 * NSLOT,
-		decide ? decide->state : (double*)nullptr, decide ? decide->lam : (Scalar*)nullptr, decide ? decide->ring : (double*)nullptr);
+		decide ? decide->state : (double*)nullptr, decide ? decide->lam : (Scalar*)nullptr, decide ? decide->ring : (double*)nullptr, publish);
 }
 
 // launch_trial_tail_fused + launch_restore_if_rejected of one graph as entries of the batched launches (no landmark with more than 64 observations)
@@ -677,6 +680,28 @@ __global__ void lm_decide_failed_kernel(DeviceSystem sys, double* lmState, Scala
 void launch_lm_decide_failed(const DeviceSystem& sys, const LmDevice& lm, hipStream_t s)
 {
 	hipLaunchKernelGGL(lm_decide_failed_kernel, dim3(1), dim3(64), 0, s, sys, lm.state, lm.lam, lm.ring);
+}
+
+// Start of a device-decided run without a host round trip: F0 from the slot group launch_residual_chi2 left (added as readSlots adds it,
+// slot by slot), lambda0 = tau * max diagonal (the largest of the 64 bit patterns, multiplied once), the decision state, the damping as the
+// kernels read it.  One thread.
+__global__ void lm_run_init_kernel(const Scalar* __restrict__ chiSlots, const unsigned long long* __restrict__ maxdiag, double* lmState, Scalar* lmLam,
+	double tau, double tagBase, double maxq)
+{
+#pragma clang fp contract(off)
+	if (threadIdx.x != 0 || blockIdx.x != 0) return;
+	double F = 0;
+	for (int i = 0; i < NSLOT; i++) F += (double)chiSlots[i];
+	unsigned long long m = 0;
+	for (int i = 0; i < 64; i++) m = maxdiag[i] > m ? maxdiag[i] : m;
+	const double lam = tau * __longlong_as_double((long long)m);
+	lmState[0] = F; lmState[1] = lam; lmState[2] = 2.0; lmState[3] = 0.0; lmState[4] = 0.0; lmState[5] = 1.0; lmState[6] = 0.0; lmState[7] = maxq; lmState[8] = tagBase;
+	lmLam[0] = (Scalar)lam;
+}
+
+void launch_lm_run_init(const Scalar* chiSlots, const unsigned long long* maxdiag, const LmDevice& lm, double tau, double tagBase, int maxq, hipStream_t s)
+{
+	hipLaunchKernelGGL(lm_run_init_kernel, dim3(1), dim3(64), 0, s, chiSlots, maxdiag, lm.state, lm.lam, tau, tagBase, (double)maxq);
 }
 
 // the reference's pop() when -- and only when -- the decision before it was a rejection

@@ -205,8 +205,11 @@ void launch_residual_chi2(const DeviceGraph& g, Scalar* parts, Scalar* slots, Sc
 // range != nullptr (landmark partitions whose reduction is cut into parts, ba_setup.hip: cutReductionParts): the block pass covers the
 // entries [begin, end) of st.od_blocks only, the first `heavy` of them with a whole wave each; launch_block_pass runs a further range
 struct BlockPassRange { int begin, end, heavy; };
+// restoreFlag != nullptr (cuba_hip_optimize; needs st.nWaves > 0 and a backup): the LM decision state's "last trial accepted" number.  When it
+// is zero the same launch undoes the rejected trial instead: the landmark workgroups read poses and landmarks from backupDst -- which holds
+// the estimate the trial started from and which nobody writes in this launch -- and the copy workgroups copy backupDst -> backupSrc
 void launch_linearize_dm(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, int mode, Scalar lambda, hipStream_t s,
-	const Scalar* backupSrc = nullptr, Scalar* backupDst = nullptr, size_t backupCount = 0, const BlockPassRange* range = nullptr);
+	Scalar* backupSrc = nullptr, Scalar* backupDst = nullptr, size_t backupCount = 0, const BlockPassRange* range = nullptr, const double* restoreFlag = nullptr);
 void launch_block_pass(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const BlockPassRange& range, hipStream_t s);
 
 // max over the diagonal of the diagonal blocks of hsc (Hpp after an assemble pass) folded into sys.maxdiag
@@ -224,8 +227,10 @@ void launch_pose_scale(const DeviceGraph& g, const DeviceSystem& sys, Scalar lam
 struct LmDevice;
 // pf (optional): the pose factors' chi2 at the updated poses, launches between the edge pass and the sums; their partials join the edges'
 // chi2 partials
+// publish = 0: the decision's record goes out with plain stores, without the system-scope fence and the ticket (the caller then does not
+// count a report): for decisions the host does not wait for
 void launch_trial_tail_fused(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, Scalar lambda, const Scalar* old, hipStream_t s,
-	const LmDevice* decide = nullptr, const DevicePoseFactors* pf = nullptr);
+	const LmDevice* decide = nullptr, const DevicePoseFactors* pf = nullptr, int publish = 1);
 size_t trial_tail_parts(const DeviceGraph& g, const DeviceStructure& st, int factorParts = 0);      // factorParts: pose_factor_chi2_parts()
 // Device-resident LM decision (control flow of CudaBundleAdjustmentImpl::optimize, /root/reference/src/cuda_bundle_adjustment.cpp:816-851):
 // state = {F, lambda, nu, halt, trials, accepted (last trial), rejections in a row, max rejections} in device memory, lam = the damping as
@@ -235,6 +240,9 @@ size_t trial_tail_parts(const DeviceGraph& g, const DeviceStructure& st, int fac
 // launch_restore_if_rejected copies the backup over the estimates when the last decision was a rejection (the reference's pop()).
 constexpr int LM_REC = 8, LM_RING = 64;
 struct LmDevice { double* state = nullptr; Scalar* lam = nullptr; double* ring = nullptr; };
+// the start of a run on the device: state = {F0 = the sum of the NSLOT numbers at chiSlots, lambda0 = tau * the largest of the 64 numbers at maxdiag, 2, 0, 0,
+// 1, 0, maxq, tagBase}, lam = lambda0
+void launch_lm_run_init(const Scalar* chiSlots, const unsigned long long* maxdiag, const LmDevice& lm, double tau, double tagBase, int maxq, hipStream_t s);
 void launch_lm_decide_failed(const DeviceSystem& sys, const LmDevice& lm, hipStream_t s);
 void launch_restore_if_rejected(Scalar* state, const Scalar* backup, size_t count, const LmDevice& lm, hipStream_t s);
 // landmark-side part recomputed from xl and the stored bl (stage API; the fused path gets it from back_substitute)

@@ -56,17 +56,26 @@ __device__ __forceinline__ void load_pose_as(const DeviceGraph& g, int ip, ET q[
 }
 
 // Workgroups beyond nLmGroups (optimize() only) copy the state into its backup: the push() of the LM loop rides in this launch.
+// restoreFlag (cuba_hip_optimize): the decision state's "last trial accepted" number.  Zero = the trial before this launch was rejected and
+// its restore rides in this launch too: the backup is the estimate to linearise at, so the landmark workgroups read poses and landmarks from
+// it (nobody writes it in this launch) while the copy workgroups copy it over the state -- the reference's pop() followed by its push().
 template <int MODE, typename ET>
 __device__ __forceinline__ void lm_pass_body(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, Scalar lambda,
-	unsigned nLmGroups, const Scalar* __restrict__ backupSrc, Scalar* __restrict__ backupDst, size_t backupCount, unsigned gridX)
+	unsigned nLmGroups, Scalar* backupSrc, Scalar* backupDst, size_t backupCount, unsigned gridX, const double* restoreFlag)
 {
 	__shared__ Scalar lds_all[(LIN_BLOCK / WAVE) * WAVE * 9];
+	const bool restore = restoreFlag != nullptr && restoreFlag[0] == 0.0;
 	if (blockIdx.x >= nLmGroups)
 	{
 		const size_t stride = (size_t)(gridX - nLmGroups) * LIN_BLOCK;
-		for (size_t i = (size_t)(blockIdx.x - nLmGroups) * LIN_BLOCK + threadIdx.x; i < backupCount; i += stride) backupDst[i] = backupSrc[i];
+		if (restore) for (size_t i = (size_t)(blockIdx.x - nLmGroups) * LIN_BLOCK + threadIdx.x; i < backupCount; i += stride) backupSrc[i] = backupDst[i];
+		else for (size_t i = (size_t)(blockIdx.x - nLmGroups) * LIN_BLOCK + threadIdx.x; i < backupCount; i += stride) backupDst[i] = backupSrc[i];
 		return;
 	}
+	// the estimate to linearise at: the state, or -- the restore rides in this launch -- its backup
+	const Scalar* __restrict__ sq = restore ? backupDst : g.q;
+	const Scalar* __restrict__ stt = restore ? backupDst + 4 * (size_t)g.Pt : g.t;
+	const Scalar* __restrict__ sX = restore ? backupDst + 7 * (size_t)g.Pt : g.Xw;
 	lambda = launch_lambda(sys, lambda);
 	const int lane = threadIdx.x & 63;
 	const int wv = threadIdx.x >> 6;
@@ -87,9 +96,14 @@ __device__ __forceinline__ void lm_pass_body(const DeviceGraph& g, const DeviceS
 		il = g.e_lm[e];
 		Scalar q[4], t[3], cam[5], Xw[3], meas[3], Xc[3];
 		EdgeLin L;
-		load_pose(g, ip, q, t, cam);
 #pragma unroll
-		for (int i = 0; i < 3; i++) Xw[i] = g.Xw[3 * (size_t)il + i];
+		for (int i = 0; i < 4; i++) q[i] = sq[4 * (size_t)ip + i];
+#pragma unroll
+		for (int i = 0; i < 3; i++) t[i] = stt[3 * (size_t)ip + i];
+#pragma unroll
+		for (int i = 0; i < 5; i++) cam[i] = g.cam[5 * (size_t)ip + i];
+#pragma unroll
+		for (int i = 0; i < 3; i++) Xw[i] = sX[3 * (size_t)il + i];
 		meas[0] = g.e_mu[e]; meas[1] = g.e_mv[e]; meas[2] = g.e_mr[e];
 		const Scalar w = g.e_w[e];
 		const Scalar ss = edge_residual(q, t, cam, Xw, meas, stereo, L.r, Xc);
@@ -159,9 +173,9 @@ __device__ __forceinline__ void lm_pass_body(const DeviceGraph& g, const DeviceS
 
 template <int MODE, typename ET>
 __global__ __launch_bounds__(LIN_BLOCK) void lm_pass_kernel(DeviceGraph g, DeviceStructure st, DeviceSystem sys, Scalar lambda,
-	unsigned nLmGroups, const Scalar* __restrict__ backupSrc, Scalar* __restrict__ backupDst, size_t backupCount)
+	unsigned nLmGroups, Scalar* __restrict__ backupSrc, Scalar* __restrict__ backupDst, size_t backupCount, const double* restoreFlag)
 {
-	lm_pass_body<MODE, ET>(g, st, sys, lambda, nLmGroups, backupSrc, backupDst, backupCount, gridDim.x);
+	lm_pass_body<MODE, ET>(g, st, sys, lambda, nLmGroups, backupSrc, backupDst, backupCount, gridDim.x, restoreFlag);
 }
 
 // batched forms (cuba_hip_optimize_batch): blockIdx.y = graph, arguments from the device table, the damping from device memory
@@ -170,7 +184,7 @@ __global__ __launch_bounds__(LIN_BLOCK) void lm_pass_batch_kernel(const BatchEnt
 {
 	const BatchEntry& e = tab[blockIdx.y];
 	if (blockIdx.x >= e.t.lmGrid) return;
-	lm_pass_body<1, ET>(e.g, e.st, e.sys, Scalar(-1), e.t.lmGroups, e.t.backupSrc, e.t.backupDst, e.t.backupCount, e.t.lmGrid);
+	lm_pass_body<1, ET>(e.g, e.st, e.sys, Scalar(-1), e.t.lmGroups, const_cast<Scalar*>(e.t.backupSrc), e.t.backupDst, e.t.backupCount, e.t.lmGrid, nullptr);
 }
 
 // landmarks with more than 64 observations: one workgroup each
@@ -557,7 +571,7 @@ static DeviceStructure block_pass_view(const DeviceStructure& st, const BlockPas
 
 template <typename ET>
 static void launch_linearize_dm_t(const DeviceGraph& g, const DeviceStructure& stAll, const DeviceSystem& sys, int mode, Scalar lambda, hipStream_t s,
-	const Scalar* backupSrc, Scalar* backupDst, size_t backupCount, const BlockPassRange* range)
+	Scalar* backupSrc, Scalar* backupDst, size_t backupCount, const BlockPassRange* range, const double* restoreFlag)
 {
 	// (the landmark and pose passes read nothing of the block list: one view serves the whole launch sequence)
 	const DeviceStructure st = range ? block_pass_view(stAll, *range) : stAll;
@@ -565,8 +579,8 @@ static void launch_linearize_dm_t(const DeviceGraph& g, const DeviceStructure& s
 	{
 		const unsigned grid = (st.nWaves + (LIN_BLOCK / WAVE) - 1) / (LIN_BLOCK / WAVE);
 		const unsigned nCopy = backupSrc ? (unsigned)std::min<size_t>(512, (backupCount + LIN_BLOCK - 1) / LIN_BLOCK) : 0;
-		if (mode == 0) hipLaunchKernelGGL((lm_pass_kernel<0, ET>), dim3(grid + nCopy), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, grid, backupSrc, backupDst, backupCount);
-		else hipLaunchKernelGGL((lm_pass_kernel<1, ET>), dim3(grid + nCopy), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, grid, backupSrc, backupDst, backupCount);
+		if (mode == 0) hipLaunchKernelGGL((lm_pass_kernel<0, ET>), dim3(grid + nCopy), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, grid, backupSrc, backupDst, backupCount, nCopy ? restoreFlag : nullptr);
+		else hipLaunchKernelGGL((lm_pass_kernel<1, ET>), dim3(grid + nCopy), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, grid, backupSrc, backupDst, backupCount, nCopy ? restoreFlag : nullptr);
 	}
 	else if (backupSrc && backupCount)
 		(void)hipMemcpyAsync(backupDst, backupSrc, backupCount * sizeof(Scalar), hipMemcpyDeviceToDevice, s);
@@ -592,10 +606,10 @@ static void launch_linearize_dm_t(const DeviceGraph& g, const DeviceStructure& s
 }
 
 void launch_linearize_dm(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, int mode, Scalar lambda, hipStream_t s,
-	const Scalar* backupSrc, Scalar* backupDst, size_t backupCount, const BlockPassRange* range)
+	Scalar* backupSrc, Scalar* backupDst, size_t backupCount, const BlockPassRange* range, const double* restoreFlag)
 {
-	if (st.mixed && sizeof(Scalar) == 8) launch_linearize_dm_t<float>(g, st, sys, mode, lambda, s, backupSrc, backupDst, backupCount, range);
-	else launch_linearize_dm_t<Scalar>(g, st, sys, mode, lambda, s, backupSrc, backupDst, backupCount, range);
+	if (st.mixed && sizeof(Scalar) == 8) launch_linearize_dm_t<float>(g, st, sys, mode, lambda, s, backupSrc, backupDst, backupCount, range, restoreFlag);
+	else launch_linearize_dm_t<Scalar>(g, st, sys, mode, lambda, s, backupSrc, backupDst, backupCount, range, restoreFlag);
 }
 
 // what launch_linearize_dm_t (mode 1, whole graph, no landmark with more than 64 observations, no duplicate observation) launches for one

@@ -151,7 +151,8 @@ void cuba_hip_solver::linearize(int mode, double lam, bool withBackup)
 {
 	waitAssembled();            // an overlapped coarse assembly may still be reading the previous reduced matrix
 	const bool parts = mode == 1 && !redParts.empty();
-	launch_linearize_dm(g, st, sys, mode, lam, stream, withBackup ? d_state.data() : nullptr, d_backup.data(), d_state.size(), parts ? &redParts[0].od : nullptr);
+	launch_linearize_dm(g, st, sys, mode, lam, stream, withBackup ? d_state.data() : nullptr, d_backup.data(), d_state.size(), parts ? &redParts[0].od : nullptr,
+		withBackup ? lmRestoreFlag : nullptr);
 	if (parts && !partsByCaller)
 		for (size_t c = 1; c < redParts.size(); c++) launch_block_pass(g, st, sys, redParts[c].od, stream);
 	// (a launch of its own: the Schur pass's block part may still update a diagonal block its pose part stored)
@@ -466,21 +467,8 @@ bool cuba_hip_solver::solveBegin(SolveCtx& sc)
 					sc.deferCoarse->push_back(CoarseJob{ this, first, firstInvPending, !deferred });
 					if (firstInvPending) { firstInvPending = false; firstInvValid = true; }
 				}
-				else
-				{
-					HIP_TRY(hipStreamWaitEvent(gjStream, evSetup, 0));
-					(void)launch_coarse_setup(g, st, sys, d_coarse[first].data(), d_coarse[1 - first].data(), gjStream, evAssembled);
-					if (fp32Inverse()) launch_coarse_to_fp32(d_coarse[0].data(), d_coarse32[1].data(), 6 * sys.cl * sys.nc, gjStream);   // (staging: the iteration graphs read [0])
-					else launch_coarse_finish(d_coarse[0].data(), d_coarse[0].data(), 6 * sys.cl * sys.nc, gjStream);                     // (the sweep leaves -inverse in the upper triangle)
-					if (firstInvPending)
-					{
-						if (fp32Inverse()) HIP_TRY(hipMemcpyAsync(d_firstInv32.data(), d_coarse32[1].data(), inv32Count() * sizeof(float), hipMemcpyDeviceToDevice, gjStream));
-						else HIP_TRY(hipMemcpyAsync(d_firstInv.data(), d_coarse[0].data(), invBytes, hipMemcpyDeviceToDevice, gjStream));
-						HIP_TRY(hipEventRecord(evFirstInv, gjStream));
-						firstInvPending = false; firstInvValid = true;
-					}
-					HIP_TRY(hipEventRecord(evInverse, gjStream));
-				}
+				else if (sc.sideLater) sc.sideFirst = first;      // (the caller enqueues it behind the first chunk of iterations: enqueueCoarseSide)
+				else enqueueCoarseSide(first);
 				pendingInv = 0;
 				assemblePending = true; cntCoarseRefresh++;
 			}
@@ -525,6 +513,27 @@ bool cuba_hip_solver::solveBegin(SolveCtx& sc)
 	return false;
 }
 
+// The overlapped inversion of this trial's coarse matrix on the second stream, behind the set-up launch (evSetup): assembly, sweep (some
+// 35 launches at 32 sweep steps, > 100 us of host time), conversion, the copy for the next run's first solve.  solveBegin enqueues it
+// between the set-up launch and the first preconditioner application; cuba_hip_optimize (SolveCtx::sideLater) enqueues the first
+// preconditioner application and the first chunk of iterations first, so that the main stream never waits for the host.
+void cuba_hip_solver::enqueueCoarseSide(int first)
+{
+	const size_t invBytes = sizeof(Scalar) * (size_t)36 * sys.cl * sys.cl * sys.nc * sys.nc;
+	HIP_TRY(hipStreamWaitEvent(gjStream, evSetup, 0));
+	(void)launch_coarse_setup(g, st, sys, d_coarse[first].data(), d_coarse[1 - first].data(), gjStream, evAssembled);
+	if (fp32Inverse()) launch_coarse_to_fp32(d_coarse[0].data(), d_coarse32[1].data(), 6 * sys.cl * sys.nc, gjStream);   // (staging: the iteration graphs read [0])
+	else launch_coarse_finish(d_coarse[0].data(), d_coarse[0].data(), 6 * sys.cl * sys.nc, gjStream);                     // (the sweep leaves -inverse in the upper triangle)
+	if (firstInvPending)
+	{
+		if (fp32Inverse()) HIP_TRY(hipMemcpyAsync(d_firstInv32.data(), d_coarse32[1].data(), inv32Count() * sizeof(float), hipMemcpyDeviceToDevice, gjStream));
+		else HIP_TRY(hipMemcpyAsync(d_firstInv.data(), d_coarse[0].data(), invBytes, hipMemcpyDeviceToDevice, gjStream));
+		HIP_TRY(hipEventRecord(evFirstInv, gjStream));
+		firstInvPending = false; firstInvValid = true;
+	}
+	HIP_TRY(hipEventRecord(evInverse, gjStream));
+}
+
 bool cuba_hip_solver::solveBrokeDown(SolveCtx& sc)
 {
 	lastSolveBrokeDown = true; lastFailCode = sc.hInts[0];
@@ -545,6 +554,7 @@ bool cuba_hip_solver::solveReducedOnce()
 {
 	StageTimer tm(this, 6);
 	SolveCtx sc;
+	sc.sideLater = coarseSideLater;
 	if (solveBegin(sc)) return sc.result;
 	const int maxIter = sc.maxIter; const Scalar tol2 = sc.tol2; const bool graphs = sc.graphs; const int predicted = sc.predicted;
 	// Iterations are enqueued in chunks (graphs of 4/8/.../256 iterations; chunk lengths are multiples of 4
@@ -582,6 +592,7 @@ bool cuba_hip_solver::solveReducedOnce()
 				if (graphs) { eagerIters += c; cntPcgPlain += c; }
 			}
 			k0 += c; todo -= c;
+			if (sc.sideFirst >= 0) { enqueueCoarseSide(sc.sideFirst); sc.sideFirst = -1; }       // (queued main-stream work now covers its host time)
 		}
 		waitReport();
 		if (sc.hInts[0] != 0) return solveBrokeDown(sc);
@@ -662,7 +673,10 @@ double cuba_hip_solver::computeScale(double lam)
 }
 
 // ---- the device-decided LM run in steps (shared by cuba_hip_optimize and cuba_hip_optimize_batch) ---------------------------------------
-void cuba_hip_solver::lmRunBegin(LmRun& r, int niter, double* chi2Out)
+// chain (cuba_hip_optimize alone): the run keeps fixed work off its dependent chain -- F0 and lambda0 are formed on the device, a decision's
+// record is published with a system-scope fence and a ticket only when the host will wait for it, and a rejected trial is undone by the next
+// trial's landmark pass
+void cuba_hip_solver::lmRunBegin(LmRun& r, int niter, double* chi2Out, bool chain)
 {
 	const double tau = 1e-5;
 	if (!h_lmRing)
@@ -677,6 +691,23 @@ void cuba_hip_solver::lmRunBegin(LmRun& r, int niter, double* chi2Out)
 	startRunHistory();
 	r = LmRun();
 	r.niter = niter; r.chi2Out = chi2Out; r.stop = niter <= 0;
+	r.lm.state = d_lmState.data(); r.lm.lam = d_lamS.data(); r.lm.ring = lmRingDev;
+	if (chain && niter > 0)
+	{
+		// no host round trip: the launches of computeErrors() and maxDiagonal(), then one thread that forms F0 and lambda0 = tau * max diagonal
+		// with the host's expressions and writes the decision state; the host takes F and lambda from the first record it absorbs
+		need();
+		r.chain = true;
+		Scalar* chiSlots = reinterpret_cast<Scalar*>(d_lmState.data() + 16);        // (NSLOT numbers)
+		launch_residual_chi2(g, d_parts.data(), chiSlots, nullptr, stream, poseFactors());
+		zeroReduced(true);
+		d_maxdiag.zero(stream);
+		linearize(0, 0.0);
+		launch_pose_maxdiag(g, st, sys, stream);
+		r.tagBase = 65536.0 * (double)(++lmRunNonce);                               // (every record of this run carries tagBase + trial number + 1)
+		launch_lm_run_init(chiSlots, d_maxdiag.data(), r.lm, tau, r.tagBase, LmRun::maxq, stream);
+		return;
+	}
 	r.F = computeErrors();
 	r.lam = tau * maxDiagonal();
 	{
@@ -688,7 +719,6 @@ void cuba_hip_solver::lmRunBegin(LmRun& r, int niter, double* chi2Out)
 		HIP_TRY(hipMemcpyAsync(d_lmState.data(), st8, sizeof(double) * 9, hipMemcpyHostToDevice, stream));
 		HIP_TRY(hipMemcpyAsync(d_lamS.data(), l1, sizeof(Scalar), hipMemcpyHostToDevice, stream));
 	}
-	r.lm.state = d_lmState.data(); r.lm.lam = d_lamS.data(); r.lm.ring = lmRingDev;
 }
 
 // outcomes of the trials [seen, upto): every one of them is complete (the caller has waited for a report that follows them in the stream)
@@ -752,10 +782,17 @@ bool cuba_hip_solver::lmAfterSolveHost(LmRun& r)
 bool cuba_hip_solver::lmAfterSolve(LmRun& r, bool ok)
 {
 	if (!lmAfterSolveHost(r)) return false;
-	if (ok) launch_trial_tail_fused(g, st, sys, (Scalar)-1, d_backup.data(), stream, &r.lm, poseFactors());
+	// Will the host wait for this very decision?  lmBeforeTrial's `!safe`, which nothing absorbed between here and there can change (and
+	// whenever lmRunEnd waits, lmBeforeTrial has waited before it).  Only then -- and after a failed solve -- does the decision carry the
+	// system-scope fence and the ticket, and only then is the conditional restore a launch of its own (the run may end there); any other
+	// decision is followed by a landmark pass of this run, which undoes a rejected trial itself (r.restoreInPass)
+	const bool waited = !r.chain || !(r.done + 1 < r.niter && r.rejRun + 1 < LmRun::maxq);
+	const bool publish = waited || !ok;
+	if (ok) launch_trial_tail_fused(g, st, sys, (Scalar)-1, d_backup.data(), stream, &r.lm, poseFactors(), publish ? 1 : 0);
 	else launch_lm_decide_failed(sys, r.lm, stream);
-	noteReport();
-	launch_restore_if_rejected(d_state.data(), d_backup.data(), d_state.size(), r.lm, stream);
+	if (publish) noteReport();                      // (expectedTicket counts exactly the tickets written)
+	r.restoreInPass = !publish && st.nWaves > 0;
+	if (!r.restoreInPass) launch_restore_if_rejected(d_state.data(), d_backup.data(), d_state.size(), r.lm, stream);
 	r.enq++;
 	(void)hipStreamQuery(stream);
 	return true;
@@ -771,11 +808,16 @@ int cuba_hip_solver::lmRunEnd(LmRun& r)
 int cuba_hip_solver::optimizeDeviceDecision(int niter, double* chi2Out)
 {
 	LmRun r;
-	lmRunBegin(r, niter, chi2Out);
+	lmRunBegin(r, niter, chi2Out, true);
 	while (lmBeforeTrial(r))
 	{
-		schur(true);
-		const bool ok = solveReduced();
+		lmRestoreFlag = r.restoreInPass ? r.lm.state + 5 : nullptr;      // (the landmark pass undoes the trial before it if that was rejected)
+		try { schur(true); } catch (...) { lmRestoreFlag = nullptr; throw; }
+		lmRestoreFlag = nullptr;
+		coarseSideLater = true;
+		bool ok = false;
+		try { ok = solveReduced(); } catch (...) { coarseSideLater = false; throw; }
+		coarseSideLater = false;
 		if (!lmAfterSolve(r, ok)) break;
 	}
 	return lmRunEnd(r);

@@ -725,11 +725,15 @@ struct cuba_hip_solver
 		std::vector<CoarseJob>* deferCoarse = nullptr;      // ... and the overlapped coarse inversion is only decided here, enqueued by launchCoarseJobs
 		bool deferLaunch = false;           // ... and neither are the set-up launch and the first preconditioner application (when `deferred` comes back true)
 		bool deferred = false;
+		bool sideLater = false;             // in: a solo solve's overlapped coarse inversion is left to the caller (sideFirst >= 0 on return: enqueueCoarseSide(sideFirst))
+		int sideFirst = -1;
 		const Scalar* copySrc = nullptr; Scalar* copyDst = nullptr; size_t copyCount = 0;      // the set-up launch's copy of a fresh coarse inverse
 		volatile int* hInts = nullptr;
 		Clock::time_point tSolve0;
 	};
 	bool solveBegin(SolveCtx& sc);
+	void enqueueCoarseSide(int first);
+	bool coarseSideLater = false;           // set around the reduced solves of cuba_hip_optimize: SolveCtx::sideLater
 	bool solveBrokeDown(SolveCtx& sc);
 	bool solveEnd(SolveCtx& sc);
 	bool solveReducedOnce();
@@ -751,8 +755,8 @@ struct cuba_hip_solver
 	int optimize(int niter, double* chi2Out);
 	// The same loop with the decision of every trial taken ON THE DEVICE (gain ratio, acceptance, next damping: lm_decide in ba_edge.hip):
 	// the host enqueues trial n + 1 behind trial n's tail without having seen its outcome -- the kernels read the damping from device
-	// memory, a rejected trial is undone by a conditional restore launch -- and learns the outcomes one trial late from device-mapped
-	// records, at the look its next reduced solve needs anyway.  One host look per trial instead of two; only a trial whose outcome may
+	// memory, a rejected trial is undone by the next trial's landmark pass (by a conditional restore launch where the run may end) -- and
+	// learns the outcomes one trial late from device-mapped records, at the look its next reduced solve needs anyway.  One host look per trial instead of two; only a trial whose outcome may
 	// END the run (last iteration, tenth rejection in a row) is waited for.  Same arithmetic as the host loop, bit for bit.
 	int optimizeDeviceDecision(int niter, double* chi2Out);
 	// (the same run in steps: cuba_hip_optimize_batch interleaves the steps of several handles and batches their PCG iterations)
@@ -761,11 +765,14 @@ struct cuba_hip_solver
 		static constexpr int maxq = 10;
 		int niter = 0, enq = 0, seen = 0, done = 0, rejRun = 0;
 		bool stop = false;
+		bool chain = false;             // cuba_hip_optimize alone (lmRunBegin)
+		bool restoreInPass = false;     // the last decision has no restore launch behind it: the next landmark pass undoes a rejected trial
 		double lam = 0, F = 0, tagBase = 0;
 		double* chi2Out = nullptr;
 		LmDevice lm;
 	};
-	void lmRunBegin(LmRun& r, int niter, double* chi2Out);
+	void lmRunBegin(LmRun& r, int niter, double* chi2Out, bool chain = false);
+	const double* lmRestoreFlag = nullptr;      // set around the schur(true) of a trial whose landmark pass carries the conditional restore
 	void lmAbsorb(LmRun& r, int upto);
 	bool lmBeforeTrial(LmRun& r);
 	bool lmAfterSolveHost(LmRun& r);
