@@ -127,6 +127,8 @@ def load_library(precision="f64"):
         "cuba_hip_set_relative_pose_edges": [H, C.c_int, _ip, _ip, _dp, _dp, _dp],
         "cuba_hip_relative_pose_chi_squares": [H, _dp],
         "cuba_hip_set_pose_factor_robust_kernels": [H, C.c_int, C.c_int, _ip, _dp],
+        "cuba_hip_set_landmark_priors": [H, C.c_int, _ip, _dp, _dp, _ip, _dp],
+        "cuba_hip_landmark_prior_chi_squares": [H, _dp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -389,6 +391,7 @@ class HipSolver:
         self.fp = fp
         self._n_priors = 0              # (every upload clears the pose priors)
         self._n_rel = 0                 # (and the relative-pose edges)
+        self._n_lm_priors = 0           # (and the landmark priors)
         q, t, cam, Xw = (np.ascontiguousarray(a, dtype=np.float64) for a in (fp.q, fp.t, fp.cam, fp.Xw))
         eP = np.ascontiguousarray(fp.eP, dtype=np.int32)
         eL = np.ascontiguousarray(fp.eL, dtype=np.int32)
@@ -539,6 +542,32 @@ class HipSolver:
         out = np.zeros(max(getattr(self, "_n_priors", 0), 1))
         self._ck(self.lib.cuba_hip_prior_chi_squares(self.h, _d(out)))
         return out[:getattr(self, "_n_priors", 0)]
+
+    def set_landmark_priors(self, landmark, xyz, info, kind=None, delta=None):
+        """Landmark position priors (cuba_hip_set_landmark_priors), replacing the handle's set: landmark[n] in the solver numbering,
+        xyz[n, 3], info[n, 3, 3] symmetric; kind[n] (0 none, 1 Huber, 2 Tukey, 3 Cauchy) and delta[n] together or not at all (scalars
+        broadcast).  An empty landmark list clears the set."""
+        landmark = np.ascontiguousarray(landmark, dtype=np.int32).reshape(-1)
+        n = int(landmark.size)
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(n, 3)
+        # (column-major 3 x 3 blocks: the transpose of the row-major reading)
+        info = np.ascontiguousarray(np.asarray(info, dtype=np.float64).reshape(n, 3, 3).transpose(0, 2, 1))
+        if kind is not None:
+            kind = np.ascontiguousarray(np.full(n, kind) if np.ndim(kind) == 0 else kind, dtype=np.int32).reshape(-1)
+        if delta is not None:
+            delta = np.ascontiguousarray(np.full(n, delta) if np.ndim(delta) == 0 else delta, dtype=np.float64).reshape(-1)
+        if (kind is not None and kind.size != n) or (delta is not None and delta.size != n):
+            raise ValueError("kind / delta differ in length from the set")
+        self._ck(self.lib.cuba_hip_set_landmark_priors(self.h, n, landmark.ctypes.data_as(_ip), _d(xyz), _d(info),
+                                                       kind.ctypes.data_as(_ip) if kind is not None else None, _d(delta)))
+        self._n_lm_priors = n
+
+    def landmark_prior_chi_squares(self):
+        """r^T Omega r of every landmark prior at the current estimate, in the order they were given (0 for priors on fixed landmarks)"""
+        n = getattr(self, "_n_lm_priors", 0)
+        out = np.zeros(max(n, 1))
+        self._ck(self.lib.cuba_hip_landmark_prior_chi_squares(self.h, _d(out)))
+        return out[:n]
 
     def chi_squares_two_step(self):
         """cuba_hip_chi_squares_begin / _end (the C++ layer does its write-back between the two)"""

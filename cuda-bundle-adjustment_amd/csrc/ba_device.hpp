@@ -1,6 +1,6 @@
 // ba_device.hpp -- device-side helpers shared by the kernel translation units (ba_edge.hip, ba_linearize.hip, ba_pcg.hip,
 // ba_coarse.hip): DPP wave reductions, flag loads on the vector path, the deterministic second-stage sums, loading +
-// linearising one edge.  Internal to csrc/ -- the launch interface is ba_kernels.hpp.
+// linearising one edge, the factors' robust kernels, the landmark pass's prior hook.  Internal to csrc/ -- the launch interface is ba_kernels.hpp.
 #pragma once
 
 #include "ba_kernels.hpp"
@@ -241,6 +241,50 @@ __device__ __forceinline__ void linearize_edge(const DeviceGraph& g, int e, Lane
 	out.wr = w * robust_weight(kind, delta, w * s);
 	const Rot3 R = quat_to_rot(q[0], q[1], q[2], q[3]);
 	edge_jacobians(Xc, R, cam, out.stereo, out.lin);
+}
+
+// rho(e) and rho'(e) of a factor's robust kernel (pose factors, landmark priors): Huber and Tukey as the reprojection edges have them, and Cauchy
+__device__ __forceinline__ Scalar factor_rho(int kind, Scalar delta, Scalar e)
+{
+	if (kind == POSE_FACTOR_KERNEL_CAUCHY) { const Scalar d2 = delta * delta; return d2 * log1p(e / d2); }
+	return robust_rho(kind, delta, e);
+}
+
+__device__ __forceinline__ Scalar factor_weight(int kind, Scalar delta, Scalar e)
+{
+	if (kind == POSE_FACTOR_KERNEL_CAUCHY) return 1 / (1 + e / (delta * delta));
+	return robust_weight(kind, delta, e);
+}
+
+// r = X - Xbar of landmark prior k, Or = Omega r; returns r^T Omega r
+__device__ __forceinline__ Scalar landmark_prior_residual(const DeviceLandmarkPriors& lp, int k, const Scalar X[3], Scalar Or[3])
+{
+	const Scalar* xb = lp.xbar + 3 * (size_t)k;
+	const Scalar* O = lp.info + 6 * (size_t)k;
+	const Scalar r[3] = { X[0] - xb[0], X[1] - xb[1], X[2] - xb[2] };
+#pragma unroll
+	for (int i = 0; i < 3; i++) Or[i] = O[sym3_idx(i, 0)] * r[0] + O[sym3_idx(i, 1)] * r[1] + O[sym3_idx(i, 2)] * r[2];
+	return r[0] * Or[0] + r[1] * Or[1] + r[2] * Or[2];
+}
+
+// The landmark pass's hook: the priors of free landmark il, in the caller's order, behind the sum over its edges -- H[0..6) += w Omega,
+// H[6..9) -= w Omega r at the position X the edges were linearised at, w = rho'(r^T Omega r).  (H[6..9) is the landmark's right-hand side
+// bl of (H + lambda I) x = b, minus half the gradient: the edges' residual is measurement minus projection, so their J^T w r has that sign
+// already; the prior's residual X - Xbar has the Jacobian +I, hence the minus.)
+__device__ __forceinline__ void add_landmark_priors(const DeviceLandmarkPriors& lp, int il, const Scalar X[3], Scalar H[9])
+{
+	const int k1 = lp.lm_ptr[il + 1];
+	for (int k = lp.lm_ptr[il]; k < k1; k++)
+	{
+		Scalar Or[3];
+		const Scalar e = landmark_prior_residual(lp, k, X, Or);
+		const Scalar w = factor_weight(lp.rk_kind[k], lp.rk_delta[k], e);
+		const Scalar* O = lp.info + 6 * (size_t)k;
+#pragma unroll
+		for (int i = 0; i < 6; i++) H[i] += w * O[i];
+#pragma unroll
+		for (int i = 0; i < 3; i++) H[6 + i] -= w * Or[i];
+	}
 }
 
 // The report a host spins on (cuba_hip_solver::waitReport): {failure code, iterations done, stop flag} and, LAST, the ticket -- all in the

@@ -1,4 +1,4 @@
-// ba_kernels.hpp -- launch interface of the gfx950 kernels (implemented in ba_edge.hip, ba_linearize.hip, ba_pcg.hip, ba_coarse.hip, ba_posefactor.hip).
+// ba_kernels.hpp -- launch interface of the gfx950 kernels (implemented in ba_edge.hip, ba_linearize.hip, ba_pcg.hip, ba_coarse.hip, ba_posefactor.hip, ba_lmfactor.hip).
 //
 // Device data model (all SoA, fp64 + int32):
 //   poses      q[4*Pt] t[3*Pt] cam[5*Pt]          free poses [0,Pf) first, fixed after
@@ -181,16 +181,36 @@ struct DeviceRelPoses
 	const Scalar* rk_delta = nullptr;   // [n]
 };
 
-// The pose factors of a handle: what the rest of the library sees of the two kinds (a kind without factors: n = 0, nothing of it is launched).
-struct DevicePoseFactors { DevicePriors priors; DeviceRelPoses rel; };
+// Landmark position priors (ba_lmfactor.hip): rho(r^T Omega r), r = X - Xbar, Omega a symmetric 3 x 3 information.  Sorted by internal landmark
+// (stable: a landmark's priors are contiguous and in the caller's order); priors on fixed landmarks come last and are ignored.  The landmark
+// pass adds a landmark's terms w Omega / -w Omega r to its Hll / bl (ba_device.hpp: add_landmark_priors), in a kernel instantiation of its
+// own that only a handle with such priors launches.
+struct DeviceLandmarkPriors
+{
+	int n = 0;                     // priors
+	const int* lm_ptr = nullptr;   // [Lf + 1] range of every free landmark in the sorted list
+	const int* lm = nullptr;       // [n] internal landmark of every prior (>= Lf: a fixed landmark)
+	const Scalar* xbar = nullptr;  // [3 n]
+	const Scalar* info = nullptr;  // [6 n] upper triangle in the packing of sym3_idx
+	const int* rk_kind = nullptr;  // [n] robust kernel of every prior (POSE_FACTOR_KERNEL_*)
+	const Scalar* rk_delta = nullptr;   // [n]
+	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 on fixed landmarks)
+};
+// per-prior chi2 (the plain r^T Omega r) into lp.chi, per-workgroup partial sums of rho(chi2) into parts[0 .. landmark_prior_chi2_parts(lp))
+void launch_landmark_prior_chi2(const DeviceGraph& g, const DeviceLandmarkPriors& lp, Scalar* parts, hipStream_t s);
+int landmark_prior_chi2_parts(const DeviceLandmarkPriors& lp);     // 0 for no priors, at most 64
+
+// The factors of a handle besides the reprojection edges: what the rest of the library sees of the kinds (a kind without factors: n = 0,
+// nothing of it is launched).  The landmark priors ride along for the chi2 sums only: their linearisation is the landmark pass's.
+struct DevicePoseFactors { DevicePriors priors; DeviceRelPoses rel; DeviceLandmarkPriors lmp; };
 // behind the Schur pass, the priors first (Omega: w Omega of a factor with a robust kernel): J^T Omega J into the diagonal blocks of hsc (upper triangle), -J^T Omega r into bp and (mode 1)
 // bsc, J = J_l(r)^-1; then the edges in two launches: per-edge records, then their sums into hsc (diagonal blocks: upper triangle; mode 1:
 // the off-diagonal blocks of the pairs, stored whole where a block has no Schur products), bp and (mode 1) bsc
 void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DevicePoseFactors& pf, int mode, hipStream_t s);
-// per-factor chi2 (the plain r^T Omega r) into priors.chi / rel.chi, per-workgroup partial sums of rho(chi2) into parts[0 .. pose_factor_chi2_parts(&pf)): the priors' first, the
-// edges' behind them
+// per-factor chi2 (the plain r^T Omega r) into priors.chi / rel.chi / lmp.chi, per-workgroup partial sums of rho(chi2) into parts[0 .. pose_factor_chi2_parts(&pf)): the priors' first, the
+// edges' behind them, the landmark priors' last
 void launch_pose_factor_chi2(const DeviceGraph& g, const DevicePoseFactors& pf, Scalar* parts, hipStream_t s);
-int pose_factor_chi2_parts(const DevicePoseFactors* pf);     // 0 for no factors (pf null), at most 64 per kind
+int pose_factor_chi2_parts(const DevicePoseFactors* pf);     // 0 for no factors (pf null), at most 64 per kind (the landmark priors' included)
 
 // residual / robust chi2 over all edges -> sys.slots[0..NSLOT) (must be zeroed by the caller).
 // per_edge (optional, sorted edge order): non-robust omega*|r|^2.
@@ -209,7 +229,8 @@ struct BlockPassRange { int begin, end, heavy; };
 // is zero the same launch undoes the rejected trial instead: the landmark workgroups read poses and landmarks from backupDst -- which holds
 // the estimate the trial started from and which nobody writes in this launch -- and the copy workgroups copy backupDst -> backupSrc
 void launch_linearize_dm(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, int mode, Scalar lambda, hipStream_t s,
-	Scalar* backupSrc = nullptr, Scalar* backupDst = nullptr, size_t backupCount = 0, const BlockPassRange* range = nullptr, const double* restoreFlag = nullptr);
+	Scalar* backupSrc = nullptr, Scalar* backupDst = nullptr, size_t backupCount = 0, const BlockPassRange* range = nullptr, const double* restoreFlag = nullptr,
+	const DeviceLandmarkPriors* lp = nullptr);
 void launch_block_pass(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const BlockPassRange& range, hipStream_t s);
 
 // max over the diagonal of the diagonal blocks of hsc (Hpp after an assemble pass) folded into sys.maxdiag

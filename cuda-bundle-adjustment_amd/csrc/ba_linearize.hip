@@ -59,9 +59,12 @@ __device__ __forceinline__ void load_pose_as(const DeviceGraph& g, int ip, ET q[
 // restoreFlag (cuba_hip_optimize): the decision state's "last trial accepted" number.  Zero = the trial before this launch was rejected and
 // its restore rides in this launch too: the backup is the estimate to linearise at, so the landmark workgroups read poses and landmarks from
 // it (nobody writes it in this launch) while the copy workgroups copy it over the state -- the reference's pop() followed by its push().
-template <int MODE, typename ET>
+// PRIOR: the head lane adds the landmark's position priors (lp; ba_device.hpp: add_landmark_priors) behind the sum over its edges, at the
+// position the edges were linearised at.  The instantiations without it hold nothing of this and never touch lp.
+template <int MODE, typename ET, bool PRIOR = false>
 __device__ __forceinline__ void lm_pass_body(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, Scalar lambda,
-	unsigned nLmGroups, Scalar* backupSrc, Scalar* backupDst, size_t backupCount, unsigned gridX, const double* restoreFlag)
+	unsigned nLmGroups, Scalar* backupSrc, Scalar* backupDst, size_t backupCount, unsigned gridX, const double* restoreFlag,
+	const DeviceLandmarkPriors& lp = DeviceLandmarkPriors())
 {
 	__shared__ Scalar lds_all[(LIN_BLOCK / WAVE) * WAVE * 9];
 	const bool restore = restoreFlag != nullptr && restoreFlag[0] == 0.0;
@@ -138,6 +141,11 @@ __device__ __forceinline__ void lm_pass_body(const DeviceGraph& g, const DeviceS
 		for (int j = seg0; j < seg1; j++)
 #pragma unroll
 			for (int k = 0; k < 9; k++) H[k] += lds[j * 9 + k];
+		if constexpr (PRIOR)
+		{
+			const Scalar X[3] = { sX[3 * (size_t)il], sX[3 * (size_t)il + 1], sX[3 * (size_t)il + 2] };
+			add_landmark_priors(lp, il, X, H);
+		}
 		Scalar* ls = sys.lm_sys + 9 * (size_t)il;
 		if (MODE == 0)
 		{
@@ -176,6 +184,14 @@ __global__ __launch_bounds__(LIN_BLOCK) void lm_pass_kernel(DeviceGraph g, Devic
 	unsigned nLmGroups, Scalar* __restrict__ backupSrc, Scalar* __restrict__ backupDst, size_t backupCount, const double* restoreFlag)
 {
 	lm_pass_body<MODE, ET>(g, st, sys, lambda, nLmGroups, backupSrc, backupDst, backupCount, gridDim.x, restoreFlag);
+}
+
+// (sibling of lm_pass_kernel for a handle with landmark priors: the same pass, the priors' arrays as one more argument)
+template <int MODE, typename ET>
+__global__ __launch_bounds__(LIN_BLOCK) void lm_pass_prior_kernel(DeviceGraph g, DeviceStructure st, DeviceSystem sys, Scalar lambda,
+	unsigned nLmGroups, Scalar* __restrict__ backupSrc, Scalar* __restrict__ backupDst, size_t backupCount, const double* restoreFlag, DeviceLandmarkPriors lp)
+{
+	lm_pass_body<MODE, ET, true>(g, st, sys, lambda, nLmGroups, backupSrc, backupDst, backupCount, gridDim.x, restoreFlag, lp);
 }
 
 // batched forms (cuba_hip_optimize_batch): blockIdx.y = graph, arguments from the device table, the damping from device memory
@@ -232,6 +248,81 @@ __global__ __launch_bounds__(256) void big_lm_pass_kernel(DeviceGraph g, DeviceS
 		Scalar H[9];
 #pragma unroll
 		for (int k = 0; k < 9; k++) H[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
+		Scalar* ls = sys.lm_sys + 9 * (size_t)il;
+		if (MODE == 0)
+		{
+#pragma unroll
+			for (int k = 0; k < 9; k++) ls[k] = H[k];
+			atomic_max_nonneg(sys.maxdiag, fmax(H[0], fmax(H[3], H[5])));
+		}
+		else
+		{
+			Scalar inv[6];
+			H[0] += lambda; H[3] += lambda; H[5] += lambda;
+			sym3_inverse(H, inv);
+#pragma unroll
+			for (int k = 0; k < 6; k++) ls[k] = inv[k];
+			if (st.inv_rows8)
+			{
+				Scalar* li = sys.lm_inv + 8 * (size_t)il;
+#pragma unroll
+				for (int k = 0; k < 6; k++) li[k] = inv[k];
+				li[6] = 0; li[7] = 0;
+			}
+#pragma unroll
+			for (int k = 0; k < 3; k++) ls[6 + k] = H[6 + k];
+		}
+	}
+}
+
+// the same pass for a handle with landmark priors (a sibling, not a template parameter of the kernel above: wrapping that kernel's body
+// changes its fp32 code, and a handle without priors must run the code it ran before): thread 0 adds the landmark's priors behind the sum
+template <int MODE, typename ET>
+__global__ __launch_bounds__(256) void big_lm_pass_prior_kernel(DeviceGraph g, DeviceStructure st, DeviceSystem sys, Scalar lambda, DeviceLandmarkPriors lp)
+{
+	__shared__ Scalar red[4][9];
+	lambda = launch_lambda(sys, lambda);
+	const int il = st.big_lm[blockIdx.x];
+	const int e0 = g.lm_ptr[il], e1 = g.lm_ptr[il + 1];
+	Scalar acc[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+	for (int e = e0 + threadIdx.x; e < e1; e += 256)
+	{
+		LaneEdge le;
+		linearize_edge(g, e, le);
+		// linearize_edge does not return Xc: recompute it for the record
+		Scalar q[4], t[3], cam[5], Xw[3], Xc[3];
+		load_pose(g, le.ip, q, t, cam);
+#pragma unroll
+		for (int i = 0; i < 3; i++) Xw[i] = g.Xw[3 * (size_t)il + i];
+		quat_rotate(q, Xw, Xc);
+		Xc[0] += t[0]; Xc[1] += t[1]; Xc[2] += t[2];
+		write_record<ET>(st.e_rec, (size_t)e, Xc, le.wr, le.lin.r, il, le.stereo);
+		if (il < g.Lf)
+		{
+			const EdgeLin& L = le.lin;
+#pragma unroll
+			for (int i = 0; i < 3; i++)
+			{
+#pragma unroll
+				for (int j = i; j < 3; j++)
+					acc[sym3_idx(i, j)] += le.wr * (L.JL[0][i] * L.JL[0][j] + L.JL[1][i] * L.JL[1][j] + L.JL[2][i] * L.JL[2][j]);
+				acc[6 + i] += le.wr * (L.JL[0][i] * L.r[0] + L.JL[1][i] * L.r[1] + L.JL[2][i] * L.r[2]);
+			}
+		}
+	}
+#pragma unroll
+	for (int k = 0; k < 9; k++) acc[k] = wave_sum(acc[k]);
+	if ((threadIdx.x & 63) == 0)
+#pragma unroll
+		for (int k = 0; k < 9; k++) red[threadIdx.x >> 6][k] = acc[k];
+	__syncthreads();
+	if (threadIdx.x == 0 && il < g.Lf)
+	{
+		Scalar H[9];
+#pragma unroll
+		for (int k = 0; k < 9; k++) H[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
+		const Scalar X[3] = { g.Xw[3 * (size_t)il], g.Xw[3 * (size_t)il + 1], g.Xw[3 * (size_t)il + 2] };
+		add_landmark_priors(lp, il, X, H);
 		Scalar* ls = sys.lm_sys + 9 * (size_t)il;
 		if (MODE == 0)
 		{
@@ -571,7 +662,7 @@ static DeviceStructure block_pass_view(const DeviceStructure& st, const BlockPas
 
 template <typename ET>
 static void launch_linearize_dm_t(const DeviceGraph& g, const DeviceStructure& stAll, const DeviceSystem& sys, int mode, Scalar lambda, hipStream_t s,
-	Scalar* backupSrc, Scalar* backupDst, size_t backupCount, const BlockPassRange* range, const double* restoreFlag)
+	Scalar* backupSrc, Scalar* backupDst, size_t backupCount, const BlockPassRange* range, const double* restoreFlag, const DeviceLandmarkPriors* lp)
 {
 	// (the landmark and pose passes read nothing of the block list: one view serves the whole launch sequence)
 	const DeviceStructure st = range ? block_pass_view(stAll, *range) : stAll;
@@ -579,14 +670,18 @@ static void launch_linearize_dm_t(const DeviceGraph& g, const DeviceStructure& s
 	{
 		const unsigned grid = (st.nWaves + (LIN_BLOCK / WAVE) - 1) / (LIN_BLOCK / WAVE);
 		const unsigned nCopy = backupSrc ? (unsigned)std::min<size_t>(512, (backupCount + LIN_BLOCK - 1) / LIN_BLOCK) : 0;
-		if (mode == 0) hipLaunchKernelGGL((lm_pass_kernel<0, ET>), dim3(grid + nCopy), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, grid, backupSrc, backupDst, backupCount, nCopy ? restoreFlag : nullptr);
+		if (lp && mode == 0) hipLaunchKernelGGL((lm_pass_prior_kernel<0, ET>), dim3(grid + nCopy), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, grid, backupSrc, backupDst, backupCount, nCopy ? restoreFlag : nullptr, *lp);
+		else if (lp) hipLaunchKernelGGL((lm_pass_prior_kernel<1, ET>), dim3(grid + nCopy), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, grid, backupSrc, backupDst, backupCount, nCopy ? restoreFlag : nullptr, *lp);
+		else if (mode == 0) hipLaunchKernelGGL((lm_pass_kernel<0, ET>), dim3(grid + nCopy), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, grid, backupSrc, backupDst, backupCount, nCopy ? restoreFlag : nullptr);
 		else hipLaunchKernelGGL((lm_pass_kernel<1, ET>), dim3(grid + nCopy), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, grid, backupSrc, backupDst, backupCount, nCopy ? restoreFlag : nullptr);
 	}
 	else if (backupSrc && backupCount)
 		(void)hipMemcpyAsync(backupDst, backupSrc, backupCount * sizeof(Scalar), hipMemcpyDeviceToDevice, s);
 	if (st.nBig > 0)
 	{
-		if (mode == 0) hipLaunchKernelGGL((big_lm_pass_kernel<0, ET>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda);
+		if (lp && mode == 0) hipLaunchKernelGGL((big_lm_pass_prior_kernel<0, ET>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, *lp);
+		else if (lp) hipLaunchKernelGGL((big_lm_pass_prior_kernel<1, ET>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, *lp);
+		else if (mode == 0) hipLaunchKernelGGL((big_lm_pass_kernel<0, ET>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda);
 		else hipLaunchKernelGGL((big_lm_pass_kernel<1, ET>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda);
 	}
 	const int nbp = block_pass_groups(st.nOd, st.nHeavy);
@@ -606,10 +701,11 @@ static void launch_linearize_dm_t(const DeviceGraph& g, const DeviceStructure& s
 }
 
 void launch_linearize_dm(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, int mode, Scalar lambda, hipStream_t s,
-	Scalar* backupSrc, Scalar* backupDst, size_t backupCount, const BlockPassRange* range, const double* restoreFlag)
+	Scalar* backupSrc, Scalar* backupDst, size_t backupCount, const BlockPassRange* range, const double* restoreFlag, const DeviceLandmarkPriors* lp)
 {
-	if (st.mixed && sizeof(Scalar) == 8) launch_linearize_dm_t<float>(g, st, sys, mode, lambda, s, backupSrc, backupDst, backupCount, range, restoreFlag);
-	else launch_linearize_dm_t<Scalar>(g, st, sys, mode, lambda, s, backupSrc, backupDst, backupCount, range, restoreFlag);
+	if (lp && lp->n == 0) lp = nullptr;
+	if (st.mixed && sizeof(Scalar) == 8) launch_linearize_dm_t<float>(g, st, sys, mode, lambda, s, backupSrc, backupDst, backupCount, range, restoreFlag, lp);
+	else launch_linearize_dm_t<Scalar>(g, st, sys, mode, lambda, s, backupSrc, backupDst, backupCount, range, restoreFlag, lp);
 }
 
 // what launch_linearize_dm_t (mode 1, whole graph, no landmark with more than 64 observations, no duplicate observation) launches for one

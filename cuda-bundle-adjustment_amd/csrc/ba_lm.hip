@@ -152,7 +152,7 @@ void cuba_hip_solver::linearize(int mode, double lam, bool withBackup)
 	waitAssembled();            // an overlapped coarse assembly may still be reading the previous reduced matrix
 	const bool parts = mode == 1 && !redParts.empty();
 	launch_linearize_dm(g, st, sys, mode, lam, stream, withBackup ? d_state.data() : nullptr, d_backup.data(), d_state.size(), parts ? &redParts[0].od : nullptr,
-		withBackup ? lmRestoreFlag : nullptr);
+		withBackup ? lmRestoreFlag : nullptr, landmarkPriors());
 	if (parts && !partsByCaller)
 		for (size_t c = 1; c < redParts.size(); c++) launch_block_pass(g, st, sys, redParts[c].od, stream);
 	// (a launch of its own: the Schur pass's block part may still update a diagonal block its pose part stored)

@@ -89,18 +89,7 @@ __device__ __forceinline__ void se3_jacobian(const Scalar A[3][3], const Scalar 
 		}
 }
 
-// rho(e) and rho'(e) of a factor's robust kernel: Huber and Tukey as the reprojection edges have them, and Cauchy
-__device__ __forceinline__ Scalar factor_rho(int kind, Scalar delta, Scalar e)
-{
-	if (kind == POSE_FACTOR_KERNEL_CAUCHY) { const Scalar d2 = delta * delta; return d2 * log1p(e / d2); }
-	return robust_rho(kind, delta, e);
-}
-
-__device__ __forceinline__ Scalar factor_weight(int kind, Scalar delta, Scalar e)
-{
-	if (kind == POSE_FACTOR_KERNEL_CAUCHY) return 1 / (1 + e / (delta * delta));
-	return robust_weight(kind, delta, e);
-}
+// (rho / rho' of a factor's robust kernel: factor_rho, factor_weight in ba_device.hpp -- the landmark priors share them)
 
 // the lanes' chi2 sums of a CHI_BLOCK workgroup -> its partial
 __device__ __forceinline__ void chi2_partial(Scalar acc, Scalar* __restrict__ parts)
@@ -404,12 +393,13 @@ static void launch_relpose_chi2(const DeviceGraph& g, const DeviceRelPoses& rp, 
 	else hipLaunchKernelGGL(relpose_chi2_kernel<false>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, rp, parts);
 }
 
-int pose_factor_chi2_parts(const DevicePoseFactors* pf) { return pf ? chi2_parts(pf->priors.n) + chi2_parts(pf->rel.n) : 0; }
+int pose_factor_chi2_parts(const DevicePoseFactors* pf) { return pf ? chi2_parts(pf->priors.n) + chi2_parts(pf->rel.n) + landmark_prior_chi2_parts(pf->lmp) : 0; }
 
 void launch_pose_factor_chi2(const DeviceGraph& g, const DevicePoseFactors& pf, Scalar* parts, hipStream_t s)
 {
 	launch_prior_chi2(g, pf.priors, parts, s);
 	launch_relpose_chi2(g, pf.rel, parts + chi2_parts(pf.priors.n), s);
+	launch_landmark_prior_chi2(g, pf.lmp, parts + chi2_parts(pf.priors.n) + chi2_parts(pf.rel.n), s);
 }
 
 void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DevicePoseFactors& pf, int mode, hipStream_t s)
@@ -467,7 +457,7 @@ static PoseFactorValues sized_factor_values(int n, bool binary)
 static void forget_factor_memories(cuba_hip_solver& s, PoseFactorSet& set)
 {
 	set.uploaded = false;
-	s.firstInvValid = false; s.firstInvPending = false; s.prevRunIters.clear(); s.runIters.clear(); s.firstSolveIters = 0;
+	s.forgetRunMemories();
 }
 
 // (the replaced set is a new set: the robust kernels of the previous one go with it)

@@ -528,6 +528,20 @@ int cuba_hip_relative_pose_chi_squares(cuba_hip_solver* s, double* chi2_per_edge
 	});
 }
 
+int cuba_hip_set_landmark_priors(cuba_hip_solver* s, int n, const int32_t* landmark, const double* xyz, const double* info, const int32_t* kind, const double* delta)
+{
+	return guarded(s, [&] { s->setLandmarkPriors(n, landmark, xyz, info, kind, delta); });
+}
+
+int cuba_hip_landmark_prior_chi_squares(cuba_hip_solver* s, double* chi2_per_prior)
+{
+	return guarded(s, [&] {
+		if (!s->haveGraph) throw StateError{ "set_graph must be called first" };
+		if (s->lmPriorSet.n() > 0 && !chi2_per_prior) throw ArgError{ "null output" };
+		s->landmarkPriorChiSquares(chi2_per_prior);
+	});
+}
+
 int cuba_hip_time_kernels(cuba_hip_solver* s, int reps, double ms_per_launch[CUBA_HIP_TIMED_KERNELS])
 {
 	return guarded(s, [&] {
@@ -553,6 +567,7 @@ int cuba_hip_set_partition(cuba_hip_solver* s, int landmark_begin, int landmark_
 		if (landmark_begin < 0 || landmark_end > s->Lt || landmark_begin > landmark_end) throw ArgError{ "bad landmark range" };
 		if (s->priorSet.n() > 0) throw StateError{ "a landmark partition is not available on a handle with pose priors" };
 		if (s->relSet.n() > 0) throw StateError{ "a landmark partition is not available on a handle with relative-pose edges" };
+		if (s->lmPriorSet.n() > 0) throw StateError{ "a landmark partition is not available on a handle with landmark priors" };
 		if (s->partHi >= 0 && landmark_begin == s->partLo && landmark_end == s->partHi) return;      // (cuba_hip_set_graph_partition set it already)
 		s->partLo = landmark_begin; s->partHi = landmark_end;
 		s->haveStructure = false;

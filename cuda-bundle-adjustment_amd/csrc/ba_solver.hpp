@@ -142,6 +142,20 @@ struct PoseFactorSet
 	int n() const { return (int)v.pi.size(); }
 };
 
+// the landmark position priors as a handle keeps them (cuba_hip_solver, ba_lmfactor.hip): the caller's set in the caller's numbering, the
+// information as its symmetrised upper triangle, every prior with a kernel (kind 0, delta 1: none)
+struct LandmarkPriorSet
+{
+	std::vector<int> lm; std::vector<double> xyz, info;      // [n], [3 n], [6 n]
+	std::vector<int> kind; std::vector<double> delta;        // [n]
+	std::vector<int> order;          // sorted position -> caller's index (set by the upload)
+	bool uploaded = false;
+	int64_t structure = -1;          // cntStructureBuilds at the upload
+	DevBuf<int> d_ints; DevBuf<Scalar> d_vals, d_chi;
+	int n() const { return (int)lm.size(); }
+	void clear() { lm.clear(); xyz.clear(); info.clear(); kind.clear(); delta.clear(); order.clear(); uploaded = false; }
+};
+
 struct cuba_hip_solver;
 int cuba_hip_optimize_batch_impl(cuba_hip_solver** hs, int n, int niter, double* chi2, int* nDone);
 
@@ -584,6 +598,7 @@ struct cuba_hip_solver
 		if (haveStructure && h_relPairs != structRelPairs) haveStructure = false;      // (the relative-pose pairs are part of the topology)
 		buildStructure(); finishValues(); g.rk[0] = rk[0]; g.rk[1] = rk[1]; st.mixed = mixedPrecision ? 1 : 0;
 		uploadPoseFactors();
+		uploadLandmarkPriors();
 	}
 
 	// The pose factors (ba_posefactor.hip): SE(3) pose priors (cuba_hip_set_pose_priors) and relative-pose edges
@@ -595,13 +610,16 @@ struct cuba_hip_solver
 	// without this feature.
 	PoseFactorSet priorSet, relSet;
 	DevicePoseFactors pf;
-	const DevicePoseFactors* poseFactors() const { return priorSet.n() + relSet.n() > 0 ? &pf : nullptr; }
+	const DevicePoseFactors* poseFactors() const { return priorSet.n() + relSet.n() + lmPriorSet.n() > 0 ? &pf : nullptr; }
 	int poseFactorParts() const { return pose_factor_chi2_parts(poseFactors()); }      // chi2 partials that follow the reprojection edges'
 	void clearPoseFactors()
 	{
 		for (PoseFactorSet* set : { &priorSet, &relSet }) { set->v = PoseFactorValues(); set->kind.clear(); set->delta.clear(); set->order.clear(); set->uploaded = false; }
+		lmPriorSet.clear();
 		h_relPairs.clear(); pf = DevicePoseFactors();
 	}
+	// the run-to-run memories that the values of the system feed (option "heuristics"): dropped by a change of the factors as by a new graph
+	void forgetRunMemories() { firstInvValid = false; firstInvPending = false; prevRunIters.clear(); runIters.clear(); firstSolveIters = 0; }
 	void uploadPoseFactors();
 	int internalPose(int p) const { return p < Pf && reorderActive ? poseNewOfOld[p] : p; }      // of a pose in the caller's numbering
 	void setPosePriors(int n, const int32_t* pose, const double* q, const double* t, const double* info);
@@ -609,6 +627,15 @@ struct cuba_hip_solver
 	void setRelativePoseEdges(int n, const int32_t* pi, const int32_t* pj, const double* q, const double* t, const double* info);
 	void relativePoseChiSquares(double* out);
 	void setPoseFactorRobustKernels(int factorType, int n, const int32_t* kind, const double* delta);
+	// Landmark position priors (ba_lmfactor.hip; cuba_hip_set_landmark_priors): kept as the caller gave them, with a device copy (pf.lmp) in the
+	// internal landmark order that need() makes once that order is known and again with every structure (a change of the landmark order
+	// rebuilds it).  The landmark pass linearises them -- linearize() hands pf.lmp to it --, the chi2 sums take them as one more kind of
+	// factor.  No such priors: nothing of this is launched or passed.
+	LandmarkPriorSet lmPriorSet;
+	const DeviceLandmarkPriors* landmarkPriors() const { return lmPriorSet.n() > 0 ? &pf.lmp : nullptr; }
+	void uploadLandmarkPriors();
+	void setLandmarkPriors(int n, const int32_t* landmark, const double* xyz, const double* info, const int32_t* kind, const double* delta);
+	void landmarkPriorChiSquares(double* out);
 	// the edges' distinct free-free pairs (sorted keys i << 32 | j, i < j, caller's numbering) and the pairs the current structure was seeded
 	// with: every such pair owns a block of the reduced matrix, so need() rebuilds the structure exactly when the two sets differ
 	std::vector<uint64_t> h_relPairs, structRelPairs;

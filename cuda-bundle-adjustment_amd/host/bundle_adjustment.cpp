@@ -138,6 +138,7 @@ public:
 		if (it == landmarks_.end()) return;
 		const std::vector<BaseEdge*> incident(it->second->edges.begin(), it->second->edges.end());
 		for (BaseEdge* e : incident) removeEdge(e);
+		lmPriors_.erase(std::remove_if(lmPriors_.begin(), lmPriors_.end(), [&](const LandmarkPrior* p) { return p->vertex == it->second; }), lmPriors_.end());
 		landmarks_.erase(it);
 		landmarksDirty_ = true;
 	}
@@ -169,6 +170,7 @@ public:
 		covPoseIndex_.clear(); covLmIndex_.clear();          // (marginal covariances describe the graph they were computed on)
 		priorsDirty_ = true;                                 // (the priors as they stand now go to the device with the next solve)
 		relDirty_ = true;                                    // (so do the relative-pose edges)
+		lmPriorsDirty_ = true;                               // (and the landmark priors)
 		poseIdx_.clear();                                    // (the factors' pose index: rebuilt below from the poses active now)
 		const auto t0 = std::chrono::steady_clock::now();
 		static const bool dbg = std::getenv("CUBA_HIP_DEBUG") != nullptr;
@@ -358,12 +360,14 @@ public:
 			check(cuba_hip_set_graph_end(solver_), "cuba_hip_set_graph_end");
 			graphDirty_ = false;
 			priorsDirty_ = true;          // (an upload clears the handle's priors)
+			lmPriorsDirty_ = true;
 			uploadedOnce_ = true; edgesChangedSinceUpload_ = valuesChangedSinceUpload_ = false;       // from here on the device holds exactly these edges and values
 			(void)cuba_hip_get_counter(solver_, "graph_uploads", &uploadGeneration_);
 		}
 		lap("create + set_graph");
 		uploadPriors();
 		uploadRelativePoseEdges();
+		uploadLandmarkPriors();
 	}
 
 	// ---- pose factors (extensions: cuba::addPosePrior, cuba::addRelativePoseEdge) --------------------
@@ -465,6 +469,48 @@ public:
 		uploadedPriors_ = priors_;
 	}
 
+	// ---- landmark position priors (extension: cuba::addLandmarkPrior) --------------------------------
+	void addLandmarkPrior(LandmarkPrior* p)
+	{
+		if (!p || !p->vertex) throw std::invalid_argument("cuba::addLandmarkPrior: a prior needs a landmark vertex");
+		if (std::find(lmPriors_.begin(), lmPriors_.end(), p) == lmPriors_.end()) lmPriors_.push_back(p);
+	}
+	void removeLandmarkPrior(LandmarkPrior* p) { lmPriors_.erase(std::remove(lmPriors_.begin(), lmPriors_.end(), p), lmPriors_.end()); }
+	double landmarkPriorChiSquared(const LandmarkPrior* p) const
+	{
+		const auto it = lmPriorChi_.find(p);
+		return it == lmPriorChi_.end() ? 0.0 : it->second;
+	}
+	// (only when priors exist -- or existed at the last initialize(), which then clears them on the device)
+	void uploadLandmarkPriors()
+	{
+		if (!lmPriorsDirty_) return;
+		lmPriorsDirty_ = false;
+		lmPriorChi_.clear();
+		uploadedLmPriors_.clear();
+		if (lmPriors_.empty() && !lmPriorsOnDevice_) return;
+		const size_t n = lmPriors_.size();
+		std::map<const LandmarkVertex*, int32_t> lmIdx;
+		for (size_t i = 0; i < activeLandmarks_.size(); i++) lmIdx[activeLandmarks_[i]] = (int32_t)i;
+		std::vector<int32_t> lm(n), kind(n);
+		std::vector<double> xyz(3 * n), info(9 * n), delta(n);
+		bool any = false;
+		for (size_t k = 0; k < n; k++)
+		{
+			const auto it = lmIdx.find(lmPriors_[k]->vertex);
+			if (it == lmIdx.end()) throw std::invalid_argument("cuba::addLandmarkPrior: the vertex of a prior is not part of the graph");
+			lm[k] = it->second;
+			for (int i = 0; i < 3; i++) xyz[3 * k + i] = lmPriors_[k]->position.data()[i];
+			std::copy(lmPriors_[k]->information.begin(), lmPriors_[k]->information.end(), info.begin() + 9 * k);
+			kind[k] = static_cast<int32_t>(lmPriors_[k]->kernel); delta[k] = lmPriors_[k]->delta;
+			any = any || lmPriors_[k]->kernel != PoseFactorKernel::NONE;
+		}
+		check(cuba_hip_set_landmark_priors(solver_, (int)n, lm.data(), xyz.data(), info.data(), any ? kind.data() : nullptr, any ? delta.data() : nullptr),
+			"cuba_hip_set_landmark_priors");
+		lmPriorsOnDevice_ = n > 0;
+		uploadedLmPriors_ = lmPriors_;
+	}
+
 	// (optimize() in three steps, so that cuba::optimizeBatch can run the middle one for several objects at once)
 	void optimize(int niterations) override
 	{
@@ -547,6 +593,12 @@ public:
 			check(cuba_hip_prior_chi_squares(solver_, pc.data()), "cuba_hip_prior_chi_squares");
 			for (size_t k = 0; k < pc.size(); k++) priorChi_[uploadedPriors_[k]] = pc[k];
 		}
+		if (!uploadedLmPriors_.empty())
+		{
+			std::vector<double> pc(uploadedLmPriors_.size());
+			check(cuba_hip_landmark_prior_chi_squares(solver_, pc.data()), "cuba_hip_landmark_prior_chi_squares");
+			for (size_t k = 0; k < pc.size(); k++) lmPriorChi_[uploadedLmPriors_[k]] = pc[k];
+		}
 		if (!uploadedRel_.empty())
 		{
 			std::vector<double> rc(uploadedRel_.size());
@@ -600,6 +652,7 @@ public:
 		poses_.clear(); landmarks_.clear(); mono_.clear(); stereo_.clear(); stats_.clear();
 		priors_.clear(); priorChi_.clear();
 		relEdges_.clear(); relChi_.clear();
+		lmPriors_.clear(); lmPriorChi_.clear();
 		posesDirty_ = landmarksDirty_ = edgesDirty_ = true;
 		initialized_ = false;
 	}
@@ -728,6 +781,9 @@ private:
 	std::vector<RelativePoseEdge*> relEdges_, uploadedRel_;   // as priors_ / uploadedPriors_
 	bool relOnDevice_ = false, relDirty_ = false;
 	std::map<const RelativePoseEdge*, double> relChi_;
+	std::vector<LandmarkPrior*> lmPriors_, uploadedLmPriors_;   // as priors_ / uploadedPriors_
+	bool lmPriorsOnDevice_ = false, lmPriorsDirty_ = false;
+	std::map<const LandmarkPrior*, double> lmPriorChi_;
 	std::map<const PoseVertex*, int32_t> poseIdx_;            // active pose -> solver index, for the factors of this initialize()
 	std::vector<LandmarkVertex*> activeLandmarks_;
 	std::vector<BaseEdge*> activeEdges_;
@@ -846,6 +902,26 @@ double priorChiSquared(const CudaBundleAdjustment* object, const PosePrior* prio
 {
 	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
 	return impl ? impl->priorChiSquared(prior) : 0.0;
+}
+
+// Extension (g2o's unary XYZ prior edge): landmark position priors, effective at the next initialize() (cuba_hip_set_landmark_priors)
+void addLandmarkPrior(CudaBundleAdjustment* object, LandmarkPrior* prior)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (!impl) throw std::runtime_error("cuba::addLandmarkPrior: not an object of this library");
+	impl->addLandmarkPrior(prior);
+}
+
+void removeLandmarkPrior(CudaBundleAdjustment* object, LandmarkPrior* prior)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (impl) impl->removeLandmarkPrior(prior);
+}
+
+double landmarkPriorChiSquared(const CudaBundleAdjustment* object, const LandmarkPrior* prior)
+{
+	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
+	return impl ? impl->landmarkPriorChiSquared(prior) : 0.0;
 }
 
 // Extension (g2o's binary SE(3) edge): relative-pose edges, effective at the next initialize() (cuba_hip_set_relative_pose_edges)

@@ -155,4 +155,24 @@ void addRelativePoseEdge(CudaBundleAdjustment* object, RelativePoseEdge* edge);
 void removeRelativePoseEdge(CudaBundleAdjustment* object, RelativePoseEdge* edge);
 double relativePoseChiSquared(const CudaBundleAdjustment* object, const RelativePoseEdge* edge);
 
+// Extension (g2o's unary XYZ prior edge; include/cuba_hip.h, cuba_hip_set_landmark_priors): a position prior on one landmark vertex --
+// surveyed ground-control points, points of a map of finite certainty, range-sensor points, the landmark half of a previous window's
+// marginal.  `position` is the prior position Xbar, `information` symmetric 3 x 3, column-major (landmarkCovariance's layout: the inverse
+// of one window's marginal is a prior of the next).  Objective term r^T Omega r with r = X - Xbar, or rho(r^T Omega r) when `kernel` is
+// set (`delta` > 0 then).  Ownership and lifetime as for PosePrior: the caller owns the prior; additions, removals and changes take
+// effect at the next initialize(); the vertex must be part of the graph then (a landmark without an edge is not).  removeLandmarkVertex
+// drops the vertex's priors, clear() all.  landmarkPriorChiSquared: r^T Omega r at the estimate of the last optimize() (0 before one, and
+// for a prior on a fixed vertex) -- the plain value under a kernel too.
+struct LandmarkPrior
+{
+	LandmarkVertex* vertex = nullptr;
+	LandmarkVertex::Point3D position;
+	std::array<double, 9> information{};
+	PoseFactorKernel kernel = PoseFactorKernel::NONE;
+	double delta = 0;
+};
+void addLandmarkPrior(CudaBundleAdjustment* object, LandmarkPrior* prior);
+void removeLandmarkPrior(CudaBundleAdjustment* object, LandmarkPrior* prior);
+double landmarkPriorChiSquared(const CudaBundleAdjustment* object, const LandmarkPrior* prior);
+
 }  // namespace cuba

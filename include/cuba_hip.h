@@ -443,6 +443,39 @@ int cuba_hip_relative_pose_chi_squares(cuba_hip_solver* s, double* chi2_per_edge
 int cuba_hip_set_pose_factor_robust_kernels(cuba_hip_solver* s, int factor_type /* 0 priors, 1 relative-pose edges */, int n, const int32_t* kind,
 	const double* delta);
 
+/* ---- landmark position priors (g2o's unary XYZ prior edge; the reference has no counterpart) -----------------------------------------
+   A prior names landmark `landmark` (the caller's solver numbering, 0 <= landmark < Lt), a position Xbar and a 3 x 3 information matrix
+   Omega (symmetric, column-major), and optionally a robust kernel (kind, delta) of the pose factors' family (table above: 0 none, 1 Huber,
+   2 Tukey, 3 Cauchy, the same formulas): surveyed ground-control points, points of a map of finite certainty, range-sensor points, the
+   landmark half of a previous window's marginal, a weak depth prior on a landmark seen under almost no parallax.
+     residual     r = X - Xbar, e = r^T Omega r
+     objective    rho(e); the LM objective F (cuba_hip_optimize's chi2, cuba_hip_compute_errors, the gain ratio) is the robust edge sum plus
+                  the pose factors' sums plus the landmark priors' sum
+     linearised   with w = rho'(e) and the identity for a Jacobian: Hll += w Omega, bl += -w Omega r (the convention (H + lambda I) x = b
+                  of the rest of the ABI: bl is minus half the gradient); no second-order term.  Both enter before the
+                  damping and the 3 x 3 inverse, so the Schur complement, bsc, back-substitution, lambda_0's maximum diagonal, the gain
+                  ratio's scale and the covariances see them without a term of their own (a graph without a fixed vertex that three such
+                  priors hold is invertible).
+   Several priors on one landmark are summed behind its edges, in the caller's order; priors on fixed landmarks are accepted and ignored
+   (chi2 0).  Every solve path honours them: the device-decision loop, the host loop, both PCG forms, the exact solver, the fp32 library,
+   mixed precision.  cuba_hip_set_landmark_priors replaces the whole set (n = 0 clears it): landmark[n], xyz[3 n], info[9 n], kind[n] and
+   delta[n] (both NULL: no kernels).  Valid any time after cuba_hip_set_graph, which clears the set.  Setting priors never rebuilds the
+   structure ("structure_builds" stays); it drops the run-to-run memories of option "heuristics" and cached covariance blocks.
+   CUBA_HIP_ERR_INVALID_ARGUMENT, the handle unchanged: an index out of range, non-finite values, an information matrix that is not
+   symmetric (beyond 1e-9 of its largest entry; within it the two triangles are averaged), a kind outside 0..3, delta <= 0 on a kind != 0,
+   one of kind / delta without the other.  A prior on a FREE landmark that no reprojection edge observes is refused too (such a landmark is
+   not part of the linearisation): the internal landmark order must be known to tell, so the first call that needs the set on the device
+   reports CUBA_HIP_ERR_INVALID_ARGUMENT; the handle stays usable and the set is dropped.
+   CUBA_HIP_ERR_STATE, the handle staying usable: a landmark-partitioned handle (and cuba_hip_set_partition on a handle with such priors,
+   hence the multi-GPU driver) and a graph without edges.  A handle with such priors takes part in cuba_hip_optimize_batch through the
+   path that batches the PCG iterations only (results stay bit-identical to solo runs).  A handle without them launches the kernels, with
+   the arguments, of a library without this entry point.
+   cuba_hip_landmark_prior_chi_squares: the plain r^T Omega r of every prior at the current estimate, in the caller's order (what a caller
+   gates a doubtful control point on). */
+int cuba_hip_set_landmark_priors(cuba_hip_solver* s, int n, const int32_t* landmark, const double* xyz, const double* info, const int32_t* kind,
+	const double* delta);
+int cuba_hip_landmark_prior_chi_squares(cuba_hip_solver* s, double* chi2_per_prior);
+
 /* ---- introspection (parity tests) and multi-GPU plumbing ------------------------------------------ */
 
 /* Structure of the reduced system: upper-triangular BSR (replaces the accessors of
