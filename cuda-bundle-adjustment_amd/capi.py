@@ -356,6 +356,7 @@ class HipSolver:
         for k, v in options.items():
             self.set_option(k, v)
         self.fp = None
+        self._n_factors = {}
         _live.add(self)
         for et, (kind, delta) in enumerate(robust):
             self.set_robust_kernel(et, kind, delta)
@@ -389,9 +390,7 @@ class HipSolver:
         landmark_range = (begin, end): cuba_hip_set_graph_partition -- the upload of one rank of a landmark partition, which sends the
         measurements and information of its own landmarks' edges only."""
         self.fp = fp
-        self._n_priors = 0              # (every upload clears the pose priors)
-        self._n_rel = 0                 # (and the relative-pose edges)
-        self._n_lm_priors = 0           # (and the landmark priors)
+        self._n_factors = {}            # (every upload clears the pose priors, the relative-pose edges and the landmark priors)
         q, t, cam, Xw = (np.ascontiguousarray(a, dtype=np.float64) for a in (fp.q, fp.t, fp.cam, fp.Xw))
         eP = np.ascontiguousarray(fp.eP, dtype=np.int32)
         eL = np.ascontiguousarray(fp.eL, dtype=np.int32)
@@ -497,7 +496,7 @@ class HipSolver:
         # (column-major 6 x 6 blocks: the transpose of the row-major reading)
         info = np.ascontiguousarray(np.asarray(info, dtype=np.float64).reshape(n, 6, 6).transpose(0, 2, 1))
         self._ck(self.lib.cuba_hip_set_pose_priors(self.h, n, pose.ctypes.data_as(_ip), _d(q), _d(t), _d(info)))
-        self._n_priors = n
+        self._n_factors["prior"] = n
 
     def set_relative_pose_edges(self, pose_i, pose_j, q, t, info):
         """SE(3) relative-pose edges (cuba_hip_set_relative_pose_edges), replacing the handle's set: pose_i[n], pose_j[n] in the solver
@@ -513,13 +512,13 @@ class HipSolver:
         if pose_j.size != n:
             raise ValueError("pose_i and pose_j differ in length")
         self._ck(self.lib.cuba_hip_set_relative_pose_edges(self.h, n, pose_i.ctypes.data_as(_ip), pose_j.ctypes.data_as(_ip), _d(q), _d(t), _d(info)))
-        self._n_rel = n
+        self._n_factors["relative_pose"] = n
 
     def set_pose_factor_robust_kernels(self, factor_type, kind, delta):
         """Robust kernels of the current pose priors (factor_type 0) or relative-pose edges (1), cuba_hip_set_pose_factor_robust_kernels:
         kind[n] (0 none, 1 Huber, 2 Tukey, 3 Cauchy) and delta[n] in the order the set was given; scalars broadcast to the set's size.
         Empty arrays clear the kernels of that type."""
-        n = getattr(self, "_n_priors", 0) if factor_type == 0 else getattr(self, "_n_rel", 0)
+        n = self._n_factors.get("prior" if factor_type == 0 else "relative_pose", 0)
         if np.ndim(kind) == 0:
             kind = np.full(n, kind)
         if np.ndim(delta) == 0:
@@ -530,18 +529,20 @@ class HipSolver:
             raise ValueError("kind and delta differ in length")
         self._ck(self.lib.cuba_hip_set_pose_factor_robust_kernels(self.h, int(factor_type), int(kind.size), kind.ctypes.data_as(_ip), _d(delta)))
 
+    def _factor_chi_squares(self, kind):
+        """cuba_hip_<kind>_chi_squares: one number per factor of the set last given"""
+        n = self._n_factors.get(kind, 0)
+        out = np.zeros(max(n, 1))
+        self._ck(getattr(self.lib, f"cuba_hip_{kind}_chi_squares")(self.h, _d(out)))
+        return out[:n]
+
     def relative_pose_chi_squares(self):
         """r^T Omega r of every relative-pose edge at the current estimate, in the order they were given (0 with both ends fixed)"""
-        n = getattr(self, "_n_rel", 0)
-        out = np.zeros(max(n, 1))
-        self._ck(self.lib.cuba_hip_relative_pose_chi_squares(self.h, _d(out)))
-        return out[:n]
+        return self._factor_chi_squares("relative_pose")
 
     def prior_chi_squares(self):
         """r^T Omega r of every prior at the current estimate, in the order they were given (0 for priors on fixed poses)"""
-        out = np.zeros(max(getattr(self, "_n_priors", 0), 1))
-        self._ck(self.lib.cuba_hip_prior_chi_squares(self.h, _d(out)))
-        return out[:getattr(self, "_n_priors", 0)]
+        return self._factor_chi_squares("prior")
 
     def set_landmark_priors(self, landmark, xyz, info, kind=None, delta=None):
         """Landmark position priors (cuba_hip_set_landmark_priors), replacing the handle's set: landmark[n] in the solver numbering,
@@ -560,14 +561,11 @@ class HipSolver:
             raise ValueError("kind / delta differ in length from the set")
         self._ck(self.lib.cuba_hip_set_landmark_priors(self.h, n, landmark.ctypes.data_as(_ip), _d(xyz), _d(info),
                                                        kind.ctypes.data_as(_ip) if kind is not None else None, _d(delta)))
-        self._n_lm_priors = n
+        self._n_factors["landmark_prior"] = n
 
     def landmark_prior_chi_squares(self):
         """r^T Omega r of every landmark prior at the current estimate, in the order they were given (0 for priors on fixed landmarks)"""
-        n = getattr(self, "_n_lm_priors", 0)
-        out = np.zeros(max(n, 1))
-        self._ck(self.lib.cuba_hip_landmark_prior_chi_squares(self.h, _d(out)))
-        return out[:n]
+        return self._factor_chi_squares("landmark_prior")
 
     def chi_squares_two_step(self):
         """cuba_hip_chi_squares_begin / _end (the C++ layer does its write-back between the two)"""

@@ -46,13 +46,13 @@ __global__ __launch_bounds__(256) void residual_chi2_kernel(DeviceGraph g, Scala
 	residual_chi2_body(g, parts, per_edge, blockIdx.x, gridDim.x);
 }
 
-void launch_residual_chi2(const DeviceGraph& g, Scalar* parts, Scalar* slots, Scalar* per_edge, hipStream_t st, const DevicePoseFactors* pf)
+void launch_residual_chi2(const DeviceGraph& g, Scalar* parts, Scalar* slots, Scalar* per_edge, hipStream_t st, const DeviceFactors* pf)
 {
 	const int n = g.e_end - g.e_begin;
 	const int grid = n > 0 ? min((n + 255) / 256, 2048) : 0;
 	if (grid > 0) hipLaunchKernelGGL(residual_chi2_kernel, dim3(grid), dim3(256), 0, st, g, parts, per_edge);
-	const int nPf = pose_factor_chi2_parts(pf);
-	if (nPf > 0) launch_pose_factor_chi2(g, *pf, parts + grid, st);
+	const int nPf = factor_chi2_parts(pf);
+	if (nPf > 0) launch_factor_chi2(g, *pf, parts + grid, st);
 	launch_reduce_parts(parts, grid + nPf, slots, st);
 }
 
@@ -633,11 +633,11 @@ size_t trial_tail_parts(const DeviceGraph& g, const DeviceStructure& st, int fac
 }
 
 void launch_trial_tail_fused(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, Scalar lambda, const Scalar* old, hipStream_t s,
-	const LmDevice* decide, const DevicePoseFactors* pf, int publish)
+	const LmDevice* decide, const DeviceFactors* pf, int publish)
 {
 	const int nLm = (st.nWaves + LIN_BLOCK / WAVE - 1) / (LIN_BLOCK / WAVE);
 	const int nA = nLm + st.nBig;
-	const int nPf = pose_factor_chi2_parts(pf);      // (the partials that follow the edges')
+	const int nPf = factor_chi2_parts(pf);      // (the partials that follow the edges')
 	Scalar* scParts = sys.parts;
 	Scalar* chiParts = sys.parts + (size_t)(nA + 63) / 64 * 64;
 	Scalar* scaleParts = chiParts + (size_t)(nA + nPf + 63) / 64 * 64;
@@ -646,7 +646,7 @@ void launch_trial_tail_fused(const DeviceGraph& g, const DeviceStructure& st, co
 	if (nLm + poseBlocks + nScale > 0)
 		hipLaunchKernelGGL(trial_tail_kernel, dim3(nLm + poseBlocks + nScale), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, old, scParts, chiParts, nLm, poseBlocks, scaleParts, nScale);
 	if (st.nBig > 0) hipLaunchKernelGGL(big_trial_tail_kernel, dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, old, scParts + nLm, chiParts + nLm);
-	if (nPf > 0) launch_pose_factor_chi2(g, *pf, chiParts + nA, s);          // (at the poses the edge pass has just updated)
+	if (nPf > 0) launch_factor_chi2(g, *pf, chiParts + nA, s);          // (at the poses the edge pass has just updated)
 	hipLaunchKernelGGL(reduce_report_kernel, dim3(1), dim3(1024), 0, s, sys, scParts, nA, sys.slots + NSLOT, chiParts, nA + nPf, sys.slots, scaleParts, 4 * nScale, sys.slots + 3 * NSLOT,
 		decide ? decide->state : (double*)nullptr, decide ? decide->lam : (Scalar*)nullptr, decide ? decide->ring : (double*)nullptr, publish);
 }

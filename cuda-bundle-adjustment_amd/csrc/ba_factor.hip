@@ -1,5 +1,6 @@
-// ba_posefactor.hip -- the pose factors: terms rho(r^T Omega r) of the objective on the SE(3) poses alone, r in the [omega, upsilon] tangent of
-// the solver's left-multiplicative update T <- exp(d) T (pose_exp_update), Omega a full symmetric 6 x 6 information.  Two kinds:
+// ba_factor.hip -- the factors besides the reprojection edges: terms rho(r^T Omega r) of the objective on the vertices alone, Omega a full
+// symmetric information.  Two kinds on the SE(3) poses, r in the [omega, upsilon] tangent of the solver's left-multiplicative update
+// T <- exp(d) T (pose_exp_update), Omega 6 x 6, and one on the landmarks:
 //
 //   pose priors (cuba_hip_set_pose_priors): unary, r = log(T Tbar^-1), linearised with the exact derivative dr/dd =
 //     J_l(r)^-1.  A prior touches the diagonal 6 x 6 block of its pose in the reduced matrix and the pose's entries of bp / bsc only.
@@ -7,14 +8,22 @@
 //     dr/dd_i = -J_l(r)^-1 Ad(T_j T_i^-1).  Such an edge owns an off-diagonal block of the reduced matrix: the set of free-free pairs seeds
 //     the block pattern (ba_setup.hip), and a pair that no landmark connects gets a block without Schur products, which only the kernels
 //     below write.
+//   landmark position priors (cuba_hip_set_landmark_priors; section 7f): unary on the free landmarks, r = X - Xbar, Omega 3 x 3 (g2o's
+//     unary XYZ prior edge; the reference has no counterpart).  The Jacobian of r is the identity, so a prior's whole linearisation is
+//     Hll += w Omega, bl -= w Omega r with w = rho'(r^T Omega r) (bl: the right-hand side of the landmark's rows, minus half the gradient).
+//     Hll and bl of a landmark have one writer, the head lane of the landmark pass (ba_linearize.hip), and everything downstream -- the
+//     3 x 3 inverse, the pose and block passes, back-substitution, the gain ratio's scale, the covariances -- reads them from sys.lm_sys.
+//     So these priors are linearised INSIDE that pass (ba_device.hpp: add_landmark_priors, in kernel instantiations that only a handle
+//     with such priors launches); this file holds their chi2 kernel and their host side.
 //
 // A factor may carry a robust kernel (cuba_hip_set_pose_factor_robust_kernels; section 7e): with e = r^T Omega r its term is rho(e) and its
 // linearisation takes w Omega, w = rho'(e), for Omega (no second-order term, as the reprojection edges).  The four kernels that see a
 // residual are templates on ROBUST; a set without kernels has null kind / delta arrays and runs the `false` instantiations, which hold
-// nothing of this.
+// nothing of this.  A landmark prior always carries a kind (none = 0) and comes with its kernel in one call.
 //
-// The two kinds keep kernels of their own (a prior is not run as a one-ended edge: its sums would be taken in another order); they share the
-// device helpers below, the host-side validation, packing, upload and read-back, and one interface (ba_kernels.hpp: DevicePoseFactors).
+// The kinds keep kernels of their own (a prior is not run as a one-ended edge: its sums would be taken in another order); they share the
+// device helpers below, the host-side validation, sorting and read-back -- the two pose kinds also packing and upload -- and one interface
+// (ba_kernels.hpp: DeviceFactors).
 //
 //   prior_linearize_kernel     lane = free pose with priors: its priors in the caller's order, J^T Omega J / J^T Omega r summed in
 //                              registers, then added to the pose's diagonal block (upper triangle), bp and (mode 1) bsc -- one writer per
@@ -28,10 +37,11 @@
 //                              edges in the caller's order -- one writer per number, fixed order, no atomics; behind the Schur pass and the
 //                              priors' launch
 //   prior_chi2_kernel,         lane = factor: r^T Omega r at the current estimate into the per-factor output and (rho of it) into per-workgroup
-//   relpose_chi2_kernel        partials that the caller sums together with the reprojection edges' partials (fixed order, no atomics)
+//   relpose_chi2_kernel,       partials that the caller sums together with the reprojection edges' partials (fixed order, no atomics)
+//   landmark_prior_chi2_kernel
 //
-// Host side: the caller's two sets (validated, kept in the caller's numbering), the edges' pair set (part of the topology) and the upload
-// of either set in the internal pose order.
+// Host side: the caller's three sets (validated, kept in the caller's numbering), the edges' pair set (part of the topology) and the upload
+// of every set in the internal pose / landmark order.
 #include "ba_solver.hpp"
 #include "ba_device.hpp"
 #include "ba_se3.hpp"
@@ -375,6 +385,27 @@ __global__ __launch_bounds__(CHI_BLOCK) void relpose_chi2_kernel(DeviceGraph g, 
 	chi2_partial(acc, parts);
 }
 
+// ---- landmark priors --------------------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(CHI_BLOCK) void landmark_prior_chi2_kernel(DeviceGraph g, DeviceLandmarkPriors lp, Scalar* __restrict__ parts)
+{
+	Scalar acc = 0;
+	for (int k = blockIdx.x * CHI_BLOCK + threadIdx.x; k < lp.n; k += gridDim.x * CHI_BLOCK)
+	{
+		const int il = lp.lm[k];
+		Scalar chi = 0;
+		if (il < g.Lf)
+		{
+			const Scalar X[3] = { g.Xw[3 * (size_t)il], g.Xw[3 * (size_t)il + 1], g.Xw[3 * (size_t)il + 2] };
+			Scalar Or[3];
+			chi = landmark_prior_residual(lp, k, X, Or);
+		}
+		lp.chi[k] = chi;
+		acc += factor_rho(lp.rk_kind[k], lp.rk_delta[k], chi);
+	}
+	chi2_partial(acc, parts);
+}
+
 // ---- launches ---------------------------------------------------------------------------------------------------------------------
 
 static void launch_prior_chi2(const DeviceGraph& g, const DevicePriors& pr, Scalar* parts, hipStream_t s)
@@ -393,16 +424,23 @@ static void launch_relpose_chi2(const DeviceGraph& g, const DeviceRelPoses& rp, 
 	else hipLaunchKernelGGL(relpose_chi2_kernel<false>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, rp, parts);
 }
 
-int pose_factor_chi2_parts(const DevicePoseFactors* pf) { return pf ? chi2_parts(pf->priors.n) + chi2_parts(pf->rel.n) + landmark_prior_chi2_parts(pf->lmp) : 0; }
+static void launch_landmark_prior_chi2(const DeviceGraph& g, const DeviceLandmarkPriors& lp, Scalar* parts, hipStream_t s)
+{
+	const int grid = chi2_parts(lp.n);
+	if (grid <= 0) return;
+	hipLaunchKernelGGL(landmark_prior_chi2_kernel, dim3(grid), dim3(CHI_BLOCK), 0, s, g, lp, parts);
+}
 
-void launch_pose_factor_chi2(const DeviceGraph& g, const DevicePoseFactors& pf, Scalar* parts, hipStream_t s)
+int factor_chi2_parts(const DeviceFactors* pf) { return pf ? chi2_parts(pf->priors.n) + chi2_parts(pf->rel.n) + chi2_parts(pf->lmp.n) : 0; }
+
+void launch_factor_chi2(const DeviceGraph& g, const DeviceFactors& pf, Scalar* parts, hipStream_t s)
 {
 	launch_prior_chi2(g, pf.priors, parts, s);
 	launch_relpose_chi2(g, pf.rel, parts + chi2_parts(pf.priors.n), s);
 	launch_landmark_prior_chi2(g, pf.lmp, parts + chi2_parts(pf.priors.n) + chi2_parts(pf.rel.n), s);
 }
 
-void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DevicePoseFactors& pf, int mode, hipStream_t s)
+void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DeviceFactors& pf, int mode, hipStream_t s)
 {
 	const DevicePriors& pr = pf.priors;
 	if (pr.nPoses > 0)
@@ -424,6 +462,28 @@ void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& s
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 
+// a factor's D x D information O as the caller gave it -> `sym`: finite, symmetric within 1e-9 of its largest entry, symmetrised (within
+// that tolerance the two triangles may differ by rounding; the pose factors' kernels read both).  `noun`: how the messages name the factor
+template <int D>
+static void take_information(const double* O, double* sym, const std::string& noun)
+{
+	double m = 0;
+	for (int i = 0; i < D * D; i++) { if (!std::isfinite(O[i])) throw ArgError{ "non-finite " + noun + " information" }; m = std::max(m, std::fabs(O[i])); }
+	for (int c = 0; c < D; c++)
+		for (int r = 0; r < c; r++)
+			if (std::fabs(O[D * c + r] - O[D * r + c]) > 1e-9 * m) throw ArgError{ noun + " information is not symmetric" };
+	for (int c = 0; c < D; c++)
+		for (int r = 0; r < D; r++) sym[D * c + r] = r == c ? O[D * c + r] : 0.5 * (O[D * c + r] + O[D * r + c]);
+}
+
+// a factor's robust kernel as the caller gave it: a known kind, a finite delta, a positive one for a real kernel
+static void check_factor_kernel(int kind, double delta, const char* noun)
+{
+	if (kind < cubahip::POSE_FACTOR_KERNEL_NONE || kind > cubahip::POSE_FACTOR_KERNEL_CAUCHY) throw ArgError{ std::string("bad ") + noun + " robust kernel" };
+	if (!std::isfinite(delta)) throw ArgError{ "non-finite robust-kernel delta" };
+	if (kind != cubahip::POSE_FACTOR_KERNEL_NONE && !(delta > 0)) throw ArgError{ "robust-kernel delta must be positive" };
+}
+
 // the q | t | information of factor k of a caller's set into `v` (sized by the caller): finite, the quaternion normalised, the information
 // symmetric and symmetrised.  `what`, `kind`: how the messages name the factor's measurement ("prior" / "relative") and its kind
 static void take_factor_values(PoseFactorValues& v, int k, const double* q, const double* t, const double* info, const std::string& what, const std::string& kind)
@@ -434,15 +494,7 @@ static void take_factor_values(PoseFactorValues& v, int k, const double* q, cons
 	if (!(nq > 0) || !std::isfinite(nq)) throw ArgError{ kind + " quaternion of zero norm" };
 	for (int i = 0; i < 4; i++) v.q[4 * (size_t)k + i] = q[4 * (size_t)k + i] / nq;
 	for (int i = 0; i < 3; i++) { if (!std::isfinite(t[3 * (size_t)k + i])) throw ArgError{ "non-finite " + what + " translation" }; v.t[3 * (size_t)k + i] = t[3 * (size_t)k + i]; }
-	const double* O = info + 36 * (size_t)k;
-	double m = 0;
-	for (int i = 0; i < 36; i++) { if (!std::isfinite(O[i])) throw ArgError{ "non-finite " + kind + " information" }; m = std::max(m, std::fabs(O[i])); }
-	for (int c = 0; c < 6; c++)
-		for (int r = 0; r < c; r++)
-			if (std::fabs(O[6 * c + r] - O[6 * r + c]) > 1e-9 * m) throw ArgError{ kind + " information is not symmetric" };
-	// (symmetrised: within the tolerance above the two triangles may differ by rounding; the kernels read both)
-	for (int c = 0; c < 6; c++)
-		for (int r = 0; r < 6; r++) v.info[36 * (size_t)k + 6 * c + r] = r == c ? O[6 * c + r] : 0.5 * (O[6 * c + r] + O[6 * r + c]);
+	take_information<6>(info + 36 * (size_t)k, v.info.data() + 36 * (size_t)k, kind);
 }
 
 static PoseFactorValues sized_factor_values(int n, bool binary)
@@ -454,7 +506,7 @@ static PoseFactorValues sized_factor_values(int n, bool binary)
 
 // a validated set replaces the handle's: its device copy is due, and the run-to-run memories that the values of the system feed go, as a
 // new graph drops them (a run after a change of the factors depends on the state and the factors only)
-static void forget_factor_memories(cuba_hip_solver& s, PoseFactorSet& set)
+static void forget_factor_memories(cuba_hip_solver& s, FactorSet& set)
 {
 	set.uploaded = false;
 	s.forgetRunMemories();
@@ -526,9 +578,7 @@ void cuba_hip_solver::setPoseFactorRobustKernels(int factorType, int n, const in
 	bool any = false;
 	for (int k = 0; k < n; k++)
 	{
-		if (kind[k] < cubahip::POSE_FACTOR_KERNEL_NONE || kind[k] > cubahip::POSE_FACTOR_KERNEL_CAUCHY) throw ArgError{ "bad pose-factor robust kernel" };
-		if (!std::isfinite(delta[k])) throw ArgError{ "non-finite robust-kernel delta" };
-		if (kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE && !(delta[k] > 0)) throw ArgError{ "robust-kernel delta must be positive" };
+		check_factor_kernel(kind[k], delta[k], "pose-factor");
 		any = any || kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE;
 	}
 	if (any) { set.kind.assign(kind, kind + n); set.delta.assign(delta, delta + n); }
@@ -553,7 +603,7 @@ std::vector<uint64_t> cuba_hip_solver::relSeedKeys() const
 }
 
 // set.order: the caller's factors stable by `key` (factors of equal key stay in the caller's order)
-static void sort_factors(PoseFactorSet& set, const std::vector<uint64_t>& key)
+static void sort_factors(FactorSet& set, const std::vector<uint64_t>& key)
 {
 	set.order.resize(key.size());
 	std::iota(set.order.begin(), set.order.end(), 0);
@@ -683,18 +733,112 @@ static void upload_relative_pose_edges(cuba_hip_solver& s)
 	rp.pose_ptr = rp.blk_id + nb; rp.pose_id = rp.pose_ptr + (np + 1); rp.pose_item = rp.pose_id + np;
 	rp.rec = s.d_relRec.data();
 	s.pf.rel = rp;
-	s.relStructure = s.cntStructureBuilds;
+	set.structure = s.cntStructureBuilds;
 }
 
-// (the priors depend on the pose order only -- a change of it marks them --, the edges' blocks on the structure)
-void cuba_hip_solver::uploadPoseFactors()
+void cuba_hip_solver::setLandmarkPriors(int n, const int32_t* landmark, const double* xyz, const double* info, const int32_t* kind, const double* delta)
+{
+	if (!haveGraph) throw StateError{ "set_graph must be called first" };
+	if (n < 0) throw ArgError{ "negative landmark prior count" };
+	if (n > 0 && (partHi >= 0 || valuesPartial)) throw StateError{ "landmark priors are not available on a landmark-partitioned handle" };
+	if (n > 0 && E == 0) throw StateError{ "landmark priors need a graph with edges" };
+	if (n > 0 && (!landmark || !xyz || !info)) throw ArgError{ "null landmark prior array" };
+	if (n > 0 && (kind == nullptr) != (delta == nullptr)) throw ArgError{ "landmark prior kernels: kind and delta come together" };
+	LandmarkPriorSet v;
+	v.lm.resize((size_t)n); v.xyz.resize((size_t)3 * n); v.info.resize((size_t)6 * n); v.kind.assign((size_t)n, cubahip::POSE_FACTOR_KERNEL_NONE); v.delta.assign((size_t)n, 1.0);
+	for (int k = 0; k < n; k++)
+	{
+		if (landmark[k] < 0 || landmark[k] >= Lt) throw ArgError{ "landmark prior: landmark index out of range" };
+		v.lm[k] = landmark[k];
+		for (int i = 0; i < 3; i++)
+		{
+			if (!std::isfinite(xyz[3 * (size_t)k + i])) throw ArgError{ "non-finite landmark prior position" };
+			v.xyz[3 * (size_t)k + i] = xyz[3 * (size_t)k + i];
+		}
+		// the symmetrised information's upper triangle, in the packing of sym3_idx
+		double S[9];
+		take_information<3>(info + 9 * (size_t)k, S, "landmark prior");
+		double* U = v.info.data() + 6 * (size_t)k;
+		U[0] = S[0]; U[1] = S[3]; U[2] = S[6]; U[3] = S[4]; U[4] = S[7]; U[5] = S[8];
+		if (kind)
+		{
+			check_factor_kernel(kind[k], delta[k], "landmark prior");
+			if (kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE) { v.kind[k] = kind[k]; v.delta[k] = delta[k]; }
+		}
+	}
+	// a validated set replaces the handle's, as a pose kind's
+	lmPriorSet.lm.swap(v.lm); lmPriorSet.xyz.swap(v.xyz); lmPriorSet.info.swap(v.info); lmPriorSet.kind.swap(v.kind); lmPriorSet.delta.swap(v.delta);
+	lmPriorSet.order.clear();
+	forget_factor_memories(*this, lmPriorSet);
+	pf.lmp = DeviceLandmarkPriors();
+	covBlocksValid = false;
+}
+
+// the caller's priors -> device, in the internal landmark order (stable by internal landmark: every landmark's priors contiguous, in the
+// caller's order; the priors on fixed landmarks last).  A prior on a free landmark without an edge cannot be honoured -- the landmark pass
+// walks the landmarks of the edge list --: the set is dropped and the call that got here reports it.
+static void upload_landmark_priors(cuba_hip_solver& s)
+{
+	LandmarkPriorSet& set = s.lmPriorSet;
+	const int n = set.n(), Lf = s.Lf;
+	std::vector<int> lmMap, lmPtr((size_t)Lf + 1, 0);
+	if (s.lmOrderActive && Lf > 0)
+	{
+		lmMap.resize(Lf);
+		HIP_TRY(hipMemcpyAsync(lmMap.data(), s.d_lmMap.data(), sizeof(int) * (size_t)Lf, hipMemcpyDeviceToHost, s.stream));
+	}
+	HIP_TRY(hipMemcpyAsync(lmPtr.data(), s.g.lm_ptr, sizeof(int) * ((size_t)Lf + 1), hipMemcpyDeviceToHost, s.stream));
+	s.sync();
+	std::vector<uint64_t> internal((size_t)n);
+	for (int k = 0; k < n; k++)
+	{
+		const int l = set.lm[k];
+		internal[k] = (uint64_t)(l < Lf && !lmMap.empty() ? lmMap[l] : l);
+		if (l < Lf && lmPtr[internal[k]] == lmPtr[internal[k] + 1])
+		{
+			set.clear(); s.pf.lmp = DeviceLandmarkPriors();
+			throw ArgError{ "landmark prior on free landmark " + std::to_string(l) + ", which no edge observes: the set is dropped" };
+		}
+	}
+	sort_factors(set, internal);
+	// ints: lm_ptr [Lf + 1] | lm [n] | kind [n];  values: xbar [3 n] | info [6 n] | delta [n]
+	std::vector<int> ints((size_t)Lf + 1 + 2 * (size_t)n, 0);
+	std::vector<Scalar> vals((size_t)10 * n);
+	int* ptr = ints.data(); int* lm = ptr + Lf + 1; int* kd = lm + n;
+	Scalar* vx = vals.data(); Scalar* vi = vx + 3 * (size_t)n; Scalar* vd = vi + 6 * (size_t)n;
+	for (int p = 0; p < n; p++)
+	{
+		const size_t k = (size_t)set.order[p];
+		lm[p] = (int)internal[k]; kd[p] = set.kind[k]; vd[p] = (Scalar)set.delta[k];
+		if (lm[p] < Lf) ptr[lm[p] + 1]++;
+		for (int i = 0; i < 3; i++) vx[3 * (size_t)p + i] = (Scalar)set.xyz[3 * k + i];
+		for (int i = 0; i < 6; i++) vi[6 * (size_t)p + i] = (Scalar)set.info[6 * k + i];
+	}
+	for (int l = 0; l < Lf; l++) ptr[l + 1] += ptr[l];
+	set.d_ints.upload(ints, s.stream);
+	set.d_vals.upload(vals, s.stream);
+	set.d_chi.resize((size_t)n);
+	s.sync();          // (the staging vectors go out of scope)
+	DeviceLandmarkPriors lp;
+	lp.n = n;
+	lp.lm_ptr = set.d_ints.data(); lp.lm = lp.lm_ptr + Lf + 1; lp.rk_kind = lp.lm + n;
+	lp.xbar = set.d_vals.data(); lp.info = lp.xbar + 3 * (size_t)n; lp.rk_delta = lp.info + 6 * (size_t)n;
+	lp.chi = set.d_chi.data();
+	s.pf.lmp = lp;
+	set.uploaded = true; set.structure = s.cntStructureBuilds;
+}
+
+// (the pose priors depend on the pose order only -- a change of it marks them --, the edges' blocks and the landmark priors' order on the
+// structure)
+void cuba_hip_solver::uploadFactors()
 {
 	if (priorSet.n() > 0 && !priorSet.uploaded) upload_priors(*this);
-	if (relSet.n() > 0 && (!relSet.uploaded || relStructure != cntStructureBuilds)) upload_relative_pose_edges(*this);
+	if (relSet.n() > 0 && (!relSet.uploaded || relSet.structure != cntStructureBuilds)) upload_relative_pose_edges(*this);
+	if (lmPriorSet.n() > 0 && (!lmPriorSet.uploaded || lmPriorSet.structure != cntStructureBuilds)) upload_landmark_priors(*this);
 }
 
 // the per-factor chi2 of the chi2 launch just issued (sorted order on the device) -> the caller's order
-static void read_factor_chi2(cuba_hip_solver& s, const PoseFactorSet& set, const Scalar* chi, double* out)
+static void read_factor_chi2(cuba_hip_solver& s, const FactorSet& set, const Scalar* chi, double* out)
 {
 	const size_t n = set.order.size();
 	std::vector<double> sorted(n);
@@ -716,4 +860,12 @@ void cuba_hip_solver::relativePoseChiSquares(double* out)
 	if (relSet.n() == 0) return;
 	launch_relpose_chi2(g, pf.rel, d_parts.data(), stream);
 	read_factor_chi2(*this, relSet, pf.rel.chi, out);
+}
+
+void cuba_hip_solver::landmarkPriorChiSquares(double* out)
+{
+	need();
+	if (lmPriorSet.n() == 0) return;
+	launch_landmark_prior_chi2(g, pf.lmp, d_parts.data(), stream);
+	read_factor_chi2(*this, lmPriorSet, pf.lmp.chi, out);
 }

@@ -1,4 +1,4 @@
-// ba_kernels.hpp -- launch interface of the gfx950 kernels (implemented in ba_edge.hip, ba_linearize.hip, ba_pcg.hip, ba_coarse.hip, ba_posefactor.hip, ba_lmfactor.hip).
+// ba_kernels.hpp -- launch interface of the gfx950 kernels (implemented in ba_edge.hip, ba_linearize.hip, ba_pcg.hip, ba_coarse.hip, ba_factor.hip).
 //
 // Device data model (all SoA, fp64 + int32):
 //   poses      q[4*Pt] t[3*Pt] cam[5*Pt]          free poses [0,Pf) first, fixed after
@@ -138,10 +138,10 @@ struct DeviceSystem
 
 // robust kernel of a pose factor (cuba_hip_set_pose_factor_robust_kernels): with e = r^T Omega r the objective term is rho(e) and the
 // linearisation takes w Omega, w = rho'(e), for Omega.  Kinds 1 and 2 are robust_rho / robust_weight (ba_math.hpp); Cauchy, rho =
-// delta^2 log1p(e / delta^2), exists for the pose factors only (helpers in ba_posefactor.hip).
+// delta^2 log1p(e / delta^2), exists for these factors only (helpers in ba_device.hpp).
 enum { POSE_FACTOR_KERNEL_NONE = 0, POSE_FACTOR_KERNEL_HUBER = 1, POSE_FACTOR_KERNEL_TUKEY = 2, POSE_FACTOR_KERNEL_CAUCHY = 3 };
 
-// SE(3) pose priors (ba_posefactor.hip): rho(r^T Omega r), r = log(T Tbar^-1) in the [omega, upsilon] tangent of the pose update.  Sorted by
+// SE(3) pose priors (ba_factor.hip): rho(r^T Omega r), r = log(T Tbar^-1) in the [omega, upsilon] tangent of the pose update.  Sorted by
 // internal pose (stable: a pose's priors are contiguous and in the caller's order); priors on fixed poses come last and are ignored.
 struct DevicePriors
 {
@@ -157,10 +157,10 @@ struct DevicePriors
 	const Scalar* rk_delta = nullptr;   // [n]
 };
 
-// SE(3) relative-pose edges (ba_posefactor.hip): rho(r^T Omega r), r = log(T_j T_i^-1 Zbar^-1), between two poses.  Sorted: the edges between two
+// SE(3) relative-pose edges (ba_factor.hip): rho(r^T Omega r), r = log(T_j T_i^-1 Zbar^-1), between two poses.  Sorted: the edges between two
 // free poses first, stable by the block (min, max) of the internal pose pair (a block's edges contiguous, in the caller's order), then the
 // edges with one fixed end (they act on the free end only), then those with two (ignored).
-constexpr int REL_REC = 90;        // numbers of an edge's linearisation record (layout: ba_posefactor.hip)
+constexpr int REL_REC = 90;        // numbers of an edge's linearisation record (layout: ba_factor.hip)
 struct DeviceRelPoses
 {
 	int n = 0;                     // edges
@@ -181,7 +181,7 @@ struct DeviceRelPoses
 	const Scalar* rk_delta = nullptr;   // [n]
 };
 
-// Landmark position priors (ba_lmfactor.hip): rho(r^T Omega r), r = X - Xbar, Omega a symmetric 3 x 3 information.  Sorted by internal landmark
+// Landmark position priors (ba_factor.hip): rho(r^T Omega r), r = X - Xbar, Omega a symmetric 3 x 3 information.  Sorted by internal landmark
 // (stable: a landmark's priors are contiguous and in the caller's order); priors on fixed landmarks come last and are ignored.  The landmark
 // pass adds a landmark's terms w Omega / -w Omega r to its Hll / bl (ba_device.hpp: add_landmark_priors), in a kernel instantiation of its
 // own that only a handle with such priors launches.
@@ -196,26 +196,23 @@ struct DeviceLandmarkPriors
 	const Scalar* rk_delta = nullptr;   // [n]
 	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 on fixed landmarks)
 };
-// per-prior chi2 (the plain r^T Omega r) into lp.chi, per-workgroup partial sums of rho(chi2) into parts[0 .. landmark_prior_chi2_parts(lp))
-void launch_landmark_prior_chi2(const DeviceGraph& g, const DeviceLandmarkPriors& lp, Scalar* parts, hipStream_t s);
-int landmark_prior_chi2_parts(const DeviceLandmarkPriors& lp);     // 0 for no priors, at most 64
 
 // The factors of a handle besides the reprojection edges: what the rest of the library sees of the kinds (a kind without factors: n = 0,
 // nothing of it is launched).  The landmark priors ride along for the chi2 sums only: their linearisation is the landmark pass's.
-struct DevicePoseFactors { DevicePriors priors; DeviceRelPoses rel; DeviceLandmarkPriors lmp; };
+struct DeviceFactors { DevicePriors priors; DeviceRelPoses rel; DeviceLandmarkPriors lmp; };
 // behind the Schur pass, the priors first (Omega: w Omega of a factor with a robust kernel): J^T Omega J into the diagonal blocks of hsc (upper triangle), -J^T Omega r into bp and (mode 1)
 // bsc, J = J_l(r)^-1; then the edges in two launches: per-edge records, then their sums into hsc (diagonal blocks: upper triangle; mode 1:
 // the off-diagonal blocks of the pairs, stored whole where a block has no Schur products), bp and (mode 1) bsc
-void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DevicePoseFactors& pf, int mode, hipStream_t s);
-// per-factor chi2 (the plain r^T Omega r) into priors.chi / rel.chi / lmp.chi, per-workgroup partial sums of rho(chi2) into parts[0 .. pose_factor_chi2_parts(&pf)): the priors' first, the
+void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DeviceFactors& pf, int mode, hipStream_t s);
+// per-factor chi2 (the plain r^T Omega r) into priors.chi / rel.chi / lmp.chi, per-workgroup partial sums of rho(chi2) into parts[0 .. factor_chi2_parts(&pf)): the priors' first, the
 // edges' behind them, the landmark priors' last
-void launch_pose_factor_chi2(const DeviceGraph& g, const DevicePoseFactors& pf, Scalar* parts, hipStream_t s);
-int pose_factor_chi2_parts(const DevicePoseFactors* pf);     // 0 for no factors (pf null), at most 64 per kind (the landmark priors' included)
+void launch_factor_chi2(const DeviceGraph& g, const DeviceFactors& pf, Scalar* parts, hipStream_t s);
+int factor_chi2_parts(const DeviceFactors* pf);     // 0 for no factors (pf null), at most 64 per kind (the landmark priors' included)
 
 // residual / robust chi2 over all edges -> sys.slots[0..NSLOT) (must be zeroed by the caller).
 // per_edge (optional, sorted edge order): non-robust omega*|r|^2.
-// pf (optional): the pose factors' chi2 partials follow the edges' and are summed with them (the objective F of the LM loop)
-void launch_residual_chi2(const DeviceGraph& g, Scalar* parts, Scalar* slots, Scalar* per_edge, hipStream_t st, const DevicePoseFactors* pf = nullptr);
+// pf (optional): the factors' chi2 partials follow the edges' and are summed with them (the objective F of the LM loop)
+void launch_residual_chi2(const DeviceGraph& g, Scalar* parts, Scalar* slots, Scalar* per_edge, hipStream_t st, const DeviceFactors* pf = nullptr);
 
 // mode 0: assemble only (Hpp -> diagonal blocks of hsc, bp, Hll/bl -> lm_sys, max diagonal of Hll)
 // mode 1: full linearise + Schur reduction with damping lambda (hsc, bsc, bp, inv(Hll+lambda)/bl -> lm_sys)
@@ -246,13 +243,13 @@ void launch_pose_scale(const DeviceGraph& g, const DeviceSystem& sys, Scalar lam
 // [q | t | Xw] made before the trial: the pass reads the pre-update estimate from it while it writes the updated one), then the sums
 // + report.  trial_tail_parts(): numbers of partial-sum scratch (sys.parts) it needs.
 struct LmDevice;
-// pf (optional): the pose factors' chi2 at the updated poses, launches between the edge pass and the sums; their partials join the edges'
+// pf (optional): the factors' chi2 at the updated estimate, launches between the edge pass and the sums; their partials join the edges'
 // chi2 partials
 // publish = 0: the decision's record goes out with plain stores, without the system-scope fence and the ticket (the caller then does not
 // count a report): for decisions the host does not wait for
 void launch_trial_tail_fused(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, Scalar lambda, const Scalar* old, hipStream_t s,
-	const LmDevice* decide = nullptr, const DevicePoseFactors* pf = nullptr, int publish = 1);
-size_t trial_tail_parts(const DeviceGraph& g, const DeviceStructure& st, int factorParts = 0);      // factorParts: pose_factor_chi2_parts()
+	const LmDevice* decide = nullptr, const DeviceFactors* pf = nullptr, int publish = 1);
+size_t trial_tail_parts(const DeviceGraph& g, const DeviceStructure& st, int factorParts = 0);      // factorParts: factor_chi2_parts()
 // Device-resident LM decision (control flow of CudaBundleAdjustmentImpl::optimize, /root/reference/src/cuda_bundle_adjustment.cpp:816-851):
 // state = {F, lambda, nu, halt, trials, accepted (last trial), rejections in a row, max rejections} in device memory, lam = the damping as
 // the kernels read it (sys.lam_dev), ring = device-mapped host records, LM_REC numbers per trial {Fhat, denominator, rho, next lambda,

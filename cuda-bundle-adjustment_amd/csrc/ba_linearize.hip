@@ -203,9 +203,13 @@ __global__ __launch_bounds__(LIN_BLOCK) void lm_pass_batch_kernel(const BatchEnt
 	lm_pass_body<1, ET>(e.g, e.st, e.sys, Scalar(-1), e.t.lmGroups, const_cast<Scalar*>(e.t.backupSrc), e.t.backupDst, e.t.backupCount, e.t.lmGrid, nullptr);
 }
 
-// landmarks with more than 64 observations: one workgroup each
-template <int MODE, typename ET>
-__global__ __launch_bounds__(256) void big_lm_pass_kernel(DeviceGraph g, DeviceStructure st, DeviceSystem sys, Scalar lambda)
+// landmarks with more than 64 observations: one workgroup each.  PRIOR (a handle with landmark priors): thread 0 adds the landmark's priors
+// behind the sum over its edges; the instantiations without it never touch lp (the launch passes an empty one).
+// One __global__ template, not two thin kernels around a shared __device__ body: inlined into a wrapper, the body's fp32 code comes out with
+// another mix of packed multiplies, adds and fmas -- other rounding -- while a template flag leaves every instantiation's code as it is, and
+// a handle without priors must compute what it computed before.
+template <int MODE, typename ET, bool PRIOR>
+__global__ __launch_bounds__(256) void big_lm_pass_kernel(DeviceGraph g, DeviceStructure st, DeviceSystem sys, Scalar lambda, DeviceLandmarkPriors lp)
 {
 	__shared__ Scalar red[4][9];
 	lambda = launch_lambda(sys, lambda);
@@ -248,81 +252,11 @@ __global__ __launch_bounds__(256) void big_lm_pass_kernel(DeviceGraph g, DeviceS
 		Scalar H[9];
 #pragma unroll
 		for (int k = 0; k < 9; k++) H[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-		Scalar* ls = sys.lm_sys + 9 * (size_t)il;
-		if (MODE == 0)
+		if constexpr (PRIOR)
 		{
-#pragma unroll
-			for (int k = 0; k < 9; k++) ls[k] = H[k];
-			atomic_max_nonneg(sys.maxdiag, fmax(H[0], fmax(H[3], H[5])));
+			const Scalar X[3] = { g.Xw[3 * (size_t)il], g.Xw[3 * (size_t)il + 1], g.Xw[3 * (size_t)il + 2] };
+			add_landmark_priors(lp, il, X, H);
 		}
-		else
-		{
-			Scalar inv[6];
-			H[0] += lambda; H[3] += lambda; H[5] += lambda;
-			sym3_inverse(H, inv);
-#pragma unroll
-			for (int k = 0; k < 6; k++) ls[k] = inv[k];
-			if (st.inv_rows8)
-			{
-				Scalar* li = sys.lm_inv + 8 * (size_t)il;
-#pragma unroll
-				for (int k = 0; k < 6; k++) li[k] = inv[k];
-				li[6] = 0; li[7] = 0;
-			}
-#pragma unroll
-			for (int k = 0; k < 3; k++) ls[6 + k] = H[6 + k];
-		}
-	}
-}
-
-// the same pass for a handle with landmark priors (a sibling, not a template parameter of the kernel above: wrapping that kernel's body
-// changes its fp32 code, and a handle without priors must run the code it ran before): thread 0 adds the landmark's priors behind the sum
-template <int MODE, typename ET>
-__global__ __launch_bounds__(256) void big_lm_pass_prior_kernel(DeviceGraph g, DeviceStructure st, DeviceSystem sys, Scalar lambda, DeviceLandmarkPriors lp)
-{
-	__shared__ Scalar red[4][9];
-	lambda = launch_lambda(sys, lambda);
-	const int il = st.big_lm[blockIdx.x];
-	const int e0 = g.lm_ptr[il], e1 = g.lm_ptr[il + 1];
-	Scalar acc[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-	for (int e = e0 + threadIdx.x; e < e1; e += 256)
-	{
-		LaneEdge le;
-		linearize_edge(g, e, le);
-		// linearize_edge does not return Xc: recompute it for the record
-		Scalar q[4], t[3], cam[5], Xw[3], Xc[3];
-		load_pose(g, le.ip, q, t, cam);
-#pragma unroll
-		for (int i = 0; i < 3; i++) Xw[i] = g.Xw[3 * (size_t)il + i];
-		quat_rotate(q, Xw, Xc);
-		Xc[0] += t[0]; Xc[1] += t[1]; Xc[2] += t[2];
-		write_record<ET>(st.e_rec, (size_t)e, Xc, le.wr, le.lin.r, il, le.stereo);
-		if (il < g.Lf)
-		{
-			const EdgeLin& L = le.lin;
-#pragma unroll
-			for (int i = 0; i < 3; i++)
-			{
-#pragma unroll
-				for (int j = i; j < 3; j++)
-					acc[sym3_idx(i, j)] += le.wr * (L.JL[0][i] * L.JL[0][j] + L.JL[1][i] * L.JL[1][j] + L.JL[2][i] * L.JL[2][j]);
-				acc[6 + i] += le.wr * (L.JL[0][i] * L.r[0] + L.JL[1][i] * L.r[1] + L.JL[2][i] * L.r[2]);
-			}
-		}
-	}
-#pragma unroll
-	for (int k = 0; k < 9; k++) acc[k] = wave_sum(acc[k]);
-	if ((threadIdx.x & 63) == 0)
-#pragma unroll
-		for (int k = 0; k < 9; k++) red[threadIdx.x >> 6][k] = acc[k];
-	__syncthreads();
-	if (threadIdx.x == 0 && il < g.Lf)
-	{
-		Scalar H[9];
-#pragma unroll
-		for (int k = 0; k < 9; k++) H[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-		const Scalar X[3] = { g.Xw[3 * (size_t)il], g.Xw[3 * (size_t)il + 1], g.Xw[3 * (size_t)il + 2] };
-		add_landmark_priors(lp, il, X, H);
 		Scalar* ls = sys.lm_sys + 9 * (size_t)il;
 		if (MODE == 0)
 		{
@@ -679,10 +613,10 @@ static void launch_linearize_dm_t(const DeviceGraph& g, const DeviceStructure& s
 		(void)hipMemcpyAsync(backupDst, backupSrc, backupCount * sizeof(Scalar), hipMemcpyDeviceToDevice, s);
 	if (st.nBig > 0)
 	{
-		if (lp && mode == 0) hipLaunchKernelGGL((big_lm_pass_prior_kernel<0, ET>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, *lp);
-		else if (lp) hipLaunchKernelGGL((big_lm_pass_prior_kernel<1, ET>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, *lp);
-		else if (mode == 0) hipLaunchKernelGGL((big_lm_pass_kernel<0, ET>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda);
-		else hipLaunchKernelGGL((big_lm_pass_kernel<1, ET>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda);
+		if (lp && mode == 0) hipLaunchKernelGGL((big_lm_pass_kernel<0, ET, true>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, *lp);
+		else if (lp) hipLaunchKernelGGL((big_lm_pass_kernel<1, ET, true>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, *lp);
+		else if (mode == 0) hipLaunchKernelGGL((big_lm_pass_kernel<0, ET, false>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, DeviceLandmarkPriors());
+		else hipLaunchKernelGGL((big_lm_pass_kernel<1, ET, false>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, DeviceLandmarkPriors());
 	}
 	const int nbp = block_pass_groups(st.nOd, st.nHeavy);
 	if (mode == 1 && g.Pf > 0 && st.nOd > 0 && st.nDiagProd == 0)     // (duplicate observations: the block pass updates diagonal blocks after the pose pass)

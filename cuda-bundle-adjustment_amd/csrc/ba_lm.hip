@@ -143,7 +143,7 @@ double cuba_hip_solver::computeErrors()
 {
 	need();
 	StageTimer tm(this, 2);
-	launch_residual_chi2(g, d_parts.data(), slotsDev, nullptr, stream, poseFactors());   // its second stage writes all NSLOT entries of the slot group
+	launch_residual_chi2(g, d_parts.data(), slotsDev, nullptr, stream, factors());   // its second stage writes all NSLOT entries of the slot group
 	return readSlots(0);
 }
 
@@ -156,7 +156,7 @@ void cuba_hip_solver::linearize(int mode, double lam, bool withBackup)
 	if (parts && !partsByCaller)
 		for (size_t c = 1; c < redParts.size(); c++) launch_block_pass(g, st, sys, redParts[c].od, stream);
 	// (a launch of its own: the Schur pass's block part may still update a diagonal block its pose part stored)
-	if (poseFactors()) launch_pose_factor_linearize(g, st, sys, pf, mode, stream);
+	if (factors()) launch_pose_factor_linearize(g, st, sys, pf, mode, stream);
 }
 
 void cuba_hip_solver::schurPart(int part, size_t ranges[4])
@@ -699,7 +699,7 @@ void cuba_hip_solver::lmRunBegin(LmRun& r, int niter, double* chi2Out, bool chai
 		need();
 		r.chain = true;
 		Scalar* chiSlots = reinterpret_cast<Scalar*>(d_lmState.data() + 16);        // (NSLOT numbers)
-		launch_residual_chi2(g, d_parts.data(), chiSlots, nullptr, stream, poseFactors());
+		launch_residual_chi2(g, d_parts.data(), chiSlots, nullptr, stream, factors());
 		zeroReduced(true);
 		d_maxdiag.zero(stream);
 		linearize(0, 0.0);
@@ -788,7 +788,7 @@ bool cuba_hip_solver::lmAfterSolve(LmRun& r, bool ok)
 	// decision is followed by a landmark pass of this run, which undoes a rejected trial itself (r.restoreInPass)
 	const bool waited = !r.chain || !(r.done + 1 < r.niter && r.rejRun + 1 < LmRun::maxq);
 	const bool publish = waited || !ok;
-	if (ok) launch_trial_tail_fused(g, st, sys, (Scalar)-1, d_backup.data(), stream, &r.lm, poseFactors(), publish ? 1 : 0);
+	if (ok) launch_trial_tail_fused(g, st, sys, (Scalar)-1, d_backup.data(), stream, &r.lm, factors(), publish ? 1 : 0);
 	else launch_lm_decide_failed(sys, r.lm, stream);
 	if (publish) noteReport();                      // (expectedTicket counts exactly the tickets written)
 	r.restoreInPass = !publish && st.nWaves > 0;
@@ -826,12 +826,12 @@ int cuba_hip_solver::optimizeDeviceDecision(int niter, double* chi2Out)
 // every launch of a trial batched (one stream for all graphs): the standard launch sequence only
 bool cuba_hip_solver::fullyBatchable() const
 {
-	return batchable() && st.nBig == 0 && st.nDiagProd == 0 && st.nOd > 0 && st.nWaves > 0 && redParts.empty() && !poseFactors();
+	return batchable() && st.nBig == 0 && st.nDiagProd == 0 && st.nOd > 0 && st.nWaves > 0 && redParts.empty() && !factors();
 }
 
 bool cuba_hip_solver::batchable() const
 {
-	return !profile && partHi < 0 && Pf > 0 && Lf > 0 && E > 0 && trial_tail_parts(g, st, poseFactorParts()) <= d_parts.size() && batch_kernel_class(g, sys) >= 0;
+	return !profile && partHi < 0 && Pf > 0 && Lf > 0 && E > 0 && trial_tail_parts(g, st, factorParts()) <= d_parts.size() && batch_kernel_class(g, sys) >= 0;
 }
 
 // The overlapped coarse inversions a batch's handles decided on in this trial (solveBegin, `regular` schedule), enqueued together on
@@ -1169,7 +1169,7 @@ int cuba_hip_solver::optimize(int niter, double* chi2Out)
 	lap("optimize: structure ready");
 	// the default: the decision of every trial on the device, the trial's tail fused into one pass over the edges.  The host loop below
 	// serves the profiled run (every stage synchronises), landmark partitions (the sums need the other ranks) and the degenerate graphs.
-	if (!profile && partHi < 0 && Pf > 0 && Lf > 0 && E > 0 && trial_tail_parts(g, st, poseFactorParts()) <= d_parts.size())
+	if (!profile && partHi < 0 && Pf > 0 && Lf > 0 && E > 0 && trial_tail_parts(g, st, factorParts()) <= d_parts.size())
 		return optimizeDeviceDecision(niter, chi2Out);
 	coarseValid = false;          // a new LM run starts from a new lambda_0: never reuse the coarse inverse across runs
 	startRunHistory();
@@ -1227,7 +1227,7 @@ int cuba_hip_solver::optimize(int niter, double* chi2Out)
 
 void cuba_hip_solver::enqueueEvaluate(double lam, bool withScale)
 {
-	launch_residual_chi2(g, d_parts.data(), slotsDev, nullptr, stream, poseFactors());
+	launch_residual_chi2(g, d_parts.data(), slotsDev, nullptr, stream, factors());
 	if (withScale) launch_pose_scale(g, sys, lam, slotsDev + 3 * NSLOT, stream);
 	launch_pcg_report(sys, stream); noteReport();       // ticket behind the results (which the kernels wrote into the mapped host block)
 }

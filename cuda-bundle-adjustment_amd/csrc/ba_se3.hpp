@@ -1,5 +1,5 @@
 // ba_se3.hpp -- SE(3) logarithm and inverse left Jacobian in the [omega, upsilon] tangent of the solver's pose update T <- exp(d) T
-// (DESIGN.md section 7c): shared by the pose priors and the relative-pose edges (ba_posefactor.hip).
+// (DESIGN.md section 7c): shared by the pose priors and the relative-pose edges (ba_factor.hip).
 #pragma once
 
 #include "ba_kernels.hpp"

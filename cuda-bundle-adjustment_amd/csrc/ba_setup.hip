@@ -31,7 +31,7 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 	if (sizeof(Scalar) == 4 && Lt_ >= (1 << 23)) throw ArgError{ "fp32 build: at most 2^23 - 1 landmarks" };
 	if ((Pt_ && (!q || !t || !cam)) || (Lt_ && !Xw) || (E_ && (!ep || !el || !edim || !meas || !omega))) throw ArgError{ "null array" };
 	const auto t0 = Clock::now();
-	clearPoseFactors();           // (they name poses of the previous graph; need() rebuilds a kept structure unless the same pairs come back)
+	clearFactors();           // (they name poses of the previous graph; need() rebuilds a kept structure unless the same pairs come back)
 	static const bool noCache = std::getenv("CUBA_HIP_NO_STRUCTURE_CACHE") != nullptr;   // A/B knob for set-up timings
 	const bool sameCounts = !noCache && !ranged && haveStructure && partHi < 0 && Pt == Pt_ && Pf == Pf_ && Lt == Lt_ && Lf == Lf_ && E == E_;
 	// the very same index arrays as in the previous call (re-initialisation of an unchanged graph): the sort, the

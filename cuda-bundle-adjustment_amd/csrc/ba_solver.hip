@@ -974,7 +974,7 @@ int cuba_hip_evaluate_device(cuba_hip_solver* s, double lambda, int with_scale, 
 		s->need();
 		if (!device_scalars3) throw ArgError{ "null output" };
 		s->d_eval.resize(4);
-		launch_residual_chi2(s->g, s->d_parts.data(), s->slotsDev, nullptr, s->stream, s->poseFactors());
+		launch_residual_chi2(s->g, s->d_parts.data(), s->slotsDev, nullptr, s->stream, s->factors());
 		if (with_scale) launch_pose_scale(s->g, s->sys, lambda, s->slotsDev + 3 * NSLOT, s->stream);
 		launch_collect_eval(s->sys, s->d_eval.data(), s->stream);
 		*device_scalars3 = s->d_eval.data();

@@ -130,30 +130,31 @@ int run_covariance_pairs(const SparseChol& d, const SparseCholPlan& plan, const 
 }  // namespace cubahip_host
 using namespace cubahip_host;
 
-// one kind of pose factor (pose priors, relative-pose edges) as a handle keeps it: cuba_hip_solver, ba_posefactor.hip
+// one kind of factor as a handle keeps it (cuba_hip_solver, ba_factor.hip): what the kinds have in common, then each kind's values in the
+// caller's numbering
+struct FactorSet
+{
+	std::vector<int> kind; std::vector<double> delta;      // [n] robust kernels in the caller's numbering
+	std::vector<int> order;          // sorted position -> caller's index (set by the upload)
+	bool uploaded = false;
+	int64_t structure = -1;          // cntStructureBuilds at the upload (the kinds whose device copy depends on the structure)
+	DevBuf<int> d_ints; DevBuf<Scalar> d_vals, d_chi;
+	void clear() { kind.clear(); delta.clear(); order.clear(); uploaded = false; }
+};
+// pose priors, relative-pose edges; kind / delta empty: no factor has a kernel
 struct PoseFactorValues { std::vector<int> pi, pj; std::vector<double> q, t, info; };      // [n] poses (pj: edges only), [4 n], [3 n], [36 n]
-struct PoseFactorSet
+struct PoseFactorSet : FactorSet
 {
 	PoseFactorValues v;
-	std::vector<int> kind; std::vector<double> delta;      // [n] robust kernels in the caller's numbering; empty: no factor has one
-	std::vector<int> order;          // sorted position -> caller's index (set by the upload)
-	bool uploaded = false;
-	DevBuf<int> d_ints; DevBuf<Scalar> d_vals, d_chi;
 	int n() const { return (int)v.pi.size(); }
+	void clear() { v = PoseFactorValues(); FactorSet::clear(); }
 };
-
-// the landmark position priors as a handle keeps them (cuba_hip_solver, ba_lmfactor.hip): the caller's set in the caller's numbering, the
-// information as its symmetrised upper triangle, every prior with a kernel (kind 0, delta 1: none)
-struct LandmarkPriorSet
+// landmark position priors: the information as its symmetrised upper triangle, every prior with a kernel (kind 0, delta 1: none)
+struct LandmarkPriorSet : FactorSet
 {
 	std::vector<int> lm; std::vector<double> xyz, info;      // [n], [3 n], [6 n]
-	std::vector<int> kind; std::vector<double> delta;        // [n]
-	std::vector<int> order;          // sorted position -> caller's index (set by the upload)
-	bool uploaded = false;
-	int64_t structure = -1;          // cntStructureBuilds at the upload
-	DevBuf<int> d_ints; DevBuf<Scalar> d_vals, d_chi;
 	int n() const { return (int)lm.size(); }
-	void clear() { lm.clear(); xyz.clear(); info.clear(); kind.clear(); delta.clear(); order.clear(); uploaded = false; }
+	void clear() { lm.clear(); xyz.clear(); info.clear(); FactorSet::clear(); }
 };
 
 struct cuba_hip_solver;
@@ -597,49 +598,44 @@ struct cuba_hip_solver
 		if (!haveGraph) throw StateError{ "set_graph must be called first" };
 		if (haveStructure && h_relPairs != structRelPairs) haveStructure = false;      // (the relative-pose pairs are part of the topology)
 		buildStructure(); finishValues(); g.rk[0] = rk[0]; g.rk[1] = rk[1]; st.mixed = mixedPrecision ? 1 : 0;
-		uploadPoseFactors();
-		uploadLandmarkPriors();
+		uploadFactors();
 	}
 
-	// The pose factors (ba_posefactor.hip): SE(3) pose priors (cuba_hip_set_pose_priors) and relative-pose edges
-	// (cuba_hip_set_relative_pose_edges).  Either set is kept as the caller gave it, in its own numbering (quaternions normalised,
+	// The factors besides the reprojection edges (ba_factor.hip).  On the poses: SE(3) pose priors (cuba_hip_set_pose_priors) and relative-pose
+	// edges (cuba_hip_set_relative_pose_edges).  Either set is kept as the caller gave it, in its own numbering (quaternions normalised,
 	// information symmetrised), with a device copy in the internal pose order that need() makes: the priors' once the pose order is known and
 	// again whenever that order changes; the edges' (their blocks are looked up in the pattern) with every structure; either again after
-	// cuba_hip_set_pose_factor_robust_kernels, whose kinds and deltas travel with the values.  No factors:
-	// poseFactors() is null, nothing of it is launched, no extra seed enters the pattern build, and every launch and kernel argument is as
+	// cuba_hip_set_pose_factor_robust_kernels, whose kinds and deltas travel with the values.
+	// On the landmarks: position priors (cuba_hip_set_landmark_priors), kept as the caller gave them, with a device copy (pf.lmp) in the
+	// internal landmark order that need() makes once that order is known and again with every structure (a change of the landmark order
+	// rebuilds it).  The landmark pass linearises them -- linearize() hands pf.lmp to it --, the chi2 sums take them as one more kind.
+	// No factors of any kind: factors() is null, nothing of it is launched, no extra seed enters the pattern build, and every launch and kernel argument is as
 	// without this feature.
 	PoseFactorSet priorSet, relSet;
-	DevicePoseFactors pf;
-	const DevicePoseFactors* poseFactors() const { return priorSet.n() + relSet.n() + lmPriorSet.n() > 0 ? &pf : nullptr; }
-	int poseFactorParts() const { return pose_factor_chi2_parts(poseFactors()); }      // chi2 partials that follow the reprojection edges'
-	void clearPoseFactors()
+	LandmarkPriorSet lmPriorSet;
+	DeviceFactors pf;
+	const DeviceFactors* factors() const { return priorSet.n() + relSet.n() + lmPriorSet.n() > 0 ? &pf : nullptr; }
+	int factorParts() const { return factor_chi2_parts(factors()); }      // chi2 partials that follow the reprojection edges'
+	void clearFactors()
 	{
-		for (PoseFactorSet* set : { &priorSet, &relSet }) { set->v = PoseFactorValues(); set->kind.clear(); set->delta.clear(); set->order.clear(); set->uploaded = false; }
-		lmPriorSet.clear();
-		h_relPairs.clear(); pf = DevicePoseFactors();
+		priorSet.clear(); relSet.clear(); lmPriorSet.clear();
+		h_relPairs.clear(); pf = DeviceFactors();
 	}
 	// the run-to-run memories that the values of the system feed (option "heuristics"): dropped by a change of the factors as by a new graph
 	void forgetRunMemories() { firstInvValid = false; firstInvPending = false; prevRunIters.clear(); runIters.clear(); firstSolveIters = 0; }
-	void uploadPoseFactors();
+	void uploadFactors();
 	int internalPose(int p) const { return p < Pf && reorderActive ? poseNewOfOld[p] : p; }      // of a pose in the caller's numbering
 	void setPosePriors(int n, const int32_t* pose, const double* q, const double* t, const double* info);
 	void priorChiSquares(double* out);
 	void setRelativePoseEdges(int n, const int32_t* pi, const int32_t* pj, const double* q, const double* t, const double* info);
 	void relativePoseChiSquares(double* out);
 	void setPoseFactorRobustKernels(int factorType, int n, const int32_t* kind, const double* delta);
-	// Landmark position priors (ba_lmfactor.hip; cuba_hip_set_landmark_priors): kept as the caller gave them, with a device copy (pf.lmp) in the
-	// internal landmark order that need() makes once that order is known and again with every structure (a change of the landmark order
-	// rebuilds it).  The landmark pass linearises them -- linearize() hands pf.lmp to it --, the chi2 sums take them as one more kind of
-	// factor.  No such priors: nothing of this is launched or passed.
-	LandmarkPriorSet lmPriorSet;
-	const DeviceLandmarkPriors* landmarkPriors() const { return lmPriorSet.n() > 0 ? &pf.lmp : nullptr; }
-	void uploadLandmarkPriors();
+	const DeviceLandmarkPriors* landmarkPriors() const { return lmPriorSet.n() > 0 ? &pf.lmp : nullptr; }      // (null: nothing of them is launched or passed)
 	void setLandmarkPriors(int n, const int32_t* landmark, const double* xyz, const double* info, const int32_t* kind, const double* delta);
 	void landmarkPriorChiSquares(double* out);
 	// the edges' distinct free-free pairs (sorted keys i << 32 | j, i < j, caller's numbering) and the pairs the current structure was seeded
 	// with: every such pair owns a block of the reduced matrix, so need() rebuilds the structure exactly when the two sets differ
 	std::vector<uint64_t> h_relPairs, structRelPairs;
-	int64_t relStructure = -1;           // cntStructureBuilds at the edges' upload
 	int64_t cntStructureBuilds = 0;      // structures published on this handle (never reset)
 	std::vector<uint64_t> h_relSeeds;    // the pairs as the last pattern build took them
 	DevBuf<int> d_relSeedFlag, d_relSeedScan; DevBuf<uint64_t> d_relSeeds; DevBuf<Scalar> d_relRec;

@@ -91,6 +91,42 @@ private:
 	std::vector<T*> items_;
 };
 
+// one kind of factor (cuba::PosePrior, cuba::RelativePoseEdge, cuba::LandmarkPrior) as an object keeps it
+template <class F>
+struct FactorList
+{
+	std::vector<F*> items, uploaded;      // in the caller's order; the set the last initialize() handed to the device
+	std::map<const F*, double> chi;       // per object of `uploaded`, from the last optimize()
+	bool onDevice = false, dirty = false;
+	void add(F* f) { if (std::find(items.begin(), items.end(), f) == items.end()) items.push_back(f); }
+	void remove(F* f) { items.erase(std::remove(items.begin(), items.end(), f), items.end()); }
+	template <class Pred> void removeIf(Pred&& pred) { items.erase(std::remove_if(items.begin(), items.end(), pred), items.end()); }
+	double chiSquared(const F* f) const
+	{
+		const auto it = chi.find(f);
+		return it == chi.end() ? 0.0 : it->second;
+	}
+	// an upload's first and last step; false: nothing to send (sent already, or no such factors now nor at the last initialize(), which
+	// would have to be cleared on the device)
+	bool beginUpload()
+	{
+		if (!dirty) return false;
+		dirty = false;
+		chi.clear();
+		uploaded.clear();
+		return !items.empty() || onDevice;
+	}
+	void endUpload() { onDevice = !items.empty(); uploaded = items; }
+	// after optimize(): read(out[uploaded.size()]) fetches the chi2 of the uploaded set
+	template <class Read> void readChi(Read&& read)
+	{
+		if (uploaded.empty()) return;
+		std::vector<double> c(uploaded.size());
+		read(c.data());
+		for (size_t k = 0; k < c.size(); k++) chi[uploaded[k]] = c[k];
+	}
+};
+
 class HipBundleAdjustment final : public CudaBundleAdjustment
 {
 public:
@@ -126,8 +162,8 @@ public:
 		if (it == poses_.end()) return;
 		const std::vector<BaseEdge*> incident(it->second->edges.begin(), it->second->edges.end());
 		for (BaseEdge* e : incident) removeEdge(e);
-		priors_.erase(std::remove_if(priors_.begin(), priors_.end(), [&](const PosePrior* p) { return p->vertex == it->second; }), priors_.end());
-		relEdges_.erase(std::remove_if(relEdges_.begin(), relEdges_.end(), [&](const RelativePoseEdge* e) { return e->vertexI == it->second || e->vertexJ == it->second; }), relEdges_.end());
+		priors_.removeIf([&](const PosePrior* p) { return p->vertex == it->second; });
+		relEdges_.removeIf([&](const RelativePoseEdge* e) { return e->vertexI == it->second || e->vertexJ == it->second; });
 		poses_.erase(it);
 		posesDirty_ = true;
 	}
@@ -138,7 +174,7 @@ public:
 		if (it == landmarks_.end()) return;
 		const std::vector<BaseEdge*> incident(it->second->edges.begin(), it->second->edges.end());
 		for (BaseEdge* e : incident) removeEdge(e);
-		lmPriors_.erase(std::remove_if(lmPriors_.begin(), lmPriors_.end(), [&](const LandmarkPrior* p) { return p->vertex == it->second; }), lmPriors_.end());
+		lmPriors_.removeIf([&](const LandmarkPrior* p) { return p->vertex == it->second; });
 		landmarks_.erase(it);
 		landmarksDirty_ = true;
 	}
@@ -168,9 +204,7 @@ public:
 	void initialize() override
 	{
 		covPoseIndex_.clear(); covLmIndex_.clear();          // (marginal covariances describe the graph they were computed on)
-		priorsDirty_ = true;                                 // (the priors as they stand now go to the device with the next solve)
-		relDirty_ = true;                                    // (so do the relative-pose edges)
-		lmPriorsDirty_ = true;                               // (and the landmark priors)
+		priors_.dirty = relEdges_.dirty = lmPriors_.dirty = true;      // (the factors as they stand now go to the device with the next solve)
 		poseIdx_.clear();                                    // (the factors' pose index: rebuilt below from the poses active now)
 		const auto t0 = std::chrono::steady_clock::now();
 		static const bool dbg = std::getenv("CUBA_HIP_DEBUG") != nullptr;
@@ -354,13 +388,12 @@ public:
 				"cuba_hip_set_graph_begin");
 			// (an upload clears the handle's relative-pose edges; their pose pairs are part of the block pattern, so they go up before the
 			// structure analysis: an unchanged pair set then keeps the structure of the previous initialize())
-			relOnDevice_ = false; relDirty_ = true;
+			relEdges_.onDevice = false; relEdges_.dirty = true;
 			uploadRelativePoseEdges();
 			check(cuba_hip_build_structure(solver_), "cuba_hip_build_structure");
 			check(cuba_hip_set_graph_end(solver_), "cuba_hip_set_graph_end");
 			graphDirty_ = false;
-			priorsDirty_ = true;          // (an upload clears the handle's priors)
-			lmPriorsDirty_ = true;
+			priors_.dirty = lmPriors_.dirty = true;          // (an upload clears the handle's priors)
 			uploadedOnce_ = true; edgesChangedSinceUpload_ = valuesChangedSinceUpload_ = false;       // from here on the device holds exactly these edges and values
 			(void)cuba_hip_get_counter(solver_, "graph_uploads", &uploadGeneration_);
 		}
@@ -370,7 +403,11 @@ public:
 		uploadLandmarkPriors();
 	}
 
-	// ---- pose factors (extensions: cuba::addPosePrior, cuba::addRelativePoseEdge) --------------------
+	// ---- factors (extensions: cuba::addPosePrior, cuba::addRelativePoseEdge, cuba::addLandmarkPrior) --
+	// (public: the extension functions below remove and look up through them)
+	FactorList<PosePrior> priors_;
+	FactorList<RelativePoseEdge> relEdges_;
+	FactorList<LandmarkPrior> lmPriors_;
 	// index of a factor's vertex among the active poses (the map is built with the first factor of an initialize()); `refusal`: the message
 	// for a vertex that is not part of the graph
 	int32_t factorPose(const PoseVertex* v, const char* refusal)
@@ -395,120 +432,90 @@ public:
 		}
 		return a;
 	}
-	// the factors' robust kernels follow the set they belong to (a set without any: nothing is sent, the handle has none after the upload)
-	template <class F> void uploadFactorKernels(int factorType, const std::vector<F*>& factors)
+	// kind | delta of a set of factors as the C ABI takes them; any: a factor has a kernel
+	struct FactorKernels { std::vector<int32_t> kind; std::vector<double> delta; bool any = false; };
+	template <class F> static FactorKernels packKernels(const std::vector<F*>& factors)
 	{
 		const size_t n = factors.size();
-		std::vector<int32_t> kind(n);
-		std::vector<double> delta(n);
-		bool any = false;
+		FactorKernels r{ std::vector<int32_t>(n), std::vector<double>(n) };
 		for (size_t k = 0; k < n; k++)
 		{
-			kind[k] = static_cast<int32_t>(factors[k]->kernel); delta[k] = factors[k]->delta;
-			any = any || factors[k]->kernel != PoseFactorKernel::NONE;
+			r.kind[k] = static_cast<int32_t>(factors[k]->kernel); r.delta[k] = factors[k]->delta;
+			r.any = r.any || factors[k]->kernel != PoseFactorKernel::NONE;
 		}
-		if (any) check(cuba_hip_set_pose_factor_robust_kernels(solver_, factorType, (int)n, kind.data(), delta.data()), "cuba_hip_set_pose_factor_robust_kernels");
+		return r;
+	}
+	// the pose factors' robust kernels follow the set they belong to (a set without any: nothing is sent, the handle has none after the upload)
+	template <class F> void uploadFactorKernels(int factorType, const std::vector<F*>& factors)
+	{
+		const FactorKernels r = packKernels(factors);
+		if (r.any) check(cuba_hip_set_pose_factor_robust_kernels(solver_, factorType, (int)factors.size(), r.kind.data(), r.delta.data()), "cuba_hip_set_pose_factor_robust_kernels");
 	}
 
 	void addRelativePoseEdge(RelativePoseEdge* e)
 	{
 		if (!e || !e->vertexI || !e->vertexJ || e->vertexI == e->vertexJ) throw std::invalid_argument("cuba::addRelativePoseEdge: an edge needs two different pose vertices");
-		if (std::find(relEdges_.begin(), relEdges_.end(), e) == relEdges_.end()) relEdges_.push_back(e);
+		relEdges_.add(e);
 	}
-	void removeRelativePoseEdge(RelativePoseEdge* e) { relEdges_.erase(std::remove(relEdges_.begin(), relEdges_.end(), e), relEdges_.end()); }
-	double relativePoseChiSquared(const RelativePoseEdge* e) const
-	{
-		const auto it = relChi_.find(e);
-		return it == relChi_.end() ? 0.0 : it->second;
-	}
-	// (only when such edges exist -- or existed at the last initialize(), which then clears them on the device)
 	void uploadRelativePoseEdges()
 	{
-		if (!relDirty_) return;
-		relDirty_ = false;
-		relChi_.clear();
-		uploadedRel_.clear();
-		if (relEdges_.empty() && !relOnDevice_) return;
-		const size_t n = relEdges_.size();
+		if (!relEdges_.beginUpload()) return;
+		const std::vector<RelativePoseEdge*>& edges = relEdges_.items;
+		const size_t n = edges.size();
 		std::vector<int32_t> pi(n), pj(n);
 		const char* refusal = "cuba::addRelativePoseEdge: a vertex of a relative-pose edge is not part of the graph";
-		for (size_t k = 0; k < n; k++) { pi[k] = factorPose(relEdges_[k]->vertexI, refusal); pj[k] = factorPose(relEdges_[k]->vertexJ, refusal); }
-		const FactorArrays a = packFactors(relEdges_);
+		for (size_t k = 0; k < n; k++) { pi[k] = factorPose(edges[k]->vertexI, refusal); pj[k] = factorPose(edges[k]->vertexJ, refusal); }
+		const FactorArrays a = packFactors(edges);
 		check(cuba_hip_set_relative_pose_edges(solver_, (int)n, pi.data(), pj.data(), a.q.data(), a.t.data(), a.info.data()), "cuba_hip_set_relative_pose_edges");
-		uploadFactorKernels(1, relEdges_);
-		relOnDevice_ = n > 0;
-		uploadedRel_ = relEdges_;
+		uploadFactorKernels(1, edges);
+		relEdges_.endUpload();
 	}
 
 	void addPosePrior(PosePrior* p)
 	{
 		if (!p || !p->vertex) throw std::invalid_argument("cuba::addPosePrior: a prior needs a pose vertex");
-		if (std::find(priors_.begin(), priors_.end(), p) == priors_.end()) priors_.push_back(p);
+		priors_.add(p);
 	}
-	void removePosePrior(PosePrior* p) { priors_.erase(std::remove(priors_.begin(), priors_.end(), p), priors_.end()); }
-	double priorChiSquared(const PosePrior* p) const
-	{
-		const auto it = priorChi_.find(p);
-		return it == priorChi_.end() ? 0.0 : it->second;
-	}
-	// (only when priors exist -- or existed at the last initialize(), which then clears them on the device)
 	void uploadPriors()
 	{
-		if (!priorsDirty_) return;
-		priorsDirty_ = false;
-		priorChi_.clear();
-		uploadedPriors_.clear();
-		if (priors_.empty() && !priorsOnDevice_) return;
-		const size_t n = priors_.size();
+		if (!priors_.beginUpload()) return;
+		const std::vector<PosePrior*>& priors = priors_.items;
+		const size_t n = priors.size();
 		std::vector<int32_t> pose(n);
-		for (size_t k = 0; k < n; k++) pose[k] = factorPose(priors_[k]->vertex, "cuba::addPosePrior: the vertex of a prior is not part of the graph");
-		const FactorArrays a = packFactors(priors_);
+		for (size_t k = 0; k < n; k++) pose[k] = factorPose(priors[k]->vertex, "cuba::addPosePrior: the vertex of a prior is not part of the graph");
+		const FactorArrays a = packFactors(priors);
 		check(cuba_hip_set_pose_priors(solver_, (int)n, pose.data(), a.q.data(), a.t.data(), a.info.data()), "cuba_hip_set_pose_priors");
-		uploadFactorKernels(0, priors_);
-		priorsOnDevice_ = n > 0;
-		uploadedPriors_ = priors_;
+		uploadFactorKernels(0, priors);
+		priors_.endUpload();
 	}
 
 	// ---- landmark position priors (extension: cuba::addLandmarkPrior) --------------------------------
 	void addLandmarkPrior(LandmarkPrior* p)
 	{
 		if (!p || !p->vertex) throw std::invalid_argument("cuba::addLandmarkPrior: a prior needs a landmark vertex");
-		if (std::find(lmPriors_.begin(), lmPriors_.end(), p) == lmPriors_.end()) lmPriors_.push_back(p);
+		lmPriors_.add(p);
 	}
-	void removeLandmarkPrior(LandmarkPrior* p) { lmPriors_.erase(std::remove(lmPriors_.begin(), lmPriors_.end(), p), lmPriors_.end()); }
-	double landmarkPriorChiSquared(const LandmarkPrior* p) const
-	{
-		const auto it = lmPriorChi_.find(p);
-		return it == lmPriorChi_.end() ? 0.0 : it->second;
-	}
-	// (only when priors exist -- or existed at the last initialize(), which then clears them on the device)
 	void uploadLandmarkPriors()
 	{
-		if (!lmPriorsDirty_) return;
-		lmPriorsDirty_ = false;
-		lmPriorChi_.clear();
-		uploadedLmPriors_.clear();
-		if (lmPriors_.empty() && !lmPriorsOnDevice_) return;
-		const size_t n = lmPriors_.size();
+		if (!lmPriors_.beginUpload()) return;
+		const std::vector<LandmarkPrior*>& priors = lmPriors_.items;
+		const size_t n = priors.size();
 		std::map<const LandmarkVertex*, int32_t> lmIdx;
 		for (size_t i = 0; i < activeLandmarks_.size(); i++) lmIdx[activeLandmarks_[i]] = (int32_t)i;
-		std::vector<int32_t> lm(n), kind(n);
-		std::vector<double> xyz(3 * n), info(9 * n), delta(n);
-		bool any = false;
+		std::vector<int32_t> lm(n);
+		std::vector<double> xyz(3 * n), info(9 * n);
 		for (size_t k = 0; k < n; k++)
 		{
-			const auto it = lmIdx.find(lmPriors_[k]->vertex);
+			const auto it = lmIdx.find(priors[k]->vertex);
 			if (it == lmIdx.end()) throw std::invalid_argument("cuba::addLandmarkPrior: the vertex of a prior is not part of the graph");
 			lm[k] = it->second;
-			for (int i = 0; i < 3; i++) xyz[3 * k + i] = lmPriors_[k]->position.data()[i];
-			std::copy(lmPriors_[k]->information.begin(), lmPriors_[k]->information.end(), info.begin() + 9 * k);
-			kind[k] = static_cast<int32_t>(lmPriors_[k]->kernel); delta[k] = lmPriors_[k]->delta;
-			any = any || lmPriors_[k]->kernel != PoseFactorKernel::NONE;
+			for (int i = 0; i < 3; i++) xyz[3 * k + i] = priors[k]->position.data()[i];
+			std::copy(priors[k]->information.begin(), priors[k]->information.end(), info.begin() + 9 * k);
 		}
-		check(cuba_hip_set_landmark_priors(solver_, (int)n, lm.data(), xyz.data(), info.data(), any ? kind.data() : nullptr, any ? delta.data() : nullptr),
+		const FactorKernels r = packKernels(priors);
+		check(cuba_hip_set_landmark_priors(solver_, (int)n, lm.data(), xyz.data(), info.data(), r.any ? r.kind.data() : nullptr, r.any ? r.delta.data() : nullptr),
 			"cuba_hip_set_landmark_priors");
-		lmPriorsOnDevice_ = n > 0;
-		uploadedLmPriors_ = lmPriors_;
+		lmPriors_.endUpload();
 	}
 
 	// (optimize() in three steps, so that cuba::optimizeBatch can run the middle one for several objects at once)
@@ -587,24 +594,9 @@ public:
 			tl = now;
 		};
 		for (int i = 0; i < done; i++) stats_.push_back({ i, chi2[i] });
-		if (!uploadedPriors_.empty())
-		{
-			std::vector<double> pc(uploadedPriors_.size());
-			check(cuba_hip_prior_chi_squares(solver_, pc.data()), "cuba_hip_prior_chi_squares");
-			for (size_t k = 0; k < pc.size(); k++) priorChi_[uploadedPriors_[k]] = pc[k];
-		}
-		if (!uploadedLmPriors_.empty())
-		{
-			std::vector<double> pc(uploadedLmPriors_.size());
-			check(cuba_hip_landmark_prior_chi_squares(solver_, pc.data()), "cuba_hip_landmark_prior_chi_squares");
-			for (size_t k = 0; k < pc.size(); k++) lmPriorChi_[uploadedLmPriors_[k]] = pc[k];
-		}
-		if (!uploadedRel_.empty())
-		{
-			std::vector<double> rc(uploadedRel_.size());
-			check(cuba_hip_relative_pose_chi_squares(solver_, rc.data()), "cuba_hip_relative_pose_chi_squares");
-			for (size_t k = 0; k < rc.size(); k++) relChi_[uploadedRel_[k]] = rc[k];
-		}
+		priors_.readChi([&](double* c) { check(cuba_hip_prior_chi_squares(solver_, c), "cuba_hip_prior_chi_squares"); });
+		lmPriors_.readChi([&](double* c) { check(cuba_hip_landmark_prior_chi_squares(solver_, c), "cuba_hip_landmark_prior_chi_squares"); });
+		relEdges_.readChi([&](double* c) { check(cuba_hip_relative_pose_chi_squares(solver_, c), "cuba_hip_relative_pose_chi_squares"); });
 
 		// finalize (ref :512-526): estimates back into the caller's vertices
 		check(cuba_hip_get_solution(solver_, q_.data(), t_.data(), Xw_.data()), "cuba_hip_get_solution");
@@ -650,9 +642,9 @@ public:
 	{
 		covPoseIndex_.clear(); covLmIndex_.clear();
 		poses_.clear(); landmarks_.clear(); mono_.clear(); stereo_.clear(); stats_.clear();
-		priors_.clear(); priorChi_.clear();
-		relEdges_.clear(); relChi_.clear();
-		lmPriors_.clear(); lmPriorChi_.clear();
+		priors_.items.clear(); priors_.chi.clear();
+		relEdges_.items.clear(); relEdges_.chi.clear();
+		lmPriors_.items.clear(); lmPriors_.chi.clear();
 		posesDirty_ = landmarksDirty_ = edgesDirty_ = true;
 		initialized_ = false;
 	}
@@ -775,15 +767,6 @@ private:
 
 	// flattened problem (solver order)
 	std::vector<PoseVertex*> activePoses_;
-	std::vector<PosePrior*> priors_, uploadedPriors_;     // in the caller's order; the set the last initialize() handed to the device
-	bool priorsOnDevice_ = false, priorsDirty_ = false;
-	std::map<const PosePrior*, double> priorChi_;
-	std::vector<RelativePoseEdge*> relEdges_, uploadedRel_;   // as priors_ / uploadedPriors_
-	bool relOnDevice_ = false, relDirty_ = false;
-	std::map<const RelativePoseEdge*, double> relChi_;
-	std::vector<LandmarkPrior*> lmPriors_, uploadedLmPriors_;   // as priors_ / uploadedPriors_
-	bool lmPriorsOnDevice_ = false, lmPriorsDirty_ = false;
-	std::map<const LandmarkPrior*, double> lmPriorChi_;
 	std::map<const PoseVertex*, int32_t> poseIdx_;            // active pose -> solver index, for the factors of this initialize()
 	std::vector<LandmarkVertex*> activeLandmarks_;
 	std::vector<BaseEdge*> activeEdges_;
@@ -895,13 +878,13 @@ void addPosePrior(CudaBundleAdjustment* object, PosePrior* prior)
 void removePosePrior(CudaBundleAdjustment* object, PosePrior* prior)
 {
 	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (impl) impl->removePosePrior(prior);
+	if (impl) impl->priors_.remove(prior);
 }
 
 double priorChiSquared(const CudaBundleAdjustment* object, const PosePrior* prior)
 {
 	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
-	return impl ? impl->priorChiSquared(prior) : 0.0;
+	return impl ? impl->priors_.chiSquared(prior) : 0.0;
 }
 
 // Extension (g2o's unary XYZ prior edge): landmark position priors, effective at the next initialize() (cuba_hip_set_landmark_priors)
@@ -915,13 +898,13 @@ void addLandmarkPrior(CudaBundleAdjustment* object, LandmarkPrior* prior)
 void removeLandmarkPrior(CudaBundleAdjustment* object, LandmarkPrior* prior)
 {
 	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (impl) impl->removeLandmarkPrior(prior);
+	if (impl) impl->lmPriors_.remove(prior);
 }
 
 double landmarkPriorChiSquared(const CudaBundleAdjustment* object, const LandmarkPrior* prior)
 {
 	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
-	return impl ? impl->landmarkPriorChiSquared(prior) : 0.0;
+	return impl ? impl->lmPriors_.chiSquared(prior) : 0.0;
 }
 
 // Extension (g2o's binary SE(3) edge): relative-pose edges, effective at the next initialize() (cuba_hip_set_relative_pose_edges)
@@ -935,13 +918,13 @@ void addRelativePoseEdge(CudaBundleAdjustment* object, RelativePoseEdge* edge)
 void removeRelativePoseEdge(CudaBundleAdjustment* object, RelativePoseEdge* edge)
 {
 	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (impl) impl->removeRelativePoseEdge(edge);
+	if (impl) impl->relEdges_.remove(edge);
 }
 
 double relativePoseChiSquared(const CudaBundleAdjustment* object, const RelativePoseEdge* edge)
 {
 	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
-	return impl ? impl->relativePoseChiSquared(edge) : 0.0;
+	return impl ? impl->relEdges_.chiSquared(edge) : 0.0;
 }
 
 }  // namespace cuba

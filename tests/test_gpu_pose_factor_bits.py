@@ -1,4 +1,4 @@
-"""The bits of the pose-factor code (pose priors and relative-pose edges, csrc/ba_posefactor.hip) against tests/golden/pose_factors_bits.json:
+"""The bits of the pose-factor code (pose priors and relative-pose edges, csrc/ba_factor.hip) against tests/golden/pose_factors_bits.json:
 the assembled system, the objective, the per-factor chi2, LM trajectories (device-decision and host loop, both kinds of factors, each kind
 alone, a graph whose pose ids are shuffled) and the final state, on the fp64 and the fp32 library.  Every entry is recomputed by the
 fixture's own generator (tests/golden/make_golden_pose_factors.py: record()) and must be EQUAL to the recorded one: the tests against the
