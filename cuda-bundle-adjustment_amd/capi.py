@@ -129,6 +129,8 @@ def load_library(precision="f64"):
         "cuba_hip_set_pose_factor_robust_kernels": [H, C.c_int, C.c_int, _ip, _dp],
         "cuba_hip_set_landmark_priors": [H, C.c_int, _ip, _dp, _dp, _ip, _dp],
         "cuba_hip_landmark_prior_chi_squares": [H, _dp],
+        "cuba_hip_set_position_factors": [H, C.c_int, _ip, _dp, _dp, _dp, _ip, _dp],
+        "cuba_hip_position_factor_chi_squares": [H, _dp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -390,7 +392,7 @@ class HipSolver:
         landmark_range = (begin, end): cuba_hip_set_graph_partition -- the upload of one rank of a landmark partition, which sends the
         measurements and information of its own landmarks' edges only."""
         self.fp = fp
-        self._n_factors = {}            # (every upload clears the pose priors, the relative-pose edges and the landmark priors)
+        self._n_factors = {}            # (every upload clears the pose priors, the relative-pose edges, the landmark priors and the position factors)
         q, t, cam, Xw = (np.ascontiguousarray(a, dtype=np.float64) for a in (fp.q, fp.t, fp.cam, fp.Xw))
         eP = np.ascontiguousarray(fp.eP, dtype=np.int32)
         eL = np.ascontiguousarray(fp.eL, dtype=np.int32)
@@ -566,6 +568,32 @@ class HipSolver:
     def landmark_prior_chi_squares(self):
         """r^T Omega r of every landmark prior at the current estimate, in the order they were given (0 for priors on fixed landmarks)"""
         return self._factor_chi_squares("landmark_prior")
+
+    def set_position_factors(self, pose, position, info, lever_arm=None, kind=None, delta=None):
+        """Position factors on the poses (cuba_hip_set_position_factors; GNSS-style fixes), replacing the handle's set: pose[n] in the
+        solver numbering, the measured world positions position[n, 3], info[n, 3, 3] symmetric, lever_arm[n, 3] (the measured point in
+        the camera frame; None: the camera centre); kind[n] (0 none, 1 Huber, 2 Tukey, 3 Cauchy) and delta[n] together or not at all
+        (scalars broadcast).  An empty pose list clears the set."""
+        pose = np.ascontiguousarray(pose, dtype=np.int32).reshape(-1)
+        n = int(pose.size)
+        position = np.ascontiguousarray(position, dtype=np.float64).reshape(n, 3)
+        # (column-major 3 x 3 blocks: the transpose of the row-major reading)
+        info = np.ascontiguousarray(np.asarray(info, dtype=np.float64).reshape(n, 3, 3).transpose(0, 2, 1))
+        if lever_arm is not None:
+            lever_arm = np.ascontiguousarray(lever_arm, dtype=np.float64).reshape(n, 3)
+        if kind is not None:
+            kind = np.ascontiguousarray(np.full(n, kind) if np.ndim(kind) == 0 else kind, dtype=np.int32).reshape(-1)
+        if delta is not None:
+            delta = np.ascontiguousarray(np.full(n, delta) if np.ndim(delta) == 0 else delta, dtype=np.float64).reshape(-1)
+        if (kind is not None and kind.size != n) or (delta is not None and delta.size != n):
+            raise ValueError("kind / delta differ in length from the set")
+        self._ck(self.lib.cuba_hip_set_position_factors(self.h, n, pose.ctypes.data_as(_ip), _d(position), _d(lever_arm), _d(info),
+                                                        kind.ctypes.data_as(_ip) if kind is not None else None, _d(delta)))
+        self._n_factors["position_factor"] = n
+
+    def position_factor_chi_squares(self):
+        """r^T Omega r of every position factor at the current estimate, in the order they were given (0 for factors on fixed poses)"""
+        return self._factor_chi_squares("position_factor")
 
     def chi_squares_two_step(self):
         """cuba_hip_chi_squares_begin / _end (the C++ layer does its write-back between the two)"""

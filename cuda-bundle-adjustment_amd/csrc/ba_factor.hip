@@ -1,6 +1,6 @@
 // ba_factor.hip -- the factors besides the reprojection edges: terms rho(r^T Omega r) of the objective on the vertices alone, Omega a full
 // symmetric information.  Two kinds on the SE(3) poses, r in the [omega, upsilon] tangent of the solver's left-multiplicative update
-// T <- exp(d) T (pose_exp_update), Omega 6 x 6, and one on the landmarks:
+// T <- exp(d) T (pose_exp_update), Omega 6 x 6, one on the landmarks, and one that ties a pose to a world position:
 //
 //   pose priors (cuba_hip_set_pose_priors): unary, r = log(T Tbar^-1), linearised with the exact derivative dr/dd =
 //     J_l(r)^-1.  A prior touches the diagonal 6 x 6 block of its pose in the reduced matrix and the pose's entries of bp / bsc only.
@@ -15,11 +15,21 @@
 //     3 x 3 inverse, the pose and block passes, back-substitution, the gain ratio's scale, the covariances -- reads them from sys.lm_sys.
 //     So these priors are linearised INSIDE that pass (ba_device.hpp: add_landmark_priors, in kernel instantiations that only a handle
 //     with such priors launches); this file holds their chi2 kernel and their host side.
+//   position factors (cuba_hip_set_position_factors; section 7g): unary on the poses, r = R^T (a - t) - z: the world position of the point a
+//     of the camera frame (the lever arm of a GNSS antenna, a prism, a marker; zero: the camera centre) against a measured world position
+//     z, Omega 3 x 3.  r lives in a vector space, so dr/dd = [R^T [a]x | -R^T] (3 x 6, d = [omega; upsilon]) is exact to first order without a
+//     J_l.  A factor touches the diagonal block of its pose and the pose's entries of bp / bsc only, as a pose prior.
 //
 // A factor may carry a robust kernel (cuba_hip_set_pose_factor_robust_kernels; section 7e): with e = r^T Omega r its term is rho(e) and its
 // linearisation takes w Omega, w = rho'(e), for Omega (no second-order term, as the reprojection edges).  The four kernels that see a
 // residual are templates on ROBUST; a set without kernels has null kind / delta arrays and runs the `false` instantiations, which hold
 // nothing of this.  A landmark prior always carries a kind (none = 0) and comes with its kernel in one call.
+//
+// Order: the pose priors, the position factors and the relative-pose edges all add to the diagonal blocks, bp and bsc that the pose and
+// Schur passes stored, by read-modify-write.  launch_pose_factor_linearize issues them in one stream in this order -- priors, position
+// factors, the edges' records, the edges' gather -- and that order is part of the result (floating-point sums do not commute): a handle's
+// bits depend on it, and a new kind goes BEHIND the ones a handle may already combine, never between two of them.  (The position factors
+// sit between the priors and the edges: no handle could hold them before, so no existing sum changes.)
 //
 // The kinds keep kernels of their own (a prior is not run as a one-ended edge: its sums would be taken in another order); they share the
 // device helpers below, the host-side validation, sorting and read-back -- the two pose kinds also packing and upload -- and one interface
@@ -36,11 +46,16 @@
 //                              or an entry of a pose's diagonal block (upper triangle) / of bp and (mode 1) bsc, summed over the pose's
 //                              edges in the caller's order -- one writer per number, fixed order, no atomics; behind the Schur pass and the
 //                              priors' launch
+//   position_linearize_kernel  lane = free pose with position factors: the rotation matrix once, then the pose's factors in the caller's order,
+//                              J^T (Omega J) (21 numbers) and J^T Omega r (6) summed in registers, one read-modify-write of the diagonal
+//                              block's upper triangle, bp and (mode 1) bsc -- one writer per number; behind the priors' launch, ahead of the
+//                              edges' launches
 //   prior_chi2_kernel,         lane = factor: r^T Omega r at the current estimate into the per-factor output and (rho of it) into per-workgroup
 //   relpose_chi2_kernel,       partials that the caller sums together with the reprojection edges' partials (fixed order, no atomics)
-//   landmark_prior_chi2_kernel
+//   landmark_prior_chi2_kernel,
+//   position_chi2_kernel
 //
-// Host side: the caller's three sets (validated, kept in the caller's numbering), the edges' pair set (part of the topology) and the upload
+// Host side: the caller's four sets (validated, kept in the caller's numbering), the edges' pair set (part of the topology) and the upload
 // of every set in the internal pose / landmark order.
 #include "ba_solver.hpp"
 #include "ba_device.hpp"
@@ -50,6 +65,7 @@ namespace cubahip
 {
 
 constexpr int PRIOR_LIN_BLOCK = 64;
+constexpr int POS_LIN_BLOCK = 64;
 constexpr int REL_LIN_BLOCK = 64;
 constexpr int REL_GATHER_BLOCK = 256;
 constexpr int CHI_BLOCK = 256;
@@ -406,6 +422,108 @@ __global__ __launch_bounds__(CHI_BLOCK) void landmark_prior_chi2_kernel(DeviceGr
 	chi2_partial(acc, parts);
 }
 
+// ---- position factors -------------------------------------------------------------------------------------------------------------
+
+// r = R^T (a - t) - z of factor k at the pose [R | t] (R row-major in Rm), Or = Omega r; returns r^T Omega r
+__device__ __forceinline__ Scalar position_residual(const DevicePositionFactors& pp, int k, const Scalar Rm[3][3], const Scalar t[3], Scalar r[3], Scalar Or[3])
+{
+	const Scalar* a = pp.arm + 3 * (size_t)k;
+	const Scalar* z = pp.z + 3 * (size_t)k;
+	const Scalar* O = pp.info + 9 * (size_t)k;
+	const Scalar d[3] = { a[0] - t[0], a[1] - t[1], a[2] - t[2] };
+#pragma unroll
+	for (int i = 0; i < 3; i++) r[i] = (Rm[0][i] * d[0] + Rm[1][i] * d[1] + Rm[2][i] * d[2]) - z[i];
+#pragma unroll
+	for (int i = 0; i < 3; i++) Or[i] = O[i] * r[0] + O[3 + i] * r[1] + O[6 + i] * r[2];
+	return r[0] * Or[0] + r[1] * Or[1] + r[2] * Or[2];
+}
+
+template <bool ROBUST>
+__global__ __launch_bounds__(POS_LIN_BLOCK) void position_linearize_kernel(DeviceGraph g, DeviceStructure st, DeviceSystem sys, DevicePositionFactors pp, int mode)
+{
+	const int i = blockIdx.x * POS_LIN_BLOCK + threadIdx.x;
+	if (i >= pp.nPoses) return;
+	const int ip = pp.pose_id[i];
+	Scalar q[4], t[3];
+	load_pose(g.q, g.t, ip, q, t);
+	const Rot3 R = quat_to_rot(q[0], q[1], q[2], q[3]);
+	Scalar H[21], gv[6];
+#pragma unroll
+	for (int k = 0; k < 21; k++) H[k] = 0;
+#pragma unroll
+	for (int k = 0; k < 6; k++) gv[k] = 0;
+	const int k1 = pp.pose_ptr[i + 1];
+	for (int k = pp.pose_ptr[i]; k < k1; k++)
+	{
+		Scalar r[3], Or[3];
+		const Scalar e = position_residual(pp, k, R.m, t, r, Or);
+		Scalar w = 1;
+		if constexpr (ROBUST) w = factor_weight(pp.rk_kind[k], pp.rk_delta[k], e);
+		// J = [R^T [a]x | -R^T] (3 x 6)
+		const Scalar* a = pp.arm + 3 * (size_t)k;
+		Scalar Ax[3][3], J[3][6];
+		hat3(a, Ax);
+#pragma unroll
+		for (int m = 0; m < 3; m++)
+#pragma unroll
+			for (int c = 0; c < 3; c++)
+			{
+				J[m][c] = R.m[0][m] * Ax[0][c] + R.m[1][m] * Ax[1][c] + R.m[2][m] * Ax[2][c];
+				J[m][3 + c] = -R.m[c][m];
+			}
+		const Scalar* O = pp.info + 9 * (size_t)k;
+		// H += J^T (Omega J), column by column (upper triangle, H[c (c + 1) / 2 + r] as the pose pass stores it); gv += J^T (Omega r)
+#pragma unroll
+		for (int c = 0; c < 6; c++)
+		{
+			Scalar oj[3];
+#pragma unroll
+			for (int x = 0; x < 3; x++) oj[x] = O[x] * J[0][c] + O[3 + x] * J[1][c] + O[6 + x] * J[2][c];
+#pragma unroll
+			for (int rr = 0; rr <= c; rr++)
+			{
+				const Scalar s = J[0][rr] * oj[0] + J[1][rr] * oj[1] + J[2][rr] * oj[2];
+				if constexpr (ROBUST) H[c * (c + 1) / 2 + rr] += w * s;
+				else H[c * (c + 1) / 2 + rr] += s;
+			}
+			const Scalar s = J[0][c] * Or[0] + J[1][c] * Or[1] + J[2][c] * Or[2];
+			if constexpr (ROBUST) gv[c] += w * s;
+			else gv[c] += s;
+		}
+	}
+	Scalar* blk = sys.hsc + 36 * (size_t)st.hsc_rowptr[ip];
+#pragma unroll
+	for (int c = 0; c < 6; c++)
+	{
+#pragma unroll
+		for (int rr = 0; rr <= c; rr++) blk[c * 6 + rr] += H[c * (c + 1) / 2 + rr];
+		sys.bp[6 * (size_t)ip + c] -= gv[c];
+		if (mode == 1) sys.bsc[6 * (size_t)ip + c] -= gv[c];
+	}
+}
+
+template <bool ROBUST>
+__global__ __launch_bounds__(CHI_BLOCK) void position_chi2_kernel(DeviceGraph g, DevicePositionFactors pp, Scalar* __restrict__ parts)
+{
+	Scalar acc = 0;
+	for (int k = blockIdx.x * CHI_BLOCK + threadIdx.x; k < pp.n; k += gridDim.x * CHI_BLOCK)
+	{
+		const int ip = pp.pose[k];
+		Scalar chi = 0;
+		if (ip < g.Pf)
+		{
+			Scalar q[4], t[3], r[3], Or[3];
+			load_pose(g.q, g.t, ip, q, t);
+			const Rot3 R = quat_to_rot(q[0], q[1], q[2], q[3]);
+			chi = position_residual(pp, k, R.m, t, r, Or);
+		}
+		pp.chi[k] = chi;
+		if constexpr (ROBUST) acc += factor_rho(pp.rk_kind[k], pp.rk_delta[k], chi);
+		else acc += chi;
+	}
+	chi2_partial(acc, parts);
+}
+
 // ---- launches ---------------------------------------------------------------------------------------------------------------------
 
 static void launch_prior_chi2(const DeviceGraph& g, const DevicePriors& pr, Scalar* parts, hipStream_t s)
@@ -431,13 +549,25 @@ static void launch_landmark_prior_chi2(const DeviceGraph& g, const DeviceLandmar
 	hipLaunchKernelGGL(landmark_prior_chi2_kernel, dim3(grid), dim3(CHI_BLOCK), 0, s, g, lp, parts);
 }
 
-int factor_chi2_parts(const DeviceFactors* pf) { return pf ? chi2_parts(pf->priors.n) + chi2_parts(pf->rel.n) + chi2_parts(pf->lmp.n) : 0; }
+static void launch_position_chi2(const DeviceGraph& g, const DevicePositionFactors& pp, Scalar* parts, hipStream_t s)
+{
+	const int grid = chi2_parts(pp.n);
+	if (grid <= 0) return;
+	if (pp.rk_kind) hipLaunchKernelGGL(position_chi2_kernel<true>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, pp, parts);
+	else hipLaunchKernelGGL(position_chi2_kernel<false>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, pp, parts);
+}
+
+int factor_chi2_parts(const DeviceFactors* pf)
+{
+	return pf ? chi2_parts(pf->priors.n) + chi2_parts(pf->rel.n) + chi2_parts(pf->lmp.n) + chi2_parts(pf->pos.n) : 0;
+}
 
 void launch_factor_chi2(const DeviceGraph& g, const DeviceFactors& pf, Scalar* parts, hipStream_t s)
 {
 	launch_prior_chi2(g, pf.priors, parts, s);
 	launch_relpose_chi2(g, pf.rel, parts + chi2_parts(pf.priors.n), s);
 	launch_landmark_prior_chi2(g, pf.lmp, parts + chi2_parts(pf.priors.n) + chi2_parts(pf.rel.n), s);
+	launch_position_chi2(g, pf.pos, parts + chi2_parts(pf.priors.n) + chi2_parts(pf.rel.n) + chi2_parts(pf.lmp.n), s);
 }
 
 void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DeviceFactors& pf, int mode, hipStream_t s)
@@ -448,6 +578,13 @@ void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& s
 		const dim3 grid((pr.nPoses + PRIOR_LIN_BLOCK - 1) / PRIOR_LIN_BLOCK);
 		if (pr.rk_kind) hipLaunchKernelGGL(prior_linearize_kernel<true>, grid, dim3(PRIOR_LIN_BLOCK), 0, s, g, st, sys, pr, mode);
 		else hipLaunchKernelGGL(prior_linearize_kernel<false>, grid, dim3(PRIOR_LIN_BLOCK), 0, s, g, st, sys, pr, mode);
+	}
+	const DevicePositionFactors& pp = pf.pos;
+	if (pp.nPoses > 0)
+	{
+		const dim3 grid((pp.nPoses + POS_LIN_BLOCK - 1) / POS_LIN_BLOCK);
+		if (pp.rk_kind) hipLaunchKernelGGL(position_linearize_kernel<true>, grid, dim3(POS_LIN_BLOCK), 0, s, g, st, sys, pp, mode);
+		else hipLaunchKernelGGL(position_linearize_kernel<false>, grid, dim3(POS_LIN_BLOCK), 0, s, g, st, sys, pp, mode);
 	}
 	const DeviceRelPoses& rp = pf.rel;
 	if (rp.nActive <= 0) return;
@@ -828,13 +965,101 @@ static void upload_landmark_priors(cuba_hip_solver& s)
 	set.uploaded = true; set.structure = s.cntStructureBuilds;
 }
 
-// (the pose priors depend on the pose order only -- a change of it marks them --, the edges' blocks and the landmark priors' order on the
-// structure)
+void cuba_hip_solver::setPositionFactors(int n, const int32_t* pose, const double* position, const double* leverArm, const double* info, const int32_t* kind,
+	const double* delta)
+{
+	if (!haveGraph) throw StateError{ "set_graph must be called first" };
+	if (n < 0) throw ArgError{ "negative position factor count" };
+	if (n > 0 && (partHi >= 0 || valuesPartial)) throw StateError{ "position factors are not available on a landmark-partitioned handle" };
+	if (n > 0 && E == 0) throw StateError{ "position factors need a graph with edges" };
+	if (n > 0 && (!pose || !position || !info)) throw ArgError{ "null position factor array" };
+	if (n > 0 && (kind == nullptr) != (delta == nullptr)) throw ArgError{ "position factor kernels: kind and delta come together" };
+	PositionFactorSet v;
+	v.pose.resize((size_t)n); v.z.resize((size_t)3 * n); v.arm.assign((size_t)3 * n, 0.0); v.info.resize((size_t)9 * n);
+	bool any = false;
+	for (int k = 0; k < n; k++)
+	{
+		if (pose[k] < 0 || pose[k] >= Pt) throw ArgError{ "position factor: pose index out of range" };
+		v.pose[k] = pose[k];
+		for (int i = 0; i < 3; i++)
+		{
+			if (!std::isfinite(position[3 * (size_t)k + i])) throw ArgError{ "non-finite position factor position" };
+			v.z[3 * (size_t)k + i] = position[3 * (size_t)k + i];
+			if (!leverArm) continue;
+			if (!std::isfinite(leverArm[3 * (size_t)k + i])) throw ArgError{ "non-finite position factor lever arm" };
+			v.arm[3 * (size_t)k + i] = leverArm[3 * (size_t)k + i];
+		}
+		take_information<3>(info + 9 * (size_t)k, v.info.data() + 9 * (size_t)k, "position factor");
+		if (kind)
+		{
+			check_factor_kernel(kind[k], delta[k], "position factor");
+			any = any || kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE;
+		}
+	}
+	// (kinds all 0: no kernels, the set runs the kernels' ROBUST = false instantiations)
+	if (any) { v.kind.assign(kind, kind + n); v.delta.assign(delta, delta + n); }
+	// a validated set replaces the handle's, as a pose kind's
+	posSet.pose.swap(v.pose); posSet.z.swap(v.z); posSet.arm.swap(v.arm); posSet.info.swap(v.info); posSet.kind.swap(v.kind); posSet.delta.swap(v.delta);
+	posSet.order.clear();
+	forget_factor_memories(*this, posSet);
+	pf.pos = DevicePositionFactors();
+	covBlocksValid = false;
+}
+
+// the caller's position factors -> device, in the internal pose order (stable by internal pose: every pose's factors contiguous, in the
+// caller's order; the factors on fixed poses last)
+static void upload_position_factors(cuba_hip_solver& s)
+{
+	PositionFactorSet& set = s.posSet;
+	const int n = set.n(), Pf = s.Pf;
+	const bool robust = !set.kind.empty();
+	std::vector<uint64_t> internal((size_t)n);
+	for (int k = 0; k < n; k++) internal[k] = (uint64_t)s.internalPose(set.pose[k]);
+	sort_factors(set, internal);
+	std::vector<int> ptr, ids, poses((size_t)n);
+	for (int p = 0; p < n; p++)
+	{
+		poses[p] = (int)internal[set.order[p]];
+		if (poses[p] < Pf && (ids.empty() || ids.back() != poses[p])) { ids.push_back(poses[p]); ptr.push_back(p); }
+	}
+	int nFree = 0;
+	while (nFree < n && poses[nFree] < Pf) nFree++;
+	ptr.push_back(nFree);
+	const int np = (int)ids.size();
+	// ints: pose_ptr [np + 1] | pose_id [np] | pose [n] | kind [n, robust];  values: z [3 n] | arm [3 n] | info [9 n] | delta [n, robust]
+	std::vector<int> ints = concat({ &ptr, &ids, &poses });
+	const size_t nInts = ints.size();
+	std::vector<Scalar> vals((robust ? 16 : 15) * (size_t)n);
+	Scalar* vz = vals.data(); Scalar* va = vz + 3 * (size_t)n; Scalar* vi = va + 3 * (size_t)n;
+	for (size_t p = 0; p < (size_t)n; p++)
+	{
+		const size_t k = (size_t)set.order[p];
+		for (int i = 0; i < 3; i++) { vz[3 * p + i] = (Scalar)set.z[3 * k + i]; va[3 * p + i] = (Scalar)set.arm[3 * k + i]; }
+		for (int i = 0; i < 9; i++) vi[9 * p + i] = (Scalar)set.info[9 * k + i];
+		if (robust) { ints.push_back(set.kind[k]); vi[9 * (size_t)n + p] = (Scalar)set.delta[k]; }
+	}
+	set.d_ints.upload(ints, s.stream);
+	set.d_vals.upload(vals, s.stream);
+	set.d_chi.resize(std::max((size_t)n, (size_t)1));
+	s.sync();          // (the staging vectors go out of scope)
+	DevicePositionFactors pp;
+	pp.n = n; pp.nPoses = np;
+	pp.pose_ptr = set.d_ints.data(); pp.pose_id = pp.pose_ptr + (np + 1); pp.pose = pp.pose_id + np;
+	pp.z = set.d_vals.data(); pp.arm = pp.z + 3 * (size_t)n; pp.info = pp.arm + 3 * (size_t)n;
+	pp.chi = set.d_chi.data();
+	pp.rk_kind = robust ? set.d_ints.data() + nInts : nullptr; pp.rk_delta = robust ? pp.info + 9 * (size_t)n : nullptr;
+	s.pf.pos = pp;
+	set.uploaded = true;
+}
+
+// (the pose priors and the position factors depend on the pose order only -- a change of it marks them --, the edges' blocks and the
+// landmark priors' order on the structure)
 void cuba_hip_solver::uploadFactors()
 {
 	if (priorSet.n() > 0 && !priorSet.uploaded) upload_priors(*this);
 	if (relSet.n() > 0 && (!relSet.uploaded || relSet.structure != cntStructureBuilds)) upload_relative_pose_edges(*this);
 	if (lmPriorSet.n() > 0 && (!lmPriorSet.uploaded || lmPriorSet.structure != cntStructureBuilds)) upload_landmark_priors(*this);
+	if (posSet.n() > 0 && !posSet.uploaded) upload_position_factors(*this);
 }
 
 // the per-factor chi2 of the chi2 launch just issued (sorted order on the device) -> the caller's order
@@ -868,4 +1093,12 @@ void cuba_hip_solver::landmarkPriorChiSquares(double* out)
 	if (lmPriorSet.n() == 0) return;
 	launch_landmark_prior_chi2(g, pf.lmp, d_parts.data(), stream);
 	read_factor_chi2(*this, lmPriorSet, pf.lmp.chi, out);
+}
+
+void cuba_hip_solver::positionFactorChiSquares(double* out)
+{
+	need();
+	if (posSet.n() == 0) return;
+	launch_position_chi2(g, pf.pos, d_parts.data(), stream);
+	read_factor_chi2(*this, posSet, pf.pos.chi, out);
 }

@@ -197,17 +197,37 @@ struct DeviceLandmarkPriors
 	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 on fixed landmarks)
 };
 
+// Position factors on the poses (ba_factor.hip; GNSS-style fixes): rho(r^T Omega r), r = R^T (a - t) - z, the world position of the point
+// a of the camera frame (the lever arm; zero: the camera centre) against a measured world position z, Omega a symmetric 3 x 3 information.
+// Sorted by internal pose (stable: a pose's factors are contiguous and in the caller's order); factors on fixed poses come last and are
+// ignored.
+struct DevicePositionFactors
+{
+	int n = 0;                     // factors
+	int nPoses = 0;                // free poses with factors
+	const int* pose_ptr = nullptr; // [nPoses + 1] range of every such pose in the sorted list
+	const int* pose_id = nullptr;  // [nPoses] its internal pose index
+	const int* pose = nullptr;     // [n] internal pose of every factor (>= Pf: a fixed pose)
+	const Scalar *z = nullptr, *arm = nullptr;       // [3 n] measured positions, [3 n] lever arms
+	const Scalar* info = nullptr;  // [9 n] column-major
+	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 on fixed poses)
+	const int* rk_kind = nullptr;  // [n] robust kernel of every factor, sorted as the values; null: no factor has one (the kernels' ROBUST = false)
+	const Scalar* rk_delta = nullptr;   // [n]
+};
+
 // The factors of a handle besides the reprojection edges: what the rest of the library sees of the kinds (a kind without factors: n = 0,
 // nothing of it is launched).  The landmark priors ride along for the chi2 sums only: their linearisation is the landmark pass's.
-struct DeviceFactors { DevicePriors priors; DeviceRelPoses rel; DeviceLandmarkPriors lmp; };
+struct DeviceFactors { DevicePriors priors; DeviceRelPoses rel; DeviceLandmarkPriors lmp; DevicePositionFactors pos; };
 // behind the Schur pass, the priors first (Omega: w Omega of a factor with a robust kernel): J^T Omega J into the diagonal blocks of hsc (upper triangle), -J^T Omega r into bp and (mode 1)
-// bsc, J = J_l(r)^-1; then the edges in two launches: per-edge records, then their sums into hsc (diagonal blocks: upper triangle; mode 1:
-// the off-diagonal blocks of the pairs, stored whole where a block has no Schur products), bp and (mode 1) bsc
+// bsc, J = J_l(r)^-1; then the position factors the same way in a launch of their own, J = [R^T [a]x | -R^T]; then the edges in two
+// launches: per-edge records, then their sums into hsc (diagonal blocks: upper triangle; mode 1: the off-diagonal blocks of the pairs,
+// stored whole where a block has no Schur products), bp and (mode 1) bsc.  All three add to the same diagonal blocks: the order of the
+// launches is part of the result
 void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DeviceFactors& pf, int mode, hipStream_t s);
-// per-factor chi2 (the plain r^T Omega r) into priors.chi / rel.chi / lmp.chi, per-workgroup partial sums of rho(chi2) into parts[0 .. factor_chi2_parts(&pf)): the priors' first, the
-// edges' behind them, the landmark priors' last
+// per-factor chi2 (the plain r^T Omega r) into priors.chi / rel.chi / lmp.chi / pos.chi, per-workgroup partial sums of rho(chi2) into
+// parts[0 .. factor_chi2_parts(&pf)): the priors' first, the edges' behind them, then the landmark priors', the position factors' last
 void launch_factor_chi2(const DeviceGraph& g, const DeviceFactors& pf, Scalar* parts, hipStream_t s);
-int factor_chi2_parts(const DeviceFactors* pf);     // 0 for no factors (pf null), at most 64 per kind (the landmark priors' included)
+int factor_chi2_parts(const DeviceFactors* pf);     // 0 for no factors (pf null), at most 64 per kind
 
 // residual / robust chi2 over all edges -> sys.slots[0..NSLOT) (must be zeroed by the caller).
 // per_edge (optional, sorted edge order): non-robust omega*|r|^2.

@@ -542,6 +542,21 @@ int cuba_hip_landmark_prior_chi_squares(cuba_hip_solver* s, double* chi2_per_pri
 	});
 }
 
+int cuba_hip_set_position_factors(cuba_hip_solver* s, int n, const int32_t* pose, const double* position, const double* lever_arm, const double* info,
+	const int32_t* kind, const double* delta)
+{
+	return guarded(s, [&] { s->setPositionFactors(n, pose, position, lever_arm, info, kind, delta); });
+}
+
+int cuba_hip_position_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor)
+{
+	return guarded(s, [&] {
+		if (!s->haveGraph) throw StateError{ "set_graph must be called first" };
+		if (s->posSet.n() > 0 && !chi2_per_factor) throw ArgError{ "null output" };
+		s->positionFactorChiSquares(chi2_per_factor);
+	});
+}
+
 int cuba_hip_time_kernels(cuba_hip_solver* s, int reps, double ms_per_launch[CUBA_HIP_TIMED_KERNELS])
 {
 	return guarded(s, [&] {
@@ -568,6 +583,7 @@ int cuba_hip_set_partition(cuba_hip_solver* s, int landmark_begin, int landmark_
 		if (s->priorSet.n() > 0) throw StateError{ "a landmark partition is not available on a handle with pose priors" };
 		if (s->relSet.n() > 0) throw StateError{ "a landmark partition is not available on a handle with relative-pose edges" };
 		if (s->lmPriorSet.n() > 0) throw StateError{ "a landmark partition is not available on a handle with landmark priors" };
+		if (s->posSet.n() > 0) throw StateError{ "a landmark partition is not available on a handle with position factors" };
 		if (s->partHi >= 0 && landmark_begin == s->partLo && landmark_end == s->partHi) return;      // (cuba_hip_set_graph_partition set it already)
 		s->partLo = landmark_begin; s->partHi = landmark_end;
 		s->haveStructure = false;

@@ -157,6 +157,14 @@ struct LandmarkPriorSet : FactorSet
 	void clear() { lm.clear(); xyz.clear(); info.clear(); FactorSet::clear(); }
 };
 
+// position factors on the poses: the information as the symmetrised 3 x 3; kind / delta empty: no factor has a kernel
+struct PositionFactorSet : FactorSet
+{
+	std::vector<int> pose; std::vector<double> z, arm, info;      // [n], [3 n], [3 n], [9 n]
+	int n() const { return (int)pose.size(); }
+	void clear() { pose.clear(); z.clear(); arm.clear(); info.clear(); FactorSet::clear(); }
+};
+
 struct cuba_hip_solver;
 int cuba_hip_optimize_batch_impl(cuba_hip_solver** hs, int n, int niter, double* chi2, int* nDone);
 
@@ -609,16 +617,20 @@ struct cuba_hip_solver
 	// On the landmarks: position priors (cuba_hip_set_landmark_priors), kept as the caller gave them, with a device copy (pf.lmp) in the
 	// internal landmark order that need() makes once that order is known and again with every structure (a change of the landmark order
 	// rebuilds it).  The landmark pass linearises them -- linearize() hands pf.lmp to it --, the chi2 sums take them as one more kind.
+	// On the poses again: position factors (cuba_hip_set_position_factors), kept as the caller gave them, with a device copy (pf.pos) in the
+	// internal pose order that need() makes once that order is known and again whenever it changes, as the pose priors'.  Their values never
+	// touch the structure.
 	// No factors of any kind: factors() is null, nothing of it is launched, no extra seed enters the pattern build, and every launch and kernel argument is as
 	// without this feature.
 	PoseFactorSet priorSet, relSet;
 	LandmarkPriorSet lmPriorSet;
+	PositionFactorSet posSet;
 	DeviceFactors pf;
-	const DeviceFactors* factors() const { return priorSet.n() + relSet.n() + lmPriorSet.n() > 0 ? &pf : nullptr; }
+	const DeviceFactors* factors() const { return priorSet.n() + relSet.n() + lmPriorSet.n() + posSet.n() > 0 ? &pf : nullptr; }
 	int factorParts() const { return factor_chi2_parts(factors()); }      // chi2 partials that follow the reprojection edges'
 	void clearFactors()
 	{
-		priorSet.clear(); relSet.clear(); lmPriorSet.clear();
+		priorSet.clear(); relSet.clear(); lmPriorSet.clear(); posSet.clear();
 		h_relPairs.clear(); pf = DeviceFactors();
 	}
 	// the run-to-run memories that the values of the system feed (option "heuristics"): dropped by a change of the factors as by a new graph
@@ -633,6 +645,8 @@ struct cuba_hip_solver
 	const DeviceLandmarkPriors* landmarkPriors() const { return lmPriorSet.n() > 0 ? &pf.lmp : nullptr; }      // (null: nothing of them is launched or passed)
 	void setLandmarkPriors(int n, const int32_t* landmark, const double* xyz, const double* info, const int32_t* kind, const double* delta);
 	void landmarkPriorChiSquares(double* out);
+	void setPositionFactors(int n, const int32_t* pose, const double* position, const double* leverArm, const double* info, const int32_t* kind, const double* delta);
+	void positionFactorChiSquares(double* out);
 	// the edges' distinct free-free pairs (sorted keys i << 32 | j, i < j, caller's numbering) and the pairs the current structure was seeded
 	// with: every such pair owns a block of the reduced matrix, so need() rebuilds the structure exactly when the two sets differ
 	std::vector<uint64_t> h_relPairs, structRelPairs;

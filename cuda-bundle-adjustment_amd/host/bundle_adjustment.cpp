@@ -91,7 +91,7 @@ private:
 	std::vector<T*> items_;
 };
 
-// one kind of factor (cuba::PosePrior, cuba::RelativePoseEdge, cuba::LandmarkPrior) as an object keeps it
+// one kind of factor (cuba::PosePrior, cuba::RelativePoseEdge, cuba::LandmarkPrior, cuba::PositionFactor) as an object keeps it
 template <class F>
 struct FactorList
 {
@@ -163,6 +163,7 @@ public:
 		const std::vector<BaseEdge*> incident(it->second->edges.begin(), it->second->edges.end());
 		for (BaseEdge* e : incident) removeEdge(e);
 		priors_.removeIf([&](const PosePrior* p) { return p->vertex == it->second; });
+		posFactors_.removeIf([&](const PositionFactor* f) { return f->vertex == it->second; });
 		relEdges_.removeIf([&](const RelativePoseEdge* e) { return e->vertexI == it->second || e->vertexJ == it->second; });
 		poses_.erase(it);
 		posesDirty_ = true;
@@ -204,7 +205,7 @@ public:
 	void initialize() override
 	{
 		covPoseIndex_.clear(); covLmIndex_.clear();          // (marginal covariances describe the graph they were computed on)
-		priors_.dirty = relEdges_.dirty = lmPriors_.dirty = true;      // (the factors as they stand now go to the device with the next solve)
+		priors_.dirty = relEdges_.dirty = lmPriors_.dirty = posFactors_.dirty = true;      // (the factors as they stand now go to the device with the next solve)
 		poseIdx_.clear();                                    // (the factors' pose index: rebuilt below from the poses active now)
 		const auto t0 = std::chrono::steady_clock::now();
 		static const bool dbg = std::getenv("CUBA_HIP_DEBUG") != nullptr;
@@ -393,7 +394,7 @@ public:
 			check(cuba_hip_build_structure(solver_), "cuba_hip_build_structure");
 			check(cuba_hip_set_graph_end(solver_), "cuba_hip_set_graph_end");
 			graphDirty_ = false;
-			priors_.dirty = lmPriors_.dirty = true;          // (an upload clears the handle's priors)
+			priors_.dirty = lmPriors_.dirty = posFactors_.dirty = true;          // (an upload clears the handle's priors and position factors)
 			uploadedOnce_ = true; edgesChangedSinceUpload_ = valuesChangedSinceUpload_ = false;       // from here on the device holds exactly these edges and values
 			(void)cuba_hip_get_counter(solver_, "graph_uploads", &uploadGeneration_);
 		}
@@ -401,13 +402,15 @@ public:
 		uploadPriors();
 		uploadRelativePoseEdges();
 		uploadLandmarkPriors();
+		uploadPositionFactors();
 	}
 
-	// ---- factors (extensions: cuba::addPosePrior, cuba::addRelativePoseEdge, cuba::addLandmarkPrior) --
+	// ---- factors (extensions: cuba::addPosePrior, cuba::addRelativePoseEdge, cuba::addLandmarkPrior, cuba::addPositionFactor) --
 	// (public: the extension functions below remove and look up through them)
 	FactorList<PosePrior> priors_;
 	FactorList<RelativePoseEdge> relEdges_;
 	FactorList<LandmarkPrior> lmPriors_;
+	FactorList<PositionFactor> posFactors_;
 	// index of a factor's vertex among the active poses (the map is built with the first factor of an initialize()); `refusal`: the message
 	// for a vertex that is not part of the graph
 	int32_t factorPose(const PoseVertex* v, const char* refusal)
@@ -518,6 +521,32 @@ public:
 		lmPriors_.endUpload();
 	}
 
+	// ---- position factors on the poses (extension: cuba::addPositionFactor) --------------------------
+	void addPositionFactor(PositionFactor* f)
+	{
+		if (!f || !f->vertex) throw std::invalid_argument("cuba::addPositionFactor: a factor needs a pose vertex");
+		posFactors_.add(f);
+	}
+	void uploadPositionFactors()
+	{
+		if (!posFactors_.beginUpload()) return;
+		const std::vector<PositionFactor*>& factors = posFactors_.items;
+		const size_t n = factors.size();
+		std::vector<int32_t> pose(n);
+		std::vector<double> z(3 * n), arm(3 * n), info(9 * n);
+		for (size_t k = 0; k < n; k++)
+		{
+			pose[k] = factorPose(factors[k]->vertex, "cuba::addPositionFactor: the vertex of a factor is not part of the graph");
+			std::copy(factors[k]->position.begin(), factors[k]->position.end(), z.begin() + 3 * k);
+			std::copy(factors[k]->leverArm.begin(), factors[k]->leverArm.end(), arm.begin() + 3 * k);
+			std::copy(factors[k]->information.begin(), factors[k]->information.end(), info.begin() + 9 * k);
+		}
+		const FactorKernels r = packKernels(factors);
+		check(cuba_hip_set_position_factors(solver_, (int)n, pose.data(), z.data(), arm.data(), info.data(), r.any ? r.kind.data() : nullptr,
+			r.any ? r.delta.data() : nullptr), "cuba_hip_set_position_factors");
+		posFactors_.endUpload();
+	}
+
 	// (optimize() in three steps, so that cuba::optimizeBatch can run the middle one for several objects at once)
 	void optimize(int niterations) override
 	{
@@ -596,6 +625,7 @@ public:
 		for (int i = 0; i < done; i++) stats_.push_back({ i, chi2[i] });
 		priors_.readChi([&](double* c) { check(cuba_hip_prior_chi_squares(solver_, c), "cuba_hip_prior_chi_squares"); });
 		lmPriors_.readChi([&](double* c) { check(cuba_hip_landmark_prior_chi_squares(solver_, c), "cuba_hip_landmark_prior_chi_squares"); });
+		posFactors_.readChi([&](double* c) { check(cuba_hip_position_factor_chi_squares(solver_, c), "cuba_hip_position_factor_chi_squares"); });
 		relEdges_.readChi([&](double* c) { check(cuba_hip_relative_pose_chi_squares(solver_, c), "cuba_hip_relative_pose_chi_squares"); });
 
 		// finalize (ref :512-526): estimates back into the caller's vertices
@@ -645,6 +675,7 @@ public:
 		priors_.items.clear(); priors_.chi.clear();
 		relEdges_.items.clear(); relEdges_.chi.clear();
 		lmPriors_.items.clear(); lmPriors_.chi.clear();
+		posFactors_.items.clear(); posFactors_.chi.clear();
 		posesDirty_ = landmarksDirty_ = edgesDirty_ = true;
 		initialized_ = false;
 	}
@@ -905,6 +936,26 @@ double landmarkPriorChiSquared(const CudaBundleAdjustment* object, const Landmar
 {
 	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
 	return impl ? impl->lmPriors_.chiSquared(prior) : 0.0;
+}
+
+// Extension (GNSS-style fixes): position factors on the poses, effective at the next initialize() (cuba_hip_set_position_factors)
+void addPositionFactor(CudaBundleAdjustment* object, PositionFactor* factor)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (!impl) throw std::runtime_error("cuba::addPositionFactor: not an object of this library");
+	impl->addPositionFactor(factor);
+}
+
+void removePositionFactor(CudaBundleAdjustment* object, PositionFactor* factor)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (impl) impl->posFactors_.remove(factor);
+}
+
+double positionFactorChiSquared(const CudaBundleAdjustment* object, const PositionFactor* factor)
+{
+	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
+	return impl ? impl->posFactors_.chiSquared(factor) : 0.0;
 }
 
 // Extension (g2o's binary SE(3) edge): relative-pose edges, effective at the next initialize() (cuba_hip_set_relative_pose_edges)

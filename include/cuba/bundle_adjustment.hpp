@@ -175,4 +175,27 @@ void addLandmarkPrior(CudaBundleAdjustment* object, LandmarkPrior* prior);
 void removeLandmarkPrior(CudaBundleAdjustment* object, LandmarkPrior* prior);
 double landmarkPriorChiSquared(const CudaBundleAdjustment* object, const LandmarkPrior* prior);
 
+// Extension (include/cuba_hip.h, cuba_hip_set_position_factors): a position factor on one pose vertex -- a measured WORLD position of a
+// point that rides on the camera, without an orientation: a GNSS fix of the antenna, a total-station prism, a mocap marker, a UWB
+// position.  `position` is the measurement z, `leverArm` the measured point a in the camera frame (zero: the camera centre),
+// `information` symmetric 3 x 3, column-major.  Objective term r^T Omega r with r = R^T (a - t) - z for the vertex's world -> camera pose
+// [R | t], or rho(r^T Omega r) when `kernel` is set (`delta` > 0 then).  A PosePrior cannot say this: its translation residual depends
+// on a prior rotation.  Three such factors give a graph without a fixed vertex its gauge, and a monocular one its scale.  The fp32
+// library evaluates r in fp32: subtract a local origin from UTM-size coordinates first.  Ownership and lifetime as for PosePrior: the
+// caller owns the factor; additions, removals and changes take effect at the next initialize(); the vertex must be part of the graph
+// then.  removePoseVertex drops the vertex's factors, clear() all.  positionFactorChiSquared: r^T Omega r at the estimate of the last
+// optimize() (0 before one, and for a factor on a fixed vertex) -- the plain value under a kernel too.
+struct PositionFactor
+{
+	PoseVertex* vertex = nullptr;
+	std::array<double, 3> position{};
+	std::array<double, 3> leverArm{};
+	std::array<double, 9> information{};
+	PoseFactorKernel kernel = PoseFactorKernel::NONE;
+	double delta = 0;
+};
+void addPositionFactor(CudaBundleAdjustment* object, PositionFactor* factor);
+void removePositionFactor(CudaBundleAdjustment* object, PositionFactor* factor);
+double positionFactorChiSquared(const CudaBundleAdjustment* object, const PositionFactor* factor);
+
 }  // namespace cuba

@@ -476,6 +476,43 @@ int cuba_hip_set_landmark_priors(cuba_hip_solver* s, int n, const int32_t* landm
 	const double* delta);
 int cuba_hip_landmark_prior_chi_squares(cuba_hip_solver* s, double* chi2_per_prior);
 
+/* ---- position factors on the poses (GNSS-style fixes with a lever arm; the reference has no counterpart) -----------------------------
+   A factor names pose `pose` (the caller's solver numbering, 0 <= pose < Pt; world -> camera T = [R | t]), a measured world position z,
+   a lever arm a -- the measured point in the camera frame, zero for the camera centre --, a 3 x 3 information matrix Omega (symmetric,
+   column-major) and optionally a robust kernel (kind, delta) of the pose factors' family (table above: 0 none, 1 Huber, 2 Tukey,
+   3 Cauchy, the same formulas): a GNSS fix of the antenna, a total-station prism, a mocap marker, a UWB position.  An SE(3) prior cannot
+   say this even with zero information on its rotation rows: the translation part of log(T Tbar^-1) depends on a prior rotation that a
+   position fix does not supply.
+     residual     r = R^T (a - t) - z, e = r^T Omega r
+     objective    rho(e); the LM objective F (cuba_hip_optimize's chi2, cuba_hip_compute_errors, the gain ratio) gains the factors' sum
+     linearised   with w = rho'(e) and dr/dd = [R^T [a]x | -R^T] (3 x 6, d = [omega; upsilon] of the update T <- exp(d) T; exact to first
+                  order, r lives in a vector space): w J^T Omega J into the pose's diagonal block of the reduced matrix, -w J^T Omega r into
+                  bp and bsc; no second-order term.  lambda is added afterwards as to everything else; the assemble-only pass adds the terms
+                  too, so lambda_0's maximum diagonal includes them.  The terms follow the pose priors' and precede the relative-pose
+                  edges' in every sum.
+   Several factors on one pose are summed in the caller's order; factors on fixed poses are accepted and ignored (chi2 0).  Every solve
+   path honours them: the device-decision loop (a rejected trial's restore included), the host loop, both PCG forms, the exact solver,
+   the fp32 library, mixed precision, and the covariance entry points (the inverse of the weighted Hessian: three such factors give a
+   graph without a fixed vertex its gauge, and a monocular one its scale).
+   The fp32 library computes R^T (a - t) - z in fp32 and the library shifts nothing: callers with UTM-size coordinates subtract a local
+   origin from the poses, the landmarks and z first.
+   cuba_hip_set_position_factors replaces the whole set (n = 0 clears it): pose[n], position[3 n], lever_arm[3 n] (NULL: zeros), info[9 n],
+   kind[n] and delta[n] (both NULL: no kernels; kinds all 0 are no kernels).  Valid any time after cuba_hip_set_graph, which clears the
+   set.  Setting factors never rebuilds the structure ("structure_builds" stays); it drops the run-to-run memories of option "heuristics"
+   and cached covariance blocks.
+   CUBA_HIP_ERR_INVALID_ARGUMENT, the handle unchanged: an index out of range, non-finite values, an information matrix that is not
+   symmetric (beyond 1e-9 of its largest entry; within it the two triangles are averaged), a kind outside 0..3, delta <= 0 on a kind != 0,
+   one of kind / delta without the other.
+   CUBA_HIP_ERR_STATE, the handle staying usable: a landmark-partitioned handle (and cuba_hip_set_partition on a handle with such factors,
+   hence the multi-GPU driver) and a graph without edges.  A handle with such factors takes part in cuba_hip_optimize_batch through the
+   path that batches the PCG iterations only (results stay bit-identical to solo runs).  A handle without them launches the kernels, with
+   the arguments, of a library without this entry point.
+   cuba_hip_position_factor_chi_squares: the plain r^T Omega r of every factor at the current estimate, in the caller's order (what a
+   caller gates a doubtful fix on). */
+int cuba_hip_set_position_factors(cuba_hip_solver* s, int n, const int32_t* pose, const double* position, const double* lever_arm, const double* info,
+	const int32_t* kind, const double* delta);
+int cuba_hip_position_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor);
+
 /* ---- introspection (parity tests) and multi-GPU plumbing ------------------------------------------ */
 
 /* Structure of the reduced system: upper-triangular BSR (replaces the accessors of
