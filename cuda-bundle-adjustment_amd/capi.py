@@ -131,6 +131,8 @@ def load_library(precision="f64"):
         "cuba_hip_landmark_prior_chi_squares": [H, _dp],
         "cuba_hip_set_position_factors": [H, C.c_int, _ip, _dp, _dp, _dp, _ip, _dp],
         "cuba_hip_position_factor_chi_squares": [H, _dp],
+        "cuba_hip_set_direction_factors": [H, C.c_int, _ip, _dp, _dp, _dp, _ip, _dp],
+        "cuba_hip_direction_factor_chi_squares": [H, _dp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -392,7 +394,7 @@ class HipSolver:
         landmark_range = (begin, end): cuba_hip_set_graph_partition -- the upload of one rank of a landmark partition, which sends the
         measurements and information of its own landmarks' edges only."""
         self.fp = fp
-        self._n_factors = {}            # (every upload clears the pose priors, the relative-pose edges, the landmark priors and the position factors)
+        self._n_factors = {}            # (every upload clears the pose priors, the relative-pose edges, the landmark priors, the position and the direction factors)
         q, t, cam, Xw = (np.ascontiguousarray(a, dtype=np.float64) for a in (fp.q, fp.t, fp.cam, fp.Xw))
         eP = np.ascontiguousarray(fp.eP, dtype=np.int32)
         eL = np.ascontiguousarray(fp.eL, dtype=np.int32)
@@ -594,6 +596,31 @@ class HipSolver:
     def position_factor_chi_squares(self):
         """r^T Omega r of every position factor at the current estimate, in the order they were given (0 for factors on fixed poses)"""
         return self._factor_chi_squares("position_factor")
+
+    def set_direction_factors(self, pose, world_dir, measured_dir, info, kind=None, delta=None):
+        """Direction factors on the poses (cuba_hip_set_direction_factors; gravity, compass, vanishing directions), replacing the handle's
+        set: pose[n] in the solver numbering, the world vectors world_dir[n, 3], the same vectors as measured in the camera frame
+        measured_dir[n, 3] (neither is normalised), info[n, 3, 3] symmetric; kind[n] (0 none, 1 Huber, 2 Tukey, 3 Cauchy) and delta[n]
+        together or not at all (scalars broadcast).  An empty pose list clears the set."""
+        pose = np.ascontiguousarray(pose, dtype=np.int32).reshape(-1)
+        n = int(pose.size)
+        world_dir = np.ascontiguousarray(world_dir, dtype=np.float64).reshape(n, 3)
+        measured_dir = np.ascontiguousarray(measured_dir, dtype=np.float64).reshape(n, 3)
+        # (column-major 3 x 3 blocks: the transpose of the row-major reading)
+        info = np.ascontiguousarray(np.asarray(info, dtype=np.float64).reshape(n, 3, 3).transpose(0, 2, 1))
+        if kind is not None:
+            kind = np.ascontiguousarray(np.full(n, kind) if np.ndim(kind) == 0 else kind, dtype=np.int32).reshape(-1)
+        if delta is not None:
+            delta = np.ascontiguousarray(np.full(n, delta) if np.ndim(delta) == 0 else delta, dtype=np.float64).reshape(-1)
+        if (kind is not None and kind.size != n) or (delta is not None and delta.size != n):
+            raise ValueError("kind / delta differ in length from the set")
+        self._ck(self.lib.cuba_hip_set_direction_factors(self.h, n, pose.ctypes.data_as(_ip), _d(world_dir), _d(measured_dir), _d(info),
+                                                         kind.ctypes.data_as(_ip) if kind is not None else None, _d(delta)))
+        self._n_factors["direction_factor"] = n
+
+    def direction_factor_chi_squares(self):
+        """r^T Omega r of every direction factor at the current estimate, in the order they were given (0 for factors on fixed poses)"""
+        return self._factor_chi_squares("direction_factor")
 
     def chi_squares_two_step(self):
         """cuba_hip_chi_squares_begin / _end (the C++ layer does its write-back between the two)"""

@@ -1,6 +1,7 @@
 // ba_factor.hip -- the factors besides the reprojection edges: terms rho(r^T Omega r) of the objective on the vertices alone, Omega a full
 // symmetric information.  Two kinds on the SE(3) poses, r in the [omega, upsilon] tangent of the solver's left-multiplicative update
-// T <- exp(d) T (pose_exp_update), Omega 6 x 6, one on the landmarks, and one that ties a pose to a world position:
+// T <- exp(d) T (pose_exp_update), Omega 6 x 6, one on the landmarks, one that ties a pose to a world position and one that ties its
+// rotation to a world direction:
 //
 //   pose priors (cuba_hip_set_pose_priors): unary, r = log(T Tbar^-1), linearised with the exact derivative dr/dd =
 //     J_l(r)^-1.  A prior touches the diagonal 6 x 6 block of its pose in the reduced matrix and the pose's entries of bp / bsc only.
@@ -19,17 +20,23 @@
 //     of the camera frame (the lever arm of a GNSS antenna, a prism, a marker; zero: the camera centre) against a measured world position
 //     z, Omega 3 x 3.  r lives in a vector space, so dr/dd = [R^T [a]x | -R^T] (3 x 6, d = [omega; upsilon]) is exact to first order without a
 //     J_l.  A factor touches the diagonal block of its pose and the pose's entries of bp / bsc only, as a pose prior.
+//   direction factors (cuba_hip_set_direction_factors; section 7h): unary on the poses, r = R d - m: a world vector d (gravity, magnetic
+//     north, a vanishing direction, a star) against the same vector as measured in the camera frame, Omega 3 x 3, rank 2 as a rule.  Under
+//     the update R' = (I + [omega]x) R, so r' = r + omega x (R d) and dr/dd = [-[R d]x | 0] (3 x 6) -- NOT the body-frame -R [d]x, which
+//     equals -[R d]x R.  The translation columns are exactly zero: a factor touches the rotation 3 x 3 of its pose's diagonal block and the
+//     first three entries of the pose's bp / bsc, nothing else.
 //
 // A factor may carry a robust kernel (cuba_hip_set_pose_factor_robust_kernels; section 7e): with e = r^T Omega r its term is rho(e) and its
 // linearisation takes w Omega, w = rho'(e), for Omega (no second-order term, as the reprojection edges).  The four kernels that see a
 // residual are templates on ROBUST; a set without kernels has null kind / delta arrays and runs the `false` instantiations, which hold
 // nothing of this.  A landmark prior always carries a kind (none = 0) and comes with its kernel in one call.
 //
-// Order: the pose priors, the position factors and the relative-pose edges all add to the diagonal blocks, bp and bsc that the pose and
-// Schur passes stored, by read-modify-write.  launch_pose_factor_linearize issues them in one stream in this order -- priors, position
-// factors, the edges' records, the edges' gather -- and that order is part of the result (floating-point sums do not commute): a handle's
-// bits depend on it, and a new kind goes BEHIND the ones a handle may already combine, never between two of them.  (The position factors
-// sit between the priors and the edges: no handle could hold them before, so no existing sum changes.)
+// Order: the pose priors, the position factors, the relative-pose edges and the direction factors all add to the diagonal blocks, bp and
+// bsc that the pose and Schur passes stored, by read-modify-write.  launch_pose_factor_linearize issues them in one stream in this order --
+// priors, position factors, the edges' records, the edges' gather, direction factors -- and that order is part of the result
+// (floating-point sums do not commute): a handle's bits depend on it, and a new kind goes BEHIND the ones a handle may already combine,
+// never between two of them.  (The position factors sit between the priors and the edges: no handle could hold them before they came, so
+// no existing sum changed.  The direction factors came when handles could combine all of the others, so they go last.)
 //
 // The kinds keep kernels of their own (a prior is not run as a one-ended edge: its sums would be taken in another order); they share the
 // device helpers below, the host-side validation, sorting and read-back -- the two pose kinds also packing and upload -- and one interface
@@ -50,12 +57,17 @@
 //                              J^T (Omega J) (21 numbers) and J^T Omega r (6) summed in registers, one read-modify-write of the diagonal
 //                              block's upper triangle, bp and (mode 1) bsc -- one writer per number; behind the priors' launch, ahead of the
 //                              edges' launches
+//   direction_linearize_kernel lane = free pose with direction factors: the rotation matrix once, then the pose's factors in the caller's order,
+//                              [v]x^T Omega [v]x, v = R d (6 numbers) and v x (Omega r) (3) summed in registers, one read-modify-write of the
+//                              upper triangle of the block's rotation 3 x 3, of bp[0..3) and (mode 1) bsc[0..3) -- one writer per number; the
+//                              last launch, behind the edges' gather
 //   prior_chi2_kernel,         lane = factor: r^T Omega r at the current estimate into the per-factor output and (rho of it) into per-workgroup
 //   relpose_chi2_kernel,       partials that the caller sums together with the reprojection edges' partials (fixed order, no atomics)
 //   landmark_prior_chi2_kernel,
-//   position_chi2_kernel
+//   position_chi2_kernel,
+//   direction_chi2_kernel
 //
-// Host side: the caller's four sets (validated, kept in the caller's numbering), the edges' pair set (part of the topology) and the upload
+// Host side: the caller's five sets (validated, kept in the caller's numbering), the edges' pair set (part of the topology) and the upload
 // of every set in the internal pose / landmark order.
 #include "ba_solver.hpp"
 #include "ba_device.hpp"
@@ -66,6 +78,7 @@ namespace cubahip
 
 constexpr int PRIOR_LIN_BLOCK = 64;
 constexpr int POS_LIN_BLOCK = 64;
+constexpr int DIR_LIN_BLOCK = 64;
 constexpr int REL_LIN_BLOCK = 64;
 constexpr int REL_GATHER_BLOCK = 256;
 constexpr int CHI_BLOCK = 256;
@@ -524,6 +537,106 @@ __global__ __launch_bounds__(CHI_BLOCK) void position_chi2_kernel(DeviceGraph g,
 	chi2_partial(acc, parts);
 }
 
+// ---- direction factors ------------------------------------------------------------------------------------------------------------
+
+// v = R d and r = v - m of factor k at the rotation R (row-major in Rm), Or = Omega r; returns r^T Omega r
+__device__ __forceinline__ Scalar direction_residual(const DeviceDirectionFactors& df, int k, const Scalar Rm[3][3], Scalar v[3], Scalar Or[3])
+{
+	const Scalar* d = df.d + 3 * (size_t)k;
+	const Scalar* m = df.m + 3 * (size_t)k;
+	const Scalar* O = df.info + 9 * (size_t)k;
+	Scalar r[3];
+#pragma unroll
+	for (int i = 0; i < 3; i++)
+	{
+		v[i] = Rm[i][0] * d[0] + Rm[i][1] * d[1] + Rm[i][2] * d[2];
+		r[i] = v[i] - m[i];
+	}
+#pragma unroll
+	for (int i = 0; i < 3; i++) Or[i] = O[i] * r[0] + O[3 + i] * r[1] + O[6 + i] * r[2];
+	return r[0] * Or[0] + r[1] * Or[1] + r[2] * Or[2];
+}
+
+template <bool ROBUST>
+__global__ __launch_bounds__(DIR_LIN_BLOCK) void direction_linearize_kernel(DeviceGraph g, DeviceStructure st, DeviceSystem sys, DeviceDirectionFactors df, int mode)
+{
+	const int i = blockIdx.x * DIR_LIN_BLOCK + threadIdx.x;
+	if (i >= df.nPoses) return;
+	const int ip = df.pose_id[i];
+	const Scalar* q = g.q + 4 * (size_t)ip;
+	const Rot3 R = quat_to_rot(q[0], q[1], q[2], q[3]);
+	Scalar H[6], gv[3];
+#pragma unroll
+	for (int k = 0; k < 6; k++) H[k] = 0;
+#pragma unroll
+	for (int k = 0; k < 3; k++) gv[k] = 0;
+	const int k1 = df.pose_ptr[i + 1];
+	for (int k = df.pose_ptr[i]; k < k1; k++)
+	{
+		Scalar v[3], Or[3];
+		const Scalar e = direction_residual(df, k, R.m, v, Or);
+		Scalar w = 1;
+		if constexpr (ROBUST) w = factor_weight(df.rk_kind[k], df.rk_delta[k], e);
+		// J = [-[v]x | 0]: J^T Omega J = [v]x^T (Omega [v]x), column by column (upper triangle, H[c (c + 1) / 2 + r]); J^T Omega r = v x (Omega r)
+		Scalar V[3][3];
+		hat3(v, V);
+		const Scalar* O = df.info + 9 * (size_t)k;
+#pragma unroll
+		for (int c = 0; c < 3; c++)
+		{
+			Scalar ov[3];
+#pragma unroll
+			for (int x = 0; x < 3; x++) ov[x] = O[x] * V[0][c] + O[3 + x] * V[1][c] + O[6 + x] * V[2][c];
+#pragma unroll
+			for (int rr = 0; rr <= c; rr++)
+			{
+				const Scalar s = V[0][rr] * ov[0] + V[1][rr] * ov[1] + V[2][rr] * ov[2];
+				if constexpr (ROBUST) H[c * (c + 1) / 2 + rr] += w * s;
+				else H[c * (c + 1) / 2 + rr] += s;
+			}
+		}
+		const Scalar x[3] = { v[1] * Or[2] - v[2] * Or[1], v[2] * Or[0] - v[0] * Or[2], v[0] * Or[1] - v[1] * Or[0] };
+#pragma unroll
+		for (int c = 0; c < 3; c++)
+		{
+			if constexpr (ROBUST) gv[c] += w * x[c];
+			else gv[c] += x[c];
+		}
+	}
+	// (the translation rows and columns of the block, bp[3..6) and bsc[3..6) are not this kind's: they are not touched)
+	Scalar* blk = sys.hsc + 36 * (size_t)st.hsc_rowptr[ip];
+#pragma unroll
+	for (int c = 0; c < 3; c++)
+	{
+#pragma unroll
+		for (int rr = 0; rr <= c; rr++) blk[c * 6 + rr] += H[c * (c + 1) / 2 + rr];
+		sys.bp[6 * (size_t)ip + c] -= gv[c];
+		if (mode == 1) sys.bsc[6 * (size_t)ip + c] -= gv[c];
+	}
+}
+
+template <bool ROBUST>
+__global__ __launch_bounds__(CHI_BLOCK) void direction_chi2_kernel(DeviceGraph g, DeviceDirectionFactors df, Scalar* __restrict__ parts)
+{
+	Scalar acc = 0;
+	for (int k = blockIdx.x * CHI_BLOCK + threadIdx.x; k < df.n; k += gridDim.x * CHI_BLOCK)
+	{
+		const int ip = df.pose[k];
+		Scalar chi = 0;
+		if (ip < g.Pf)
+		{
+			const Scalar* q = g.q + 4 * (size_t)ip;
+			const Rot3 R = quat_to_rot(q[0], q[1], q[2], q[3]);
+			Scalar v[3], Or[3];
+			chi = direction_residual(df, k, R.m, v, Or);
+		}
+		df.chi[k] = chi;
+		if constexpr (ROBUST) acc += factor_rho(df.rk_kind[k], df.rk_delta[k], chi);
+		else acc += chi;
+	}
+	chi2_partial(acc, parts);
+}
+
 // ---- launches ---------------------------------------------------------------------------------------------------------------------
 
 static void launch_prior_chi2(const DeviceGraph& g, const DevicePriors& pr, Scalar* parts, hipStream_t s)
@@ -557,9 +670,17 @@ static void launch_position_chi2(const DeviceGraph& g, const DevicePositionFacto
 	else hipLaunchKernelGGL(position_chi2_kernel<false>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, pp, parts);
 }
 
+static void launch_direction_chi2(const DeviceGraph& g, const DeviceDirectionFactors& df, Scalar* parts, hipStream_t s)
+{
+	const int grid = chi2_parts(df.n);
+	if (grid <= 0) return;
+	if (df.rk_kind) hipLaunchKernelGGL(direction_chi2_kernel<true>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, df, parts);
+	else hipLaunchKernelGGL(direction_chi2_kernel<false>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, df, parts);
+}
+
 int factor_chi2_parts(const DeviceFactors* pf)
 {
-	return pf ? chi2_parts(pf->priors.n) + chi2_parts(pf->rel.n) + chi2_parts(pf->lmp.n) + chi2_parts(pf->pos.n) : 0;
+	return pf ? chi2_parts(pf->priors.n) + chi2_parts(pf->rel.n) + chi2_parts(pf->lmp.n) + chi2_parts(pf->pos.n) + chi2_parts(pf->dir.n) : 0;
 }
 
 void launch_factor_chi2(const DeviceGraph& g, const DeviceFactors& pf, Scalar* parts, hipStream_t s)
@@ -568,6 +689,7 @@ void launch_factor_chi2(const DeviceGraph& g, const DeviceFactors& pf, Scalar* p
 	launch_relpose_chi2(g, pf.rel, parts + chi2_parts(pf.priors.n), s);
 	launch_landmark_prior_chi2(g, pf.lmp, parts + chi2_parts(pf.priors.n) + chi2_parts(pf.rel.n), s);
 	launch_position_chi2(g, pf.pos, parts + chi2_parts(pf.priors.n) + chi2_parts(pf.rel.n) + chi2_parts(pf.lmp.n), s);
+	launch_direction_chi2(g, pf.dir, parts + chi2_parts(pf.priors.n) + chi2_parts(pf.rel.n) + chi2_parts(pf.lmp.n) + chi2_parts(pf.pos.n), s);
 }
 
 void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DeviceFactors& pf, int mode, hipStream_t s)
@@ -587,12 +709,21 @@ void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& s
 		else hipLaunchKernelGGL(position_linearize_kernel<false>, grid, dim3(POS_LIN_BLOCK), 0, s, g, st, sys, pp, mode);
 	}
 	const DeviceRelPoses& rp = pf.rel;
-	if (rp.nActive <= 0) return;
-	const dim3 linGrid((rp.nActive + REL_LIN_BLOCK - 1) / REL_LIN_BLOCK);
-	if (rp.rk_kind) hipLaunchKernelGGL(relpose_linearize_kernel<true>, linGrid, dim3(REL_LIN_BLOCK), 0, s, g, rp);
-	else hipLaunchKernelGGL(relpose_linearize_kernel<false>, linGrid, dim3(REL_LIN_BLOCK), 0, s, g, rp);
-	const size_t numbers = (mode == 1 ? (size_t)36 * rp.nBlocks : 0) + (size_t)REL_POSE_NUMBERS * rp.nPoses;
-	hipLaunchKernelGGL(relpose_gather_kernel, dim3((unsigned)((numbers + REL_GATHER_BLOCK - 1) / REL_GATHER_BLOCK)), dim3(REL_GATHER_BLOCK), 0, s, st, sys, rp, mode);
+	if (rp.nActive > 0)
+	{
+		const dim3 linGrid((rp.nActive + REL_LIN_BLOCK - 1) / REL_LIN_BLOCK);
+		if (rp.rk_kind) hipLaunchKernelGGL(relpose_linearize_kernel<true>, linGrid, dim3(REL_LIN_BLOCK), 0, s, g, rp);
+		else hipLaunchKernelGGL(relpose_linearize_kernel<false>, linGrid, dim3(REL_LIN_BLOCK), 0, s, g, rp);
+		const size_t numbers = (mode == 1 ? (size_t)36 * rp.nBlocks : 0) + (size_t)REL_POSE_NUMBERS * rp.nPoses;
+		hipLaunchKernelGGL(relpose_gather_kernel, dim3((unsigned)((numbers + REL_GATHER_BLOCK - 1) / REL_GATHER_BLOCK)), dim3(REL_GATHER_BLOCK), 0, s, st, sys, rp, mode);
+	}
+	const DeviceDirectionFactors& df = pf.dir;
+	if (df.nPoses > 0)
+	{
+		const dim3 grid((df.nPoses + DIR_LIN_BLOCK - 1) / DIR_LIN_BLOCK);
+		if (df.rk_kind) hipLaunchKernelGGL(direction_linearize_kernel<true>, grid, dim3(DIR_LIN_BLOCK), 0, s, g, st, sys, df, mode);
+		else hipLaunchKernelGGL(direction_linearize_kernel<false>, grid, dim3(DIR_LIN_BLOCK), 0, s, g, st, sys, df, mode);
+	}
 }
 
 }  // namespace cubahip
@@ -1052,14 +1183,102 @@ static void upload_position_factors(cuba_hip_solver& s)
 	set.uploaded = true;
 }
 
-// (the pose priors and the position factors depend on the pose order only -- a change of it marks them --, the edges' blocks and the
-// landmark priors' order on the structure)
+void cuba_hip_solver::setDirectionFactors(int n, const int32_t* pose, const double* worldDir, const double* measuredDir, const double* info, const int32_t* kind,
+	const double* delta)
+{
+	if (!haveGraph) throw StateError{ "set_graph must be called first" };
+	if (n < 0) throw ArgError{ "negative direction factor count" };
+	if (n > 0 && (partHi >= 0 || valuesPartial)) throw StateError{ "direction factors are not available on a landmark-partitioned handle" };
+	if (n > 0 && E == 0) throw StateError{ "direction factors need a graph with edges" };
+	if (n > 0 && (!pose || !worldDir || !measuredDir || !info)) throw ArgError{ "null direction factor array" };
+	if (n > 0 && (kind == nullptr) != (delta == nullptr)) throw ArgError{ "direction factor kernels: kind and delta come together" };
+	DirectionFactorSet v;
+	v.pose.resize((size_t)n); v.d.resize((size_t)3 * n); v.m.resize((size_t)3 * n); v.info.resize((size_t)9 * n);
+	bool any = false;
+	for (int k = 0; k < n; k++)
+	{
+		if (pose[k] < 0 || pose[k] >= Pt) throw ArgError{ "direction factor: pose index out of range" };
+		v.pose[k] = pose[k];
+		// (taken as given: neither vector is normalised)
+		for (int i = 0; i < 3; i++)
+		{
+			if (!std::isfinite(worldDir[3 * (size_t)k + i])) throw ArgError{ "non-finite direction factor world direction" };
+			if (!std::isfinite(measuredDir[3 * (size_t)k + i])) throw ArgError{ "non-finite direction factor measurement" };
+			v.d[3 * (size_t)k + i] = worldDir[3 * (size_t)k + i];
+			v.m[3 * (size_t)k + i] = measuredDir[3 * (size_t)k + i];
+		}
+		take_information<3>(info + 9 * (size_t)k, v.info.data() + 9 * (size_t)k, "direction factor");
+		if (kind)
+		{
+			check_factor_kernel(kind[k], delta[k], "direction factor");
+			any = any || kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE;
+		}
+	}
+	// (kinds all 0: no kernels, the set runs the kernels' ROBUST = false instantiations)
+	if (any) { v.kind.assign(kind, kind + n); v.delta.assign(delta, delta + n); }
+	// a validated set replaces the handle's, as a pose kind's
+	dirSet.pose.swap(v.pose); dirSet.d.swap(v.d); dirSet.m.swap(v.m); dirSet.info.swap(v.info); dirSet.kind.swap(v.kind); dirSet.delta.swap(v.delta);
+	dirSet.order.clear();
+	forget_factor_memories(*this, dirSet);
+	pf.dir = DeviceDirectionFactors();
+	covBlocksValid = false;
+}
+
+// the caller's direction factors -> device, in the internal pose order (stable by internal pose: every pose's factors contiguous, in the
+// caller's order; the factors on fixed poses last)
+static void upload_direction_factors(cuba_hip_solver& s)
+{
+	DirectionFactorSet& set = s.dirSet;
+	const int n = set.n(), Pf = s.Pf;
+	const bool robust = !set.kind.empty();
+	std::vector<uint64_t> internal((size_t)n);
+	for (int k = 0; k < n; k++) internal[k] = (uint64_t)s.internalPose(set.pose[k]);
+	sort_factors(set, internal);
+	std::vector<int> ptr, ids, poses((size_t)n);
+	for (int p = 0; p < n; p++)
+	{
+		poses[p] = (int)internal[set.order[p]];
+		if (poses[p] < Pf && (ids.empty() || ids.back() != poses[p])) { ids.push_back(poses[p]); ptr.push_back(p); }
+	}
+	int nFree = 0;
+	while (nFree < n && poses[nFree] < Pf) nFree++;
+	ptr.push_back(nFree);
+	const int np = (int)ids.size();
+	// ints: pose_ptr [np + 1] | pose_id [np] | pose [n] | kind [n, robust];  values: d [3 n] | m [3 n] | info [9 n] | delta [n, robust]
+	std::vector<int> ints = concat({ &ptr, &ids, &poses });
+	const size_t nInts = ints.size();
+	std::vector<Scalar> vals((robust ? 16 : 15) * (size_t)n);
+	Scalar* vd = vals.data(); Scalar* vm = vd + 3 * (size_t)n; Scalar* vi = vm + 3 * (size_t)n;
+	for (size_t p = 0; p < (size_t)n; p++)
+	{
+		const size_t k = (size_t)set.order[p];
+		for (int i = 0; i < 3; i++) { vd[3 * p + i] = (Scalar)set.d[3 * k + i]; vm[3 * p + i] = (Scalar)set.m[3 * k + i]; }
+		for (int i = 0; i < 9; i++) vi[9 * p + i] = (Scalar)set.info[9 * k + i];
+		if (robust) { ints.push_back(set.kind[k]); vi[9 * (size_t)n + p] = (Scalar)set.delta[k]; }
+	}
+	set.d_ints.upload(ints, s.stream);
+	set.d_vals.upload(vals, s.stream);
+	set.d_chi.resize(std::max((size_t)n, (size_t)1));
+	s.sync();          // (the staging vectors go out of scope)
+	DeviceDirectionFactors df;
+	df.n = n; df.nPoses = np;
+	df.pose_ptr = set.d_ints.data(); df.pose_id = df.pose_ptr + (np + 1); df.pose = df.pose_id + np;
+	df.d = set.d_vals.data(); df.m = df.d + 3 * (size_t)n; df.info = df.m + 3 * (size_t)n;
+	df.chi = set.d_chi.data();
+	df.rk_kind = robust ? set.d_ints.data() + nInts : nullptr; df.rk_delta = robust ? df.info + 9 * (size_t)n : nullptr;
+	s.pf.dir = df;
+	set.uploaded = true;
+}
+
+// (the pose priors, the position factors and the direction factors depend on the pose order only -- a change of it marks them --, the
+// edges' blocks and the landmark priors' order on the structure)
 void cuba_hip_solver::uploadFactors()
 {
 	if (priorSet.n() > 0 && !priorSet.uploaded) upload_priors(*this);
 	if (relSet.n() > 0 && (!relSet.uploaded || relSet.structure != cntStructureBuilds)) upload_relative_pose_edges(*this);
 	if (lmPriorSet.n() > 0 && (!lmPriorSet.uploaded || lmPriorSet.structure != cntStructureBuilds)) upload_landmark_priors(*this);
 	if (posSet.n() > 0 && !posSet.uploaded) upload_position_factors(*this);
+	if (dirSet.n() > 0 && !dirSet.uploaded) upload_direction_factors(*this);
 }
 
 // the per-factor chi2 of the chi2 launch just issued (sorted order on the device) -> the caller's order
@@ -1101,4 +1320,12 @@ void cuba_hip_solver::positionFactorChiSquares(double* out)
 	if (posSet.n() == 0) return;
 	launch_position_chi2(g, pf.pos, d_parts.data(), stream);
 	read_factor_chi2(*this, posSet, pf.pos.chi, out);
+}
+
+void cuba_hip_solver::directionFactorChiSquares(double* out)
+{
+	need();
+	if (dirSet.n() == 0) return;
+	launch_direction_chi2(g, pf.dir, d_parts.data(), stream);
+	read_factor_chi2(*this, dirSet, pf.dir.chi, out);
 }

@@ -215,17 +215,37 @@ struct DevicePositionFactors
 	const Scalar* rk_delta = nullptr;   // [n]
 };
 
+// Direction factors on the poses (ba_factor.hip; gravity, compass, vanishing directions): rho(r^T Omega r), r = R d - m, a world vector d
+// against the same vector as measured in the camera frame, m (neither is normalised), Omega a symmetric 3 x 3 information (rank 2 as a
+// rule).  Sorted by internal pose (stable: a pose's factors are contiguous and in the caller's order); factors on fixed poses come last and
+// are ignored.
+struct DeviceDirectionFactors
+{
+	int n = 0;                     // factors
+	int nPoses = 0;                // free poses with factors
+	const int* pose_ptr = nullptr; // [nPoses + 1] range of every such pose in the sorted list
+	const int* pose_id = nullptr;  // [nPoses] its internal pose index
+	const int* pose = nullptr;     // [n] internal pose of every factor (>= Pf: a fixed pose)
+	const Scalar *d = nullptr, *m = nullptr;         // [3 n] world vectors, [3 n] their measurements in the camera frame
+	const Scalar* info = nullptr;  // [9 n] column-major
+	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 on fixed poses)
+	const int* rk_kind = nullptr;  // [n] robust kernel of every factor, sorted as the values; null: no factor has one (the kernels' ROBUST = false)
+	const Scalar* rk_delta = nullptr;   // [n]
+};
+
 // The factors of a handle besides the reprojection edges: what the rest of the library sees of the kinds (a kind without factors: n = 0,
 // nothing of it is launched).  The landmark priors ride along for the chi2 sums only: their linearisation is the landmark pass's.
-struct DeviceFactors { DevicePriors priors; DeviceRelPoses rel; DeviceLandmarkPriors lmp; DevicePositionFactors pos; };
+struct DeviceFactors { DevicePriors priors; DeviceRelPoses rel; DeviceLandmarkPriors lmp; DevicePositionFactors pos; DeviceDirectionFactors dir; };
 // behind the Schur pass, the priors first (Omega: w Omega of a factor with a robust kernel): J^T Omega J into the diagonal blocks of hsc (upper triangle), -J^T Omega r into bp and (mode 1)
 // bsc, J = J_l(r)^-1; then the position factors the same way in a launch of their own, J = [R^T [a]x | -R^T]; then the edges in two
 // launches: per-edge records, then their sums into hsc (diagonal blocks: upper triangle; mode 1: the off-diagonal blocks of the pairs,
-// stored whole where a block has no Schur products), bp and (mode 1) bsc.  All three add to the same diagonal blocks: the order of the
-// launches is part of the result
+// stored whole where a block has no Schur products), bp and (mode 1) bsc; last the direction factors in a launch of their own, J =
+// [-[R d]x | 0]: the rotation 3 x 3 of the diagonal block and the first three entries of bp / bsc only.  All four add to the same diagonal
+// blocks: the order of the launches is part of the result
 void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DeviceFactors& pf, int mode, hipStream_t s);
-// per-factor chi2 (the plain r^T Omega r) into priors.chi / rel.chi / lmp.chi / pos.chi, per-workgroup partial sums of rho(chi2) into
-// parts[0 .. factor_chi2_parts(&pf)): the priors' first, the edges' behind them, then the landmark priors', the position factors' last
+// per-factor chi2 (the plain r^T Omega r) into priors.chi / rel.chi / lmp.chi / pos.chi / dir.chi, per-workgroup partial sums of rho(chi2)
+// into parts[0 .. factor_chi2_parts(&pf)): the priors' first, the edges' behind them, then the landmark priors', the position factors',
+// the direction factors' last
 void launch_factor_chi2(const DeviceGraph& g, const DeviceFactors& pf, Scalar* parts, hipStream_t s);
 int factor_chi2_parts(const DeviceFactors* pf);     // 0 for no factors (pf null), at most 64 per kind
 

@@ -557,6 +557,21 @@ int cuba_hip_position_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_fa
 	});
 }
 
+int cuba_hip_set_direction_factors(cuba_hip_solver* s, int n, const int32_t* pose, const double* world_dir, const double* measured_dir, const double* info,
+	const int32_t* kind, const double* delta)
+{
+	return guarded(s, [&] { s->setDirectionFactors(n, pose, world_dir, measured_dir, info, kind, delta); });
+}
+
+int cuba_hip_direction_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor)
+{
+	return guarded(s, [&] {
+		if (!s->haveGraph) throw StateError{ "set_graph must be called first" };
+		if (s->dirSet.n() > 0 && !chi2_per_factor) throw ArgError{ "null output" };
+		s->directionFactorChiSquares(chi2_per_factor);
+	});
+}
+
 int cuba_hip_time_kernels(cuba_hip_solver* s, int reps, double ms_per_launch[CUBA_HIP_TIMED_KERNELS])
 {
 	return guarded(s, [&] {
@@ -584,6 +599,7 @@ int cuba_hip_set_partition(cuba_hip_solver* s, int landmark_begin, int landmark_
 		if (s->relSet.n() > 0) throw StateError{ "a landmark partition is not available on a handle with relative-pose edges" };
 		if (s->lmPriorSet.n() > 0) throw StateError{ "a landmark partition is not available on a handle with landmark priors" };
 		if (s->posSet.n() > 0) throw StateError{ "a landmark partition is not available on a handle with position factors" };
+		if (s->dirSet.n() > 0) throw StateError{ "a landmark partition is not available on a handle with direction factors" };
 		if (s->partHi >= 0 && landmark_begin == s->partLo && landmark_end == s->partHi) return;      // (cuba_hip_set_graph_partition set it already)
 		s->partLo = landmark_begin; s->partHi = landmark_end;
 		s->haveStructure = false;

@@ -165,6 +165,14 @@ struct PositionFactorSet : FactorSet
 	void clear() { pose.clear(); z.clear(); arm.clear(); info.clear(); FactorSet::clear(); }
 };
 
+// direction factors on the poses: the information as the symmetrised 3 x 3; kind / delta empty: no factor has a kernel
+struct DirectionFactorSet : FactorSet
+{
+	std::vector<int> pose; std::vector<double> d, m, info;        // [n], [3 n], [3 n], [9 n]
+	int n() const { return (int)pose.size(); }
+	void clear() { pose.clear(); d.clear(); m.clear(); info.clear(); FactorSet::clear(); }
+};
+
 struct cuba_hip_solver;
 int cuba_hip_optimize_batch_impl(cuba_hip_solver** hs, int n, int niter, double* chi2, int* nDone);
 
@@ -619,18 +627,19 @@ struct cuba_hip_solver
 	// rebuilds it).  The landmark pass linearises them -- linearize() hands pf.lmp to it --, the chi2 sums take them as one more kind.
 	// On the poses again: position factors (cuba_hip_set_position_factors), kept as the caller gave them, with a device copy (pf.pos) in the
 	// internal pose order that need() makes once that order is known and again whenever it changes, as the pose priors'.  Their values never
-	// touch the structure.
+	// touch the structure.  Direction factors (cuba_hip_set_direction_factors; pf.dir) are kept and uploaded the same way.
 	// No factors of any kind: factors() is null, nothing of it is launched, no extra seed enters the pattern build, and every launch and kernel argument is as
 	// without this feature.
 	PoseFactorSet priorSet, relSet;
 	LandmarkPriorSet lmPriorSet;
 	PositionFactorSet posSet;
+	DirectionFactorSet dirSet;
 	DeviceFactors pf;
-	const DeviceFactors* factors() const { return priorSet.n() + relSet.n() + lmPriorSet.n() + posSet.n() > 0 ? &pf : nullptr; }
+	const DeviceFactors* factors() const { return priorSet.n() + relSet.n() + lmPriorSet.n() + posSet.n() + dirSet.n() > 0 ? &pf : nullptr; }
 	int factorParts() const { return factor_chi2_parts(factors()); }      // chi2 partials that follow the reprojection edges'
 	void clearFactors()
 	{
-		priorSet.clear(); relSet.clear(); lmPriorSet.clear(); posSet.clear();
+		priorSet.clear(); relSet.clear(); lmPriorSet.clear(); posSet.clear(); dirSet.clear();
 		h_relPairs.clear(); pf = DeviceFactors();
 	}
 	// the run-to-run memories that the values of the system feed (option "heuristics"): dropped by a change of the factors as by a new graph
@@ -647,6 +656,8 @@ struct cuba_hip_solver
 	void landmarkPriorChiSquares(double* out);
 	void setPositionFactors(int n, const int32_t* pose, const double* position, const double* leverArm, const double* info, const int32_t* kind, const double* delta);
 	void positionFactorChiSquares(double* out);
+	void setDirectionFactors(int n, const int32_t* pose, const double* worldDir, const double* measuredDir, const double* info, const int32_t* kind, const double* delta);
+	void directionFactorChiSquares(double* out);
 	// the edges' distinct free-free pairs (sorted keys i << 32 | j, i < j, caller's numbering) and the pairs the current structure was seeded
 	// with: every such pair owns a block of the reduced matrix, so need() rebuilds the structure exactly when the two sets differ
 	std::vector<uint64_t> h_relPairs, structRelPairs;

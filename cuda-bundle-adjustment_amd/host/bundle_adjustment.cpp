@@ -91,7 +91,7 @@ private:
 	std::vector<T*> items_;
 };
 
-// one kind of factor (cuba::PosePrior, cuba::RelativePoseEdge, cuba::LandmarkPrior, cuba::PositionFactor) as an object keeps it
+// one kind of factor (cuba::PosePrior, cuba::RelativePoseEdge, cuba::LandmarkPrior, cuba::PositionFactor, cuba::DirectionFactor) as an object keeps it
 template <class F>
 struct FactorList
 {
@@ -164,6 +164,7 @@ public:
 		for (BaseEdge* e : incident) removeEdge(e);
 		priors_.removeIf([&](const PosePrior* p) { return p->vertex == it->second; });
 		posFactors_.removeIf([&](const PositionFactor* f) { return f->vertex == it->second; });
+		dirFactors_.removeIf([&](const DirectionFactor* f) { return f->vertex == it->second; });
 		relEdges_.removeIf([&](const RelativePoseEdge* e) { return e->vertexI == it->second || e->vertexJ == it->second; });
 		poses_.erase(it);
 		posesDirty_ = true;
@@ -205,7 +206,7 @@ public:
 	void initialize() override
 	{
 		covPoseIndex_.clear(); covLmIndex_.clear();          // (marginal covariances describe the graph they were computed on)
-		priors_.dirty = relEdges_.dirty = lmPriors_.dirty = posFactors_.dirty = true;      // (the factors as they stand now go to the device with the next solve)
+		priors_.dirty = relEdges_.dirty = lmPriors_.dirty = posFactors_.dirty = dirFactors_.dirty = true;      // (the factors as they stand now go to the device with the next solve)
 		poseIdx_.clear();                                    // (the factors' pose index: rebuilt below from the poses active now)
 		const auto t0 = std::chrono::steady_clock::now();
 		static const bool dbg = std::getenv("CUBA_HIP_DEBUG") != nullptr;
@@ -394,7 +395,7 @@ public:
 			check(cuba_hip_build_structure(solver_), "cuba_hip_build_structure");
 			check(cuba_hip_set_graph_end(solver_), "cuba_hip_set_graph_end");
 			graphDirty_ = false;
-			priors_.dirty = lmPriors_.dirty = posFactors_.dirty = true;          // (an upload clears the handle's priors and position factors)
+			priors_.dirty = lmPriors_.dirty = posFactors_.dirty = dirFactors_.dirty = true;          // (an upload clears the handle's priors, position and direction factors)
 			uploadedOnce_ = true; edgesChangedSinceUpload_ = valuesChangedSinceUpload_ = false;       // from here on the device holds exactly these edges and values
 			(void)cuba_hip_get_counter(solver_, "graph_uploads", &uploadGeneration_);
 		}
@@ -403,14 +404,16 @@ public:
 		uploadRelativePoseEdges();
 		uploadLandmarkPriors();
 		uploadPositionFactors();
+		uploadDirectionFactors();
 	}
 
-	// ---- factors (extensions: cuba::addPosePrior, cuba::addRelativePoseEdge, cuba::addLandmarkPrior, cuba::addPositionFactor) --
+	// ---- factors (extensions: cuba::addPosePrior, cuba::addRelativePoseEdge, cuba::addLandmarkPrior, cuba::addPositionFactor, cuba::addDirectionFactor) --
 	// (public: the extension functions below remove and look up through them)
 	FactorList<PosePrior> priors_;
 	FactorList<RelativePoseEdge> relEdges_;
 	FactorList<LandmarkPrior> lmPriors_;
 	FactorList<PositionFactor> posFactors_;
+	FactorList<DirectionFactor> dirFactors_;
 	// index of a factor's vertex among the active poses (the map is built with the first factor of an initialize()); `refusal`: the message
 	// for a vertex that is not part of the graph
 	int32_t factorPose(const PoseVertex* v, const char* refusal)
@@ -547,6 +550,32 @@ public:
 		posFactors_.endUpload();
 	}
 
+	// ---- direction factors on the poses (extension: cuba::addDirectionFactor) ------------------------
+	void addDirectionFactor(DirectionFactor* f)
+	{
+		if (!f || !f->vertex) throw std::invalid_argument("cuba::addDirectionFactor: a factor needs a pose vertex");
+		dirFactors_.add(f);
+	}
+	void uploadDirectionFactors()
+	{
+		if (!dirFactors_.beginUpload()) return;
+		const std::vector<DirectionFactor*>& factors = dirFactors_.items;
+		const size_t n = factors.size();
+		std::vector<int32_t> pose(n);
+		std::vector<double> d(3 * n), m(3 * n), info(9 * n);
+		for (size_t k = 0; k < n; k++)
+		{
+			pose[k] = factorPose(factors[k]->vertex, "cuba::addDirectionFactor: the vertex of a factor is not part of the graph");
+			std::copy(factors[k]->worldDirection.begin(), factors[k]->worldDirection.end(), d.begin() + 3 * k);
+			std::copy(factors[k]->measurement.begin(), factors[k]->measurement.end(), m.begin() + 3 * k);
+			std::copy(factors[k]->information.begin(), factors[k]->information.end(), info.begin() + 9 * k);
+		}
+		const FactorKernels r = packKernels(factors);
+		check(cuba_hip_set_direction_factors(solver_, (int)n, pose.data(), d.data(), m.data(), info.data(), r.any ? r.kind.data() : nullptr,
+			r.any ? r.delta.data() : nullptr), "cuba_hip_set_direction_factors");
+		dirFactors_.endUpload();
+	}
+
 	// (optimize() in three steps, so that cuba::optimizeBatch can run the middle one for several objects at once)
 	void optimize(int niterations) override
 	{
@@ -626,6 +655,7 @@ public:
 		priors_.readChi([&](double* c) { check(cuba_hip_prior_chi_squares(solver_, c), "cuba_hip_prior_chi_squares"); });
 		lmPriors_.readChi([&](double* c) { check(cuba_hip_landmark_prior_chi_squares(solver_, c), "cuba_hip_landmark_prior_chi_squares"); });
 		posFactors_.readChi([&](double* c) { check(cuba_hip_position_factor_chi_squares(solver_, c), "cuba_hip_position_factor_chi_squares"); });
+		dirFactors_.readChi([&](double* c) { check(cuba_hip_direction_factor_chi_squares(solver_, c), "cuba_hip_direction_factor_chi_squares"); });
 		relEdges_.readChi([&](double* c) { check(cuba_hip_relative_pose_chi_squares(solver_, c), "cuba_hip_relative_pose_chi_squares"); });
 
 		// finalize (ref :512-526): estimates back into the caller's vertices
@@ -676,6 +706,7 @@ public:
 		relEdges_.items.clear(); relEdges_.chi.clear();
 		lmPriors_.items.clear(); lmPriors_.chi.clear();
 		posFactors_.items.clear(); posFactors_.chi.clear();
+		dirFactors_.items.clear(); dirFactors_.chi.clear();
 		posesDirty_ = landmarksDirty_ = edgesDirty_ = true;
 		initialized_ = false;
 	}
@@ -956,6 +987,27 @@ double positionFactorChiSquared(const CudaBundleAdjustment* object, const Positi
 {
 	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
 	return impl ? impl->posFactors_.chiSquared(factor) : 0.0;
+}
+
+// Extension (gravity, compass, vanishing directions): direction factors on the poses, effective at the next initialize()
+// (cuba_hip_set_direction_factors)
+void addDirectionFactor(CudaBundleAdjustment* object, DirectionFactor* factor)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (!impl) throw std::runtime_error("cuba::addDirectionFactor: not an object of this library");
+	impl->addDirectionFactor(factor);
+}
+
+void removeDirectionFactor(CudaBundleAdjustment* object, DirectionFactor* factor)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (impl) impl->dirFactors_.remove(factor);
+}
+
+double directionFactorChiSquared(const CudaBundleAdjustment* object, const DirectionFactor* factor)
+{
+	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
+	return impl ? impl->dirFactors_.chiSquared(factor) : 0.0;
 }
 
 // Extension (g2o's binary SE(3) edge): relative-pose edges, effective at the next initialize() (cuba_hip_set_relative_pose_edges)

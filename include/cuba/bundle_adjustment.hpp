@@ -198,4 +198,27 @@ void addPositionFactor(CudaBundleAdjustment* object, PositionFactor* factor);
 void removePositionFactor(CudaBundleAdjustment* object, PositionFactor* factor);
 double positionFactorChiSquared(const CudaBundleAdjustment* object, const PositionFactor* factor);
 
+// Extension (include/cuba_hip.h, cuba_hip_set_direction_factors): a direction factor on one pose vertex -- a known WORLD direction as seen
+// in the camera frame: the gravity vector of an accelerometer (roll and pitch, no yaw), a magnetometer or sun-sensor bearing, the
+// vanishing direction of a Manhattan world, one star of a star tracker.  `worldDirection` is d, `measurement` the same vector measured in
+// the camera frame, m (neither is normalised: unit vectors, or gravity in m/s^2 against a specific-force reading), `information`
+// symmetric 3 x 3, column-major; (I - m m^T) / sigma^2, of rank 2, is the usual one.  Objective term r^T Omega r with r = R d - m for the
+// vertex's world -> camera rotation R, or rho(r^T Omega r) when `kernel` is set (`delta` > 0 then).  A PosePrior cannot say this: it
+// needs a whole prior rotation.  Ownership and lifetime as for PosePrior: the caller owns the factor; additions, removals and changes
+// take effect at the next initialize(); the vertex must be part of the graph then.  removePoseVertex drops the vertex's factors, clear()
+// all.  directionFactorChiSquared: r^T Omega r at the estimate of the last optimize() (0 before one, and for a factor on a fixed vertex)
+// -- the plain value under a kernel too.
+struct DirectionFactor
+{
+	PoseVertex* vertex = nullptr;
+	std::array<double, 3> worldDirection{};
+	std::array<double, 3> measurement{};
+	std::array<double, 9> information{};
+	PoseFactorKernel kernel = PoseFactorKernel::NONE;
+	double delta = 0;
+};
+void addDirectionFactor(CudaBundleAdjustment* object, DirectionFactor* factor);
+void removeDirectionFactor(CudaBundleAdjustment* object, DirectionFactor* factor);
+double directionFactorChiSquared(const CudaBundleAdjustment* object, const DirectionFactor* factor);
+
 }  // namespace cuba

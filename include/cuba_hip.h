@@ -513,6 +513,44 @@ int cuba_hip_set_position_factors(cuba_hip_solver* s, int n, const int32_t* pose
 	const int32_t* kind, const double* delta);
 int cuba_hip_position_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor);
 
+/* ---- direction factors on the poses (gravity, compass, vanishing directions; the reference has no counterpart) ------------------------
+   A factor names pose `pose` (the caller's solver numbering, 0 <= pose < Pt; world -> camera T = [R | t]), a world vector d, the same
+   vector as measured in the camera frame, m, a 3 x 3 information matrix Omega (symmetric, column-major) and optionally a robust kernel
+   (kind, delta) of the pose factors' family (table above: 0 none, 1 Huber, 2 Tukey, 3 Cauchy, the same formulas): the gravity vector of
+   an accelerometer (roll and pitch, no yaw), a magnetometer or sun-sensor bearing, the vanishing direction of a Manhattan world, one star
+   of a star tracker.  An SE(3) prior cannot say this: it needs a whole prior rotation Rbar, and information that nulls the rotation about
+   Rbar d is exact only for a pure rotation about that axis.
+     residual     r = R d - m, e = r^T Omega r.  d and m are taken as given and are NOT normalised: unit vectors are the usual case, gravity
+                  in m/s^2 against a specific-force reading is another.  Omega = (I - m m^T) / sigma^2 (rank 2) is the usual information;
+                  full rank and all-zero information are valid too.
+     objective    rho(e); the LM objective F (cuba_hip_optimize's chi2, cuba_hip_compute_errors, the gain ratio) gains the factors' sum
+     linearised   with w = rho'(e) and dr/dd = [-[R d]x | 0] (3 x 6, d = [omega; upsilon] of the update T <- exp(d) T: R' = (I + [omega]x) R,
+                  so r' = r + omega x (R d); r lives in a vector space and needs no J_l; the translation columns are exactly zero).  With
+                  v = R d: w [v]x^T Omega [v]x into the rotation 3 x 3 of the pose's diagonal block of the reduced matrix, -w v x (Omega r)
+                  into the first three entries of the pose's bp and bsc; no second-order term.  The rest of the block and bp[3..6) are not
+                  touched.  lambda is added afterwards as to everything else; the assemble-only pass adds the terms too, so lambda_0's
+                  maximum diagonal includes them.  The terms follow those of every other kind in every sum.
+   Several factors on one pose are summed in the caller's order; factors on fixed poses are accepted and ignored (chi2 0).  Every solve
+   path honours them: the device-decision loop (a rejected trial's restore included), the host loop, both PCG forms, the exact solver,
+   the fp32 library, mixed precision, and the covariance entry points (the inverse of the weighted Hessian: with position fixes on two
+   poses, one direction factor off their line gives a graph without a fixed vertex its gauge).
+   cuba_hip_set_direction_factors replaces the whole set (n = 0 clears it): pose[n], world_dir[3 n], measured_dir[3 n], info[9 n], kind[n]
+   and delta[n] (both NULL: no kernels; kinds all 0 are no kernels).  Valid any time after cuba_hip_set_graph, which clears the set.
+   Setting factors never rebuilds the structure ("structure_builds" stays); it drops the run-to-run memories of option "heuristics" and
+   cached covariance blocks.
+   CUBA_HIP_ERR_INVALID_ARGUMENT, the handle unchanged: an index out of range, non-finite values, an information matrix that is not
+   symmetric (beyond 1e-9 of its largest entry; within it the two triangles are averaged), a kind outside 0..3, delta <= 0 on a kind != 0,
+   one of kind / delta without the other.
+   CUBA_HIP_ERR_STATE, the handle staying usable: a landmark-partitioned handle (and cuba_hip_set_partition on a handle with such factors,
+   hence the multi-GPU driver) and a graph without edges.  A handle with such factors takes part in cuba_hip_optimize_batch through the
+   path that batches the PCG iterations only (results stay bit-identical to solo runs).  A handle without them launches the kernels, with
+   the arguments, of a library without this entry point.
+   cuba_hip_direction_factor_chi_squares: the plain r^T Omega r of every factor at the current estimate, in the caller's order (what a
+   caller gates a doubtful reading on). */
+int cuba_hip_set_direction_factors(cuba_hip_solver* s, int n, const int32_t* pose, const double* world_dir, const double* measured_dir, const double* info,
+	const int32_t* kind, const double* delta);
+int cuba_hip_direction_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor);
+
 /* ---- introspection (parity tests) and multi-GPU plumbing ------------------------------------------ */
 
 /* Structure of the reduced system: upper-triangular BSR (replaces the accessors of
