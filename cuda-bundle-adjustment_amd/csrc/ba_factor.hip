@@ -27,7 +27,7 @@
 //     first three entries of the pose's bp / bsc, nothing else.
 //
 // A factor may carry a robust kernel (cuba_hip_set_pose_factor_robust_kernels; section 7e): with e = r^T Omega r its term is rho(e) and its
-// linearisation takes w Omega, w = rho'(e), for Omega (no second-order term, as the reprojection edges).  The four kernels that see a
+// linearisation takes w Omega, w = rho'(e), for Omega (no second-order term, as the reprojection edges).  The kernels that see a
 // residual are templates on ROBUST; a set without kernels has null kind / delta arrays and runs the `false` instantiations, which hold
 // nothing of this.  A landmark prior always carries a kind (none = 0) and comes with its kernel in one call.
 //
@@ -38,9 +38,12 @@
 // never between two of them.  (The position factors sit between the priors and the edges: no handle could hold them before they came, so
 // no existing sum changed.  The direction factors came when handles could combine all of the others, so they go last.)
 //
-// The kinds keep kernels of their own (a prior is not run as a one-ended edge: its sums would be taken in another order); they share the
-// device helpers below, the host-side validation, sorting and read-back -- the two pose kinds also packing and upload -- and one interface
-// (ba_kernels.hpp: DeviceFactors).
+// The kinds keep linearisation kernels of their own (a prior is not run as a one-ended edge: its sums would be taken in another order).
+// Everything else exists once: the device helpers below (the unary kinds' accumulators and their read-modify-write: zero_pose_sums,
+// add_pose_sums), one chi2 kernel over a per-kind residual, one device layout and one upload for the three unary kinds on the poses
+// (ba_kernels.hpp: DevicePoseGroups), the host-side validation, sorting and read-back, and one interface (ba_kernels.hpp: DeviceFactors;
+// ba_solver.hpp: the handle's table of its sets).  A new kind brings a residual, a Jacobian, a setter with its widths and nouns, and its
+// entry there.
 //
 //   prior_linearize_kernel     lane = free pose with priors: its priors in the caller's order, J^T Omega J / J^T Omega r summed in
 //                              registers, then added to the pose's diagonal block (upper triangle), bp and (mode 1) bsc -- one writer per
@@ -61,11 +64,9 @@
 //                              [v]x^T Omega [v]x, v = R d (6 numbers) and v x (Omega r) (3) summed in registers, one read-modify-write of the
 //                              upper triangle of the block's rotation 3 x 3, of bp[0..3) and (mode 1) bsc[0..3) -- one writer per number; the
 //                              last launch, behind the edges' gather
-//   prior_chi2_kernel,         lane = factor: r^T Omega r at the current estimate into the per-factor output and (rho of it) into per-workgroup
-//   relpose_chi2_kernel,       partials that the caller sums together with the reprojection edges' partials (fixed order, no atomics)
-//   landmark_prior_chi2_kernel,
-//   position_chi2_kernel,
-//   direction_chi2_kernel
+//   factor_chi2_kernel         lane = factor of one kind: r^T Omega r at the current estimate (factor_chi, an overload per kind) into the per-factor
+//                              output and (rho of it) into per-workgroup partials that the caller sums together with the reprojection
+//                              edges' partials (fixed order, no atomics)
 //
 // Host side: the caller's five sets (validated, kept in the caller's numbering), the edges' pair set (part of the topology) and the upload
 // of every set in the internal pose / landmark order.
@@ -143,6 +144,36 @@ __device__ __forceinline__ void chi2_partial(Scalar acc, Scalar* __restrict__ pa
 // workgroups (= partials) of a chi2 launch over n factors
 static int chi2_parts(int n) { return n > 0 ? std::min((n + CHI_BLOCK - 1) / CHI_BLOCK, CHI_MAX_GROUPS) : 0; }
 
+// ---- what the kinds' kernels share --------------------------------------------------------------------------------------------------
+
+// the sums of a lane of a unary kind's linearisation kernel over its pose's factors, in registers: J^T Omega J over the first D rows and
+// columns of the pose's diagonal block (upper triangle, H[c (c + 1) / 2 + r] as the pose pass stores it) and J^T Omega r.  D = 6, or 3 for a
+// kind whose translation columns are zero
+template <int D>
+__device__ __forceinline__ void zero_pose_sums(Scalar (&H)[D * (D + 1) / 2], Scalar (&gv)[D])
+{
+#pragma unroll
+	for (int k = 0; k < D * (D + 1) / 2; k++) H[k] = 0;
+#pragma unroll
+	for (int k = 0; k < D; k++) gv[k] = 0;
+}
+
+// one read-modify-write of the block's upper triangle, of bp and (mode 1) bsc of internal pose ip -- one writer per number; what lies beyond
+// D is not touched
+template <int D>
+__device__ __forceinline__ void add_pose_sums(const DeviceStructure& st, const DeviceSystem& sys, int ip, int mode, const Scalar (&H)[D * (D + 1) / 2], const Scalar (&gv)[D])
+{
+	Scalar* blk = sys.hsc + 36 * (size_t)st.hsc_rowptr[ip];
+#pragma unroll
+	for (int c = 0; c < D; c++)
+	{
+#pragma unroll
+		for (int rr = 0; rr <= c; rr++) blk[c * 6 + rr] += H[c * (c + 1) / 2 + rr];
+		sys.bp[6 * (size_t)ip + c] -= gv[c];
+		if (mode == 1) sys.bsc[6 * (size_t)ip + c] -= gv[c];
+	}
+}
+
 // ---- pose priors ------------------------------------------------------------------------------------------------------------------
 
 template <bool ROBUST>
@@ -154,10 +185,7 @@ __global__ __launch_bounds__(PRIOR_LIN_BLOCK) void prior_linearize_kernel(Device
 	Scalar q[4], t[3];
 	load_pose(g.q, g.t, ip, q, t);
 	Scalar H[21], gv[6];
-#pragma unroll
-	for (int k = 0; k < 21; k++) H[k] = 0;
-#pragma unroll
-	for (int k = 0; k < 6; k++) gv[k] = 0;
+	zero_pose_sums<6>(H, gv);
 	const int k1 = pr.pose_ptr[i + 1];
 	for (int k = pr.pose_ptr[i]; k < k1; k++)
 	{
@@ -206,38 +234,19 @@ __global__ __launch_bounds__(PRIOR_LIN_BLOCK) void prior_linearize_kernel(Device
 			else gv[c] += s;
 		}
 	}
-	Scalar* blk = sys.hsc + 36 * (size_t)st.hsc_rowptr[ip];
-#pragma unroll
-	for (int c = 0; c < 6; c++)
-	{
-#pragma unroll
-		for (int rr = 0; rr <= c; rr++) blk[c * 6 + rr] += H[c * (c + 1) / 2 + rr];
-		sys.bp[6 * (size_t)ip + c] -= gv[c];
-		if (mode == 1) sys.bsc[6 * (size_t)ip + c] -= gv[c];
-	}
+	add_pose_sums<6>(st, sys, ip, mode, H, gv);
 }
 
-template <bool ROBUST>
-__global__ __launch_bounds__(CHI_BLOCK) void prior_chi2_kernel(DeviceGraph g, DevicePriors pr, Scalar* __restrict__ parts)
+// r^T Omega r of prior k at the current estimate (factor_chi2_kernel)
+__device__ __forceinline__ Scalar factor_chi(const DeviceGraph& g, const DevicePriors& pr, int k)
 {
-	Scalar acc = 0;
-	for (int k = blockIdx.x * CHI_BLOCK + threadIdx.x; k < pr.n; k += gridDim.x * CHI_BLOCK)
-	{
-		const int ip = pr.pose[k];
-		Scalar chi = 0;
-		if (ip < g.Pf)
-		{
-			Scalar q[4], t[3], qb[4], tb[3], r[6], A[3][3], Or[6];
-			load_pose(g.q, g.t, ip, q, t);
-			load_pose(pr.qbar, pr.tbar, k, qb, tb);
-			prior_residual(q, t, qb, tb, r, A);
-			chi = info_times(pr.info + 36 * (size_t)k, r, Or);
-		}
-		pr.chi[k] = chi;
-		if constexpr (ROBUST) acc += factor_rho(pr.rk_kind[k], pr.rk_delta[k], chi);
-		else acc += chi;
-	}
-	chi2_partial(acc, parts);
+	const int ip = pr.pose[k];
+	if (ip >= g.Pf) return 0;
+	Scalar q[4], t[3], qb[4], tb[3], r[6], A[3][3], Or[6];
+	load_pose(g.q, g.t, ip, q, t);
+	load_pose(pr.qbar, pr.tbar, k, qb, tb);
+	prior_residual(q, t, qb, tb, r, A);
+	return info_times(pr.info + 36 * (size_t)k, r, Or);
 }
 
 // ---- relative-pose edges ----------------------------------------------------------------------------------------------------------
@@ -392,47 +401,27 @@ __global__ __launch_bounds__(REL_GATHER_BLOCK) void relpose_gather_kernel(Device
 	}
 }
 
-template <bool ROBUST>
-__global__ __launch_bounds__(CHI_BLOCK) void relpose_chi2_kernel(DeviceGraph g, DeviceRelPoses rp, Scalar* __restrict__ parts)
+// r^T Omega r of edge k at the current estimate (factor_chi2_kernel)
+__device__ __forceinline__ Scalar factor_chi(const DeviceGraph& g, const DeviceRelPoses& rp, int k)
 {
-	Scalar acc = 0;
-	for (int k = blockIdx.x * CHI_BLOCK + threadIdx.x; k < rp.n; k += gridDim.x * CHI_BLOCK)
-	{
-		Scalar chi = 0;
-		if (k < rp.nActive)
-		{
-			RelEnds e;
-			load_rel_ends(g, rp, k, e);
-			Scalar r[6], A[3][3], Or[6];
-			rel_residual(e, rp, k, r, A);
-			chi = info_times(rp.info + 36 * (size_t)k, r, Or);
-		}
-		rp.chi[k] = chi;
-		if constexpr (ROBUST) acc += factor_rho(rp.rk_kind[k], rp.rk_delta[k], chi);
-		else acc += chi;
-	}
-	chi2_partial(acc, parts);
+	if (k >= rp.nActive) return 0;
+	RelEnds e;
+	load_rel_ends(g, rp, k, e);
+	Scalar r[6], A[3][3], Or[6];
+	rel_residual(e, rp, k, r, A);
+	return info_times(rp.info + 36 * (size_t)k, r, Or);
 }
 
 // ---- landmark priors --------------------------------------------------------------------------------------------------------------
 
-__global__ __launch_bounds__(CHI_BLOCK) void landmark_prior_chi2_kernel(DeviceGraph g, DeviceLandmarkPriors lp, Scalar* __restrict__ parts)
+// r^T Omega r of prior k at the current estimate (factor_chi2_kernel; the landmark pass linearises these priors)
+__device__ __forceinline__ Scalar factor_chi(const DeviceGraph& g, const DeviceLandmarkPriors& lp, int k)
 {
-	Scalar acc = 0;
-	for (int k = blockIdx.x * CHI_BLOCK + threadIdx.x; k < lp.n; k += gridDim.x * CHI_BLOCK)
-	{
-		const int il = lp.lm[k];
-		Scalar chi = 0;
-		if (il < g.Lf)
-		{
-			const Scalar X[3] = { g.Xw[3 * (size_t)il], g.Xw[3 * (size_t)il + 1], g.Xw[3 * (size_t)il + 2] };
-			Scalar Or[3];
-			chi = landmark_prior_residual(lp, k, X, Or);
-		}
-		lp.chi[k] = chi;
-		acc += factor_rho(lp.rk_kind[k], lp.rk_delta[k], chi);
-	}
-	chi2_partial(acc, parts);
+	const int il = lp.lm[k];
+	if (il >= g.Lf) return 0;
+	const Scalar X[3] = { g.Xw[3 * (size_t)il], g.Xw[3 * (size_t)il + 1], g.Xw[3 * (size_t)il + 2] };
+	Scalar Or[3];
+	return landmark_prior_residual(lp, k, X, Or);
 }
 
 // ---- position factors -------------------------------------------------------------------------------------------------------------
@@ -461,10 +450,7 @@ __global__ __launch_bounds__(POS_LIN_BLOCK) void position_linearize_kernel(Devic
 	load_pose(g.q, g.t, ip, q, t);
 	const Rot3 R = quat_to_rot(q[0], q[1], q[2], q[3]);
 	Scalar H[21], gv[6];
-#pragma unroll
-	for (int k = 0; k < 21; k++) H[k] = 0;
-#pragma unroll
-	for (int k = 0; k < 6; k++) gv[k] = 0;
+	zero_pose_sums<6>(H, gv);
 	const int k1 = pp.pose_ptr[i + 1];
 	for (int k = pp.pose_ptr[i]; k < k1; k++)
 	{
@@ -504,37 +490,18 @@ __global__ __launch_bounds__(POS_LIN_BLOCK) void position_linearize_kernel(Devic
 			else gv[c] += s;
 		}
 	}
-	Scalar* blk = sys.hsc + 36 * (size_t)st.hsc_rowptr[ip];
-#pragma unroll
-	for (int c = 0; c < 6; c++)
-	{
-#pragma unroll
-		for (int rr = 0; rr <= c; rr++) blk[c * 6 + rr] += H[c * (c + 1) / 2 + rr];
-		sys.bp[6 * (size_t)ip + c] -= gv[c];
-		if (mode == 1) sys.bsc[6 * (size_t)ip + c] -= gv[c];
-	}
+	add_pose_sums<6>(st, sys, ip, mode, H, gv);
 }
 
-template <bool ROBUST>
-__global__ __launch_bounds__(CHI_BLOCK) void position_chi2_kernel(DeviceGraph g, DevicePositionFactors pp, Scalar* __restrict__ parts)
+// r^T Omega r of factor k at the current estimate (factor_chi2_kernel)
+__device__ __forceinline__ Scalar factor_chi(const DeviceGraph& g, const DevicePositionFactors& pp, int k)
 {
-	Scalar acc = 0;
-	for (int k = blockIdx.x * CHI_BLOCK + threadIdx.x; k < pp.n; k += gridDim.x * CHI_BLOCK)
-	{
-		const int ip = pp.pose[k];
-		Scalar chi = 0;
-		if (ip < g.Pf)
-		{
-			Scalar q[4], t[3], r[3], Or[3];
-			load_pose(g.q, g.t, ip, q, t);
-			const Rot3 R = quat_to_rot(q[0], q[1], q[2], q[3]);
-			chi = position_residual(pp, k, R.m, t, r, Or);
-		}
-		pp.chi[k] = chi;
-		if constexpr (ROBUST) acc += factor_rho(pp.rk_kind[k], pp.rk_delta[k], chi);
-		else acc += chi;
-	}
-	chi2_partial(acc, parts);
+	const int ip = pp.pose[k];
+	if (ip >= g.Pf) return 0;
+	Scalar q[4], t[3], r[3], Or[3];
+	load_pose(g.q, g.t, ip, q, t);
+	const Rot3 R = quat_to_rot(q[0], q[1], q[2], q[3]);
+	return position_residual(pp, k, R.m, t, r, Or);
 }
 
 // ---- direction factors ------------------------------------------------------------------------------------------------------------
@@ -566,10 +533,7 @@ __global__ __launch_bounds__(DIR_LIN_BLOCK) void direction_linearize_kernel(Devi
 	const Scalar* q = g.q + 4 * (size_t)ip;
 	const Rot3 R = quat_to_rot(q[0], q[1], q[2], q[3]);
 	Scalar H[6], gv[3];
-#pragma unroll
-	for (int k = 0; k < 6; k++) H[k] = 0;
-#pragma unroll
-	for (int k = 0; k < 3; k++) gv[k] = 0;
+	zero_pose_sums<3>(H, gv);
 	const int k1 = df.pose_ptr[i + 1];
 	for (int k = df.pose_ptr[i]; k < k1; k++)
 	{
@@ -603,35 +567,35 @@ __global__ __launch_bounds__(DIR_LIN_BLOCK) void direction_linearize_kernel(Devi
 			else gv[c] += x[c];
 		}
 	}
-	// (the translation rows and columns of the block, bp[3..6) and bsc[3..6) are not this kind's: they are not touched)
-	Scalar* blk = sys.hsc + 36 * (size_t)st.hsc_rowptr[ip];
-#pragma unroll
-	for (int c = 0; c < 3; c++)
-	{
-#pragma unroll
-		for (int rr = 0; rr <= c; rr++) blk[c * 6 + rr] += H[c * (c + 1) / 2 + rr];
-		sys.bp[6 * (size_t)ip + c] -= gv[c];
-		if (mode == 1) sys.bsc[6 * (size_t)ip + c] -= gv[c];
-	}
+	// (the translation rows and columns of the block, bp[3..6) and bsc[3..6) are not this kind's: add_pose_sums<3> does not touch them)
+	add_pose_sums<3>(st, sys, ip, mode, H, gv);
 }
 
-template <bool ROBUST>
-__global__ __launch_bounds__(CHI_BLOCK) void direction_chi2_kernel(DeviceGraph g, DeviceDirectionFactors df, Scalar* __restrict__ parts)
+// r^T Omega r of factor k at the current estimate (factor_chi2_kernel)
+__device__ __forceinline__ Scalar factor_chi(const DeviceGraph& g, const DeviceDirectionFactors& df, int k)
+{
+	const int ip = df.pose[k];
+	if (ip >= g.Pf) return 0;
+	const Scalar* q = g.q + 4 * (size_t)ip;
+	const Rot3 R = quat_to_rot(q[0], q[1], q[2], q[3]);
+	Scalar v[3], Or[3];
+	return direction_residual(df, k, R.m, v, Or);
+}
+
+// ---- chi2 -------------------------------------------------------------------------------------------------------------------------
+
+// The chi2 of a kind: lane = factor, r^T Omega r at the current estimate -- factor_chi(g, kind, k), one overload per kind above, 0 for a factor
+// on a fixed vertex -- into the per-factor output and (rho of it) into per-workgroup partials that the caller sums together with the
+// reprojection edges' partials (fixed order, no atomics)
+template <class Kind, bool ROBUST>
+__global__ __launch_bounds__(CHI_BLOCK) void factor_chi2_kernel(DeviceGraph g, Kind f, Scalar* __restrict__ parts)
 {
 	Scalar acc = 0;
-	for (int k = blockIdx.x * CHI_BLOCK + threadIdx.x; k < df.n; k += gridDim.x * CHI_BLOCK)
+	for (int k = blockIdx.x * CHI_BLOCK + threadIdx.x; k < f.n; k += gridDim.x * CHI_BLOCK)
 	{
-		const int ip = df.pose[k];
-		Scalar chi = 0;
-		if (ip < g.Pf)
-		{
-			const Scalar* q = g.q + 4 * (size_t)ip;
-			const Rot3 R = quat_to_rot(q[0], q[1], q[2], q[3]);
-			Scalar v[3], Or[3];
-			chi = direction_residual(df, k, R.m, v, Or);
-		}
-		df.chi[k] = chi;
-		if constexpr (ROBUST) acc += factor_rho(df.rk_kind[k], df.rk_delta[k], chi);
+		const Scalar chi = factor_chi(g, f, k);
+		f.chi[k] = chi;
+		if constexpr (ROBUST) acc += factor_rho(f.rk_kind[k], f.rk_delta[k], chi);
 		else acc += chi;
 	}
 	chi2_partial(acc, parts);
@@ -639,57 +603,35 @@ __global__ __launch_bounds__(CHI_BLOCK) void direction_chi2_kernel(DeviceGraph g
 
 // ---- launches ---------------------------------------------------------------------------------------------------------------------
 
-static void launch_prior_chi2(const DeviceGraph& g, const DevicePriors& pr, Scalar* parts, hipStream_t s)
-{
-	const int grid = chi2_parts(pr.n);
-	if (grid <= 0) return;
-	if (pr.rk_kind) hipLaunchKernelGGL(prior_chi2_kernel<true>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, pr, parts);
-	else hipLaunchKernelGGL(prior_chi2_kernel<false>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, pr, parts);
-}
+// (a landmark prior always carries a kind: that kind has no ROBUST = false instantiation)
+template <class Kind> constexpr bool ALWAYS_ROBUST = std::is_same<Kind, DeviceLandmarkPriors>::value;
 
-static void launch_relpose_chi2(const DeviceGraph& g, const DeviceRelPoses& rp, Scalar* parts, hipStream_t s)
+// the chi2 launch of one kind; returns its workgroups (= partials)
+template <class Kind>
+static int launch_chi2(const DeviceGraph& g, const Kind& f, Scalar* parts, hipStream_t s)
 {
-	const int grid = chi2_parts(rp.n);
-	if (grid <= 0) return;
-	if (rp.rk_kind) hipLaunchKernelGGL(relpose_chi2_kernel<true>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, rp, parts);
-	else hipLaunchKernelGGL(relpose_chi2_kernel<false>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, rp, parts);
-}
-
-static void launch_landmark_prior_chi2(const DeviceGraph& g, const DeviceLandmarkPriors& lp, Scalar* parts, hipStream_t s)
-{
-	const int grid = chi2_parts(lp.n);
-	if (grid <= 0) return;
-	hipLaunchKernelGGL(landmark_prior_chi2_kernel, dim3(grid), dim3(CHI_BLOCK), 0, s, g, lp, parts);
-}
-
-static void launch_position_chi2(const DeviceGraph& g, const DevicePositionFactors& pp, Scalar* parts, hipStream_t s)
-{
-	const int grid = chi2_parts(pp.n);
-	if (grid <= 0) return;
-	if (pp.rk_kind) hipLaunchKernelGGL(position_chi2_kernel<true>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, pp, parts);
-	else hipLaunchKernelGGL(position_chi2_kernel<false>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, pp, parts);
-}
-
-static void launch_direction_chi2(const DeviceGraph& g, const DeviceDirectionFactors& df, Scalar* parts, hipStream_t s)
-{
-	const int grid = chi2_parts(df.n);
-	if (grid <= 0) return;
-	if (df.rk_kind) hipLaunchKernelGGL(direction_chi2_kernel<true>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, df, parts);
-	else hipLaunchKernelGGL(direction_chi2_kernel<false>, dim3(grid), dim3(CHI_BLOCK), 0, s, g, df, parts);
+	const int grid = chi2_parts(f.n);
+	if (grid <= 0) return 0;
+	if (ALWAYS_ROBUST<Kind> || f.rk_kind) hipLaunchKernelGGL((factor_chi2_kernel<Kind, true>), dim3(grid), dim3(CHI_BLOCK), 0, s, g, f, parts);
+	else if constexpr (!ALWAYS_ROBUST<Kind>) hipLaunchKernelGGL((factor_chi2_kernel<Kind, false>), dim3(grid), dim3(CHI_BLOCK), 0, s, g, f, parts);
+	return grid;
 }
 
 int factor_chi2_parts(const DeviceFactors* pf)
 {
-	return pf ? chi2_parts(pf->priors.n) + chi2_parts(pf->rel.n) + chi2_parts(pf->lmp.n) + chi2_parts(pf->pos.n) + chi2_parts(pf->dir.n) : 0;
+	int parts = 0;
+	if (pf) pf->each([&](const auto& f) { parts += chi2_parts(f.n); });
+	return parts;
 }
 
-void launch_factor_chi2(const DeviceGraph& g, const DeviceFactors& pf, Scalar* parts, hipStream_t s)
+void launch_factor_chi2(const DeviceGraph& g, const DeviceFactors& pf, Scalar* parts, hipStream_t s, int only)
 {
-	launch_prior_chi2(g, pf.priors, parts, s);
-	launch_relpose_chi2(g, pf.rel, parts + chi2_parts(pf.priors.n), s);
-	launch_landmark_prior_chi2(g, pf.lmp, parts + chi2_parts(pf.priors.n) + chi2_parts(pf.rel.n), s);
-	launch_position_chi2(g, pf.pos, parts + chi2_parts(pf.priors.n) + chi2_parts(pf.rel.n) + chi2_parts(pf.lmp.n), s);
-	launch_direction_chi2(g, pf.dir, parts + chi2_parts(pf.priors.n) + chi2_parts(pf.rel.n) + chi2_parts(pf.lmp.n) + chi2_parts(pf.pos.n), s);
+	int kind = 0, offset = 0;
+	pf.each([&](const auto& f) {
+		if (only < 0) offset += launch_chi2(g, f, parts + offset, s);
+		else if (only == kind) launch_chi2(g, f, parts, s);
+		kind++;
+	});
 }
 
 void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DeviceFactors& pf, int mode, hipStream_t s)
@@ -752,24 +694,68 @@ static void check_factor_kernel(int kind, double delta, const char* noun)
 	if (kind != cubahip::POSE_FACTOR_KERNEL_NONE && !(delta > 0)) throw ArgError{ "robust-kernel delta must be positive" };
 }
 
-// the q | t | information of factor k of a caller's set into `v` (sized by the caller): finite, the quaternion normalised, the information
-// symmetric and symmetrised.  `what`, `kind`: how the messages name the factor's measurement ("prior" / "relative") and its kind
-static void take_factor_values(PoseFactorValues& v, int k, const double* q, const double* t, const double* info, const std::string& what, const std::string& kind)
+// what every setter checks before it reads its arrays: the state of the handle, the count, and for a non-empty set that the arrays are
+// there (`arrays`) and that kind and delta come together.  The messages name the kind by the set's nouns; `edges`: what the graph must have
+static void check_factor_call(const cuba_hip_solver& s, const FactorSet& set, int n, bool arrays, const int32_t* kind, const double* delta, const char* edges = "edges")
+{
+	const std::string noun = set.noun, plural = set.plural;
+	if (!s.haveGraph) throw StateError{ "set_graph must be called first" };
+	if (n < 0) throw ArgError{ "negative " + noun + " count" };
+	if (n == 0) return;
+	if (s.partHi >= 0 || s.valuesPartial) throw StateError{ plural + " are not available on a landmark-partitioned handle" };
+	if (s.E == 0) throw StateError{ plural + " need a graph with " + edges };
+	if (!arrays) throw ArgError{ "null " + noun + " array" };
+	if ((kind == nullptr) != (delta == nullptr)) throw ArgError{ noun + " kernels: kind and delta come together" };
+}
+
+// a caller's set, validated: the vertex of every factor, its two measurement arrays, the symmetrised information and the kernels
+struct TakenFactors { std::vector<int> idx; std::vector<double> a, b, info; std::vector<int> kind; std::vector<double> delta; };
+
+// a caller's set of factors with a 3-vector residual, factor by factor: the index of its vertex (`vertex`: "pose" / "landmark") within
+// [0, limit), the vectors a and -- where given; zero otherwise, none at all without a whatB -- b finite, the information symmetric, the
+// kernel a known one.  kind / delta come back as given, or empty when no factor has a real kernel (kinds all 0: no kernels, the set runs
+// the kernels' ROBUST = false instantiations)
+static TakenFactors take_factors3(const FactorSet& set, int n, const int32_t* idx, int limit, const char* vertex, const double* a, const char* whatA, const double* b,
+	const char* whatB, const double* info, const int32_t* kind, const double* delta)
+{
+	const std::string noun = set.noun;
+	TakenFactors v;
+	v.idx.resize((size_t)n); v.a.resize((size_t)3 * n); v.b.assign(whatB ? (size_t)3 * n : 0, 0.0); v.info.resize((size_t)9 * n);
+	bool any = false;
+	for (int k = 0; k < n; k++)
+	{
+		if (idx[k] < 0 || idx[k] >= limit) throw ArgError{ noun + ": " + vertex + " index out of range" };
+		v.idx[k] = idx[k];
+		for (size_t x = 3 * (size_t)k; x < 3 * (size_t)k + 3; x++)
+		{
+			if (!std::isfinite(a[x])) throw ArgError{ "non-finite " + noun + " " + whatA };
+			v.a[x] = a[x];
+			if (!b) continue;
+			if (!std::isfinite(b[x])) throw ArgError{ "non-finite " + noun + " " + whatB };
+			v.b[x] = b[x];
+		}
+		take_information<3>(info + 9 * (size_t)k, v.info.data() + 9 * (size_t)k, noun);
+		if (kind)
+		{
+			check_factor_kernel(kind[k], delta[k], set.noun);
+			any = any || kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE;
+		}
+	}
+	if (any) { v.kind.assign(kind, kind + n); v.delta.assign(delta, delta + n); }
+	return v;
+}
+
+// the q | t | information of factor k of a caller's set into vq | vt | vinfo (sized by the caller): finite, the quaternion normalised, the
+// information symmetric and symmetrised.  `what`, `kind`: how the messages name the factor's measurement ("prior" / "relative") and its kind
+static void take_factor_values(double* vq, double* vt, double* vinfo, int k, const double* q, const double* t, const double* info, const std::string& what, const std::string& kind)
 {
 	double nq = 0;
 	for (int i = 0; i < 4; i++) { if (!std::isfinite(q[4 * (size_t)k + i])) throw ArgError{ "non-finite " + what + " rotation" }; nq += q[4 * (size_t)k + i] * q[4 * (size_t)k + i]; }
 	nq = std::sqrt(nq);
 	if (!(nq > 0) || !std::isfinite(nq)) throw ArgError{ kind + " quaternion of zero norm" };
-	for (int i = 0; i < 4; i++) v.q[4 * (size_t)k + i] = q[4 * (size_t)k + i] / nq;
-	for (int i = 0; i < 3; i++) { if (!std::isfinite(t[3 * (size_t)k + i])) throw ArgError{ "non-finite " + what + " translation" }; v.t[3 * (size_t)k + i] = t[3 * (size_t)k + i]; }
-	take_information<6>(info + 36 * (size_t)k, v.info.data() + 36 * (size_t)k, kind);
-}
-
-static PoseFactorValues sized_factor_values(int n, bool binary)
-{
-	PoseFactorValues v;
-	v.pi.resize((size_t)n); v.pj.resize(binary ? (size_t)n : 0); v.q.resize((size_t)4 * n); v.t.resize((size_t)3 * n); v.info.resize((size_t)36 * n);
-	return v;
+	for (int i = 0; i < 4; i++) vq[4 * (size_t)k + i] = q[4 * (size_t)k + i] / nq;
+	for (int i = 0; i < 3; i++) { if (!std::isfinite(t[3 * (size_t)k + i])) throw ArgError{ "non-finite " + what + " translation" }; vt[3 * (size_t)k + i] = t[3 * (size_t)k + i]; }
+	take_information<6>(info + 36 * (size_t)k, vinfo + 36 * (size_t)k, kind);
 }
 
 // a validated set replaces the handle's: its device copy is due, and the run-to-run memories that the values of the system feed go, as a
@@ -781,55 +767,51 @@ static void forget_factor_memories(cuba_hip_solver& s, FactorSet& set)
 }
 
 // (the replaced set is a new set: the robust kernels of the previous one go with it)
-static void adopt_factor_values(cuba_hip_solver& s, PoseFactorSet& set, PoseFactorValues&& v)
+static void adopt_unary_pose_factors(cuba_hip_solver& s, UnaryPoseFactorSet& set, TakenFactors& v)
 {
-	set.v = std::move(v);
-	set.kind.clear(); set.delta.clear();
+	set.pose.swap(v.idx); set.a.swap(v.a); set.b.swap(v.b); set.info.swap(v.info); set.kind.swap(v.kind); set.delta.swap(v.delta);
 	forget_factor_memories(s, set);
+	set.dev = cubahip::DevicePoseGroups();
 }
 
 void cuba_hip_solver::setPosePriors(int n, const int32_t* pose, const double* q, const double* t, const double* info)
 {
-	if (!haveGraph) throw StateError{ "set_graph must be called first" };
-	if (n < 0) throw ArgError{ "negative prior count" };
-	if (n > 0 && (partHi >= 0 || valuesPartial)) throw StateError{ "pose priors are not available on a landmark-partitioned handle" };
-	if (n > 0 && E == 0) throw StateError{ "pose priors need a graph with edges" };
-	if (n > 0 && (!pose || !q || !t || !info)) throw ArgError{ "null prior array" };
-	PoseFactorValues v = sized_factor_values(n, false);
+	check_factor_call(*this, priorSet, n, pose && q && t && info, nullptr, nullptr);
+	TakenFactors v;
+	v.idx.resize((size_t)n); v.a.resize((size_t)4 * n); v.b.resize((size_t)3 * n); v.info.resize((size_t)36 * n);
 	for (int k = 0; k < n; k++)
 	{
 		if (pose[k] < 0 || pose[k] >= Pt) throw ArgError{ "prior pose index out of range" };
-		v.pi[k] = pose[k];
-		take_factor_values(v, k, q, t, info, "prior", "prior");
+		v.idx[k] = pose[k];
+		take_factor_values(v.a.data(), v.b.data(), v.info.data(), k, q, t, info, "prior", "prior");
 	}
-	adopt_factor_values(*this, priorSet, std::move(v));
-	pf.priors = DevicePriors();
+	adopt_unary_pose_factors(*this, priorSet, v);
 }
 
 void cuba_hip_solver::setRelativePoseEdges(int n, const int32_t* pi, const int32_t* pj, const double* q, const double* t, const double* info)
 {
-	if (!haveGraph) throw StateError{ "set_graph must be called first" };
-	if (n < 0) throw ArgError{ "negative relative-pose edge count" };
-	if (n > 0 && (partHi >= 0 || valuesPartial)) throw StateError{ "relative-pose edges are not available on a landmark-partitioned handle" };
-	if (n > 0 && E == 0) throw StateError{ "relative-pose edges need a graph with reprojection edges" };
-	if (n > 0 && (!pi || !pj || !q || !t || !info)) throw ArgError{ "null relative-pose edge array" };
-	PoseFactorValues v = sized_factor_values(n, true);
+	check_factor_call(*this, relSet, n, pi && pj && q && t && info, nullptr, nullptr, "reprojection edges");
+	std::vector<int> vi((size_t)n), vj((size_t)n);
+	std::vector<double> vq((size_t)4 * n), vt((size_t)3 * n), vinfo((size_t)36 * n);
 	for (int k = 0; k < n; k++)
 	{
 		if (pi[k] < 0 || pi[k] >= Pt || pj[k] < 0 || pj[k] >= Pt) throw ArgError{ "relative-pose edge: pose index out of range" };
 		if (pi[k] == pj[k]) throw ArgError{ "relative-pose edge between a pose and itself" };
-		v.pi[k] = pi[k]; v.pj[k] = pj[k];
-		take_factor_values(v, k, q, t, info, "relative", "relative-pose");
+		vi[k] = pi[k]; vj[k] = pj[k];
+		take_factor_values(vq.data(), vt.data(), vinfo.data(), k, q, t, info, "relative", "relative-pose");
 	}
 	// the distinct free-free pairs (caller's numbering, smaller index first): part of the topology -- need() rebuilds the structure when
 	// they differ from the pairs the current one was seeded with
 	std::vector<uint64_t> pairs;
 	for (int k = 0; k < n; k++)
-		if (v.pi[k] < Pf && v.pj[k] < Pf) pairs.push_back(((uint64_t)(uint32_t)std::min(v.pi[k], v.pj[k]) << 32) | (uint32_t)std::max(v.pi[k], v.pj[k]));
+		if (vi[k] < Pf && vj[k] < Pf) pairs.push_back(((uint64_t)(uint32_t)std::min(vi[k], vj[k]) << 32) | (uint32_t)std::max(vi[k], vj[k]));
 	std::sort(pairs.begin(), pairs.end());
 	pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
 	h_relPairs.swap(pairs);
-	adopt_factor_values(*this, relSet, std::move(v));
+	// (the replaced set is a new set: the robust kernels of the previous one go with it)
+	relSet.pi.swap(vi); relSet.pj.swap(vj); relSet.q.swap(vq); relSet.t.swap(vt); relSet.info.swap(vinfo);
+	relSet.kind.clear(); relSet.delta.clear();
+	forget_factor_memories(*this, relSet);
 	pf.rel = DeviceRelPoses();
 	covBlocksValid = false;          // (the covariance blocks describe the edge set -- and the block pattern -- they were computed on)
 }
@@ -840,7 +822,7 @@ void cuba_hip_solver::setPoseFactorRobustKernels(int factorType, int n, const in
 {
 	if (!haveGraph) throw StateError{ "set_graph must be called first" };
 	if (factorType < 0 || factorType > 1) throw ArgError{ "bad pose-factor type" };
-	PoseFactorSet& set = factorType == 0 ? priorSet : relSet;
+	FactorSet& set = factorType == 0 ? static_cast<FactorSet&>(priorSet) : relSet;
 	if (n != 0 && n != set.n()) throw ArgError{ "robust kernels: the count differs from the set's" };
 	if (n > 0 && (!kind || !delta)) throw ArgError{ "null robust-kernel array" };
 	bool any = false;
@@ -854,6 +836,45 @@ void cuba_hip_solver::setPoseFactorRobustKernels(int factorType, int n, const in
 	forget_factor_memories(*this, set);
 	(factorType == 0 ? pf.priors.rk_kind : pf.rel.rk_kind) = nullptr;
 	(factorType == 0 ? pf.priors.rk_delta : pf.rel.rk_delta) = nullptr;
+	covBlocksValid = false;
+}
+
+void cuba_hip_solver::setLandmarkPriors(int n, const int32_t* landmark, const double* xyz, const double* info, const int32_t* kind, const double* delta)
+{
+	check_factor_call(*this, lmPriorSet, n, landmark && xyz && info, kind, delta);
+	TakenFactors v = take_factors3(lmPriorSet, n, landmark, Lt, "landmark", xyz, "position", nullptr, nullptr, info, kind, delta);
+	// the symmetrised information's upper triangle, in the packing of sym3_idx; every prior with a kernel (none: kind 0, delta 1)
+	std::vector<double> U((size_t)6 * n), dl((size_t)n, 1.0);
+	std::vector<int> kd((size_t)n, cubahip::POSE_FACTOR_KERNEL_NONE);
+	for (int k = 0; k < n; k++)
+	{
+		const double* S = v.info.data() + 9 * (size_t)k;
+		double* u = U.data() + 6 * (size_t)k;
+		u[0] = S[0]; u[1] = S[3]; u[2] = S[6]; u[3] = S[4]; u[4] = S[7]; u[5] = S[8];
+		if (!v.kind.empty() && v.kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE) { kd[k] = v.kind[k]; dl[k] = v.delta[k]; }
+	}
+	lmPriorSet.lm.swap(v.idx); lmPriorSet.xyz.swap(v.a); lmPriorSet.info.swap(U); lmPriorSet.kind.swap(kd); lmPriorSet.delta.swap(dl);
+	forget_factor_memories(*this, lmPriorSet);
+	pf.lmp = DeviceLandmarkPriors();
+	covBlocksValid = false;
+}
+
+void cuba_hip_solver::setPositionFactors(int n, const int32_t* pose, const double* position, const double* leverArm, const double* info, const int32_t* kind,
+	const double* delta)
+{
+	check_factor_call(*this, posSet, n, pose && position && info, kind, delta);
+	TakenFactors v = take_factors3(posSet, n, pose, Pt, "pose", position, "position", leverArm, "lever arm", info, kind, delta);
+	adopt_unary_pose_factors(*this, posSet, v);
+	covBlocksValid = false;
+}
+
+// (the vectors are taken as given: neither is normalised)
+void cuba_hip_solver::setDirectionFactors(int n, const int32_t* pose, const double* worldDir, const double* measuredDir, const double* info, const int32_t* kind,
+	const double* delta)
+{
+	check_factor_call(*this, dirSet, n, pose && worldDir && measuredDir && info, kind, delta);
+	TakenFactors v = take_factors3(dirSet, n, pose, Pt, "pose", worldDir, "world direction", measuredDir, "measurement", info, kind, delta);
+	adopt_unary_pose_factors(*this, dirSet, v);
 	covBlocksValid = false;
 }
 
@@ -878,10 +899,10 @@ static void sort_factors(FactorSet& set, const std::vector<uint64_t>& key)
 	std::stable_sort(set.order.begin(), set.order.end(), [&](int a, int b) { return key[a] < key[b]; });
 }
 
-// a set's index arrays (`ints`, laid out by the caller) and its values q | t | information in the sorted order -> device; the device
+// the edges' index arrays (`ints`, laid out by the caller) and their values q | t | information in the sorted order -> device; the device
 // pointers of the values and of the per-factor chi2 come back through q, t, info, chi.  A set with robust kernels: their kinds follow the
 // index arrays, their deltas the values, by the same permutation (rk_kind, rk_delta; null without)
-static void upload_factor_arrays(cuba_hip_solver& s, PoseFactorSet& set, std::vector<int> ints, const Scalar*& q, const Scalar*& t, const Scalar*& info, Scalar*& chi,
+static void upload_factor_arrays(cuba_hip_solver& s, RelPoseSet& set, std::vector<int> ints, const Scalar*& q, const Scalar*& t, const Scalar*& info, Scalar*& chi,
 	const int*& rk_kind, const Scalar*& rk_delta)
 {
 	const size_t n = set.order.size();
@@ -892,9 +913,9 @@ static void upload_factor_arrays(cuba_hip_solver& s, PoseFactorSet& set, std::ve
 	for (size_t p = 0; p < n; p++)
 	{
 		const size_t k = (size_t)set.order[p];
-		for (int i = 0; i < 4; i++) vq[4 * p + i] = (Scalar)set.v.q[4 * k + i];
-		for (int i = 0; i < 3; i++) vt[3 * p + i] = (Scalar)set.v.t[3 * k + i];
-		for (int i = 0; i < 36; i++) vi[36 * p + i] = (Scalar)set.v.info[36 * k + i];
+		for (int i = 0; i < 4; i++) vq[4 * p + i] = (Scalar)set.q[4 * k + i];
+		for (int i = 0; i < 3; i++) vt[3 * p + i] = (Scalar)set.t[3 * k + i];
+		for (int i = 0; i < 36; i++) vi[36 * p + i] = (Scalar)set.info[36 * k + i];
 		if (robust) { ints.push_back(set.kind[k]); vi[36 * n + p] = (Scalar)set.delta[k]; }
 	}
 	set.d_ints.upload(ints, s.stream);
@@ -914,42 +935,62 @@ static std::vector<int> concat(std::initializer_list<const std::vector<int>*> pa
 	return out;
 }
 
-// the caller's priors -> device, in the internal pose order (stable by internal pose: every pose's priors contiguous, in the caller's order)
-static void upload_priors(cuba_hip_solver& s)
+// a unary kind's factors on the poses -> device, in the internal pose order (stable by internal pose: every pose's factors contiguous, in
+// the caller's order; the factors on fixed poses last).  The same layout for the three kinds:
+// ints: pose_ptr [np + 1] | pose_id [np] | pose [n] | kind [n, robust];  values: a [wa n] | b [wb n] | info [wi n] | delta [n, robust]
+void UnaryPoseFactorSet::upload(cuba_hip_solver& s)
 {
-	PoseFactorSet& set = s.priorSet;
-	const int n = set.n(), Pf = s.Pf;
-	std::vector<uint64_t> internal((size_t)n);
-	for (int k = 0; k < n; k++) internal[k] = (uint64_t)s.internalPose(set.v.pi[k]);
-	sort_factors(set, internal);
-	std::vector<int> ptr, ids, poses((size_t)n);
-	for (int p = 0; p < n; p++)
+	const int Pf = s.Pf;
+	const size_t N = (size_t)n();
+	const bool robust = !kind.empty();
+	std::vector<uint64_t> internal(N);
+	for (size_t k = 0; k < N; k++) internal[k] = (uint64_t)s.internalPose(pose[k]);
+	sort_factors(*this, internal);
+	std::vector<int> ptr, ids, poses(N);
+	for (size_t p = 0; p < N; p++)
 	{
-		poses[p] = (int)internal[set.order[p]];
-		if (poses[p] < Pf && (ids.empty() || ids.back() != poses[p])) { ids.push_back(poses[p]); ptr.push_back(p); }
+		poses[p] = (int)internal[order[p]];
+		if (poses[p] < Pf && (ids.empty() || ids.back() != poses[p])) { ids.push_back(poses[p]); ptr.push_back((int)p); }
 	}
-	int nFree = 0;
-	while (nFree < n && poses[nFree] < Pf) nFree++;
-	ptr.push_back(nFree);
+	size_t nFree = 0;
+	while (nFree < N && poses[nFree] < Pf) nFree++;
+	ptr.push_back((int)nFree);
 	const int np = (int)ids.size();
-	DevicePriors pr;
-	upload_factor_arrays(s, set, concat({ &ptr, &ids, &poses }), pr.qbar, pr.tbar, pr.info, pr.chi, pr.rk_kind, pr.rk_delta);
-	pr.n = n; pr.nPoses = np;
-	pr.pose_ptr = set.d_ints.data(); pr.pose_id = pr.pose_ptr + (np + 1); pr.pose = pr.pose_id + np;
-	s.pf.priors = pr;
+	std::vector<int> ints = concat({ &ptr, &ids, &poses });
+	const size_t nInts = ints.size();
+	std::vector<Scalar> vals((size_t)(wa + wb + wi + (robust ? 1 : 0)) * N);
+	Scalar* va = vals.data(); Scalar* vb = va + wa * N; Scalar* vi = vb + wb * N;
+	for (size_t p = 0; p < N; p++)
+	{
+		const size_t k = (size_t)order[p];
+		for (int i = 0; i < wa; i++) va[wa * p + i] = (Scalar)a[wa * k + i];
+		for (int i = 0; i < wb; i++) vb[wb * p + i] = (Scalar)b[wb * k + i];
+		for (int i = 0; i < wi; i++) vi[wi * p + i] = (Scalar)info[wi * k + i];
+		if (robust) { ints.push_back(kind[k]); vi[wi * N + p] = (Scalar)delta[k]; }
+	}
+	d_ints.upload(ints, s.stream);
+	d_vals.upload(vals, s.stream);
+	d_chi.resize(std::max(N, (size_t)1));
+	s.sync();          // (the staging vectors go out of scope)
+	dev.n = (int)N; dev.nPoses = np;
+	dev.pose_ptr = d_ints.data(); dev.pose_id = dev.pose_ptr + (np + 1); dev.pose = dev.pose_id + np;
+	da = d_vals.data(); db = da + wa * N; dev.info = db + wb * N;
+	dev.chi = d_chi.data();
+	dev.rk_kind = robust ? d_ints.data() + nInts : nullptr; dev.rk_delta = robust ? dev.info + wi * N : nullptr;
+	uploaded = true;
 }
 
 // the caller's edges -> device, in the internal pose order: free-free edges first, stable by the block (min, max) of the internal pair -- a
 // block's edges contiguous and in the caller's order --, then the edges with one fixed end, then (inactive) those with two
-static void upload_relative_pose_edges(cuba_hip_solver& s)
+void RelPoseSet::upload(cuba_hip_solver& s)
 {
-	PoseFactorSet& set = s.relSet;
+	RelPoseSet& set = *this;
 	const int n = set.n(), Pf = s.Pf;
 	std::vector<int> a((size_t)n), b((size_t)n);
 	std::vector<uint64_t> key((size_t)n);
 	for (int k = 0; k < n; k++)
 	{
-		a[k] = s.internalPose(set.v.pi[k]); b[k] = s.internalPose(set.v.pj[k]);
+		a[k] = s.internalPose(set.pi[k]); b[k] = s.internalPose(set.pj[k]);
 		const int nFixed = (a[k] >= Pf) + (b[k] >= Pf);
 		key[k] = nFixed == 0 ? (((uint64_t)(uint32_t)std::min(a[k], b[k]) << 32) | (uint32_t)std::max(a[k], b[k])) : (~0ull - (uint64_t)(2 - nFixed));
 	}
@@ -1004,50 +1045,12 @@ static void upload_relative_pose_edges(cuba_hip_solver& s)
 	set.structure = s.cntStructureBuilds;
 }
 
-void cuba_hip_solver::setLandmarkPriors(int n, const int32_t* landmark, const double* xyz, const double* info, const int32_t* kind, const double* delta)
-{
-	if (!haveGraph) throw StateError{ "set_graph must be called first" };
-	if (n < 0) throw ArgError{ "negative landmark prior count" };
-	if (n > 0 && (partHi >= 0 || valuesPartial)) throw StateError{ "landmark priors are not available on a landmark-partitioned handle" };
-	if (n > 0 && E == 0) throw StateError{ "landmark priors need a graph with edges" };
-	if (n > 0 && (!landmark || !xyz || !info)) throw ArgError{ "null landmark prior array" };
-	if (n > 0 && (kind == nullptr) != (delta == nullptr)) throw ArgError{ "landmark prior kernels: kind and delta come together" };
-	LandmarkPriorSet v;
-	v.lm.resize((size_t)n); v.xyz.resize((size_t)3 * n); v.info.resize((size_t)6 * n); v.kind.assign((size_t)n, cubahip::POSE_FACTOR_KERNEL_NONE); v.delta.assign((size_t)n, 1.0);
-	for (int k = 0; k < n; k++)
-	{
-		if (landmark[k] < 0 || landmark[k] >= Lt) throw ArgError{ "landmark prior: landmark index out of range" };
-		v.lm[k] = landmark[k];
-		for (int i = 0; i < 3; i++)
-		{
-			if (!std::isfinite(xyz[3 * (size_t)k + i])) throw ArgError{ "non-finite landmark prior position" };
-			v.xyz[3 * (size_t)k + i] = xyz[3 * (size_t)k + i];
-		}
-		// the symmetrised information's upper triangle, in the packing of sym3_idx
-		double S[9];
-		take_information<3>(info + 9 * (size_t)k, S, "landmark prior");
-		double* U = v.info.data() + 6 * (size_t)k;
-		U[0] = S[0]; U[1] = S[3]; U[2] = S[6]; U[3] = S[4]; U[4] = S[7]; U[5] = S[8];
-		if (kind)
-		{
-			check_factor_kernel(kind[k], delta[k], "landmark prior");
-			if (kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE) { v.kind[k] = kind[k]; v.delta[k] = delta[k]; }
-		}
-	}
-	// a validated set replaces the handle's, as a pose kind's
-	lmPriorSet.lm.swap(v.lm); lmPriorSet.xyz.swap(v.xyz); lmPriorSet.info.swap(v.info); lmPriorSet.kind.swap(v.kind); lmPriorSet.delta.swap(v.delta);
-	lmPriorSet.order.clear();
-	forget_factor_memories(*this, lmPriorSet);
-	pf.lmp = DeviceLandmarkPriors();
-	covBlocksValid = false;
-}
-
 // the caller's priors -> device, in the internal landmark order (stable by internal landmark: every landmark's priors contiguous, in the
 // caller's order; the priors on fixed landmarks last).  A prior on a free landmark without an edge cannot be honoured -- the landmark pass
 // walks the landmarks of the edge list --: the set is dropped and the call that got here reports it.
-static void upload_landmark_priors(cuba_hip_solver& s)
+void LandmarkPriorSet::upload(cuba_hip_solver& s)
 {
-	LandmarkPriorSet& set = s.lmPriorSet;
+	LandmarkPriorSet& set = *this;
 	const int n = set.n(), Lf = s.Lf;
 	std::vector<int> lmMap, lmPtr((size_t)Lf + 1, 0);
 	if (s.lmOrderActive && Lf > 0)
@@ -1096,236 +1099,23 @@ static void upload_landmark_priors(cuba_hip_solver& s)
 	set.uploaded = true; set.structure = s.cntStructureBuilds;
 }
 
-void cuba_hip_solver::setPositionFactors(int n, const int32_t* pose, const double* position, const double* leverArm, const double* info, const int32_t* kind,
-	const double* delta)
-{
-	if (!haveGraph) throw StateError{ "set_graph must be called first" };
-	if (n < 0) throw ArgError{ "negative position factor count" };
-	if (n > 0 && (partHi >= 0 || valuesPartial)) throw StateError{ "position factors are not available on a landmark-partitioned handle" };
-	if (n > 0 && E == 0) throw StateError{ "position factors need a graph with edges" };
-	if (n > 0 && (!pose || !position || !info)) throw ArgError{ "null position factor array" };
-	if (n > 0 && (kind == nullptr) != (delta == nullptr)) throw ArgError{ "position factor kernels: kind and delta come together" };
-	PositionFactorSet v;
-	v.pose.resize((size_t)n); v.z.resize((size_t)3 * n); v.arm.assign((size_t)3 * n, 0.0); v.info.resize((size_t)9 * n);
-	bool any = false;
-	for (int k = 0; k < n; k++)
-	{
-		if (pose[k] < 0 || pose[k] >= Pt) throw ArgError{ "position factor: pose index out of range" };
-		v.pose[k] = pose[k];
-		for (int i = 0; i < 3; i++)
-		{
-			if (!std::isfinite(position[3 * (size_t)k + i])) throw ArgError{ "non-finite position factor position" };
-			v.z[3 * (size_t)k + i] = position[3 * (size_t)k + i];
-			if (!leverArm) continue;
-			if (!std::isfinite(leverArm[3 * (size_t)k + i])) throw ArgError{ "non-finite position factor lever arm" };
-			v.arm[3 * (size_t)k + i] = leverArm[3 * (size_t)k + i];
-		}
-		take_information<3>(info + 9 * (size_t)k, v.info.data() + 9 * (size_t)k, "position factor");
-		if (kind)
-		{
-			check_factor_kernel(kind[k], delta[k], "position factor");
-			any = any || kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE;
-		}
-	}
-	// (kinds all 0: no kernels, the set runs the kernels' ROBUST = false instantiations)
-	if (any) { v.kind.assign(kind, kind + n); v.delta.assign(delta, delta + n); }
-	// a validated set replaces the handle's, as a pose kind's
-	posSet.pose.swap(v.pose); posSet.z.swap(v.z); posSet.arm.swap(v.arm); posSet.info.swap(v.info); posSet.kind.swap(v.kind); posSet.delta.swap(v.delta);
-	posSet.order.clear();
-	forget_factor_memories(*this, posSet);
-	pf.pos = DevicePositionFactors();
-	covBlocksValid = false;
-}
-
-// the caller's position factors -> device, in the internal pose order (stable by internal pose: every pose's factors contiguous, in the
-// caller's order; the factors on fixed poses last)
-static void upload_position_factors(cuba_hip_solver& s)
-{
-	PositionFactorSet& set = s.posSet;
-	const int n = set.n(), Pf = s.Pf;
-	const bool robust = !set.kind.empty();
-	std::vector<uint64_t> internal((size_t)n);
-	for (int k = 0; k < n; k++) internal[k] = (uint64_t)s.internalPose(set.pose[k]);
-	sort_factors(set, internal);
-	std::vector<int> ptr, ids, poses((size_t)n);
-	for (int p = 0; p < n; p++)
-	{
-		poses[p] = (int)internal[set.order[p]];
-		if (poses[p] < Pf && (ids.empty() || ids.back() != poses[p])) { ids.push_back(poses[p]); ptr.push_back(p); }
-	}
-	int nFree = 0;
-	while (nFree < n && poses[nFree] < Pf) nFree++;
-	ptr.push_back(nFree);
-	const int np = (int)ids.size();
-	// ints: pose_ptr [np + 1] | pose_id [np] | pose [n] | kind [n, robust];  values: z [3 n] | arm [3 n] | info [9 n] | delta [n, robust]
-	std::vector<int> ints = concat({ &ptr, &ids, &poses });
-	const size_t nInts = ints.size();
-	std::vector<Scalar> vals((robust ? 16 : 15) * (size_t)n);
-	Scalar* vz = vals.data(); Scalar* va = vz + 3 * (size_t)n; Scalar* vi = va + 3 * (size_t)n;
-	for (size_t p = 0; p < (size_t)n; p++)
-	{
-		const size_t k = (size_t)set.order[p];
-		for (int i = 0; i < 3; i++) { vz[3 * p + i] = (Scalar)set.z[3 * k + i]; va[3 * p + i] = (Scalar)set.arm[3 * k + i]; }
-		for (int i = 0; i < 9; i++) vi[9 * p + i] = (Scalar)set.info[9 * k + i];
-		if (robust) { ints.push_back(set.kind[k]); vi[9 * (size_t)n + p] = (Scalar)set.delta[k]; }
-	}
-	set.d_ints.upload(ints, s.stream);
-	set.d_vals.upload(vals, s.stream);
-	set.d_chi.resize(std::max((size_t)n, (size_t)1));
-	s.sync();          // (the staging vectors go out of scope)
-	DevicePositionFactors pp;
-	pp.n = n; pp.nPoses = np;
-	pp.pose_ptr = set.d_ints.data(); pp.pose_id = pp.pose_ptr + (np + 1); pp.pose = pp.pose_id + np;
-	pp.z = set.d_vals.data(); pp.arm = pp.z + 3 * (size_t)n; pp.info = pp.arm + 3 * (size_t)n;
-	pp.chi = set.d_chi.data();
-	pp.rk_kind = robust ? set.d_ints.data() + nInts : nullptr; pp.rk_delta = robust ? pp.info + 9 * (size_t)n : nullptr;
-	s.pf.pos = pp;
-	set.uploaded = true;
-}
-
-void cuba_hip_solver::setDirectionFactors(int n, const int32_t* pose, const double* worldDir, const double* measuredDir, const double* info, const int32_t* kind,
-	const double* delta)
-{
-	if (!haveGraph) throw StateError{ "set_graph must be called first" };
-	if (n < 0) throw ArgError{ "negative direction factor count" };
-	if (n > 0 && (partHi >= 0 || valuesPartial)) throw StateError{ "direction factors are not available on a landmark-partitioned handle" };
-	if (n > 0 && E == 0) throw StateError{ "direction factors need a graph with edges" };
-	if (n > 0 && (!pose || !worldDir || !measuredDir || !info)) throw ArgError{ "null direction factor array" };
-	if (n > 0 && (kind == nullptr) != (delta == nullptr)) throw ArgError{ "direction factor kernels: kind and delta come together" };
-	DirectionFactorSet v;
-	v.pose.resize((size_t)n); v.d.resize((size_t)3 * n); v.m.resize((size_t)3 * n); v.info.resize((size_t)9 * n);
-	bool any = false;
-	for (int k = 0; k < n; k++)
-	{
-		if (pose[k] < 0 || pose[k] >= Pt) throw ArgError{ "direction factor: pose index out of range" };
-		v.pose[k] = pose[k];
-		// (taken as given: neither vector is normalised)
-		for (int i = 0; i < 3; i++)
-		{
-			if (!std::isfinite(worldDir[3 * (size_t)k + i])) throw ArgError{ "non-finite direction factor world direction" };
-			if (!std::isfinite(measuredDir[3 * (size_t)k + i])) throw ArgError{ "non-finite direction factor measurement" };
-			v.d[3 * (size_t)k + i] = worldDir[3 * (size_t)k + i];
-			v.m[3 * (size_t)k + i] = measuredDir[3 * (size_t)k + i];
-		}
-		take_information<3>(info + 9 * (size_t)k, v.info.data() + 9 * (size_t)k, "direction factor");
-		if (kind)
-		{
-			check_factor_kernel(kind[k], delta[k], "direction factor");
-			any = any || kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE;
-		}
-	}
-	// (kinds all 0: no kernels, the set runs the kernels' ROBUST = false instantiations)
-	if (any) { v.kind.assign(kind, kind + n); v.delta.assign(delta, delta + n); }
-	// a validated set replaces the handle's, as a pose kind's
-	dirSet.pose.swap(v.pose); dirSet.d.swap(v.d); dirSet.m.swap(v.m); dirSet.info.swap(v.info); dirSet.kind.swap(v.kind); dirSet.delta.swap(v.delta);
-	dirSet.order.clear();
-	forget_factor_memories(*this, dirSet);
-	pf.dir = DeviceDirectionFactors();
-	covBlocksValid = false;
-}
-
-// the caller's direction factors -> device, in the internal pose order (stable by internal pose: every pose's factors contiguous, in the
-// caller's order; the factors on fixed poses last)
-static void upload_direction_factors(cuba_hip_solver& s)
-{
-	DirectionFactorSet& set = s.dirSet;
-	const int n = set.n(), Pf = s.Pf;
-	const bool robust = !set.kind.empty();
-	std::vector<uint64_t> internal((size_t)n);
-	for (int k = 0; k < n; k++) internal[k] = (uint64_t)s.internalPose(set.pose[k]);
-	sort_factors(set, internal);
-	std::vector<int> ptr, ids, poses((size_t)n);
-	for (int p = 0; p < n; p++)
-	{
-		poses[p] = (int)internal[set.order[p]];
-		if (poses[p] < Pf && (ids.empty() || ids.back() != poses[p])) { ids.push_back(poses[p]); ptr.push_back(p); }
-	}
-	int nFree = 0;
-	while (nFree < n && poses[nFree] < Pf) nFree++;
-	ptr.push_back(nFree);
-	const int np = (int)ids.size();
-	// ints: pose_ptr [np + 1] | pose_id [np] | pose [n] | kind [n, robust];  values: d [3 n] | m [3 n] | info [9 n] | delta [n, robust]
-	std::vector<int> ints = concat({ &ptr, &ids, &poses });
-	const size_t nInts = ints.size();
-	std::vector<Scalar> vals((robust ? 16 : 15) * (size_t)n);
-	Scalar* vd = vals.data(); Scalar* vm = vd + 3 * (size_t)n; Scalar* vi = vm + 3 * (size_t)n;
-	for (size_t p = 0; p < (size_t)n; p++)
-	{
-		const size_t k = (size_t)set.order[p];
-		for (int i = 0; i < 3; i++) { vd[3 * p + i] = (Scalar)set.d[3 * k + i]; vm[3 * p + i] = (Scalar)set.m[3 * k + i]; }
-		for (int i = 0; i < 9; i++) vi[9 * p + i] = (Scalar)set.info[9 * k + i];
-		if (robust) { ints.push_back(set.kind[k]); vi[9 * (size_t)n + p] = (Scalar)set.delta[k]; }
-	}
-	set.d_ints.upload(ints, s.stream);
-	set.d_vals.upload(vals, s.stream);
-	set.d_chi.resize(std::max((size_t)n, (size_t)1));
-	s.sync();          // (the staging vectors go out of scope)
-	DeviceDirectionFactors df;
-	df.n = n; df.nPoses = np;
-	df.pose_ptr = set.d_ints.data(); df.pose_id = df.pose_ptr + (np + 1); df.pose = df.pose_id + np;
-	df.d = set.d_vals.data(); df.m = df.d + 3 * (size_t)n; df.info = df.m + 3 * (size_t)n;
-	df.chi = set.d_chi.data();
-	df.rk_kind = robust ? set.d_ints.data() + nInts : nullptr; df.rk_delta = robust ? df.info + 9 * (size_t)n : nullptr;
-	s.pf.dir = df;
-	set.uploaded = true;
-}
-
-// (the pose priors, the position factors and the direction factors depend on the pose order only -- a change of it marks them --, the
-// edges' blocks and the landmark priors' order on the structure)
+// (the unary kinds on the poses depend on the pose order only -- a change of it marks them: poseOrderChanged() --, the edges' blocks and the
+// landmark priors' order on the structure)
 void cuba_hip_solver::uploadFactors()
 {
-	if (priorSet.n() > 0 && !priorSet.uploaded) upload_priors(*this);
-	if (relSet.n() > 0 && (!relSet.uploaded || relSet.structure != cntStructureBuilds)) upload_relative_pose_edges(*this);
-	if (lmPriorSet.n() > 0 && (!lmPriorSet.uploaded || lmPriorSet.structure != cntStructureBuilds)) upload_landmark_priors(*this);
-	if (posSet.n() > 0 && !posSet.uploaded) upload_position_factors(*this);
-	if (dirSet.n() > 0 && !dirSet.uploaded) upload_direction_factors(*this);
+	for (FactorSet* set : factorSets)
+		if (set->n() > 0 && (!set->uploaded || (set->onStructure && set->structure != cntStructureBuilds))) set->upload(*this);
 }
 
-// the per-factor chi2 of the chi2 launch just issued (sorted order on the device) -> the caller's order
-static void read_factor_chi2(cuba_hip_solver& s, const FactorSet& set, const Scalar* chi, double* out)
+void cuba_hip_solver::factorChiSquares(int kind, double* out)
 {
+	need();
+	const FactorSet& set = *factorSets[kind];
+	if (set.n() == 0) return;
+	launch_factor_chi2(g, pf, d_parts.data(), stream, kind);
+	// the per-factor chi2 of the launch just issued (sorted order on the device) -> the caller's order
 	const size_t n = set.order.size();
 	std::vector<double> sorted(n);
-	s.downloadAsDouble(chi, sorted.data(), n);
+	downloadAsDouble(set.d_chi.data(), sorted.data(), n);
 	for (size_t p = 0; p < n; p++) out[set.order[p]] = sorted[p];
-}
-
-void cuba_hip_solver::priorChiSquares(double* out)
-{
-	need();
-	if (priorSet.n() == 0) return;
-	launch_prior_chi2(g, pf.priors, d_parts.data(), stream);
-	read_factor_chi2(*this, priorSet, pf.priors.chi, out);
-}
-
-void cuba_hip_solver::relativePoseChiSquares(double* out)
-{
-	need();
-	if (relSet.n() == 0) return;
-	launch_relpose_chi2(g, pf.rel, d_parts.data(), stream);
-	read_factor_chi2(*this, relSet, pf.rel.chi, out);
-}
-
-void cuba_hip_solver::landmarkPriorChiSquares(double* out)
-{
-	need();
-	if (lmPriorSet.n() == 0) return;
-	launch_landmark_prior_chi2(g, pf.lmp, d_parts.data(), stream);
-	read_factor_chi2(*this, lmPriorSet, pf.lmp.chi, out);
-}
-
-void cuba_hip_solver::positionFactorChiSquares(double* out)
-{
-	need();
-	if (posSet.n() == 0) return;
-	launch_position_chi2(g, pf.pos, d_parts.data(), stream);
-	read_factor_chi2(*this, posSet, pf.pos.chi, out);
-}
-
-void cuba_hip_solver::directionFactorChiSquares(double* out)
-{
-	need();
-	if (dirSet.n() == 0) return;
-	launch_direction_chi2(g, pf.dir, d_parts.data(), stream);
-	read_factor_chi2(*this, dirSet, pf.dir.chi, out);
 }

@@ -141,21 +141,29 @@ struct DeviceSystem
 // delta^2 log1p(e / delta^2), exists for these factors only (helpers in ba_device.hpp).
 enum { POSE_FACTOR_KERNEL_NONE = 0, POSE_FACTOR_KERNEL_HUBER = 1, POSE_FACTOR_KERNEL_TUKEY = 2, POSE_FACTOR_KERNEL_CAUCHY = 3 };
 
-// SE(3) pose priors (ba_factor.hip): rho(r^T Omega r), r = log(T Tbar^-1) in the [omega, upsilon] tangent of the pose update.  Sorted by
-// internal pose (stable: a pose's priors are contiguous and in the caller's order); priors on fixed poses come last and are ignored.
-struct DevicePriors
+// The unary kinds of factor on the poses (ba_factor.hip) -- SE(3) pose priors, position factors, direction factors -- share their device
+// layout: rho(r^T Omega r) per factor, sorted by internal pose (stable: a pose's factors are contiguous and in the caller's order); factors
+// on fixed poses come last and are ignored.  A kind adds its two measurement arrays.
+struct DevicePoseGroups
 {
-	int n = 0;                     // priors
-	int nPoses = 0;                // free poses with priors
+	int n = 0;                     // factors
+	int nPoses = 0;                // free poses with factors
 	const int* pose_ptr = nullptr; // [nPoses + 1] range of every such pose in the sorted list
 	const int* pose_id = nullptr;  // [nPoses] its internal pose index
-	const int* pose = nullptr;     // [n] internal pose of every prior (>= Pf: a fixed pose)
-	const Scalar *qbar = nullptr, *tbar = nullptr;   // [4 n] unit quaternions, [3 n]
-	const Scalar* info = nullptr;  // [36 n] column-major
+	const int* pose = nullptr;     // [n] internal pose of every factor (>= Pf: a fixed pose)
+	const Scalar* info = nullptr;  // [D D n] column-major, D the dimension of r
 	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 on fixed poses)
-	const int* rk_kind = nullptr;  // [n] robust kernel of every prior, sorted as the values; null: no prior has one (the kernels' ROBUST = false)
+	const int* rk_kind = nullptr;  // [n] robust kernel of every factor, sorted as the values; null: no factor has one (the kernels' ROBUST = false)
 	const Scalar* rk_delta = nullptr;   // [n]
 };
+// SE(3) pose priors: r = log(T Tbar^-1) in the [omega, upsilon] tangent of the pose update, D = 6
+struct DevicePriors : DevicePoseGroups { const Scalar *qbar = nullptr, *tbar = nullptr; };       // [4 n] unit quaternions, [3 n]
+// Position factors (GNSS-style fixes): r = R^T (a - t) - z, the world position of the point a of the camera frame (the lever arm; zero: the
+// camera centre) against a measured world position z, D = 3
+struct DevicePositionFactors : DevicePoseGroups { const Scalar *z = nullptr, *arm = nullptr; };  // [3 n] measured positions, [3 n] lever arms
+// Direction factors (gravity, compass, vanishing directions): r = R d - m, a world vector d against the same vector as measured in the
+// camera frame, m (neither is normalised), D = 3 (Omega of rank 2 as a rule)
+struct DeviceDirectionFactors : DevicePoseGroups { const Scalar *d = nullptr, *m = nullptr; };   // [3 n] world vectors, [3 n] their measurements
 
 // SE(3) relative-pose edges (ba_factor.hip): rho(r^T Omega r), r = log(T_j T_i^-1 Zbar^-1), between two poses.  Sorted: the edges between two
 // free poses first, stable by the block (min, max) of the internal pose pair (a block's edges contiguous, in the caller's order), then the
@@ -197,45 +205,15 @@ struct DeviceLandmarkPriors
 	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 on fixed landmarks)
 };
 
-// Position factors on the poses (ba_factor.hip; GNSS-style fixes): rho(r^T Omega r), r = R^T (a - t) - z, the world position of the point
-// a of the camera frame (the lever arm; zero: the camera centre) against a measured world position z, Omega a symmetric 3 x 3 information.
-// Sorted by internal pose (stable: a pose's factors are contiguous and in the caller's order); factors on fixed poses come last and are
-// ignored.
-struct DevicePositionFactors
-{
-	int n = 0;                     // factors
-	int nPoses = 0;                // free poses with factors
-	const int* pose_ptr = nullptr; // [nPoses + 1] range of every such pose in the sorted list
-	const int* pose_id = nullptr;  // [nPoses] its internal pose index
-	const int* pose = nullptr;     // [n] internal pose of every factor (>= Pf: a fixed pose)
-	const Scalar *z = nullptr, *arm = nullptr;       // [3 n] measured positions, [3 n] lever arms
-	const Scalar* info = nullptr;  // [9 n] column-major
-	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 on fixed poses)
-	const int* rk_kind = nullptr;  // [n] robust kernel of every factor, sorted as the values; null: no factor has one (the kernels' ROBUST = false)
-	const Scalar* rk_delta = nullptr;   // [n]
-};
-
-// Direction factors on the poses (ba_factor.hip; gravity, compass, vanishing directions): rho(r^T Omega r), r = R d - m, a world vector d
-// against the same vector as measured in the camera frame, m (neither is normalised), Omega a symmetric 3 x 3 information (rank 2 as a
-// rule).  Sorted by internal pose (stable: a pose's factors are contiguous and in the caller's order); factors on fixed poses come last and
-// are ignored.
-struct DeviceDirectionFactors
-{
-	int n = 0;                     // factors
-	int nPoses = 0;                // free poses with factors
-	const int* pose_ptr = nullptr; // [nPoses + 1] range of every such pose in the sorted list
-	const int* pose_id = nullptr;  // [nPoses] its internal pose index
-	const int* pose = nullptr;     // [n] internal pose of every factor (>= Pf: a fixed pose)
-	const Scalar *d = nullptr, *m = nullptr;         // [3 n] world vectors, [3 n] their measurements in the camera frame
-	const Scalar* info = nullptr;  // [9 n] column-major
-	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 on fixed poses)
-	const int* rk_kind = nullptr;  // [n] robust kernel of every factor, sorted as the values; null: no factor has one (the kernels' ROBUST = false)
-	const Scalar* rk_delta = nullptr;   // [n]
-};
-
 // The factors of a handle besides the reprojection edges: what the rest of the library sees of the kinds (a kind without factors: n = 0,
 // nothing of it is launched).  The landmark priors ride along for the chi2 sums only: their linearisation is the landmark pass's.
-struct DeviceFactors { DevicePriors priors; DeviceRelPoses rel; DeviceLandmarkPriors lmp; DevicePositionFactors pos; DeviceDirectionFactors dir; };
+// FACTOR_*: the kinds in the order of their chi2 partials, of each() below and of the handle's table of sets (ba_solver.hpp: factorSets).
+enum { FACTOR_PRIORS = 0, FACTOR_REL, FACTOR_LMP, FACTOR_POS, FACTOR_DIR, FACTOR_KINDS };
+struct DeviceFactors
+{
+	DevicePriors priors; DeviceRelPoses rel; DeviceLandmarkPriors lmp; DevicePositionFactors pos; DeviceDirectionFactors dir;
+	template <class F> void each(F&& f) const { f(priors); f(rel); f(lmp); f(pos); f(dir); }      // every kind's device struct, in that order
+};
 // behind the Schur pass, the priors first (Omega: w Omega of a factor with a robust kernel): J^T Omega J into the diagonal blocks of hsc (upper triangle), -J^T Omega r into bp and (mode 1)
 // bsc, J = J_l(r)^-1; then the position factors the same way in a launch of their own, J = [R^T [a]x | -R^T]; then the edges in two
 // launches: per-edge records, then their sums into hsc (diagonal blocks: upper triangle; mode 1: the off-diagonal blocks of the pairs,
@@ -243,10 +221,9 @@ struct DeviceFactors { DevicePriors priors; DeviceRelPoses rel; DeviceLandmarkPr
 // [-[R d]x | 0]: the rotation 3 x 3 of the diagonal block and the first three entries of bp / bsc only.  All four add to the same diagonal
 // blocks: the order of the launches is part of the result
 void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DeviceFactors& pf, int mode, hipStream_t s);
-// per-factor chi2 (the plain r^T Omega r) into priors.chi / rel.chi / lmp.chi / pos.chi / dir.chi, per-workgroup partial sums of rho(chi2)
-// into parts[0 .. factor_chi2_parts(&pf)): the priors' first, the edges' behind them, then the landmark priors', the position factors',
-// the direction factors' last
-void launch_factor_chi2(const DeviceGraph& g, const DeviceFactors& pf, Scalar* parts, hipStream_t s);
+// per-factor chi2 (the plain r^T Omega r) into every kind's chi, per-workgroup partial sums of rho(chi2) into
+// parts[0 .. factor_chi2_parts(&pf)), kind behind kind in the order of FACTOR_*.  only >= 0: that kind alone, its partials at parts[0]
+void launch_factor_chi2(const DeviceGraph& g, const DeviceFactors& pf, Scalar* parts, hipStream_t s, int only = -1);
 int factor_chi2_parts(const DeviceFactors* pf);     // 0 for no factors (pf null), at most 64 per kind
 
 // residual / robust chi2 over all edges -> sys.slots[0..NSLOT) (must be zeroed by the caller).

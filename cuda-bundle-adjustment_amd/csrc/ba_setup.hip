@@ -904,7 +904,7 @@ void cuba_hip_solver::resetPoseOrder()
 {
 	if (reorderActive) dropSnapshots();          // (they hold rows in the order that ends here)
 	reorderActive = false;
-	priorSet.uploaded = false; posSet.uploaded = false; dirSet.uploaded = false;
+	poseOrderChanged();
 	poseNewOfOld.resize(Pf); poseOldOfNew.resize(Pf);
 	for (int i = 0; i < Pf; i++) poseNewOfOld[i] = poseOldOfNew[i] = i;
 }
@@ -999,7 +999,7 @@ void cuba_hip_solver::applyPoseOrder(const std::vector<int>& newOfOld)
 	permutePoseArray(state.data(), 4, false); permutePoseArray(state.data() + 4 * (size_t)Pt, 3, false); permutePoseArray(camv.data(), 5, false);
 	poseNewOfOld = newOfOld;
 	reorderActive = false;
-	priorSet.uploaded = false; posSet.uploaded = false; dirSet.uploaded = false;
+	poseOrderChanged();
 	for (int i = 0; i < Pf; i++) { poseOldOfNew[newOfOld[i]] = i; if (newOfOld[i] != i) reorderActive = true; }
 	permuteStateRows(state, camv);
 	d_state.upload(state, stream); d_cam.upload(camv, stream);

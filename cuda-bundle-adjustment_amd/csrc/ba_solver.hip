@@ -495,19 +495,22 @@ int cuba_hip_compute_covariance_pairs(cuba_hip_solver* s, int n, const int32_t* 
 	});
 }
 
+// the per-factor chi2 of one kind (cubahip::FACTOR_*)
+static int factor_chi_squares(cuba_hip_solver* s, int kind, double* out)
+{
+	return guarded(s, [&] {
+		if (!s->haveGraph) throw StateError{ "set_graph must be called first" };
+		if (s->factorSets[kind]->n() > 0 && !out) throw ArgError{ "null output" };
+		s->factorChiSquares(kind, out);
+	});
+}
+
 int cuba_hip_set_pose_priors(cuba_hip_solver* s, int n, const int32_t* pose, const double* q, const double* t, const double* info)
 {
 	return guarded(s, [&] { s->setPosePriors(n, pose, q, t, info); });
 }
 
-int cuba_hip_prior_chi_squares(cuba_hip_solver* s, double* chi2_per_prior)
-{
-	return guarded(s, [&] {
-		if (!s->haveGraph) throw StateError{ "set_graph must be called first" };
-		if (s->priorSet.n() > 0 && !chi2_per_prior) throw ArgError{ "null output" };
-		s->priorChiSquares(chi2_per_prior);
-	});
-}
+int cuba_hip_prior_chi_squares(cuba_hip_solver* s, double* chi2_per_prior) { return factor_chi_squares(s, cubahip::FACTOR_PRIORS, chi2_per_prior); }
 
 int cuba_hip_set_relative_pose_edges(cuba_hip_solver* s, int n, const int32_t* pose_i, const int32_t* pose_j, const double* q, const double* t, const double* info)
 {
@@ -519,28 +522,14 @@ int cuba_hip_set_pose_factor_robust_kernels(cuba_hip_solver* s, int factor_type,
 	return guarded(s, [&] { s->setPoseFactorRobustKernels(factor_type, n, kind, delta); });
 }
 
-int cuba_hip_relative_pose_chi_squares(cuba_hip_solver* s, double* chi2_per_edge)
-{
-	return guarded(s, [&] {
-		if (!s->haveGraph) throw StateError{ "set_graph must be called first" };
-		if (s->relSet.n() > 0 && !chi2_per_edge) throw ArgError{ "null output" };
-		s->relativePoseChiSquares(chi2_per_edge);
-	});
-}
+int cuba_hip_relative_pose_chi_squares(cuba_hip_solver* s, double* chi2_per_edge) { return factor_chi_squares(s, cubahip::FACTOR_REL, chi2_per_edge); }
 
 int cuba_hip_set_landmark_priors(cuba_hip_solver* s, int n, const int32_t* landmark, const double* xyz, const double* info, const int32_t* kind, const double* delta)
 {
 	return guarded(s, [&] { s->setLandmarkPriors(n, landmark, xyz, info, kind, delta); });
 }
 
-int cuba_hip_landmark_prior_chi_squares(cuba_hip_solver* s, double* chi2_per_prior)
-{
-	return guarded(s, [&] {
-		if (!s->haveGraph) throw StateError{ "set_graph must be called first" };
-		if (s->lmPriorSet.n() > 0 && !chi2_per_prior) throw ArgError{ "null output" };
-		s->landmarkPriorChiSquares(chi2_per_prior);
-	});
-}
+int cuba_hip_landmark_prior_chi_squares(cuba_hip_solver* s, double* chi2_per_prior) { return factor_chi_squares(s, cubahip::FACTOR_LMP, chi2_per_prior); }
 
 int cuba_hip_set_position_factors(cuba_hip_solver* s, int n, const int32_t* pose, const double* position, const double* lever_arm, const double* info,
 	const int32_t* kind, const double* delta)
@@ -548,14 +537,7 @@ int cuba_hip_set_position_factors(cuba_hip_solver* s, int n, const int32_t* pose
 	return guarded(s, [&] { s->setPositionFactors(n, pose, position, lever_arm, info, kind, delta); });
 }
 
-int cuba_hip_position_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor)
-{
-	return guarded(s, [&] {
-		if (!s->haveGraph) throw StateError{ "set_graph must be called first" };
-		if (s->posSet.n() > 0 && !chi2_per_factor) throw ArgError{ "null output" };
-		s->positionFactorChiSquares(chi2_per_factor);
-	});
-}
+int cuba_hip_position_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor) { return factor_chi_squares(s, cubahip::FACTOR_POS, chi2_per_factor); }
 
 int cuba_hip_set_direction_factors(cuba_hip_solver* s, int n, const int32_t* pose, const double* world_dir, const double* measured_dir, const double* info,
 	const int32_t* kind, const double* delta)
@@ -563,14 +545,7 @@ int cuba_hip_set_direction_factors(cuba_hip_solver* s, int n, const int32_t* pos
 	return guarded(s, [&] { s->setDirectionFactors(n, pose, world_dir, measured_dir, info, kind, delta); });
 }
 
-int cuba_hip_direction_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor)
-{
-	return guarded(s, [&] {
-		if (!s->haveGraph) throw StateError{ "set_graph must be called first" };
-		if (s->dirSet.n() > 0 && !chi2_per_factor) throw ArgError{ "null output" };
-		s->directionFactorChiSquares(chi2_per_factor);
-	});
-}
+int cuba_hip_direction_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor) { return factor_chi_squares(s, cubahip::FACTOR_DIR, chi2_per_factor); }
 
 int cuba_hip_time_kernels(cuba_hip_solver* s, int reps, double ms_per_launch[CUBA_HIP_TIMED_KERNELS])
 {
@@ -595,11 +570,8 @@ int cuba_hip_set_partition(cuba_hip_solver* s, int landmark_begin, int landmark_
 			return;
 		}
 		if (landmark_begin < 0 || landmark_end > s->Lt || landmark_begin > landmark_end) throw ArgError{ "bad landmark range" };
-		if (s->priorSet.n() > 0) throw StateError{ "a landmark partition is not available on a handle with pose priors" };
-		if (s->relSet.n() > 0) throw StateError{ "a landmark partition is not available on a handle with relative-pose edges" };
-		if (s->lmPriorSet.n() > 0) throw StateError{ "a landmark partition is not available on a handle with landmark priors" };
-		if (s->posSet.n() > 0) throw StateError{ "a landmark partition is not available on a handle with position factors" };
-		if (s->dirSet.n() > 0) throw StateError{ "a landmark partition is not available on a handle with direction factors" };
+		for (const FactorSet* set : s->factorSets)
+			if (set->n() > 0) throw StateError{ std::string("a landmark partition is not available on a handle with ") + set->plural };
 		if (s->partHi >= 0 && landmark_begin == s->partLo && landmark_end == s->partHi) return;      // (cuba_hip_set_graph_partition set it already)
 		s->partLo = landmark_begin; s->partHi = landmark_end;
 		s->haveStructure = false;

@@ -130,50 +130,58 @@ int run_covariance_pairs(const SparseChol& d, const SparseCholPlan& plan, const 
 }  // namespace cubahip_host
 using namespace cubahip_host;
 
-// one kind of factor as a handle keeps it (cuba_hip_solver, ba_factor.hip): what the kinds have in common, then each kind's values in the
-// caller's numbering
+struct cuba_hip_solver;
+// one kind of factor as a handle keeps it (cuba_hip_solver, ba_factor.hip): what the kinds have in common -- how the messages name the
+// kind, the robust kernels, the device copy and when it is due -- then each kind's values in the caller's numbering.  The handle's table of
+// its sets (factorSets) is all that the bookkeeping outside the setters knows of the kinds.
 struct FactorSet
 {
+	const char* const noun; const char* const plural;      // "position factor", "position factors"
+	const bool onStructure;          // the device copy depends on the structure (else on the pose order only)
 	std::vector<int> kind; std::vector<double> delta;      // [n] robust kernels in the caller's numbering
 	std::vector<int> order;          // sorted position -> caller's index (set by the upload)
 	bool uploaded = false;
 	int64_t structure = -1;          // cntStructureBuilds at the upload (the kinds whose device copy depends on the structure)
-	DevBuf<int> d_ints; DevBuf<Scalar> d_vals, d_chi;
-	void clear() { kind.clear(); delta.clear(); order.clear(); uploaded = false; }
+	DevBuf<int> d_ints; DevBuf<Scalar> d_vals, d_chi;      // (d_chi: the per-factor chi2 of the kind's device struct)
+	FactorSet(const char* noun, const char* plural, bool onStructure) : noun(noun), plural(plural), onStructure(onStructure) {}
+	virtual ~FactorSet() = default;
+	virtual int n() const = 0;
+	virtual void clear() { kind.clear(); delta.clear(); order.clear(); uploaded = false; }
+	virtual void upload(cuba_hip_solver& s) = 0;           // the caller's set -> device, in the internal order
 };
-// pose priors, relative-pose edges; kind / delta empty: no factor has a kernel
-struct PoseFactorValues { std::vector<int> pi, pj; std::vector<double> q, t, info; };      // [n] poses (pj: edges only), [4 n], [3 n], [36 n]
-struct PoseFactorSet : FactorSet
+// the unary kinds on the poses -- pose priors (a = q, b = t: widths 4, 3, 36), position factors (z, arm: 3, 3, 9), direction factors
+// (d, m: 3, 3, 9) --: the information as the symmetrised D x D; kind / delta empty: no factor has a kernel.  dev, da, db: the kind's device
+// struct and its two measurement arrays there
+struct UnaryPoseFactorSet : FactorSet
 {
-	PoseFactorValues v;
-	int n() const { return (int)v.pi.size(); }
-	void clear() { v = PoseFactorValues(); FactorSet::clear(); }
+	const int wa, wb, wi;
+	DevicePoseGroups& dev; const Scalar*& da; const Scalar*& db;
+	std::vector<int> pose; std::vector<double> a, b, info;       // [n], [wa n], [wb n], [wi n]
+	UnaryPoseFactorSet(const char* noun, const char* plural, int wa, int wb, int wi, DevicePoseGroups& dev, const Scalar*& da, const Scalar*& db)
+		: FactorSet(noun, plural, false), wa(wa), wb(wb), wi(wi), dev(dev), da(da), db(db) {}
+	int n() const override { return (int)pose.size(); }
+	void clear() override { pose.clear(); a.clear(); b.clear(); info.clear(); FactorSet::clear(); }
+	void upload(cuba_hip_solver& s) override;
+};
+// relative-pose edges; kind / delta empty: no edge has a kernel
+struct RelPoseSet : FactorSet
+{
+	std::vector<int> pi, pj; std::vector<double> q, t, info;     // [n], [n], [4 n], [3 n], [36 n]
+	RelPoseSet() : FactorSet("relative-pose edge", "relative-pose edges", true) {}
+	int n() const override { return (int)pi.size(); }
+	void clear() override { pi.clear(); pj.clear(); q.clear(); t.clear(); info.clear(); FactorSet::clear(); }
+	void upload(cuba_hip_solver& s) override;
 };
 // landmark position priors: the information as its symmetrised upper triangle, every prior with a kernel (kind 0, delta 1: none)
 struct LandmarkPriorSet : FactorSet
 {
 	std::vector<int> lm; std::vector<double> xyz, info;      // [n], [3 n], [6 n]
-	int n() const { return (int)lm.size(); }
-	void clear() { lm.clear(); xyz.clear(); info.clear(); FactorSet::clear(); }
+	LandmarkPriorSet() : FactorSet("landmark prior", "landmark priors", true) {}
+	int n() const override { return (int)lm.size(); }
+	void clear() override { lm.clear(); xyz.clear(); info.clear(); FactorSet::clear(); }
+	void upload(cuba_hip_solver& s) override;
 };
 
-// position factors on the poses: the information as the symmetrised 3 x 3; kind / delta empty: no factor has a kernel
-struct PositionFactorSet : FactorSet
-{
-	std::vector<int> pose; std::vector<double> z, arm, info;      // [n], [3 n], [3 n], [9 n]
-	int n() const { return (int)pose.size(); }
-	void clear() { pose.clear(); z.clear(); arm.clear(); info.clear(); FactorSet::clear(); }
-};
-
-// direction factors on the poses: the information as the symmetrised 3 x 3; kind / delta empty: no factor has a kernel
-struct DirectionFactorSet : FactorSet
-{
-	std::vector<int> pose; std::vector<double> d, m, info;        // [n], [3 n], [3 n], [9 n]
-	int n() const { return (int)pose.size(); }
-	void clear() { pose.clear(); d.clear(); m.clear(); info.clear(); FactorSet::clear(); }
-};
-
-struct cuba_hip_solver;
 int cuba_hip_optimize_batch_impl(cuba_hip_solver** hs, int n, int niter, double* chi2, int* nDone);
 
 struct cuba_hip_solver
@@ -617,47 +625,46 @@ struct cuba_hip_solver
 		uploadFactors();
 	}
 
-	// The factors besides the reprojection edges (ba_factor.hip).  On the poses: SE(3) pose priors (cuba_hip_set_pose_priors) and relative-pose
-	// edges (cuba_hip_set_relative_pose_edges).  Either set is kept as the caller gave it, in its own numbering (quaternions normalised,
-	// information symmetrised), with a device copy in the internal pose order that need() makes: the priors' once the pose order is known and
-	// again whenever that order changes; the edges' (their blocks are looked up in the pattern) with every structure; either again after
-	// cuba_hip_set_pose_factor_robust_kernels, whose kinds and deltas travel with the values.
-	// On the landmarks: position priors (cuba_hip_set_landmark_priors), kept as the caller gave them, with a device copy (pf.lmp) in the
-	// internal landmark order that need() makes once that order is known and again with every structure (a change of the landmark order
-	// rebuilds it).  The landmark pass linearises them -- linearize() hands pf.lmp to it --, the chi2 sums take them as one more kind.
-	// On the poses again: position factors (cuba_hip_set_position_factors), kept as the caller gave them, with a device copy (pf.pos) in the
-	// internal pose order that need() makes once that order is known and again whenever it changes, as the pose priors'.  Their values never
-	// touch the structure.  Direction factors (cuba_hip_set_direction_factors; pf.dir) are kept and uploaded the same way.
+	// The factors besides the reprojection edges (ba_factor.hip): five kinds, each a set kept as the caller gave it, in the caller's numbering
+	// (quaternions normalised, information symmetrised), with a device copy (pf) in the internal order that need() makes -- uploadFactors():
+	// once that order is known, again when it changes (the unary kinds on the poses: with the pose order; the relative-pose edges, whose
+	// blocks are looked up in the pattern, and the landmark priors: with every structure), and again after a setter or
+	// cuba_hip_set_pose_factor_robust_kernels, whose kinds and deltas travel with the values.  The landmark pass linearises the landmark
+	// priors -- linearize() hands pf.lmp to it --, the chi2 sums take them as one more kind.
 	// No factors of any kind: factors() is null, nothing of it is launched, no extra seed enters the pattern build, and every launch and kernel argument is as
 	// without this feature.
-	PoseFactorSet priorSet, relSet;
-	LandmarkPriorSet lmPriorSet;
-	PositionFactorSet posSet;
-	DirectionFactorSet dirSet;
 	DeviceFactors pf;
-	const DeviceFactors* factors() const { return priorSet.n() + relSet.n() + lmPriorSet.n() + posSet.n() + dirSet.n() > 0 ? &pf : nullptr; }
+	UnaryPoseFactorSet priorSet{ "prior", "pose priors", 4, 3, 36, pf.priors, pf.priors.qbar, pf.priors.tbar };
+	RelPoseSet relSet;
+	LandmarkPriorSet lmPriorSet;
+	UnaryPoseFactorSet posSet{ "position factor", "position factors", 3, 3, 9, pf.pos, pf.pos.z, pf.pos.arm };
+	UnaryPoseFactorSet dirSet{ "direction factor", "direction factors", 3, 3, 9, pf.dir, pf.dir.d, pf.dir.m };
+	FactorSet* const factorSets[FACTOR_KINDS] = { &priorSet, &relSet, &lmPriorSet, &posSet, &dirSet };      // in the order of FACTOR_* (ba_kernels.hpp)
+	const DeviceFactors* factors() const
+	{
+		for (const FactorSet* set : factorSets) if (set->n() > 0) return &pf;
+		return nullptr;
+	}
 	int factorParts() const { return factor_chi2_parts(factors()); }      // chi2 partials that follow the reprojection edges'
 	void clearFactors()
 	{
-		priorSet.clear(); relSet.clear(); lmPriorSet.clear(); posSet.clear(); dirSet.clear();
+		for (FactorSet* set : factorSets) set->clear();
 		h_relPairs.clear(); pf = DeviceFactors();
 	}
+	// a new pose order: the device copies that depend on it alone are due again (the others follow the structure)
+	void poseOrderChanged() { for (FactorSet* set : factorSets) if (!set->onStructure) set->uploaded = false; }
 	// the run-to-run memories that the values of the system feed (option "heuristics"): dropped by a change of the factors as by a new graph
 	void forgetRunMemories() { firstInvValid = false; firstInvPending = false; prevRunIters.clear(); runIters.clear(); firstSolveIters = 0; }
 	void uploadFactors();
 	int internalPose(int p) const { return p < Pf && reorderActive ? poseNewOfOld[p] : p; }      // of a pose in the caller's numbering
 	void setPosePriors(int n, const int32_t* pose, const double* q, const double* t, const double* info);
-	void priorChiSquares(double* out);
 	void setRelativePoseEdges(int n, const int32_t* pi, const int32_t* pj, const double* q, const double* t, const double* info);
-	void relativePoseChiSquares(double* out);
 	void setPoseFactorRobustKernels(int factorType, int n, const int32_t* kind, const double* delta);
 	const DeviceLandmarkPriors* landmarkPriors() const { return lmPriorSet.n() > 0 ? &pf.lmp : nullptr; }      // (null: nothing of them is launched or passed)
 	void setLandmarkPriors(int n, const int32_t* landmark, const double* xyz, const double* info, const int32_t* kind, const double* delta);
-	void landmarkPriorChiSquares(double* out);
 	void setPositionFactors(int n, const int32_t* pose, const double* position, const double* leverArm, const double* info, const int32_t* kind, const double* delta);
-	void positionFactorChiSquares(double* out);
 	void setDirectionFactors(int n, const int32_t* pose, const double* worldDir, const double* measuredDir, const double* info, const int32_t* kind, const double* delta);
-	void directionFactorChiSquares(double* out);
+	void factorChiSquares(int kind, double* out);      // r^T Omega r of every factor of the kind (FACTOR_*), in the caller's order
 	// the edges' distinct free-free pairs (sorted keys i << 32 | j, i < j, caller's numbering) and the pairs the current structure was seeded
 	// with: every such pair owns a block of the reduced matrix, so need() rebuilds the structure exactly when the two sets differ
 	std::vector<uint64_t> h_relPairs, structRelPairs;

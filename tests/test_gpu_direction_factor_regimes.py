@@ -1,4 +1,4 @@
-"""The direction-factor kernels (csrc/ba_factor.hip: direction_linearize_kernel, direction_chi2_kernel) against the 60-digit reference
+"""The direction-factor kernels (csrc/ba_factor.hip: direction_linearize_kernel, factor_chi2_kernel<DeviceDirectionFactors>) against the 60-digit reference
 recorded in tests/golden/direction_cases.npz (tests/golden/make_golden_direction_cases.py), by the method of
 tests/test_gpu_factor_regimes.py: pose rotations of 1e-8, 1 and pi - 1e-6, a negated quaternion, residuals |r| of 1e-8, 0.1 and 2
 (m = -R d), rank-2 and full information, and e / delta^2 at 0, 0.25, 1 -+ 1e-9, 4 and 1e6 under every kernel.  This module reads the
