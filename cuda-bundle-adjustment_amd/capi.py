@@ -133,6 +133,8 @@ def load_library(precision="f64"):
         "cuba_hip_position_factor_chi_squares": [H, _dp],
         "cuba_hip_set_direction_factors": [H, C.c_int, _ip, _dp, _dp, _dp, _ip, _dp],
         "cuba_hip_direction_factor_chi_squares": [H, _dp],
+        "cuba_hip_set_range_factors": [H, C.c_int, _ip, _dp, _dp, _dp, _dp, _ip, _dp],
+        "cuba_hip_range_factor_chi_squares": [H, _dp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -394,7 +396,7 @@ class HipSolver:
         landmark_range = (begin, end): cuba_hip_set_graph_partition -- the upload of one rank of a landmark partition, which sends the
         measurements and information of its own landmarks' edges only."""
         self.fp = fp
-        self._n_factors = {}            # (every upload clears the pose priors, the relative-pose edges, the landmark priors, the position and the direction factors)
+        self._n_factors = {}            # (every upload clears the pose priors, the relative-pose edges, the landmark priors, the position, the direction and the range factors)
         q, t, cam, Xw = (np.ascontiguousarray(a, dtype=np.float64) for a in (fp.q, fp.t, fp.cam, fp.Xw))
         eP = np.ascontiguousarray(fp.eP, dtype=np.int32)
         eL = np.ascontiguousarray(fp.eL, dtype=np.int32)
@@ -621,6 +623,33 @@ class HipSolver:
     def direction_factor_chi_squares(self):
         """r^T Omega r of every direction factor at the current estimate, in the order they were given (0 for factors on fixed poses)"""
         return self._factor_chi_squares("direction_factor")
+
+    def set_range_factors(self, pose, anchor, range, info, lever_arm=None, kind=None, delta=None):
+        """Range factors on the poses (cuba_hip_set_range_factors; UWB-style distances to known anchors), replacing the handle's set:
+        pose[n] in the solver numbering, the anchors' world positions anchor[n, 3], the measured distances range[n] (>= 0), the scalar
+        informations info[n] (1 / sigma^2, >= 0), lever_arm[n, 3] (the ranging antenna in the camera frame; None: the camera centre);
+        kind[n] (0 none, 1 Huber, 2 Tukey, 3 Cauchy) and delta[n] together or not at all (scalars broadcast).  An empty pose list clears
+        the set."""
+        pose = np.ascontiguousarray(pose, dtype=np.int32).reshape(-1)
+        n = int(pose.size)
+        anchor = np.ascontiguousarray(anchor, dtype=np.float64).reshape(n, 3)
+        range = np.ascontiguousarray(np.broadcast_to(np.asarray(range, dtype=np.float64), (n,)))
+        info = np.ascontiguousarray(np.broadcast_to(np.asarray(info, dtype=np.float64), (n,)))
+        if lever_arm is not None:
+            lever_arm = np.ascontiguousarray(lever_arm, dtype=np.float64).reshape(n, 3)
+        if kind is not None:
+            kind = np.ascontiguousarray(np.full(n, kind) if np.ndim(kind) == 0 else kind, dtype=np.int32).reshape(-1)
+        if delta is not None:
+            delta = np.ascontiguousarray(np.full(n, delta) if np.ndim(delta) == 0 else delta, dtype=np.float64).reshape(-1)
+        if (kind is not None and kind.size != n) or (delta is not None and delta.size != n):
+            raise ValueError("kind / delta differ in length from the set")
+        self._ck(self.lib.cuba_hip_set_range_factors(self.h, n, pose.ctypes.data_as(_ip), _d(anchor), _d(range), _d(lever_arm), _d(info),
+                                                     kind.ctypes.data_as(_ip) if kind is not None else None, _d(delta)))
+        self._n_factors["range_factor"] = n
+
+    def range_factor_chi_squares(self):
+        """info r^2 of every range factor at the current estimate, in the order they were given (0 for factors on fixed poses)"""
+        return self._factor_chi_squares("range_factor")
 
     def chi_squares_two_step(self):
         """cuba_hip_chi_squares_begin / _end (the C++ layer does its write-back between the two)"""

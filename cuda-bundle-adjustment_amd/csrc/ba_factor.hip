@@ -1,7 +1,7 @@
 // ba_factor.hip -- the factors besides the reprojection edges: terms rho(r^T Omega r) of the objective on the vertices alone, Omega a full
 // symmetric information.  Two kinds on the SE(3) poses, r in the [omega, upsilon] tangent of the solver's left-multiplicative update
-// T <- exp(d) T (pose_exp_update), Omega 6 x 6, one on the landmarks, one that ties a pose to a world position and one that ties its
-// rotation to a world direction:
+// T <- exp(d) T (pose_exp_update), Omega 6 x 6, one on the landmarks, one that ties a pose to a world position, one that ties its
+// rotation to a world direction and one that ties it to a measured distance from a world point:
 //
 //   pose priors (cuba_hip_set_pose_priors): unary, r = log(T Tbar^-1), linearised with the exact derivative dr/dd =
 //     J_l(r)^-1.  A prior touches the diagonal 6 x 6 block of its pose in the reduced matrix and the pose's entries of bp / bsc only.
@@ -25,22 +25,30 @@
 //     the update R' = (I + [omega]x) R, so r' = r + omega x (R d) and dr/dd = [-[R d]x | 0] (3 x 6) -- NOT the body-frame -R [d]x, which
 //     equals -[R d]x R.  The translation columns are exactly zero: a factor touches the rotation 3 x 3 of its pose's diagonal block and the
 //     first three entries of the pose's bp / bsc, nothing else.
+//   range factors (cuba_hip_set_range_factors; section 7i): unary on the poses, the first kind with a SCALAR, non-linear residual:
+//     r = rho - rbar, rho = |u|, u = a - (R b + t): the distance of the point a of the camera frame (the lever arm of the ranging antenna;
+//     zero: the camera centre) from the world point b (a UWB anchor, a beacon, a total station) against a measured range rbar; Omega the
+//     scalar 1 / sigma^2.  With m = u / rho (camera frame) and b_c = R b + t, the update gives b_c' = b_c + omega x b_c + upsilon, so
+//     d rho = -m . (omega x b_c + upsilon), and b_c x m = a x m: dr/dd = [(m x a)^T | -m^T] (1 x 6) -- NOT with the world-frame direction
+//     R^T m, and the rotation columns vanish only for a = 0.  J^T J has rank 1.  THE POINT rho = 0 (the antenna at the anchor): m is undefined
+//     there; the rule is m = 0 when the computed rho is exactly 0, so J = 0: the factor adds nothing to H or g and its e = Omega rbar^2.
 //
 // A factor may carry a robust kernel (cuba_hip_set_pose_factor_robust_kernels; section 7e): with e = r^T Omega r its term is rho(e) and its
 // linearisation takes w Omega, w = rho'(e), for Omega (no second-order term, as the reprojection edges).  The kernels that see a
 // residual are templates on ROBUST; a set without kernels has null kind / delta arrays and runs the `false` instantiations, which hold
 // nothing of this.  A landmark prior always carries a kind (none = 0) and comes with its kernel in one call.
 //
-// Order: the pose priors, the position factors, the relative-pose edges and the direction factors all add to the diagonal blocks, bp and
-// bsc that the pose and Schur passes stored, by read-modify-write.  launch_pose_factor_linearize issues them in one stream in this order --
-// priors, position factors, the edges' records, the edges' gather, direction factors -- and that order is part of the result
+// Order: the pose priors, the position factors, the relative-pose edges, the direction factors and the range factors all add to the diagonal
+// blocks, bp and bsc that the pose and Schur passes stored, by read-modify-write.  launch_pose_factor_linearize issues them in one stream in
+// this order -- priors, position factors, the edges' records, the edges' gather, direction factors, range factors -- and that order is part of the result
 // (floating-point sums do not commute): a handle's bits depend on it, and a new kind goes BEHIND the ones a handle may already combine,
 // never between two of them.  (The position factors sit between the priors and the edges: no handle could hold them before they came, so
-// no existing sum changed.  The direction factors came when handles could combine all of the others, so they go last.)
+// no existing sum changed.  The direction factors came when handles could combine all of the others, so they went last; the range factors came after them and go
+// behind them.)
 //
 // The kinds keep linearisation kernels of their own (a prior is not run as a one-ended edge: its sums would be taken in another order).
 // Everything else exists once: the device helpers below (the unary kinds' accumulators and their read-modify-write: zero_pose_sums,
-// add_pose_sums), one chi2 kernel over a per-kind residual, one device layout and one upload for the three unary kinds on the poses
+// add_pose_sums), one chi2 kernel over a per-kind residual, one device layout and one upload for the four unary kinds on the poses
 // (ba_kernels.hpp: DevicePoseGroups), the host-side validation, sorting and read-back, and one interface (ba_kernels.hpp: DeviceFactors;
 // ba_solver.hpp: the handle's table of its sets).  A new kind brings a residual, a Jacobian, a setter with its widths and nouns, and its
 // entry there.
@@ -63,12 +71,16 @@
 //   direction_linearize_kernel lane = free pose with direction factors: the rotation matrix once, then the pose's factors in the caller's order,
 //                              [v]x^T Omega [v]x, v = R d (6 numbers) and v x (Omega r) (3) summed in registers, one read-modify-write of the
 //                              upper triangle of the block's rotation 3 x 3, of bp[0..3) and (mode 1) bsc[0..3) -- one writer per number; the
-//                              last launch, behind the edges' gather
+//                              launch behind the edges' gather
+//   range_linearize_kernel     lane = free pose with range factors: the rotation matrix once, then the pose's factors in the caller's order,
+//                              w Omega J^T J (21 numbers, rank 1 per factor) and w Omega r J^T (6) summed in registers, one read-modify-write of
+//                              the diagonal block's upper triangle, bp and (mode 1) bsc -- one writer per number; the last launch, behind the
+//                              direction factors'
 //   factor_chi2_kernel         lane = factor of one kind: r^T Omega r at the current estimate (factor_chi, an overload per kind) into the per-factor
 //                              output and (rho of it) into per-workgroup partials that the caller sums together with the reprojection
 //                              edges' partials (fixed order, no atomics)
 //
-// Host side: the caller's five sets (validated, kept in the caller's numbering), the edges' pair set (part of the topology) and the upload
+// Host side: the caller's six sets (validated, kept in the caller's numbering), the edges' pair set (part of the topology) and the upload
 // of every set in the internal pose / landmark order.
 #include "ba_solver.hpp"
 #include "ba_device.hpp"
@@ -80,6 +92,7 @@ namespace cubahip
 constexpr int PRIOR_LIN_BLOCK = 64;
 constexpr int POS_LIN_BLOCK = 64;
 constexpr int DIR_LIN_BLOCK = 64;
+constexpr int RNG_LIN_BLOCK = 64;
 constexpr int REL_LIN_BLOCK = 64;
 constexpr int REL_GATHER_BLOCK = 256;
 constexpr int CHI_BLOCK = 256;
@@ -582,6 +595,71 @@ __device__ __forceinline__ Scalar factor_chi(const DeviceGraph& g, const DeviceD
 	return direction_residual(df, k, R.m, v, Or);
 }
 
+// ---- range factors ----------------------------------------------------------------------------------------------------------------
+
+// u = (a - t) - R b, rho = |u| and r = rho - rbar of factor k at the pose [R | t] (R row-major in Rm); m = u / rho, the unit vector from the
+// anchor to the antenna in the camera frame.  THE POINT rho = 0 (the antenna at the anchor): there m is undefined, and 0 / 0 would put NaN
+// into the system.  The rule: when the computed rho is exactly 0, m = 0 -- so J = 0, the factor adds nothing to H or g, and its
+// e = info rbar^2.  Returns e = info r^2
+__device__ __forceinline__ Scalar range_residual(const DeviceRangeFactors& rf, int k, const Scalar Rm[3][3], const Scalar t[3], Scalar m[3], Scalar& r)
+{
+	const Scalar* a = rf.arm + 3 * (size_t)k;
+	const Scalar* b = rf.br + 4 * (size_t)k;
+	Scalar u[3];
+#pragma unroll
+	for (int i = 0; i < 3; i++) u[i] = (a[i] - t[i]) - (Rm[i][0] * b[0] + Rm[i][1] * b[1] + Rm[i][2] * b[2]);
+	const Scalar rho = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+	const Scalar inv = rho > 0 ? 1 / rho : 0;
+#pragma unroll
+	for (int i = 0; i < 3; i++) m[i] = u[i] * inv;
+	r = rho - b[3];
+	return rf.info[k] * r * r;
+}
+
+template <bool ROBUST>
+__global__ __launch_bounds__(RNG_LIN_BLOCK) void range_linearize_kernel(DeviceGraph g, DeviceStructure st, DeviceSystem sys, DeviceRangeFactors rf, int mode)
+{
+	const int i = blockIdx.x * RNG_LIN_BLOCK + threadIdx.x;
+	if (i >= rf.nPoses) return;
+	const int ip = rf.pose_id[i];
+	Scalar q[4], t[3];
+	load_pose(g.q, g.t, ip, q, t);
+	const Rot3 R = quat_to_rot(q[0], q[1], q[2], q[3]);
+	Scalar H[21], gv[6];
+	zero_pose_sums<6>(H, gv);
+	const int k1 = rf.pose_ptr[i + 1];
+	for (int k = rf.pose_ptr[i]; k < k1; k++)
+	{
+		Scalar m[3], r;
+		const Scalar e = range_residual(rf, k, R.m, t, m, r);
+		Scalar w = rf.info[k];
+		if constexpr (ROBUST) w *= factor_weight(rf.rk_kind[k], rf.rk_delta[k], e);
+		// J = [(m x a)^T | -m^T] (1 x 6; all zero at rho = 0): H += w info J^T J (upper triangle, H[c (c + 1) / 2 + r]), gv += w info r J^T
+		const Scalar* a = rf.arm + 3 * (size_t)k;
+		const Scalar J[6] = { m[1] * a[2] - m[2] * a[1], m[2] * a[0] - m[0] * a[2], m[0] * a[1] - m[1] * a[0], -m[0], -m[1], -m[2] };
+#pragma unroll
+		for (int c = 0; c < 6; c++)
+		{
+			const Scalar wj = w * J[c];
+#pragma unroll
+			for (int rr = 0; rr <= c; rr++) H[c * (c + 1) / 2 + rr] += J[rr] * wj;
+			gv[c] += wj * r;
+		}
+	}
+	add_pose_sums<6>(st, sys, ip, mode, H, gv);
+}
+
+// info r^2 of factor k at the current estimate (factor_chi2_kernel)
+__device__ __forceinline__ Scalar factor_chi(const DeviceGraph& g, const DeviceRangeFactors& rf, int k)
+{
+	const int ip = rf.pose[k];
+	if (ip >= g.Pf) return 0;
+	Scalar q[4], t[3], m[3], r;
+	load_pose(g.q, g.t, ip, q, t);
+	const Rot3 R = quat_to_rot(q[0], q[1], q[2], q[3]);
+	return range_residual(rf, k, R.m, t, m, r);
+}
+
 // ---- chi2 -------------------------------------------------------------------------------------------------------------------------
 
 // The chi2 of a kind: lane = factor, r^T Omega r at the current estimate -- factor_chi(g, kind, k), one overload per kind above, 0 for a factor
@@ -665,6 +743,13 @@ void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& s
 		const dim3 grid((df.nPoses + DIR_LIN_BLOCK - 1) / DIR_LIN_BLOCK);
 		if (df.rk_kind) hipLaunchKernelGGL(direction_linearize_kernel<true>, grid, dim3(DIR_LIN_BLOCK), 0, s, g, st, sys, df, mode);
 		else hipLaunchKernelGGL(direction_linearize_kernel<false>, grid, dim3(DIR_LIN_BLOCK), 0, s, g, st, sys, df, mode);
+	}
+	const DeviceRangeFactors& rf = pf.rng;
+	if (rf.nPoses > 0)
+	{
+		const dim3 grid((rf.nPoses + RNG_LIN_BLOCK - 1) / RNG_LIN_BLOCK);
+		if (rf.rk_kind) hipLaunchKernelGGL(range_linearize_kernel<true>, grid, dim3(RNG_LIN_BLOCK), 0, s, g, st, sys, rf, mode);
+		else hipLaunchKernelGGL(range_linearize_kernel<false>, grid, dim3(RNG_LIN_BLOCK), 0, s, g, st, sys, rf, mode);
 	}
 }
 
@@ -878,6 +963,53 @@ void cuba_hip_solver::setDirectionFactors(int n, const int32_t* pose, const doub
 	covBlocksValid = false;
 }
 
+// a caller's set of range factors, factor by factor (the scalar kind's counterpart of take_factors3): the pose index within [0, limit), the
+// anchor, the lever arm (where given; zero otherwise) and the range finite, the range and the information not negative (0: no factor), the
+// kernel a known one.  a: {anchor, range} (width 4), b: the arm.  kind / delta as take_factors3
+static TakenFactors take_range_factors(const FactorSet& set, int n, const int32_t* pose, int limit, const double* anchor, const double* range, const double* arm,
+	const double* info, const int32_t* kind, const double* delta)
+{
+	const std::string noun = set.noun;
+	TakenFactors v;
+	v.idx.resize((size_t)n); v.a.resize((size_t)4 * n); v.b.assign((size_t)3 * n, 0.0); v.info.resize((size_t)n);
+	bool any = false;
+	for (int k = 0; k < n; k++)
+	{
+		if (pose[k] < 0 || pose[k] >= limit) throw ArgError{ noun + ": pose index out of range" };
+		v.idx[k] = pose[k];
+		for (int i = 0; i < 3; i++)
+		{
+			if (!std::isfinite(anchor[3 * (size_t)k + i])) throw ArgError{ "non-finite " + noun + " anchor" };
+			v.a[4 * (size_t)k + i] = anchor[3 * (size_t)k + i];
+			if (!arm) continue;
+			if (!std::isfinite(arm[3 * (size_t)k + i])) throw ArgError{ "non-finite " + noun + " lever arm" };
+			v.b[3 * (size_t)k + i] = arm[3 * (size_t)k + i];
+		}
+		if (!std::isfinite(range[k])) throw ArgError{ "non-finite " + noun + " range" };
+		if (range[k] < 0) throw ArgError{ "negative " + noun + " range" };
+		v.a[4 * (size_t)k + 3] = range[k];
+		if (!std::isfinite(info[k])) throw ArgError{ "non-finite " + noun + " information" };
+		if (info[k] < 0) throw ArgError{ "negative " + noun + " information" };
+		v.info[k] = info[k];
+		if (kind)
+		{
+			check_factor_kernel(kind[k], delta[k], set.noun);
+			any = any || kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE;
+		}
+	}
+	if (any) { v.kind.assign(kind, kind + n); v.delta.assign(delta, delta + n); }
+	return v;
+}
+
+void cuba_hip_solver::setRangeFactors(int n, const int32_t* pose, const double* anchor, const double* range, const double* leverArm, const double* info,
+	const int32_t* kind, const double* delta)
+{
+	check_factor_call(*this, rngSet, n, pose && anchor && range && info, kind, delta);
+	TakenFactors v = take_range_factors(rngSet, n, pose, Pt, anchor, range, leverArm, info, kind, delta);
+	adopt_unary_pose_factors(*this, rngSet, v);
+	covBlocksValid = false;
+}
+
 std::vector<uint64_t> cuba_hip_solver::relSeedKeys() const
 {
 	std::vector<uint64_t> keys(h_relPairs.size());
@@ -936,7 +1068,7 @@ static std::vector<int> concat(std::initializer_list<const std::vector<int>*> pa
 }
 
 // a unary kind's factors on the poses -> device, in the internal pose order (stable by internal pose: every pose's factors contiguous, in
-// the caller's order; the factors on fixed poses last).  The same layout for the three kinds:
+// the caller's order; the factors on fixed poses last).  The same layout for the four kinds:
 // ints: pose_ptr [np + 1] | pose_id [np] | pose [n] | kind [n, robust];  values: a [wa n] | b [wb n] | info [wi n] | delta [n, robust]
 void UnaryPoseFactorSet::upload(cuba_hip_solver& s)
 {

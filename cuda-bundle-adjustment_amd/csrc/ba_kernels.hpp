@@ -141,7 +141,7 @@ struct DeviceSystem
 // delta^2 log1p(e / delta^2), exists for these factors only (helpers in ba_device.hpp).
 enum { POSE_FACTOR_KERNEL_NONE = 0, POSE_FACTOR_KERNEL_HUBER = 1, POSE_FACTOR_KERNEL_TUKEY = 2, POSE_FACTOR_KERNEL_CAUCHY = 3 };
 
-// The unary kinds of factor on the poses (ba_factor.hip) -- SE(3) pose priors, position factors, direction factors -- share their device
+// The unary kinds of factor on the poses (ba_factor.hip) -- SE(3) pose priors, position, direction and range factors -- share their device
 // layout: rho(r^T Omega r) per factor, sorted by internal pose (stable: a pose's factors are contiguous and in the caller's order); factors
 // on fixed poses come last and are ignored.  A kind adds its two measurement arrays.
 struct DevicePoseGroups
@@ -164,6 +164,10 @@ struct DevicePositionFactors : DevicePoseGroups { const Scalar *z = nullptr, *ar
 // Direction factors (gravity, compass, vanishing directions): r = R d - m, a world vector d against the same vector as measured in the
 // camera frame, m (neither is normalised), D = 3 (Omega of rank 2 as a rule)
 struct DeviceDirectionFactors : DevicePoseGroups { const Scalar *d = nullptr, *m = nullptr; };   // [3 n] world vectors, [3 n] their measurements
+// Range factors (UWB anchors, acoustic beacons, slope distances): r = |a - t - R b| - rbar, the distance of the point a of the camera frame
+// (the lever arm of the ranging antenna; zero: the camera centre) from the world point b (the anchor) against a measured range rbar, D = 1
+// (info: the scalar 1 / sigma^2).  At a computed distance of exactly 0 the direction is undefined: the factor then has J = 0 (ba_factor.hip)
+struct DeviceRangeFactors : DevicePoseGroups { const Scalar *br = nullptr, *arm = nullptr; };    // [4 n] {anchor, measured range}, [3 n] lever arms
 
 // SE(3) relative-pose edges (ba_factor.hip): rho(r^T Omega r), r = log(T_j T_i^-1 Zbar^-1), between two poses.  Sorted: the edges between two
 // free poses first, stable by the block (min, max) of the internal pose pair (a block's edges contiguous, in the caller's order), then the
@@ -208,18 +212,19 @@ struct DeviceLandmarkPriors
 // The factors of a handle besides the reprojection edges: what the rest of the library sees of the kinds (a kind without factors: n = 0,
 // nothing of it is launched).  The landmark priors ride along for the chi2 sums only: their linearisation is the landmark pass's.
 // FACTOR_*: the kinds in the order of their chi2 partials, of each() below and of the handle's table of sets (ba_solver.hpp: factorSets).
-enum { FACTOR_PRIORS = 0, FACTOR_REL, FACTOR_LMP, FACTOR_POS, FACTOR_DIR, FACTOR_KINDS };
+enum { FACTOR_PRIORS = 0, FACTOR_REL, FACTOR_LMP, FACTOR_POS, FACTOR_DIR, FACTOR_RNG, FACTOR_KINDS };
 struct DeviceFactors
 {
-	DevicePriors priors; DeviceRelPoses rel; DeviceLandmarkPriors lmp; DevicePositionFactors pos; DeviceDirectionFactors dir;
-	template <class F> void each(F&& f) const { f(priors); f(rel); f(lmp); f(pos); f(dir); }      // every kind's device struct, in that order
+	DevicePriors priors; DeviceRelPoses rel; DeviceLandmarkPriors lmp; DevicePositionFactors pos; DeviceDirectionFactors dir; DeviceRangeFactors rng;
+	template <class F> void each(F&& f) const { f(priors); f(rel); f(lmp); f(pos); f(dir); f(rng); }      // every kind's device struct, in that order
 };
 // behind the Schur pass, the priors first (Omega: w Omega of a factor with a robust kernel): J^T Omega J into the diagonal blocks of hsc (upper triangle), -J^T Omega r into bp and (mode 1)
 // bsc, J = J_l(r)^-1; then the position factors the same way in a launch of their own, J = [R^T [a]x | -R^T]; then the edges in two
 // launches: per-edge records, then their sums into hsc (diagonal blocks: upper triangle; mode 1: the off-diagonal blocks of the pairs,
-// stored whole where a block has no Schur products), bp and (mode 1) bsc; last the direction factors in a launch of their own, J =
-// [-[R d]x | 0]: the rotation 3 x 3 of the diagonal block and the first three entries of bp / bsc only.  All four add to the same diagonal
-// blocks: the order of the launches is part of the result
+// stored whole where a block has no Schur products), bp and (mode 1) bsc; then the direction factors in a launch of their own, J =
+// [-[R d]x | 0]: the rotation 3 x 3 of the diagonal block and the first three entries of bp / bsc only; last the range factors in a launch
+// of their own, J = [(m x a)^T | -m^T] (1 x 6, m the unit vector from the anchor to the antenna in the camera frame).  All five add to the
+// same diagonal blocks: the order of the launches is part of the result
 void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DeviceFactors& pf, int mode, hipStream_t s);
 // per-factor chi2 (the plain r^T Omega r) into every kind's chi, per-workgroup partial sums of rho(chi2) into
 // parts[0 .. factor_chi2_parts(&pf)), kind behind kind in the order of FACTOR_*.  only >= 0: that kind alone, its partials at parts[0]

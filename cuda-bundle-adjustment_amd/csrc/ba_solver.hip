@@ -547,6 +547,14 @@ int cuba_hip_set_direction_factors(cuba_hip_solver* s, int n, const int32_t* pos
 
 int cuba_hip_direction_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor) { return factor_chi_squares(s, cubahip::FACTOR_DIR, chi2_per_factor); }
 
+int cuba_hip_set_range_factors(cuba_hip_solver* s, int n, const int32_t* pose, const double* anchor, const double* range, const double* lever_arm, const double* info,
+	const int32_t* kind, const double* delta)
+{
+	return guarded(s, [&] { s->setRangeFactors(n, pose, anchor, range, lever_arm, info, kind, delta); });
+}
+
+int cuba_hip_range_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor) { return factor_chi_squares(s, cubahip::FACTOR_RNG, chi2_per_factor); }
+
 int cuba_hip_time_kernels(cuba_hip_solver* s, int reps, double ms_per_launch[CUBA_HIP_TIMED_KERNELS])
 {
 	return guarded(s, [&] {

@@ -150,7 +150,7 @@ struct FactorSet
 	virtual void upload(cuba_hip_solver& s) = 0;           // the caller's set -> device, in the internal order
 };
 // the unary kinds on the poses -- pose priors (a = q, b = t: widths 4, 3, 36), position factors (z, arm: 3, 3, 9), direction factors
-// (d, m: 3, 3, 9) --: the information as the symmetrised D x D; kind / delta empty: no factor has a kernel.  dev, da, db: the kind's device
+// (d, m: 3, 3, 9), range factors ({anchor, range}, arm: 4, 3, 1) --: the information as the symmetrised D x D; kind / delta empty: no factor has a kernel.  dev, da, db: the kind's device
 // struct and its two measurement arrays there
 struct UnaryPoseFactorSet : FactorSet
 {
@@ -625,7 +625,7 @@ struct cuba_hip_solver
 		uploadFactors();
 	}
 
-	// The factors besides the reprojection edges (ba_factor.hip): five kinds, each a set kept as the caller gave it, in the caller's numbering
+	// The factors besides the reprojection edges (ba_factor.hip): six kinds, each a set kept as the caller gave it, in the caller's numbering
 	// (quaternions normalised, information symmetrised), with a device copy (pf) in the internal order that need() makes -- uploadFactors():
 	// once that order is known, again when it changes (the unary kinds on the poses: with the pose order; the relative-pose edges, whose
 	// blocks are looked up in the pattern, and the landmark priors: with every structure), and again after a setter or
@@ -639,7 +639,8 @@ struct cuba_hip_solver
 	LandmarkPriorSet lmPriorSet;
 	UnaryPoseFactorSet posSet{ "position factor", "position factors", 3, 3, 9, pf.pos, pf.pos.z, pf.pos.arm };
 	UnaryPoseFactorSet dirSet{ "direction factor", "direction factors", 3, 3, 9, pf.dir, pf.dir.d, pf.dir.m };
-	FactorSet* const factorSets[FACTOR_KINDS] = { &priorSet, &relSet, &lmPriorSet, &posSet, &dirSet };      // in the order of FACTOR_* (ba_kernels.hpp)
+	UnaryPoseFactorSet rngSet{ "range factor", "range factors", 4, 3, 1, pf.rng, pf.rng.br, pf.rng.arm };
+	FactorSet* const factorSets[FACTOR_KINDS] = { &priorSet, &relSet, &lmPriorSet, &posSet, &dirSet, &rngSet };      // in the order of FACTOR_* (ba_kernels.hpp)
 	const DeviceFactors* factors() const
 	{
 		for (const FactorSet* set : factorSets) if (set->n() > 0) return &pf;
@@ -664,6 +665,8 @@ struct cuba_hip_solver
 	void setLandmarkPriors(int n, const int32_t* landmark, const double* xyz, const double* info, const int32_t* kind, const double* delta);
 	void setPositionFactors(int n, const int32_t* pose, const double* position, const double* leverArm, const double* info, const int32_t* kind, const double* delta);
 	void setDirectionFactors(int n, const int32_t* pose, const double* worldDir, const double* measuredDir, const double* info, const int32_t* kind, const double* delta);
+	void setRangeFactors(int n, const int32_t* pose, const double* anchor, const double* range, const double* leverArm, const double* info, const int32_t* kind,
+		const double* delta);
 	void factorChiSquares(int kind, double* out);      // r^T Omega r of every factor of the kind (FACTOR_*), in the caller's order
 	// the edges' distinct free-free pairs (sorted keys i << 32 | j, i < j, caller's numbering) and the pairs the current structure was seeded
 	// with: every such pair owns a block of the reduced matrix, so need() rebuilds the structure exactly when the two sets differ

@@ -91,7 +91,7 @@ private:
 	std::vector<T*> items_;
 };
 
-// one kind of factor (cuba::PosePrior, cuba::RelativePoseEdge, cuba::LandmarkPrior, cuba::PositionFactor, cuba::DirectionFactor) as an object keeps it
+// one kind of factor (cuba::PosePrior, cuba::RelativePoseEdge, cuba::LandmarkPrior, cuba::PositionFactor, cuba::DirectionFactor, cuba::RangeFactor) as an object keeps it
 template <class F>
 struct FactorList
 {
@@ -165,6 +165,7 @@ public:
 		priors_.removeIf([&](const PosePrior* p) { return p->vertex == it->second; });
 		posFactors_.removeIf([&](const PositionFactor* f) { return f->vertex == it->second; });
 		dirFactors_.removeIf([&](const DirectionFactor* f) { return f->vertex == it->second; });
+		rngFactors_.removeIf([&](const RangeFactor* f) { return f->vertex == it->second; });
 		relEdges_.removeIf([&](const RelativePoseEdge* e) { return e->vertexI == it->second || e->vertexJ == it->second; });
 		poses_.erase(it);
 		posesDirty_ = true;
@@ -206,7 +207,7 @@ public:
 	void initialize() override
 	{
 		covPoseIndex_.clear(); covLmIndex_.clear();          // (marginal covariances describe the graph they were computed on)
-		priors_.dirty = relEdges_.dirty = lmPriors_.dirty = posFactors_.dirty = dirFactors_.dirty = true;      // (the factors as they stand now go to the device with the next solve)
+		priors_.dirty = relEdges_.dirty = lmPriors_.dirty = posFactors_.dirty = dirFactors_.dirty = rngFactors_.dirty = true;      // (the factors as they stand now go to the device with the next solve)
 		poseIdx_.clear();                                    // (the factors' pose index: rebuilt below from the poses active now)
 		const auto t0 = std::chrono::steady_clock::now();
 		static const bool dbg = std::getenv("CUBA_HIP_DEBUG") != nullptr;
@@ -395,7 +396,7 @@ public:
 			check(cuba_hip_build_structure(solver_), "cuba_hip_build_structure");
 			check(cuba_hip_set_graph_end(solver_), "cuba_hip_set_graph_end");
 			graphDirty_ = false;
-			priors_.dirty = lmPriors_.dirty = posFactors_.dirty = dirFactors_.dirty = true;          // (an upload clears the handle's priors, position and direction factors)
+			priors_.dirty = lmPriors_.dirty = posFactors_.dirty = dirFactors_.dirty = rngFactors_.dirty = true;          // (an upload clears the handle's priors, position, direction and range factors)
 			uploadedOnce_ = true; edgesChangedSinceUpload_ = valuesChangedSinceUpload_ = false;       // from here on the device holds exactly these edges and values
 			(void)cuba_hip_get_counter(solver_, "graph_uploads", &uploadGeneration_);
 		}
@@ -405,15 +406,17 @@ public:
 		uploadLandmarkPriors();
 		uploadPositionFactors();
 		uploadDirectionFactors();
+		uploadRangeFactors();
 	}
 
-	// ---- factors (extensions: cuba::addPosePrior, cuba::addRelativePoseEdge, cuba::addLandmarkPrior, cuba::addPositionFactor, cuba::addDirectionFactor) --
+	// ---- factors (extensions: cuba::addPosePrior, cuba::addRelativePoseEdge, cuba::addLandmarkPrior, cuba::addPositionFactor, cuba::addDirectionFactor, cuba::addRangeFactor) --
 	// (public: the extension functions below remove and look up through them)
 	FactorList<PosePrior> priors_;
 	FactorList<RelativePoseEdge> relEdges_;
 	FactorList<LandmarkPrior> lmPriors_;
 	FactorList<PositionFactor> posFactors_;
 	FactorList<DirectionFactor> dirFactors_;
+	FactorList<RangeFactor> rngFactors_;
 	// index of a factor's vertex among the active poses (the map is built with the first factor of an initialize()); `refusal`: the message
 	// for a vertex that is not part of the graph
 	int32_t factorPose(const PoseVertex* v, const char* refusal)
@@ -576,6 +579,33 @@ public:
 		dirFactors_.endUpload();
 	}
 
+	// ---- range factors on the poses (extension: cuba::addRangeFactor) --------------------------------
+	void addRangeFactor(RangeFactor* f)
+	{
+		if (!f || !f->vertex) throw std::invalid_argument("cuba::addRangeFactor: a factor needs a pose vertex");
+		rngFactors_.add(f);
+	}
+	void uploadRangeFactors()
+	{
+		if (!rngFactors_.beginUpload()) return;
+		const std::vector<RangeFactor*>& factors = rngFactors_.items;
+		const size_t n = factors.size();
+		std::vector<int32_t> pose(n);
+		std::vector<double> anchor(3 * n), arm(3 * n), range(n), info(n);
+		for (size_t k = 0; k < n; k++)
+		{
+			pose[k] = factorPose(factors[k]->vertex, "cuba::addRangeFactor: the vertex of a factor is not part of the graph");
+			std::copy(factors[k]->anchor.begin(), factors[k]->anchor.end(), anchor.begin() + 3 * k);
+			std::copy(factors[k]->leverArm.begin(), factors[k]->leverArm.end(), arm.begin() + 3 * k);
+			range[k] = factors[k]->range;
+			info[k] = factors[k]->information;
+		}
+		const FactorKernels r = packKernels(factors);
+		check(cuba_hip_set_range_factors(solver_, (int)n, pose.data(), anchor.data(), range.data(), arm.data(), info.data(), r.any ? r.kind.data() : nullptr,
+			r.any ? r.delta.data() : nullptr), "cuba_hip_set_range_factors");
+		rngFactors_.endUpload();
+	}
+
 	// (optimize() in three steps, so that cuba::optimizeBatch can run the middle one for several objects at once)
 	void optimize(int niterations) override
 	{
@@ -656,6 +686,7 @@ public:
 		lmPriors_.readChi([&](double* c) { check(cuba_hip_landmark_prior_chi_squares(solver_, c), "cuba_hip_landmark_prior_chi_squares"); });
 		posFactors_.readChi([&](double* c) { check(cuba_hip_position_factor_chi_squares(solver_, c), "cuba_hip_position_factor_chi_squares"); });
 		dirFactors_.readChi([&](double* c) { check(cuba_hip_direction_factor_chi_squares(solver_, c), "cuba_hip_direction_factor_chi_squares"); });
+		rngFactors_.readChi([&](double* c) { check(cuba_hip_range_factor_chi_squares(solver_, c), "cuba_hip_range_factor_chi_squares"); });
 		relEdges_.readChi([&](double* c) { check(cuba_hip_relative_pose_chi_squares(solver_, c), "cuba_hip_relative_pose_chi_squares"); });
 
 		// finalize (ref :512-526): estimates back into the caller's vertices
@@ -707,6 +738,7 @@ public:
 		lmPriors_.items.clear(); lmPriors_.chi.clear();
 		posFactors_.items.clear(); posFactors_.chi.clear();
 		dirFactors_.items.clear(); dirFactors_.chi.clear();
+		rngFactors_.items.clear(); rngFactors_.chi.clear();
 		posesDirty_ = landmarksDirty_ = edgesDirty_ = true;
 		initialized_ = false;
 	}
@@ -1008,6 +1040,27 @@ double directionFactorChiSquared(const CudaBundleAdjustment* object, const Direc
 {
 	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
 	return impl ? impl->dirFactors_.chiSquared(factor) : 0.0;
+}
+
+// Extension (UWB-style distances to known anchors): range factors on the poses, effective at the next initialize()
+// (cuba_hip_set_range_factors)
+void addRangeFactor(CudaBundleAdjustment* object, RangeFactor* factor)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (!impl) throw std::runtime_error("cuba::addRangeFactor: not an object of this library");
+	impl->addRangeFactor(factor);
+}
+
+void removeRangeFactor(CudaBundleAdjustment* object, RangeFactor* factor)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (impl) impl->rngFactors_.remove(factor);
+}
+
+double rangeFactorChiSquared(const CudaBundleAdjustment* object, const RangeFactor* factor)
+{
+	auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
+	return impl ? impl->rngFactors_.chiSquared(factor) : 0.0;
 }
 
 // Extension (g2o's binary SE(3) edge): relative-pose edges, effective at the next initialize() (cuba_hip_set_relative_pose_edges)

@@ -34,6 +34,19 @@ int main()
 	try { ba->poseVertex(1234); } catch (const std::out_of_range&) { threw = true; }
 	REQUIRE(threw);
 
+	// a range factor needs a pose vertex: refused at once, nothing is kept (cuba::addRangeFactor)
+	{
+		RangeFactor none;
+		for (RangeFactor* f : { &none, static_cast<RangeFactor*>(nullptr) })
+		{
+			threw = false;
+			try { addRangeFactor(ba.get(), f); } catch (const std::invalid_argument&) { threw = true; }
+			REQUIRE(threw);
+		}
+		REQUIRE(rangeFactorChiSquared(ba.get(), &none) == 0.0);
+		removeRangeFactor(ba.get(), &none);      // (removing what was never added is no error)
+	}
+
 	ba->initialize();
 	// free poses in id order (5, 7), then the fixed one (3); pose 9 has no edges and keeps iP = -1
 	REQUIRE(p5.iP == 0 && p7.iP == 1 && p3.iP == 2 && p9.iP == -1);

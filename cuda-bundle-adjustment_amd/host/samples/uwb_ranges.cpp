@@ -1,0 +1,209 @@
+// uwb_ranges.cpp -- reads a bundle-adjustment graph (the JSON schema of the reference's datasets) as a MONOCULAR one -- a stereo edge is
+// taken without its disparity --, frees every pose and every landmark, and blows the whole estimate up by `scale0` about the origin: for
+// the reprojection edges alone that is as good an estimate as the file's, since a monocular graph without a fixed vertex knows neither
+// where it is nor how large.  Range factors (cuba::addRangeFactor) give it both: four non-coplanar anchors -- the corners of a
+// tetrahedron about the trajectory -- each heard from every `stride`-th pose with an edge (file order), the measured range being the
+// distance of the antenna (lever arm 0.1 / -0.2 / 0.5 in the camera frame) at the FILE's estimate, sigma = 0.05 m.  One range -- the
+// second -- is grossly wrong (a reflection: 5 m long); under the Cauchy kernel it is weighted down instead of bending the trajectory.
+// Prints the LM objective per iteration (edges plus factors), the recovered scale -- the spread of the camera centres about their mean
+// against the file's --, every range's chi2 at the result and which of them a gate of `gate` rejects; then removes those factors
+// (cuba::removeRangeFactor), runs again and prints the same; last the tag of the last ranged pose leaves: the pose is removed
+// (removePoseVertex), its ranges go with it without being removed one by one, and a third run prints the same again.
+//
+//   usage: uwb_ranges graph.json [iterations=10] [stride=5] [kernel=3] [delta=3] [scale0=1.05] [gate=25]
+//          kernel: 0 none, 1 Huber, 2 Tukey, 3 Cauchy
+//   output: "iter: <i>, chi2: <F>" per iteration, "scale <s>", per range "range <pose id> <anchor> chi2 <Omega r^2>", per range beyond the gate
+//           "gated <pose id> <anchor>", then "refit iter: <i>, chi2: <F>", "refit scale <s>" and "refit range <pose id> <anchor> chi2 <Omega r^2>",
+//           then "dropped <pose id>" and "dropped iter: ..." / "dropped range ..." in the same form (0 for the ranges that went with the pose)
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <memory>
+#include <vector>
+
+#include <opencv2/core.hpp>   // mini_opencv stand-in (JSON reader) unless real OpenCV is on the include path
+
+#include <cuda_bundle_adjustment.h>
+
+namespace
+{
+using Vec3 = std::array<double, 3>;
+
+template <int N>
+cuba::Array<double, N> readVec(const cv::FileNode& node)
+{
+	cuba::Array<double, N> a;
+	int k = 0;
+	for (const auto& v : node) { if (k >= N) break; a[k++] = double(v); }
+	return a;
+}
+
+// the rotation of the world -> camera pose of v, row-major
+void rotation(const cuba::PoseVertex& v, double R[3][3])
+{
+	const double* c = v.q.coeffs().data();      // (x, y, z, w)
+	const double x = c[0], y = c[1], z = c[2], w = c[3];
+	const double M[3][3] = {
+		{ 1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w) },
+		{ 2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w) },
+		{ 2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y) } };
+	for (int i = 0; i < 3; i++)
+		for (int j = 0; j < 3; j++) R[i][j] = M[i][j];
+}
+
+// R^T (a - t): the world position of the point a of the camera frame of v (a = 0: the camera centre)
+Vec3 inWorld(const cuba::PoseVertex& v, const Vec3& a)
+{
+	double R[3][3];
+	rotation(v, R);
+	const double d[3] = { a[0] - v.t[0], a[1] - v.t[1], a[2] - v.t[2] };
+	return { R[0][0] * d[0] + R[1][0] * d[1] + R[2][0] * d[2], R[0][1] * d[0] + R[1][1] * d[1] + R[2][1] * d[2], R[0][2] * d[0] + R[1][2] * d[1] + R[2][2] * d[2] };
+}
+
+Vec3 mean(const std::vector<Vec3>& pts)
+{
+	Vec3 m = { 0, 0, 0 };
+	for (const Vec3& p : pts)
+		for (int i = 0; i < 3; i++) m[i] += p[i] / (double)pts.size();
+	return m;
+}
+
+// root of the summed squared distances of the points from their mean
+double spread(const std::vector<Vec3>& pts)
+{
+	const Vec3 m = mean(pts);
+	double s = 0;
+	for (const Vec3& p : pts)
+		for (int i = 0; i < 3; i++) s += (p[i] - m[i]) * (p[i] - m[i]);
+	return std::sqrt(s);
+}
+
+std::vector<Vec3> centres(const std::vector<cuba::PoseVertex*>& poses)
+{
+	std::vector<Vec3> c;
+	for (const cuba::PoseVertex* v : poses) c.push_back(inWorld(*v, { 0, 0, 0 }));
+	return c;
+}
+}  // namespace
+
+int main(int argc, char** argv)
+{
+	if (argc < 2) { std::printf("usage: %s graph.json [iterations=10] [stride=5] [kernel=3] [delta=3] [scale0=1.05] [gate=25]\n", argv[0]); return 0; }
+	const int iterations = argc > 2 ? std::atoi(argv[2]) : 10;
+	const int stride = argc > 3 ? std::max(1, std::atoi(argv[3])) : 5;
+	const int kernel = argc > 4 ? std::atoi(argv[4]) : 3;
+	const double delta = argc > 5 ? std::atof(argv[5]) : 3.0;
+	const double scale0 = argc > 6 ? std::atof(argv[6]) : 1.05;
+	const double gate = argc > 7 ? std::atof(argv[7]) : 25.0;
+
+	cv::FileStorage fs(argv[1], cv::FileStorage::READ);
+	if (!fs.isOpened()) { std::fprintf(stderr, "cannot open %s\n", argv[1]); return 1; }
+	cuba::CameraParams cam;
+	cam.fx = fs["fx"]; cam.fy = fs["fy"]; cam.cx = fs["cx"]; cam.cy = fs["cy"]; cam.bf = fs["bf"];
+
+	std::vector<std::unique_ptr<cuba::PoseVertex>> poses;
+	std::vector<std::unique_ptr<cuba::LandmarkVertex>> landmarks;
+	std::vector<std::unique_ptr<cuba::MonoEdge>> mono;
+	auto ba = cuba::CudaBundleAdjustment::create();
+	for (const auto& n : fs["pose_vertices"])
+	{
+		const Eigen::Quaterniond q(readVec<4>(n["q"]));
+		poses.push_back(std::make_unique<cuba::PoseVertex>(int(n["id"]), q, readVec<3>(n["t"]), cam, false));     // every pose free
+		ba->addPoseVertex(poses.back().get());
+	}
+	for (const auto& n : fs["landmark_vertices"])
+	{
+		landmarks.push_back(std::make_unique<cuba::LandmarkVertex>(int(n["id"]), readVec<3>(n["Xw"]), false));     // every landmark free
+		ba->addLandmarkVertex(landmarks.back().get());
+	}
+	// monocular edges only: a stereo edge gives its (u, v) and keeps its disparity to itself
+	for (const char* list : { "monocular_edges", "stereo_edges" })
+		for (const auto& n : fs[list])
+		{
+			mono.push_back(std::make_unique<cuba::MonoEdge>(readVec<2>(n["measurement"]), double(n["information"]),
+				ba->poseVertex(int(n["vertexP"])), ba->landmarkVertex(int(n["vertexL"]))));
+			ba->addMonocularEdge(mono.back().get());
+		}
+	ba->setRobustKernels(cuba::RobustKernelType::HUBER, std::sqrt(5.991), cuba::EdgeType::MONOCULAR);
+
+	std::vector<cuba::PoseVertex*> observed;
+	for (const auto& p : poses) if (!p->edges.empty()) observed.push_back(p.get());
+	if (observed.size() < 3) { std::fprintf(stderr, "fewer than 3 poses with edges\n"); return 1; }
+
+	// the anchors: the corners of a tetrahedron about the camera centres of the file's estimate, as far out as the trajectory is wide
+	const std::vector<Vec3> fileCentres = centres(observed);
+	const Vec3 mid = mean(fileCentres);
+	const double fileSpread = spread(fileCentres);
+	const double reach = std::max(5.0, fileSpread / std::sqrt((double)fileCentres.size()));
+	const double corner[4][3] = { { 1, 1, 1 }, { 1, -1, -1 }, { -1, 1, -1 }, { -1, -1, 1 } };
+	Vec3 anchors[4];
+	for (int k = 0; k < 4; k++)
+		for (int i = 0; i < 3; i++) anchors[k][i] = mid[i] + reach * corner[k][i];
+
+	// the ranges: all four anchors from every stride-th pose with an edge, measured at the file's estimate; the second is 5 m long
+	const Vec3 arm = { 0.1, -0.2, 0.5 };
+	const double sigma = 0.05;
+	std::vector<std::unique_ptr<cuba::RangeFactor>> ranges;
+	std::vector<int> anchorOf;
+	for (size_t j = 0; j < observed.size(); j += (size_t)stride)
+		for (int k = 0; k < 4; k++)
+		{
+			auto f = std::make_unique<cuba::RangeFactor>();
+			f->vertex = observed[j];
+			f->anchor = anchors[k];
+			f->leverArm = arm;
+			const Vec3 antenna = inWorld(*f->vertex, arm);
+			f->range = std::sqrt((antenna[0] - anchors[k][0]) * (antenna[0] - anchors[k][0]) + (antenna[1] - anchors[k][1]) * (antenna[1] - anchors[k][1]) +
+				(antenna[2] - anchors[k][2]) * (antenna[2] - anchors[k][2]));
+			if (ranges.size() == 1) f->range += 5.0;      // the gross one
+			f->information = 1.0 / (sigma * sigma);
+			f->kernel = static_cast<cuba::PoseFactorKernel>(kernel);
+			f->delta = delta;
+			cuba::addRangeFactor(ba.get(), f.get());
+			ranges.push_back(std::move(f));
+			anchorOf.push_back(k);
+		}
+	if (ranges.size() < 12) { std::fprintf(stderr, "fewer than 3 poses with ranges\n"); return 1; }
+
+	// the start: the file's estimate blown up by scale0 about the origin (camera centres and landmarks; the rotations stay)
+	for (const auto& p : poses)
+		for (int i = 0; i < 3; i++) p->t[i] *= scale0;
+	for (const auto& l : landmarks)
+		for (int i = 0; i < 3; i++) l->Xw[i] *= scale0;
+	std::printf("start scale %.17g\n", spread(centres(observed)) / fileSpread);
+
+	ba->initialize();
+	ba->optimize(iterations);
+	for (const auto& s : ba->batchStatistics()) std::printf("iter: %d, chi2: %.17g\n", s.iteration + 1, s.chi2);
+	std::printf("scale %.17g\n", spread(centres(observed)) / fileSpread);
+	std::vector<size_t> gated;
+	for (size_t k = 0; k < ranges.size(); k++)
+	{
+		const double e = cuba::rangeFactorChiSquared(ba.get(), ranges[k].get());
+		std::printf("range %d %d chi2 %.17g\n", ranges[k]->vertex->id, anchorOf[k], e);
+		if (e > gate) gated.push_back(k);
+	}
+	for (size_t k : gated) std::printf("gated %d %d\n", ranges[k]->vertex->id, anchorOf[k]);
+
+	// without the gated ranges, from where the first run ended
+	for (size_t k : gated) cuba::removeRangeFactor(ba.get(), ranges[k].get());
+	ba->initialize();
+	ba->optimize(iterations);
+	for (const auto& s : ba->batchStatistics()) std::printf("refit iter: %d, chi2: %.17g\n", s.iteration + 1, s.chi2);
+	std::printf("refit scale %.17g\n", spread(centres(observed)) / fileSpread);
+	for (size_t k = 0; k < ranges.size(); k++)
+		std::printf("refit range %d %d chi2 %.17g\n", ranges[k]->vertex->id, anchorOf[k], cuba::rangeFactorChiSquared(ba.get(), ranges[k].get()));
+
+	// the last ranged pose leaves the graph: its edges and its range factors go with it (the objects stay the caller's)
+	cuba::PoseVertex* gone = ranges.back()->vertex;
+	ba->removePoseVertex(gone);
+	std::printf("dropped %d\n", gone->id);
+	ba->initialize();
+	ba->optimize(iterations);
+	for (const auto& s : ba->batchStatistics()) std::printf("dropped iter: %d, chi2: %.17g\n", s.iteration + 1, s.chi2);
+	for (size_t k = 0; k < ranges.size(); k++)
+		std::printf("dropped range %d %d chi2 %.17g\n", ranges[k]->vertex->id, anchorOf[k], cuba::rangeFactorChiSquared(ba.get(), ranges[k].get()));
+	return 0;
+}

@@ -221,4 +221,30 @@ void addDirectionFactor(CudaBundleAdjustment* object, DirectionFactor* factor);
 void removeDirectionFactor(CudaBundleAdjustment* object, DirectionFactor* factor);
 double directionFactorChiSquared(const CudaBundleAdjustment* object, const DirectionFactor* factor);
 
+// Extension (include/cuba_hip.h, cuba_hip_set_range_factors): a range factor on one pose vertex -- a measured DISTANCE from a point of the
+// platform to a known world point: a UWB anchor, an acoustic beacon, DME, a total station that reports slope distance only.  `anchor` is
+// the world point b, `range` the measured distance (>= 0), `leverArm` the ranging antenna in the camera frame (zero: the camera centre),
+// `information` the scalar 1 / sigma^2 (>= 0).  Objective term information * r^2 with r = |a - (R b + t)| - range for the vertex's
+// world -> camera pose [R | t], or rho(information * r^2) when `kernel` is set (`delta` > 0 then).  One range constrains the pose to a
+// sphere, which neither a PositionFactor (a 3-D fix; rank-1 information on it is a plane) nor a PosePrior can say; four non-coplanar
+// anchors heard from three poses off a line give a graph without a fixed vertex its gauge, and a monocular one its scale.  With the
+// antenna exactly at the anchor the direction is undefined: the factor then adds nothing to the system and keeps its chi2,
+// information * range^2.  Ownership and lifetime as for PositionFactor: the caller owns the factor; additions, removals and changes take
+// effect at the next initialize(); the vertex must be part of the graph then.  removePoseVertex drops the vertex's factors, clear() all.
+// rangeFactorChiSquared: information * r^2 at the estimate of the last optimize() (0 before one, and for a factor on a fixed vertex) --
+// the plain value under a kernel too.
+struct RangeFactor
+{
+	PoseVertex* vertex = nullptr;
+	std::array<double, 3> anchor{};
+	std::array<double, 3> leverArm{};
+	double range = 0;
+	double information = 0;
+	PoseFactorKernel kernel = PoseFactorKernel::NONE;
+	double delta = 0;
+};
+void addRangeFactor(CudaBundleAdjustment* object, RangeFactor* factor);
+void removeRangeFactor(CudaBundleAdjustment* object, RangeFactor* factor);
+double rangeFactorChiSquared(const CudaBundleAdjustment* object, const RangeFactor* factor);
+
 }  // namespace cuba

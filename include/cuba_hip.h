@@ -551,6 +551,44 @@ int cuba_hip_set_direction_factors(cuba_hip_solver* s, int n, const int32_t* pos
 	const int32_t* kind, const double* delta);
 int cuba_hip_direction_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor);
 
+/* ---- range factors on the poses (UWB-style distances to known anchors; the reference has no counterpart) ------------------------------
+   A factor names pose `pose` (the caller's solver numbering, 0 <= pose < Pt; world -> camera T = [R | t]), an anchor b (a known world
+   point), a measured range rbar >= 0, a lever arm a -- the ranging antenna in the camera frame, zero for the camera centre --, a scalar
+   information Omega = 1 / sigma^2 >= 0 and optionally a robust kernel (kind, delta) of the pose factors' family (table above: 0 none,
+   1 Huber, 2 Tukey, 3 Cauchy, the same formulas): a UWB anchor, an acoustic beacon, DME, a total station that reports slope distance
+   only.  One range constrains the pose to a sphere: a position factor cannot say this (it needs a 3-D fix, and rank-1 information on it
+   is a plane), nor can an SE(3) prior.
+     residual     u = a - (R b + t) (camera frame; |u| = |R^T (a - t) - b|), rho = |u|, m = u / rho, r = rho - rbar, e = Omega r^2
+     objective    rho_k(e); the LM objective F (cuba_hip_optimize's chi2, cuba_hip_compute_errors, the gain ratio) gains the factors' sum
+     linearised   with w = rho_k'(e) and dr/dd = J = [(m x a)^T | -m^T] (1 x 6, d = [omega; upsilon] of the update T <- exp(d) T: b_c = R b + t
+                  becomes b_c + omega x b_c + upsilon, so d rho = -m . (omega x b_c + upsilon), and b_c x m = a x m): w Omega J^T J (rank 1)
+                  into the pose's diagonal block of the reduced matrix, -w Omega r J^T into bp and bsc; no second-order term.  lambda is
+                  added afterwards as to everything else; the assemble-only pass adds the terms too, so lambda_0's maximum diagonal
+                  includes them.  The terms follow those of every other kind in every sum.
+     rho = 0      (the antenna at the anchor) m is undefined there.  The rule: when the computed rho is exactly 0, m = 0, so J = 0: the
+                  factor adds nothing to the system and contributes e = Omega rbar^2.
+   Several factors on one pose are summed in the caller's order; factors on fixed poses are accepted and ignored (chi2 0).  Every solve
+   path honours them: the device-decision loop (a rejected trial's restore included), the host loop, both PCG forms, the exact solver,
+   the fp32 library, mixed precision, and the covariance entry points (the inverse of the weighted Hessian: four non-coplanar anchors
+   heard from three poses off a line give a graph without a fixed vertex its gauge, and a monocular one its scale).
+   The fp32 library computes a - t - R b in fp32 and the library shifts nothing: callers with UTM-size coordinates subtract a local
+   origin from the poses, the landmarks and the anchors first.
+   cuba_hip_set_range_factors replaces the whole set (n = 0 clears it): pose[n], anchor[3 n], range[n], lever_arm[3 n] (NULL: zeros),
+   info[n], kind[n] and delta[n] (both NULL: no kernels; kinds all 0 are no kernels).  Valid any time after cuba_hip_set_graph, which
+   clears the set.  Setting factors never rebuilds the structure ("structure_builds" stays); it drops the run-to-run memories of option
+   "heuristics" and cached covariance blocks.
+   CUBA_HIP_ERR_INVALID_ARGUMENT, the handle unchanged: an index out of range, non-finite values, a negative range, a negative
+   information (0 is valid and is no factor), a kind outside 0..3, delta <= 0 on a kind != 0, one of kind / delta without the other.
+   CUBA_HIP_ERR_STATE, the handle staying usable: a landmark-partitioned handle (and cuba_hip_set_partition on a handle with such factors,
+   hence the multi-GPU driver) and a graph without edges.  A handle with such factors takes part in cuba_hip_optimize_batch through the
+   path that batches the PCG iterations only (results stay bit-identical to solo runs).  A handle without them launches the kernels, with
+   the arguments, of a library without this entry point.
+   cuba_hip_range_factor_chi_squares: the plain Omega r^2 of every factor at the current estimate, in the caller's order (what a caller
+   gates a doubtful range -- a non-line-of-sight one -- on). */
+int cuba_hip_set_range_factors(cuba_hip_solver* s, int n, const int32_t* pose, const double* anchor, const double* range, const double* lever_arm, const double* info,
+	const int32_t* kind, const double* delta);
+int cuba_hip_range_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor);
+
 /* ---- introspection (parity tests) and multi-GPU plumbing ------------------------------------------ */
 
 /* Structure of the reduced system: upper-triangular BSR (replaces the accessors of
