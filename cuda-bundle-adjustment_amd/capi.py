@@ -135,6 +135,8 @@ def load_library(precision="f64"):
         "cuba_hip_direction_factor_chi_squares": [H, _dp],
         "cuba_hip_set_range_factors": [H, C.c_int, _ip, _dp, _dp, _dp, _dp, _ip, _dp],
         "cuba_hip_range_factor_chi_squares": [H, _dp],
+        "cuba_hip_set_pose_range_factors": [H, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _dp],
+        "cuba_hip_pose_range_factor_chi_squares": [H, _dp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -396,7 +398,7 @@ class HipSolver:
         landmark_range = (begin, end): cuba_hip_set_graph_partition -- the upload of one rank of a landmark partition, which sends the
         measurements and information of its own landmarks' edges only."""
         self.fp = fp
-        self._n_factors = {}            # (every upload clears the pose priors, the relative-pose edges, the landmark priors, the position, the direction and the range factors)
+        self._n_factors = {}            # (every upload clears the pose priors, the relative-pose edges, the landmark priors, the position, the direction and both kinds of range factors)
         q, t, cam, Xw = (np.ascontiguousarray(a, dtype=np.float64) for a in (fp.q, fp.t, fp.cam, fp.Xw))
         eP = np.ascontiguousarray(fp.eP, dtype=np.int32)
         eL = np.ascontiguousarray(fp.eL, dtype=np.int32)
@@ -650,6 +652,37 @@ class HipSolver:
     def range_factor_chi_squares(self):
         """info r^2 of every range factor at the current estimate, in the order they were given (0 for factors on fixed poses)"""
         return self._factor_chi_squares("range_factor")
+
+    def set_pose_range_factors(self, pose_i, pose_j, range, info, lever_arm_i=None, lever_arm_j=None, kind=None, delta=None):
+        """Range factors between two poses (cuba_hip_set_pose_range_factors; odometer distances, peer UWB ranging, rig baselines),
+        replacing the handle's set: pose_i[n] != pose_j[n] in the solver numbering, the measured distances range[n] (>= 0), the scalar
+        informations info[n] (1 / sigma^2, >= 0), lever_arm_i[n, 3] and lever_arm_j[n, 3] (the two points in their camera frames; None:
+        the camera centre); kind[n] (0 none, 1 Huber, 2 Tukey, 3 Cauchy) and delta[n] together or not at all (scalars broadcast).  An
+        empty pose list clears the set.  The free-free pairs are part of the topology, as the relative-pose edges'."""
+        pose_i = np.ascontiguousarray(pose_i, dtype=np.int32).reshape(-1)
+        pose_j = np.ascontiguousarray(pose_j, dtype=np.int32).reshape(-1)
+        n = int(pose_i.size)
+        if pose_j.size != n:
+            raise ValueError("pose_i / pose_j differ in length")
+        range = np.ascontiguousarray(np.broadcast_to(np.asarray(range, dtype=np.float64), (n,)))
+        info = np.ascontiguousarray(np.broadcast_to(np.asarray(info, dtype=np.float64), (n,)))
+        if lever_arm_i is not None:
+            lever_arm_i = np.ascontiguousarray(lever_arm_i, dtype=np.float64).reshape(n, 3)
+        if lever_arm_j is not None:
+            lever_arm_j = np.ascontiguousarray(lever_arm_j, dtype=np.float64).reshape(n, 3)
+        if kind is not None:
+            kind = np.ascontiguousarray(np.full(n, kind) if np.ndim(kind) == 0 else kind, dtype=np.int32).reshape(-1)
+        if delta is not None:
+            delta = np.ascontiguousarray(np.full(n, delta) if np.ndim(delta) == 0 else delta, dtype=np.float64).reshape(-1)
+        if (kind is not None and kind.size != n) or (delta is not None and delta.size != n):
+            raise ValueError("kind / delta differ in length from the set")
+        self._ck(self.lib.cuba_hip_set_pose_range_factors(self.h, n, pose_i.ctypes.data_as(_ip), pose_j.ctypes.data_as(_ip), _d(range), _d(lever_arm_i),
+                                                          _d(lever_arm_j), _d(info), kind.ctypes.data_as(_ip) if kind is not None else None, _d(delta)))
+        self._n_factors["pose_range_factor"] = n
+
+    def pose_range_factor_chi_squares(self):
+        """info r^2 of every range factor between two poses at the current estimate, in the order they were given (0 with both ends fixed)"""
+        return self._factor_chi_squares("pose_range_factor")
 
     def chi_squares_two_step(self):
         """cuba_hip_chi_squares_begin / _end (the C++ layer does its write-back between the two)"""

@@ -1,7 +1,8 @@
 // ba_factor.hip -- the factors besides the reprojection edges: terms rho(r^T Omega r) of the objective on the vertices alone, Omega a full
 // symmetric information.  Two kinds on the SE(3) poses, r in the [omega, upsilon] tangent of the solver's left-multiplicative update
 // T <- exp(d) T (pose_exp_update), Omega 6 x 6, one on the landmarks, one that ties a pose to a world position, one that ties its
-// rotation to a world direction and one that ties it to a measured distance from a world point:
+// rotation to a world direction, one that ties it to a measured distance from a world point and one that ties two poses to a measured
+// distance between them:
 //
 //   pose priors (cuba_hip_set_pose_priors): unary, r = log(T Tbar^-1), linearised with the exact derivative dr/dd =
 //     J_l(r)^-1.  A prior touches the diagonal 6 x 6 block of its pose in the reduced matrix and the pose's entries of bp / bsc only.
@@ -32,6 +33,11 @@
 //     d rho = -m . (omega x b_c + upsilon), and b_c x m = a x m: dr/dd = [(m x a)^T | -m^T] (1 x 6) -- NOT with the world-frame direction
 //     R^T m, and the rotation columns vanish only for a = 0.  J^T J has rank 1.  THE POINT rho = 0 (the antenna at the anchor): m is undefined
 //     there; the rule is m = 0 when the computed rho is exactly 0, so J = 0: the factor adds nothing to H or g and its e = Omega rbar^2.
+//   range factors between two poses (cuba_hip_set_pose_range_factors; section 7j): binary, the scalar residual of the range factors with
+//     the other end's point as the anchor: w_i = R_i^T (a_i - t_i), u = (a_j - t_j) - R_j w_i, rho = |u|, m_j = u / rho, m_i = -R_i R_j^T m_j
+//     (both from the ONE computed u: one rho, one rule at rho = 0 for both ends), r = rho - rbar, dr/dd_j = [(m_j x a_j)^T | -m_j^T],
+//     dr/dd_i = [(m_i x a_i)^T | -m_i^T].  The first binary kind with a low-rank term: rank-1 terms on both diagonal blocks and
+//     w Omega J_i^T J_j on the pair's off-diagonal block; the free-free pairs seed the block pattern together with the edges' (the union).
 //
 // A factor may carry a robust kernel (cuba_hip_set_pose_factor_robust_kernels; section 7e): with e = r^T Omega r its term is rho(e) and its
 // linearisation takes w Omega, w = rho'(e), for Omega (no second-order term, as the reprojection edges).  The kernels that see a
@@ -40,11 +46,12 @@
 //
 // Order: the pose priors, the position factors, the relative-pose edges, the direction factors and the range factors all add to the diagonal
 // blocks, bp and bsc that the pose and Schur passes stored, by read-modify-write.  launch_pose_factor_linearize issues them in one stream in
-// this order -- priors, position factors, the edges' records, the edges' gather, direction factors, range factors -- and that order is part of the result
+// this order -- priors, position factors, the edges' records, the edges' gather, direction factors, range factors, the records and the
+// gather of the range factors between poses -- and that order is part of the result
 // (floating-point sums do not commute): a handle's bits depend on it, and a new kind goes BEHIND the ones a handle may already combine,
 // never between two of them.  (The position factors sit between the priors and the edges: no handle could hold them before they came, so
 // no existing sum changed.  The direction factors came when handles could combine all of the others, so they went last; the range factors came after them and go
-// behind them.)
+// behind them, the range factors between poses after those.)
 //
 // The kinds keep linearisation kernels of their own (a prior is not run as a one-ended edge: its sums would be taken in another order).
 // Everything else exists once: the device helpers below (the unary kinds' accumulators and their read-modify-write: zero_pose_sums,
@@ -76,11 +83,17 @@
 //                              w Omega J^T J (21 numbers, rank 1 per factor) and w Omega r J^T (6) summed in registers, one read-modify-write of
 //                              the diagonal block's upper triangle, bp and (mode 1) bsc -- one writer per number; the last launch, behind the
 //                              direction factors'
+//   pose_range_linearize_kernel lane = range factor between poses with a free end: the record {J_i, J_j, w Omega, w Omega r}, 14 numbers
+//   pose_range_gather_kernel   lane = one number of the reduced system, as relpose_gather_kernel: an entry of an off-diagonal block with such
+//                              factors (mode 1: J_min[r] w Omega J_max[c] summed over the block's factors; stored whole where the block has
+//                              neither Schur products nor a relative-pose edge, added to what those stored otherwise), or an entry of a
+//                              pose's diagonal block (upper triangle) / of bp and (mode 1) bsc, summed over the pose's factors in the
+//                              caller's order -- one writer per number, fixed order, no atomics; the last two launches
 //   factor_chi2_kernel         lane = factor of one kind: r^T Omega r at the current estimate (factor_chi, an overload per kind) into the per-factor
 //                              output and (rho of it) into per-workgroup partials that the caller sums together with the reprojection
 //                              edges' partials (fixed order, no atomics)
 //
-// Host side: the caller's six sets (validated, kept in the caller's numbering), the edges' pair set (part of the topology) and the upload
+// Host side: the caller's seven sets (validated, kept in the caller's numbering), the binary kinds' pair set (part of the topology) and the upload
 // of every set in the internal pose / landmark order.
 #include "ba_solver.hpp"
 #include "ba_device.hpp"
@@ -102,6 +115,12 @@ constexpr int CHI_MAX_GROUPS = 64;     // a chi2 launch's partials (a grid-strid
 constexpr int REL_HII = 0, REL_HJJ = 21, REL_HX = 42, REL_GI = 78, REL_GJ = 84;
 static_assert(REL_GJ + 6 == REL_REC, "record layout");
 constexpr int REL_POSE_NUMBERS = 27;        // 21 entries of a diagonal block + 6 of bp / bsc
+// the range factors between two poses run as the edges do (tiny, latency-bound launches: the siblings' block sizes)
+constexpr int PRNG_LIN_BLOCK = 64;
+constexpr int PRNG_GATHER_BLOCK = 256;
+// record of such a factor: [0, 6) J_i, [6, 12) J_j, w Omega, w Omega r
+constexpr int PRNG_JI = 0, PRNG_JJ = 6, PRNG_W = 12, PRNG_WR = 13;
+static_assert(PRNG_WR + 1 == PRNG_REC, "record layout");
 
 // ---- shared device helpers --------------------------------------------------------------------------------------------------------
 
@@ -660,6 +679,120 @@ __device__ __forceinline__ Scalar factor_chi(const DeviceGraph& g, const DeviceR
 	return range_residual(rf, k, R.m, t, m, r);
 }
 
+// ---- range factors between two poses ----------------------------------------------------------------------------------------------
+
+// number `el` of the record of factor k: number-major as rel_rec, so that the lanes of the linearisation store to consecutive addresses
+__device__ __forceinline__ Scalar& prng_rec(const DevicePoseRanges& pr, int k, int el) { return pr.rec[(size_t)el * pr.n + k]; }
+
+// w_i = R_i^T (a_i - t_i), the world position of the point on pose i; u = (a_j - t_j) - R_j w_i: the unary range factor on pose j with the
+// anchor w_i; rho = |u|, r = rho - rbar, mj = u / rho (frame j) and mi = -R_i R_j^T mj (frame i) -- from the ONE computed u, so that rho
+// and the rule at rho = 0 (range_residual: mi = mj = 0, e = info rbar^2) are the same for both ends.  Returns e = info r^2
+__device__ __forceinline__ Scalar pose_range_residual(const DeviceGraph& g, const DevicePoseRanges& pr, int k, Scalar mi[3], Scalar mj[3], Scalar& r)
+{
+	Scalar qi[4], ti[3], qj[4], tj[3];
+	load_pose(g.q, g.t, pr.pose_i[k], qi, ti);
+	load_pose(g.q, g.t, pr.pose_j[k], qj, tj);
+	const Rot3 Ri = quat_to_rot(qi[0], qi[1], qi[2], qi[3]);
+	const Rot3 Rj = quat_to_rot(qj[0], qj[1], qj[2], qj[3]);
+	const Scalar* ai = pr.arm_i + 3 * (size_t)k;
+	const Scalar* aj = pr.arm_j + 3 * (size_t)k;
+	const Scalar d[3] = { ai[0] - ti[0], ai[1] - ti[1], ai[2] - ti[2] };
+	Scalar w[3], u[3], v[3];
+#pragma unroll
+	for (int i = 0; i < 3; i++) w[i] = Ri.m[0][i] * d[0] + Ri.m[1][i] * d[1] + Ri.m[2][i] * d[2];
+#pragma unroll
+	for (int i = 0; i < 3; i++) u[i] = (aj[i] - tj[i]) - (Rj.m[i][0] * w[0] + Rj.m[i][1] * w[1] + Rj.m[i][2] * w[2]);
+	const Scalar rho = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+	const Scalar inv = rho > 0 ? 1 / rho : 0;
+#pragma unroll
+	for (int i = 0; i < 3; i++) mj[i] = u[i] * inv;
+#pragma unroll
+	for (int i = 0; i < 3; i++) v[i] = Rj.m[0][i] * mj[0] + Rj.m[1][i] * mj[1] + Rj.m[2][i] * mj[2];
+#pragma unroll
+	for (int i = 0; i < 3; i++) mi[i] = -(Ri.m[i][0] * v[0] + Ri.m[i][1] * v[1] + Ri.m[i][2] * v[2]);
+	r = rho - pr.range[k];
+	return pr.info[k] * r * r;
+}
+
+template <bool ROBUST>
+__global__ __launch_bounds__(PRNG_LIN_BLOCK) void pose_range_linearize_kernel(DeviceGraph g, DevicePoseRanges pr)
+{
+	const int k = blockIdx.x * PRNG_LIN_BLOCK + threadIdx.x;
+	if (k >= pr.nActive) return;
+	Scalar mi[3], mj[3], r;
+	const Scalar e = pose_range_residual(g, pr, k, mi, mj, r);
+	Scalar w = pr.info[k];
+	if constexpr (ROBUST) w *= factor_weight(pr.rk_kind[k], pr.rk_delta[k], e);
+	// J_i = [(m_i x a_i)^T | -m_i^T], J_j = [(m_j x a_j)^T | -m_j^T] (1 x 6 each; all zero at rho = 0)
+	const Scalar* ai = pr.arm_i + 3 * (size_t)k;
+	const Scalar* aj = pr.arm_j + 3 * (size_t)k;
+	const Scalar J[12] = { mi[1] * ai[2] - mi[2] * ai[1], mi[2] * ai[0] - mi[0] * ai[2], mi[0] * ai[1] - mi[1] * ai[0], -mi[0], -mi[1], -mi[2],
+		mj[1] * aj[2] - mj[2] * aj[1], mj[2] * aj[0] - mj[0] * aj[2], mj[0] * aj[1] - mj[1] * aj[0], -mj[0], -mj[1], -mj[2] };
+#pragma unroll
+	for (int c = 0; c < 12; c++) prng_rec(pr, k, PRNG_JI + c) = J[c];
+	prng_rec(pr, k, PRNG_W) = w;
+	prng_rec(pr, k, PRNG_WR) = w * r;
+}
+
+__global__ __launch_bounds__(PRNG_GATHER_BLOCK) void pose_range_gather_kernel(DeviceStructure st, DeviceSystem sys, DevicePoseRanges pr, int mode)
+{
+	const int x = blockIdx.x * PRNG_GATHER_BLOCK + threadIdx.x;
+	const int nBlkNumbers = mode == 1 ? 36 * pr.nBlocks : 0;
+	if (x < nBlkNumbers)
+	{
+		// entry (rr, c) of the block (min, max) of the internal pair, column-major: J_min[rr] w Omega J_max[c]
+		const int b = x / 36, el = x - 36 * b;
+		const int c = el / 6, rr = el - 6 * c;
+		const int blk = pr.blk_id[b];
+		Scalar s = 0;
+		const int k1 = pr.blk_ptr[b + 1];
+		for (int k = pr.blk_ptr[b]; k < k1; k++)
+		{
+			const bool flip = pr.pose_i[k] > pr.pose_j[k];
+			s += prng_rec(pr, k, (flip ? PRNG_JJ : PRNG_JI) + rr) * (prng_rec(pr, k, PRNG_W) * prng_rec(pr, k, (flip ? PRNG_JI : PRNG_JJ) + c));
+		}
+		Scalar* dst = sys.hsc + 36 * (size_t)blk + el;
+		// (a block with products was stored by the Schur pass of this linearisation, one with a relative-pose edge by relpose_gather_kernel;
+		// a block with neither has no other writer)
+		*dst = st.prod_end[blk] > st.prod_beg[blk] || pr.blk_rel[b] ? *dst + s : s;
+		return;
+	}
+	const int y = x - nBlkNumbers;
+	const int p = y / REL_POSE_NUMBERS, el = y - REL_POSE_NUMBERS * p;
+	if (p >= pr.nPoses) return;
+	const int ip = pr.pose_id[p];
+	// packed upper-triangle index -> (rr, c); el >= 21: entry c of bp / bsc
+	int c = el - 21, rr = 0;
+	if (el < 21)
+	{
+		c = 0;
+		while ((c + 1) * (c + 2) / 2 <= el) c++;
+		rr = el - c * (c + 1) / 2;
+	}
+	Scalar s = 0;
+	const int k1 = pr.pose_ptr[p + 1];
+	for (int k = pr.pose_ptr[p]; k < k1; k++)
+	{
+		const int item = pr.pose_item[k], f = item >> 1, J = item & 1 ? PRNG_JJ : PRNG_JI;
+		if (el < 21) s += prng_rec(pr, f, J + rr) * (prng_rec(pr, f, PRNG_W) * prng_rec(pr, f, J + c));
+		else s += prng_rec(pr, f, J + c) * prng_rec(pr, f, PRNG_WR);
+	}
+	if (el < 21) sys.hsc[36 * (size_t)st.hsc_rowptr[ip] + c * 6 + rr] += s;
+	else
+	{
+		sys.bp[6 * (size_t)ip + c] -= s;
+		if (mode == 1) sys.bsc[6 * (size_t)ip + c] -= s;
+	}
+}
+
+// info r^2 of factor k at the current estimate (factor_chi2_kernel)
+__device__ __forceinline__ Scalar factor_chi(const DeviceGraph& g, const DevicePoseRanges& pr, int k)
+{
+	if (k >= pr.nActive) return 0;
+	Scalar mi[3], mj[3], r;
+	return pose_range_residual(g, pr, k, mi, mj, r);
+}
+
 // ---- chi2 -------------------------------------------------------------------------------------------------------------------------
 
 // The chi2 of a kind: lane = factor, r^T Omega r at the current estimate -- factor_chi(g, kind, k), one overload per kind above, 0 for a factor
@@ -750,6 +883,15 @@ void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& s
 		const dim3 grid((rf.nPoses + RNG_LIN_BLOCK - 1) / RNG_LIN_BLOCK);
 		if (rf.rk_kind) hipLaunchKernelGGL(range_linearize_kernel<true>, grid, dim3(RNG_LIN_BLOCK), 0, s, g, st, sys, rf, mode);
 		else hipLaunchKernelGGL(range_linearize_kernel<false>, grid, dim3(RNG_LIN_BLOCK), 0, s, g, st, sys, rf, mode);
+	}
+	const DevicePoseRanges& pg = pf.prng;
+	if (pg.nActive > 0)
+	{
+		const dim3 linGrid((pg.nActive + PRNG_LIN_BLOCK - 1) / PRNG_LIN_BLOCK);
+		if (pg.rk_kind) hipLaunchKernelGGL(pose_range_linearize_kernel<true>, linGrid, dim3(PRNG_LIN_BLOCK), 0, s, g, pg);
+		else hipLaunchKernelGGL(pose_range_linearize_kernel<false>, linGrid, dim3(PRNG_LIN_BLOCK), 0, s, g, pg);
+		const size_t numbers = (mode == 1 ? (size_t)36 * pg.nBlocks : 0) + (size_t)REL_POSE_NUMBERS * pg.nPoses;
+		hipLaunchKernelGGL(pose_range_gather_kernel, dim3((unsigned)((numbers + PRNG_GATHER_BLOCK - 1) / PRNG_GATHER_BLOCK)), dim3(PRNG_GATHER_BLOCK), 0, s, st, sys, pg, mode);
 	}
 }
 
@@ -885,20 +1027,32 @@ void cuba_hip_solver::setRelativePoseEdges(int n, const int32_t* pi, const int32
 		vi[k] = pi[k]; vj[k] = pj[k];
 		take_factor_values(vq.data(), vt.data(), vinfo.data(), k, q, t, info, "relative", "relative-pose");
 	}
-	// the distinct free-free pairs (caller's numbering, smaller index first): part of the topology -- need() rebuilds the structure when
-	// they differ from the pairs the current one was seeded with
-	std::vector<uint64_t> pairs;
-	for (int k = 0; k < n; k++)
-		if (vi[k] < Pf && vj[k] < Pf) pairs.push_back(((uint64_t)(uint32_t)std::min(vi[k], vj[k]) << 32) | (uint32_t)std::max(vi[k], vj[k]));
-	std::sort(pairs.begin(), pairs.end());
-	pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
-	h_relPairs.swap(pairs);
 	// (the replaced set is a new set: the robust kernels of the previous one go with it)
 	relSet.pi.swap(vi); relSet.pj.swap(vj); relSet.q.swap(vq); relSet.t.swap(vt); relSet.info.swap(vinfo);
 	relSet.kind.clear(); relSet.delta.clear();
+	collectBinaryPairs();
 	forget_factor_memories(*this, relSet);
 	pf.rel = DeviceRelPoses();
+	// (the range factors between poses store or add into a block by whether these edges write it: their device copy is due again)
+	prngSet.uploaded = false;
 	covBlocksValid = false;          // (the covariance blocks describe the edge set -- and the block pattern -- they were computed on)
+}
+
+// the distinct free-free pairs of both binary kinds (caller's numbering, smaller index first): part of the topology -- need() rebuilds the
+// structure when they differ from the pairs the current one was seeded with.  Either kind's setter recomputes the union, so that setting or
+// clearing one kind keeps the other's pairs
+void cuba_hip_solver::collectBinaryPairs()
+{
+	std::vector<uint64_t> pairs;
+	const auto take = [&](const std::vector<int>& vi, const std::vector<int>& vj) {
+		for (size_t k = 0; k < vi.size(); k++)
+			if (vi[k] < Pf && vj[k] < Pf) pairs.push_back(((uint64_t)(uint32_t)std::min(vi[k], vj[k]) << 32) | (uint32_t)std::max(vi[k], vj[k]));
+	};
+	take(relSet.pi, relSet.pj);
+	take(prngSet.pi, prngSet.pj);
+	std::sort(pairs.begin(), pairs.end());
+	pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+	h_relPairs.swap(pairs);
 }
 
 // kernels of the current set of one type, in the caller's order; n = 0 (or kinds all 0) clears them.  The values of the system change, its
@@ -1010,6 +1164,46 @@ void cuba_hip_solver::setRangeFactors(int n, const int32_t* pose, const double* 
 	covBlocksValid = false;
 }
 
+void cuba_hip_solver::setPoseRangeFactors(int n, const int32_t* pi, const int32_t* pj, const double* range, const double* armI, const double* armJ, const double* info,
+	const int32_t* kind, const double* delta)
+{
+	check_factor_call(*this, prngSet, n, pi && pj && range && info, kind, delta, "reprojection edges");
+	const std::string noun = prngSet.noun;
+	std::vector<int> vi((size_t)n), vj((size_t)n), vk;
+	std::vector<double> vai((size_t)3 * n, 0.0), vaj((size_t)3 * n, 0.0), vr((size_t)n), vinfo((size_t)n), vd;
+	bool any = false;
+	for (int k = 0; k < n; k++)
+	{
+		if (pi[k] < 0 || pi[k] >= Pt || pj[k] < 0 || pj[k] >= Pt) throw ArgError{ noun + ": pose index out of range" };
+		if (pi[k] == pj[k]) throw ArgError{ noun + " between a pose and itself" };
+		vi[k] = pi[k]; vj[k] = pj[k];
+		for (size_t x = 3 * (size_t)k; x < 3 * (size_t)k + 3; x++)
+		{
+			if ((armI && !std::isfinite(armI[x])) || (armJ && !std::isfinite(armJ[x]))) throw ArgError{ "non-finite " + noun + " lever arm" };
+			if (armI) vai[x] = armI[x];
+			if (armJ) vaj[x] = armJ[x];
+		}
+		if (!std::isfinite(range[k])) throw ArgError{ "non-finite " + noun + " range" };
+		if (range[k] < 0) throw ArgError{ "negative " + noun + " range" };
+		vr[k] = range[k];
+		if (!std::isfinite(info[k])) throw ArgError{ "non-finite " + noun + " information" };
+		if (info[k] < 0) throw ArgError{ "negative " + noun + " information" };
+		vinfo[k] = info[k];
+		if (kind)
+		{
+			check_factor_kernel(kind[k], delta[k], prngSet.noun);
+			any = any || kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE;
+		}
+	}
+	if (any) { vk.assign(kind, kind + n); vd.assign(delta, delta + n); }
+	prngSet.pi.swap(vi); prngSet.pj.swap(vj); prngSet.ai.swap(vai); prngSet.aj.swap(vaj); prngSet.range.swap(vr); prngSet.info.swap(vinfo);
+	prngSet.kind.swap(vk); prngSet.delta.swap(vd);
+	collectBinaryPairs();
+	forget_factor_memories(*this, prngSet);
+	pf.prng = DevicePoseRanges();
+	covBlocksValid = false;          // (the covariance blocks describe the factors -- and the block pattern -- they were computed on)
+}
+
 std::vector<uint64_t> cuba_hip_solver::relSeedKeys() const
 {
 	std::vector<uint64_t> keys(h_relPairs.size());
@@ -1114,15 +1308,16 @@ void UnaryPoseFactorSet::upload(cuba_hip_solver& s)
 
 // the caller's edges -> device, in the internal pose order: free-free edges first, stable by the block (min, max) of the internal pair -- a
 // block's edges contiguous and in the caller's order --, then the edges with one fixed end, then (inactive) those with two
-void RelPoseSet::upload(cuba_hip_solver& s)
+// (shared by the two binary kinds: sets set.order; blkKey: the (min << 32 | max) key of every block of blkId, ascending)
+struct BinaryLayout { std::vector<int> si, sj, blkPtr, blkId, posePtr, poseId, poseItem; std::vector<uint64_t> blkKey; int nActive = 0; };
+static BinaryLayout sort_binary_factors(cuba_hip_solver& s, FactorSet& set, const std::vector<int>& pi, const std::vector<int>& pj)
 {
-	RelPoseSet& set = *this;
-	const int n = set.n(), Pf = s.Pf;
+	const int n = (int)pi.size(), Pf = s.Pf;
 	std::vector<int> a((size_t)n), b((size_t)n);
 	std::vector<uint64_t> key((size_t)n);
 	for (int k = 0; k < n; k++)
 	{
-		a[k] = s.internalPose(set.pi[k]); b[k] = s.internalPose(set.pj[k]);
+		a[k] = s.internalPose(pi[k]); b[k] = s.internalPose(pj[k]);
 		const int nFixed = (a[k] >= Pf) + (b[k] >= Pf);
 		key[k] = nFixed == 0 ? (((uint64_t)(uint32_t)std::min(a[k], b[k]) << 32) | (uint32_t)std::max(a[k], b[k])) : (~0ull - (uint64_t)(2 - nFixed));
 	}
@@ -1130,8 +1325,10 @@ void RelPoseSet::upload(cuba_hip_solver& s)
 	std::vector<int> posOf((size_t)n);
 	for (int p = 0; p < n; p++) posOf[set.order[p]] = p;
 	s.ensureHostPattern();
-	std::vector<int> si((size_t)n), sj((size_t)n), blkPtr, blkId;
-	int nActive = 0;
+	BinaryLayout lay;
+	std::vector<int>&si = lay.si, &sj = lay.sj, &blkPtr = lay.blkPtr, &blkId = lay.blkId, &posePtr = lay.posePtr, &poseId = lay.poseId, &poseItem = lay.poseItem;
+	si.resize((size_t)n); sj.resize((size_t)n);
+	int& nActive = lay.nActive;
 	for (int p = 0; p < n; p++)
 	{
 		const int k = set.order[p];
@@ -1142,8 +1339,8 @@ void RelPoseSet::upload(cuba_hip_solver& s)
 			const int row = std::min(a[k], b[k]), col = std::max(a[k], b[k]);
 			const int* c0 = s.h_colind.data() + s.h_rowptr[row]; const int* c1 = s.h_colind.data() + s.h_rowptr[row + 1];
 			const int* it = std::lower_bound(c0, c1, col);
-			if (it == c1 || *it != col) throw StateError{ "relative-pose edge without its block in the pattern" };
-			blkPtr.push_back(p); blkId.push_back((int)(it - s.h_colind.data()));
+			if (it == c1 || *it != col) throw StateError{ std::string(set.noun) + " without its block in the pattern" };
+			blkPtr.push_back(p); blkId.push_back((int)(it - s.h_colind.data())); lay.blkKey.push_back(key[k]);
 		}
 	}
 	int nFreeFree = 0;
@@ -1157,16 +1354,24 @@ void RelPoseSet::upload(cuba_hip_solver& s)
 		if (b[k] < Pf) items.emplace_back(b[k], 2 * posOf[k] + 1);
 	}
 	std::stable_sort(items.begin(), items.end(), [](const std::pair<int, int>& x, const std::pair<int, int>& y) { return x.first < y.first; });
-	std::vector<int> posePtr, poseId, poseItem;
 	for (size_t x = 0; x < items.size(); x++)
 	{
 		if (x == 0 || items[x].first != items[x - 1].first) { posePtr.push_back((int)x); poseId.push_back(items[x].first); }
 		poseItem.push_back(items[x].second);
 	}
 	posePtr.push_back((int)items.size());
-	const int nb = (int)blkId.size(), np = (int)poseId.size();
+	return lay;
+}
+
+void RelPoseSet::upload(cuba_hip_solver& s)
+{
+	RelPoseSet& set = *this;
+	const int n = set.n();
+	const BinaryLayout lay = sort_binary_factors(s, set, set.pi, set.pj);
+	const int nActive = lay.nActive, nb = (int)lay.blkId.size(), np = (int)lay.poseId.size();
 	DeviceRelPoses rp;
-	upload_factor_arrays(s, set, concat({ &si, &sj, &blkPtr, &blkId, &posePtr, &poseId, &poseItem }), rp.q, rp.t, rp.info, rp.chi, rp.rk_kind, rp.rk_delta);
+	upload_factor_arrays(s, set, concat({ &lay.si, &lay.sj, &lay.blkPtr, &lay.blkId, &lay.posePtr, &lay.poseId, &lay.poseItem }), rp.q, rp.t, rp.info, rp.chi, rp.rk_kind,
+		rp.rk_delta);
 	s.d_relRec.resize((size_t)cubahip::REL_REC * std::max(n, 1));
 	rp.n = n; rp.nActive = nActive; rp.nBlocks = nb; rp.nPoses = np;
 	rp.pose_i = set.d_ints.data(); rp.pose_j = rp.pose_i + n;
@@ -1175,6 +1380,54 @@ void RelPoseSet::upload(cuba_hip_solver& s)
 	rp.rec = s.d_relRec.data();
 	s.pf.rel = rp;
 	set.structure = s.cntStructureBuilds;
+}
+
+// the caller's range factors between two poses -> device, sorted as the relative-pose edges.  blk_rel: the blocks that the relative-pose
+// edges' gather writes too (it stores a block without Schur products, so this kind's gather, which runs behind it, adds there) -- this
+// device copy depends on the structure AND on the relative-pose set: setRelativePoseEdges marks it due again.
+// ints: pose_i [n] | pose_j [n] | blk_ptr [nb + 1] | blk_id [nb] | blk_rel [nb] | pose_ptr [np + 1] | pose_id [np] | pose_item | kind [n, robust]
+// values: arm_i [3 n] | arm_j [3 n] | range [n] | info [n] | delta [n, robust]
+void PoseRangeSet::upload(cuba_hip_solver& s)
+{
+	const size_t N = (size_t)n();
+	const bool robust = !kind.empty();
+	const BinaryLayout lay = sort_binary_factors(s, *this, pi, pj);
+	std::vector<uint64_t> relKeys;
+	for (int k = 0; k < s.relSet.n(); k++)
+	{
+		const int a = s.internalPose(s.relSet.pi[k]), b = s.internalPose(s.relSet.pj[k]);
+		if (a < s.Pf && b < s.Pf) relKeys.push_back(((uint64_t)(uint32_t)std::min(a, b) << 32) | (uint32_t)std::max(a, b));
+	}
+	std::sort(relKeys.begin(), relKeys.end());
+	const int nb = (int)lay.blkId.size(), np = (int)lay.poseId.size();
+	std::vector<int> blkRel((size_t)nb);
+	for (int b = 0; b < nb; b++) blkRel[b] = std::binary_search(relKeys.begin(), relKeys.end(), lay.blkKey[b]) ? 1 : 0;
+	std::vector<int> ints = concat({ &lay.si, &lay.sj, &lay.blkPtr, &lay.blkId, &blkRel, &lay.posePtr, &lay.poseId, &lay.poseItem });
+	const size_t nInts = ints.size();
+	std::vector<Scalar> vals((robust ? 9 : 8) * N);
+	Scalar* vai = vals.data(); Scalar* vaj = vai + 3 * N; Scalar* vr = vaj + 3 * N; Scalar* vi = vr + N;
+	for (size_t p = 0; p < N; p++)
+	{
+		const size_t k = (size_t)order[p];
+		for (int i = 0; i < 3; i++) { vai[3 * p + i] = (Scalar)ai[3 * k + i]; vaj[3 * p + i] = (Scalar)aj[3 * k + i]; }
+		vr[p] = (Scalar)range[k]; vi[p] = (Scalar)info[k];
+		if (robust) { ints.push_back(kind[k]); vi[N + p] = (Scalar)delta[k]; }
+	}
+	d_ints.upload(ints, s.stream);
+	d_vals.upload(vals, s.stream);
+	d_chi.resize(std::max(N, (size_t)1));
+	d_rec.resize((size_t)cubahip::PRNG_REC * std::max(N, (size_t)1));
+	s.sync();          // (the staging vectors go out of scope)
+	DevicePoseRanges pr;
+	pr.n = (int)N; pr.nActive = lay.nActive; pr.nBlocks = nb; pr.nPoses = np;
+	pr.pose_i = d_ints.data(); pr.pose_j = pr.pose_i + N;
+	pr.blk_ptr = pr.pose_j + N; pr.blk_id = pr.blk_ptr + (nb + 1); pr.blk_rel = pr.blk_id + nb;
+	pr.pose_ptr = pr.blk_rel + nb; pr.pose_id = pr.pose_ptr + (np + 1); pr.pose_item = pr.pose_id + np;
+	pr.arm_i = d_vals.data(); pr.arm_j = pr.arm_i + 3 * N; pr.range = pr.arm_j + 3 * N; pr.info = pr.range + N;
+	pr.rec = d_rec.data(); pr.chi = d_chi.data();
+	pr.rk_kind = robust ? d_ints.data() + nInts : nullptr; pr.rk_delta = robust ? pr.info + N : nullptr;
+	s.pf.prng = pr;
+	uploaded = true; structure = s.cntStructureBuilds;
 }
 
 // the caller's priors -> device, in the internal landmark order (stable by internal landmark: every landmark's priors contiguous, in the

@@ -193,6 +193,34 @@ struct DeviceRelPoses
 	const Scalar* rk_delta = nullptr;   // [n]
 };
 
+// Range factors between two poses (peer UWB, odometer distances, rig baselines; ba_factor.hip): rho(Omega r^2), r = |u| - rbar with
+// u = a_j - (R_j w_i + t_j), w_i = R_i^T (a_i - t_i): the distance of the point a_i of camera frame i from the point a_j of camera frame j
+// against a measured range; info the scalar 1 / sigma^2.  The first binary kind with a low-rank term: J_i and J_j are 1 x 6 each.  Sorted as
+// the relative-pose edges: the factors between two free poses first, stable by the block (min, max) of the internal pose pair, then those
+// with one fixed end (they act on the free end only), then those with two (ignored).  At a computed distance of exactly 0 both J are 0.
+constexpr int PRNG_REC = 14;       // numbers of a factor's linearisation record: J_i [6] | J_j [6] | w Omega | w Omega r
+struct DevicePoseRanges
+{
+	int n = 0;                     // factors
+	int nActive = 0;               // the first nActive have a free end
+	int nBlocks = 0;               // off-diagonal blocks of hsc with such factors
+	int nPoses = 0;                // free poses with such factors
+	const int *pose_i = nullptr, *pose_j = nullptr;   // [n] internal poses of every factor (>= Pf: a fixed pose)
+	const int* blk_ptr = nullptr;  // [nBlocks + 1] range of every such block in the sorted list
+	const int* blk_id = nullptr;   // [nBlocks] its block of hsc
+	const int* blk_rel = nullptr;  // [nBlocks] 1: the block has a relative-pose edge too (relpose_gather_kernel wrote it in this linearisation)
+	const int* pose_ptr = nullptr; // [nPoses + 1] range of every such pose in pose_item
+	const int* pose_id = nullptr;  // [nPoses] its internal pose index
+	const int* pose_item = nullptr;// the pose's factors in the caller's order: 2 * sorted factor + (0: the pose is the factor's i, 1: its j)
+	const Scalar *arm_i = nullptr, *arm_j = nullptr;  // [3 n] lever arms in the two camera frames
+	const Scalar* range = nullptr; // [n] measured distances
+	const Scalar* info = nullptr;  // [n]
+	Scalar* rec = nullptr;         // [PRNG_REC n] linearisation records, number-major (number el of factor k at el n + k)
+	Scalar* chi = nullptr;         // [n] Omega r^2 of the last chi2 launch (0 with both ends fixed)
+	const int* rk_kind = nullptr;  // [n] robust kernel of every factor, sorted as the values; null: no factor has one (the kernels' ROBUST = false)
+	const Scalar* rk_delta = nullptr;   // [n]
+};
+
 // Landmark position priors (ba_factor.hip): rho(r^T Omega r), r = X - Xbar, Omega a symmetric 3 x 3 information.  Sorted by internal landmark
 // (stable: a landmark's priors are contiguous and in the caller's order); priors on fixed landmarks come last and are ignored.  The landmark
 // pass adds a landmark's terms w Omega / -w Omega r to its Hll / bl (ba_device.hpp: add_landmark_priors), in a kernel instantiation of its
@@ -212,19 +240,22 @@ struct DeviceLandmarkPriors
 // The factors of a handle besides the reprojection edges: what the rest of the library sees of the kinds (a kind without factors: n = 0,
 // nothing of it is launched).  The landmark priors ride along for the chi2 sums only: their linearisation is the landmark pass's.
 // FACTOR_*: the kinds in the order of their chi2 partials, of each() below and of the handle's table of sets (ba_solver.hpp: factorSets).
-enum { FACTOR_PRIORS = 0, FACTOR_REL, FACTOR_LMP, FACTOR_POS, FACTOR_DIR, FACTOR_RNG, FACTOR_KINDS };
+enum { FACTOR_PRIORS = 0, FACTOR_REL, FACTOR_LMP, FACTOR_POS, FACTOR_DIR, FACTOR_RNG, FACTOR_PRNG, FACTOR_KINDS };
 struct DeviceFactors
 {
 	DevicePriors priors; DeviceRelPoses rel; DeviceLandmarkPriors lmp; DevicePositionFactors pos; DeviceDirectionFactors dir; DeviceRangeFactors rng;
-	template <class F> void each(F&& f) const { f(priors); f(rel); f(lmp); f(pos); f(dir); f(rng); }      // every kind's device struct, in that order
+	DevicePoseRanges prng;
+	template <class F> void each(F&& f) const { f(priors); f(rel); f(lmp); f(pos); f(dir); f(rng); f(prng); }      // every kind's device struct, in that order
 };
 // behind the Schur pass, the priors first (Omega: w Omega of a factor with a robust kernel): J^T Omega J into the diagonal blocks of hsc (upper triangle), -J^T Omega r into bp and (mode 1)
 // bsc, J = J_l(r)^-1; then the position factors the same way in a launch of their own, J = [R^T [a]x | -R^T]; then the edges in two
 // launches: per-edge records, then their sums into hsc (diagonal blocks: upper triangle; mode 1: the off-diagonal blocks of the pairs,
 // stored whole where a block has no Schur products), bp and (mode 1) bsc; then the direction factors in a launch of their own, J =
-// [-[R d]x | 0]: the rotation 3 x 3 of the diagonal block and the first three entries of bp / bsc only; last the range factors in a launch
-// of their own, J = [(m x a)^T | -m^T] (1 x 6, m the unit vector from the anchor to the antenna in the camera frame).  All five add to the
-// same diagonal blocks: the order of the launches is part of the result
+// [-[R d]x | 0]: the rotation 3 x 3 of the diagonal block and the first three entries of bp / bsc only; then the range factors in a launch
+// of their own, J = [(m x a)^T | -m^T] (1 x 6, m the unit vector from the anchor to the antenna in the camera frame); last the range factors
+// between two poses in two launches as the edges: per-factor records {J_i, J_j, w Omega, w Omega r}, then their sums into hsc (mode 1: the
+// off-diagonal blocks of the pairs, stored whole where a block has neither Schur products nor a relative-pose edge), bp and (mode 1) bsc.
+// All six add to the same diagonal blocks: the order of the launches is part of the result
 void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DeviceFactors& pf, int mode, hipStream_t s);
 // per-factor chi2 (the plain r^T Omega r) into every kind's chi, per-workgroup partial sums of rho(chi2) into
 // parts[0 .. factor_chi2_parts(&pf)), kind behind kind in the order of FACTOR_*.  only >= 0: that kind alone, its partials at parts[0]

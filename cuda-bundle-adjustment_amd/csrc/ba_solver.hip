@@ -555,6 +555,14 @@ int cuba_hip_set_range_factors(cuba_hip_solver* s, int n, const int32_t* pose, c
 
 int cuba_hip_range_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor) { return factor_chi_squares(s, cubahip::FACTOR_RNG, chi2_per_factor); }
 
+int cuba_hip_set_pose_range_factors(cuba_hip_solver* s, int n, const int32_t* pose_i, const int32_t* pose_j, const double* range, const double* lever_arm_i,
+	const double* lever_arm_j, const double* info, const int32_t* kind, const double* delta)
+{
+	return guarded(s, [&] { s->setPoseRangeFactors(n, pose_i, pose_j, range, lever_arm_i, lever_arm_j, info, kind, delta); });
+}
+
+int cuba_hip_pose_range_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor) { return factor_chi_squares(s, cubahip::FACTOR_PRNG, chi2_per_factor); }
+
 int cuba_hip_time_kernels(cuba_hip_solver* s, int reps, double ms_per_launch[CUBA_HIP_TIMED_KERNELS])
 {
 	return guarded(s, [&] {

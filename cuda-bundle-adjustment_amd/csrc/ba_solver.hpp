@@ -172,6 +172,17 @@ struct RelPoseSet : FactorSet
 	void clear() override { pi.clear(); pj.clear(); q.clear(); t.clear(); info.clear(); FactorSet::clear(); }
 	void upload(cuba_hip_solver& s) override;
 };
+// range factors between two poses: lever arms (zero where the caller gave none), measured distance, scalar information; kind / delta empty:
+// no factor has a kernel.  d_rec: the linearisation records
+struct PoseRangeSet : FactorSet
+{
+	std::vector<int> pi, pj; std::vector<double> ai, aj, range, info;      // [n], [n], [3 n], [3 n], [n], [n]
+	DevBuf<Scalar> d_rec;
+	PoseRangeSet() : FactorSet("pose-range factor", "pose-range factors", true) {}
+	int n() const override { return (int)pi.size(); }
+	void clear() override { pi.clear(); pj.clear(); ai.clear(); aj.clear(); range.clear(); info.clear(); FactorSet::clear(); }
+	void upload(cuba_hip_solver& s) override;
+};
 // landmark position priors: the information as its symmetrised upper triangle, every prior with a kernel (kind 0, delta 1: none)
 struct LandmarkPriorSet : FactorSet
 {
@@ -625,10 +636,11 @@ struct cuba_hip_solver
 		uploadFactors();
 	}
 
-	// The factors besides the reprojection edges (ba_factor.hip): six kinds, each a set kept as the caller gave it, in the caller's numbering
+	// The factors besides the reprojection edges (ba_factor.hip): seven kinds, each a set kept as the caller gave it, in the caller's numbering
 	// (quaternions normalised, information symmetrised), with a device copy (pf) in the internal order that need() makes -- uploadFactors():
-	// once that order is known, again when it changes (the unary kinds on the poses: with the pose order; the relative-pose edges, whose
-	// blocks are looked up in the pattern, and the landmark priors: with every structure), and again after a setter or
+	// once that order is known, again when it changes (the unary kinds on the poses: with the pose order; the two binary kinds, whose
+	// blocks are looked up in the pattern, and the landmark priors: with every structure; the range factors between poses also with the
+	// relative-pose set), and again after a setter or
 	// cuba_hip_set_pose_factor_robust_kernels, whose kinds and deltas travel with the values.  The landmark pass linearises the landmark
 	// priors -- linearize() hands pf.lmp to it --, the chi2 sums take them as one more kind.
 	// No factors of any kind: factors() is null, nothing of it is launched, no extra seed enters the pattern build, and every launch and kernel argument is as
@@ -640,7 +652,8 @@ struct cuba_hip_solver
 	UnaryPoseFactorSet posSet{ "position factor", "position factors", 3, 3, 9, pf.pos, pf.pos.z, pf.pos.arm };
 	UnaryPoseFactorSet dirSet{ "direction factor", "direction factors", 3, 3, 9, pf.dir, pf.dir.d, pf.dir.m };
 	UnaryPoseFactorSet rngSet{ "range factor", "range factors", 4, 3, 1, pf.rng, pf.rng.br, pf.rng.arm };
-	FactorSet* const factorSets[FACTOR_KINDS] = { &priorSet, &relSet, &lmPriorSet, &posSet, &dirSet, &rngSet };      // in the order of FACTOR_* (ba_kernels.hpp)
+	PoseRangeSet prngSet;
+	FactorSet* const factorSets[FACTOR_KINDS] = { &priorSet, &relSet, &lmPriorSet, &posSet, &dirSet, &rngSet, &prngSet };      // in the order of FACTOR_* (ba_kernels.hpp)
 	const DeviceFactors* factors() const
 	{
 		for (const FactorSet* set : factorSets) if (set->n() > 0) return &pf;
@@ -667,8 +680,12 @@ struct cuba_hip_solver
 	void setDirectionFactors(int n, const int32_t* pose, const double* worldDir, const double* measuredDir, const double* info, const int32_t* kind, const double* delta);
 	void setRangeFactors(int n, const int32_t* pose, const double* anchor, const double* range, const double* leverArm, const double* info, const int32_t* kind,
 		const double* delta);
+	void setPoseRangeFactors(int n, const int32_t* pi, const int32_t* pj, const double* range, const double* armI, const double* armJ, const double* info,
+		const int32_t* kind, const double* delta);
+	void collectBinaryPairs();       // h_relPairs from the two binary kinds' sets
 	void factorChiSquares(int kind, double* out);      // r^T Omega r of every factor of the kind (FACTOR_*), in the caller's order
-	// the edges' distinct free-free pairs (sorted keys i << 32 | j, i < j, caller's numbering) and the pairs the current structure was seeded
+	// the distinct free-free pairs of the two binary kinds, the relative-pose edges and the range factors between poses (their union; sorted
+	// keys i << 32 | j, i < j, caller's numbering) and the pairs the current structure was seeded
 	// with: every such pair owns a block of the reduced matrix, so need() rebuilds the structure exactly when the two sets differ
 	std::vector<uint64_t> h_relPairs, structRelPairs;
 	int64_t cntStructureBuilds = 0;      // structures published on this handle (never reset)

@@ -91,7 +91,7 @@ private:
 	std::vector<T*> items_;
 };
 
-// one kind of factor (cuba::PosePrior, cuba::RelativePoseEdge, cuba::LandmarkPrior, cuba::PositionFactor, cuba::DirectionFactor, cuba::RangeFactor) as an object keeps it
+// one kind of factor (cuba::PosePrior, cuba::RelativePoseEdge, cuba::LandmarkPrior, cuba::PositionFactor, cuba::DirectionFactor, cuba::RangeFactor, cuba::PoseRangeFactor) as an object keeps it
 template <class F>
 struct FactorList
 {
@@ -167,6 +167,7 @@ public:
 		dirFactors_.removeIf([&](const DirectionFactor* f) { return f->vertex == it->second; });
 		rngFactors_.removeIf([&](const RangeFactor* f) { return f->vertex == it->second; });
 		relEdges_.removeIf([&](const RelativePoseEdge* e) { return e->vertexI == it->second || e->vertexJ == it->second; });
+		prngFactors_.removeIf([&](const PoseRangeFactor* f) { return f->vertexI == it->second || f->vertexJ == it->second; });
 		poses_.erase(it);
 		posesDirty_ = true;
 	}
@@ -207,7 +208,7 @@ public:
 	void initialize() override
 	{
 		covPoseIndex_.clear(); covLmIndex_.clear();          // (marginal covariances describe the graph they were computed on)
-		priors_.dirty = relEdges_.dirty = lmPriors_.dirty = posFactors_.dirty = dirFactors_.dirty = rngFactors_.dirty = true;      // (the factors as they stand now go to the device with the next solve)
+		priors_.dirty = relEdges_.dirty = lmPriors_.dirty = posFactors_.dirty = dirFactors_.dirty = rngFactors_.dirty = prngFactors_.dirty = true;      // (the factors as they stand now go to the device with the next solve)
 		poseIdx_.clear();                                    // (the factors' pose index: rebuilt below from the poses active now)
 		const auto t0 = std::chrono::steady_clock::now();
 		static const bool dbg = std::getenv("CUBA_HIP_DEBUG") != nullptr;
@@ -389,10 +390,12 @@ public:
 				static_cast<int>(activeLandmarks_.size()), numFreeLandmarks_, q_.data(), t_.data(), cam_.data(), Xw_.data(),
 				static_cast<int>(activeEdges_.size()), edgePose_.data(), edgeLandmark_.data(), edgeDim_.data(), meas_.data(), omega_.data()),
 				"cuba_hip_set_graph_begin");
-			// (an upload clears the handle's relative-pose edges; their pose pairs are part of the block pattern, so they go up before the
-			// structure analysis: an unchanged pair set then keeps the structure of the previous initialize())
+			// (an upload clears the handle's relative-pose edges and range factors between poses; their pose pairs are part of the block
+			// pattern, so they go up before the structure analysis: an unchanged pair set then keeps the structure of the previous initialize())
 			relEdges_.onDevice = false; relEdges_.dirty = true;
+			prngFactors_.onDevice = false; prngFactors_.dirty = true;
 			uploadRelativePoseEdges();
+			uploadPoseRangeFactors();
 			check(cuba_hip_build_structure(solver_), "cuba_hip_build_structure");
 			check(cuba_hip_set_graph_end(solver_), "cuba_hip_set_graph_end");
 			graphDirty_ = false;
@@ -407,9 +410,10 @@ public:
 		uploadPositionFactors();
 		uploadDirectionFactors();
 		uploadRangeFactors();
+		uploadPoseRangeFactors();
 	}
 
-	// ---- factors (extensions: cuba::addPosePrior, cuba::addRelativePoseEdge, cuba::addLandmarkPrior, cuba::addPositionFactor, cuba::addDirectionFactor, cuba::addRangeFactor) --
+	// ---- factors (extensions: cuba::addPosePrior, cuba::addRelativePoseEdge, cuba::addLandmarkPrior, cuba::addPositionFactor, cuba::addDirectionFactor, cuba::addRangeFactor, cuba::addPoseRangeFactor) --
 	// (public: the extension functions below remove and look up through them)
 	FactorList<PosePrior> priors_;
 	FactorList<RelativePoseEdge> relEdges_;
@@ -417,6 +421,7 @@ public:
 	FactorList<PositionFactor> posFactors_;
 	FactorList<DirectionFactor> dirFactors_;
 	FactorList<RangeFactor> rngFactors_;
+	FactorList<PoseRangeFactor> prngFactors_;
 	// index of a factor's vertex among the active poses (the map is built with the first factor of an initialize()); `refusal`: the message
 	// for a vertex that is not part of the graph
 	int32_t factorPose(const PoseVertex* v, const char* refusal)
@@ -606,6 +611,34 @@ public:
 		rngFactors_.endUpload();
 	}
 
+	// ---- range factors between two poses (extension: cuba::addPoseRangeFactor) ------------------------
+	void addPoseRangeFactor(PoseRangeFactor* f)
+	{
+		if (!f || !f->vertexI || !f->vertexJ || f->vertexI == f->vertexJ) throw std::invalid_argument("cuba::addPoseRangeFactor: a factor needs two different pose vertices");
+		prngFactors_.add(f);
+	}
+	void uploadPoseRangeFactors()
+	{
+		if (!prngFactors_.beginUpload()) return;
+		const std::vector<PoseRangeFactor*>& factors = prngFactors_.items;
+		const size_t n = factors.size();
+		std::vector<int32_t> pi(n), pj(n);
+		std::vector<double> armI(3 * n), armJ(3 * n), range(n), info(n);
+		const char* refusal = "cuba::addPoseRangeFactor: a vertex of a factor is not part of the graph";
+		for (size_t k = 0; k < n; k++)
+		{
+			pi[k] = factorPose(factors[k]->vertexI, refusal); pj[k] = factorPose(factors[k]->vertexJ, refusal);
+			std::copy(factors[k]->leverArmI.begin(), factors[k]->leverArmI.end(), armI.begin() + 3 * k);
+			std::copy(factors[k]->leverArmJ.begin(), factors[k]->leverArmJ.end(), armJ.begin() + 3 * k);
+			range[k] = factors[k]->range;
+			info[k] = factors[k]->information;
+		}
+		const FactorKernels r = packKernels(factors);
+		check(cuba_hip_set_pose_range_factors(solver_, (int)n, pi.data(), pj.data(), range.data(), armI.data(), armJ.data(), info.data(), r.any ? r.kind.data() : nullptr,
+			r.any ? r.delta.data() : nullptr), "cuba_hip_set_pose_range_factors");
+		prngFactors_.endUpload();
+	}
+
 	// (optimize() in three steps, so that cuba::optimizeBatch can run the middle one for several objects at once)
 	void optimize(int niterations) override
 	{
@@ -688,6 +721,7 @@ public:
 		dirFactors_.readChi([&](double* c) { check(cuba_hip_direction_factor_chi_squares(solver_, c), "cuba_hip_direction_factor_chi_squares"); });
 		rngFactors_.readChi([&](double* c) { check(cuba_hip_range_factor_chi_squares(solver_, c), "cuba_hip_range_factor_chi_squares"); });
 		relEdges_.readChi([&](double* c) { check(cuba_hip_relative_pose_chi_squares(solver_, c), "cuba_hip_relative_pose_chi_squares"); });
+		prngFactors_.readChi([&](double* c) { check(cuba_hip_pose_range_factor_chi_squares(solver_, c), "cuba_hip_pose_range_factor_chi_squares"); });
 
 		// finalize (ref :512-526): estimates back into the caller's vertices
 		check(cuba_hip_get_solution(solver_, q_.data(), t_.data(), Xw_.data()), "cuba_hip_get_solution");
@@ -739,6 +773,7 @@ public:
 		posFactors_.items.clear(); posFactors_.chi.clear();
 		dirFactors_.items.clear(); dirFactors_.chi.clear();
 		rngFactors_.items.clear(); rngFactors_.chi.clear();
+		prngFactors_.items.clear(); prngFactors_.chi.clear();
 		posesDirty_ = landmarksDirty_ = edgesDirty_ = true;
 		initialized_ = false;
 	}
@@ -1061,6 +1096,27 @@ double rangeFactorChiSquared(const CudaBundleAdjustment* object, const RangeFact
 {
 	auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
 	return impl ? impl->rngFactors_.chiSquared(factor) : 0.0;
+}
+
+// Extension (odometer distances, peer UWB ranging, rig baselines): range factors between two poses, effective at the next initialize()
+// (cuba_hip_set_pose_range_factors)
+void addPoseRangeFactor(CudaBundleAdjustment* object, PoseRangeFactor* factor)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (!impl) throw std::runtime_error("cuba::addPoseRangeFactor: not an object of this library");
+	impl->addPoseRangeFactor(factor);
+}
+
+void removePoseRangeFactor(CudaBundleAdjustment* object, PoseRangeFactor* factor)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (impl) impl->prngFactors_.remove(factor);
+}
+
+double poseRangeFactorChiSquared(const CudaBundleAdjustment* object, const PoseRangeFactor* factor)
+{
+	auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
+	return impl ? impl->prngFactors_.chiSquared(factor) : 0.0;
 }
 
 // Extension (g2o's binary SE(3) edge): relative-pose edges, effective at the next initialize() (cuba_hip_set_relative_pose_edges)

@@ -47,6 +47,21 @@ int main()
 		removeRangeFactor(ba.get(), &none);      // (removing what was never added is no error)
 	}
 
+	// a range factor between poses needs two different pose vertices: refused at once, nothing is kept (cuba::addPoseRangeFactor)
+	{
+		PoseRangeFactor none, oneEnd, loop;
+		oneEnd.vertexI = &p5;
+		loop.vertexI = loop.vertexJ = &p7;
+		for (PoseRangeFactor* f : { &none, &oneEnd, &loop, static_cast<PoseRangeFactor*>(nullptr) })
+		{
+			threw = false;
+			try { addPoseRangeFactor(ba.get(), f); } catch (const std::invalid_argument&) { threw = true; }
+			REQUIRE(threw);
+		}
+		REQUIRE(poseRangeFactorChiSquared(ba.get(), &loop) == 0.0);
+		removePoseRangeFactor(ba.get(), &loop);      // (removing what was never added is no error)
+	}
+
 	ba->initialize();
 	// free poses in id order (5, 7), then the fixed one (3); pose 9 has no edges and keeps iP = -1
 	REQUIRE(p5.iP == 0 && p7.iP == 1 && p3.iP == 2 && p9.iP == -1);

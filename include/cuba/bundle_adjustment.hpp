@@ -247,4 +247,31 @@ void addRangeFactor(CudaBundleAdjustment* object, RangeFactor* factor);
 void removeRangeFactor(CudaBundleAdjustment* object, RangeFactor* factor);
 double rangeFactorChiSquared(const CudaBundleAdjustment* object, const RangeFactor* factor);
 
+// Extension (include/cuba_hip.h, cuba_hip_set_pose_range_factors): a range factor BETWEEN two pose vertices -- a measured distance from
+// a point riding on pose i to a point riding on pose j: the travelled distance of a wheel odometer between two keyframes (the scale of a
+// monocular graph, without any orientation), peer-to-peer UWB ranging, the baseline length of a rig whose cameras are separate poses, a
+// taped distance between two stations.  `leverArmI` / `leverArmJ` are the two points in their camera frames (zero: the camera centres),
+// `range` the measured distance (>= 0), `information` the scalar 1 / sigma^2 (>= 0).  Objective term information * r^2 with
+// r = |R_i^T (a_i - t_i) - R_j^T (a_j - t_j)| - range, or rho(information * r^2) when `kernel` is set (`delta` > 0 then).  The pair owns a
+// block of the reduced matrix also where no landmark connects the two poses.  A factor with one fixed vertex acts on the free one only; one
+// with two fixed vertices is ignored.  With the two points exactly on each other the direction is undefined: the factor then adds nothing to
+// the system and keeps its chi2, information * range^2.  Ownership and lifetime as for RelativePoseEdge: the caller owns the factor;
+// additions, removals and changes take effect at the next initialize(); both vertices must be part of the graph then.  removePoseVertex
+// drops the factors touching the vertex, clear() all.  poseRangeFactorChiSquared: information * r^2 at the estimate of the last optimize()
+// (0 before one, and for a factor between two fixed vertices) -- the plain value under a kernel too.
+struct PoseRangeFactor
+{
+	PoseVertex* vertexI = nullptr;
+	PoseVertex* vertexJ = nullptr;
+	std::array<double, 3> leverArmI{};
+	std::array<double, 3> leverArmJ{};
+	double range = 0;
+	double information = 0;
+	PoseFactorKernel kernel = PoseFactorKernel::NONE;
+	double delta = 0;
+};
+void addPoseRangeFactor(CudaBundleAdjustment* object, PoseRangeFactor* factor);
+void removePoseRangeFactor(CudaBundleAdjustment* object, PoseRangeFactor* factor);
+double poseRangeFactorChiSquared(const CudaBundleAdjustment* object, const PoseRangeFactor* factor);
+
 }  // namespace cuba

@@ -589,6 +589,40 @@ int cuba_hip_set_range_factors(cuba_hip_solver* s, int n, const int32_t* pose, c
 	const int32_t* kind, const double* delta);
 int cuba_hip_range_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor);
 
+/* Range factors between two poses (no counterpart in the reference): the binary counterpart of the range factors
+   above.  A factor names poses i != j, a measured distance rbar >= 0 between the point a_i of camera frame i and the point a_j of camera
+   frame j (the lever arms: antennas, wheel centres, rig points; zero for the camera centres), a scalar information Omega = 1 / sigma^2
+   >= 0 and optionally a robust kernel (kind, delta) of the pose factors' family: the travelled distance of a wheel odometer between two
+   keyframes (the scale of a monocular graph, without any orientation), peer-to-peer UWB ranging, the baseline length of a rig whose
+   cameras are separate poses, a taped distance between two stations.  A relative-pose edge with a rank-deficient information cannot say
+   this: its residual mixes rotation into translation, and a distance is no linear function of it.
+     residual     w_i = R_i^T (a_i - t_i) (world), u = a_j - (R_j w_i + t_j) (frame j), rho = |u|, m_j = u / rho, m_i = -R_i R_j^T m_j,
+                  r = rho - rbar, e = Omega r^2
+     objective    rho_k(e); the LM objective F gains the factors' sum
+     linearised   with w = rho_k'(e), J_j = [(m_j x a_j)^T | -m_j^T] and J_i = [(m_i x a_i)^T | -m_i^T] (1 x 6 each: the range factor's
+                  Jacobian with the other end's point as the anchor): w Omega J_i^T J_i and w Omega J_j^T J_j (rank 1 each) into the two
+                  diagonal blocks of the reduced matrix, w Omega J_i^T J_j into the off-diagonal block of the pair, -w Omega r J^T into bp
+                  and bsc; no second-order term.  The terms follow those of every other kind in every sum.
+     rho = 0      when the computed rho is exactly 0, m_i = m_j = 0: the factor adds nothing to the system and contributes e = Omega rbar^2.
+   Several factors on one pair or pose are summed in the caller's order.  A factor with one fixed end acts on the free end only, as a range
+   factor with the fixed end's point as the anchor; one with two fixed ends is accepted and ignored (chi2 0).  The free-free pairs are part
+   of the TOPOLOGY, together with the relative-pose edges' (the union of both kinds' pairs): every such pair owns a block of the reduced
+   matrix, also where no landmark connects the two poses, and the structure is rebuilt ("structure_builds") exactly when a call changes
+   that union; setting or clearing one kind keeps the other's blocks.  Every solve path honours the factors: the device-decision loop, the
+   host loop, both PCG forms, the exact solver, the fp32 library and the covariance entry points.
+   cuba_hip_set_pose_range_factors replaces the whole set (n = 0 clears it): pose_i[n], pose_j[n], range[n], lever_arm_i[3 n] and
+   lever_arm_j[3 n] (either NULL: zeros), info[n], kind[n] and delta[n] (both NULL: no kernels; kinds all 0 are no kernels).  Valid any time
+   after cuba_hip_set_graph, which clears the set.  It drops the run-to-run memories of option "heuristics" and cached covariance blocks.
+   CUBA_HIP_ERR_INVALID_ARGUMENT, the handle unchanged: an index out of range, i = j, non-finite values, a negative range, a negative
+   information (0 is valid and is no factor), a kind outside 0..3, delta <= 0 on a kind != 0, one of kind / delta without the other.
+   CUBA_HIP_ERR_STATE, the handle staying usable: a landmark-partitioned handle (and cuba_hip_set_partition on a handle with such factors)
+   and a graph without reprojection edges.  A handle without such factors launches the kernels, with the arguments, of a library without
+   this entry point.
+   cuba_hip_pose_range_factor_chi_squares: the plain Omega r^2 of every factor at the current estimate, in the caller's order. */
+int cuba_hip_set_pose_range_factors(cuba_hip_solver* s, int n, const int32_t* pose_i, const int32_t* pose_j, const double* range, const double* lever_arm_i,
+	const double* lever_arm_j, const double* info, const int32_t* kind, const double* delta);
+int cuba_hip_pose_range_factor_chi_squares(cuba_hip_solver* s, double* chi2_per_factor);
+
 /* ---- introspection (parity tests) and multi-GPU plumbing ------------------------------------------ */
 
 /* Structure of the reduced system: upper-triangular BSR (replaces the accessors of
