@@ -44,21 +44,19 @@
 // residual are templates on ROBUST; a set without kernels has null kind / delta arrays and runs the `false` instantiations, which hold
 // nothing of this.  A landmark prior always carries a kind (none = 0) and comes with its kernel in one call.
 //
-// Order: the pose priors, the position factors, the relative-pose edges, the direction factors and the range factors all add to the diagonal
-// blocks, bp and bsc that the pose and Schur passes stored, by read-modify-write.  launch_pose_factor_linearize issues them in one stream in
-// this order -- priors, position factors, the edges' records, the edges' gather, direction factors, range factors, the records and the
-// gather of the range factors between poses -- and that order is part of the result
-// (floating-point sums do not commute): a handle's bits depend on it, and a new kind goes BEHIND the ones a handle may already combine,
-// never between two of them.  (The position factors sit between the priors and the edges: no handle could hold them before they came, so
-// no existing sum changed.  The direction factors came when handles could combine all of the others, so they went last; the range factors came after them and go
-// behind them, the range factors between poses after those.)
+// Order: the six kinds on the poses add to the same diagonal blocks, bp and bsc by read-modify-write, in launches of their own in one
+// stream; the order of those launches is part of the result.  It is written down once, with the rule for a new kind (it goes BEHIND the
+// others), at launch_pose_factor_linearize (ba_kernels.hpp).
 //
 // The kinds keep linearisation kernels of their own (a prior is not run as a one-ended edge: its sums would be taken in another order).
 // Everything else exists once: the device helpers below (the unary kinds' accumulators and their read-modify-write: zero_pose_sums,
 // add_pose_sums), one chi2 kernel over a per-kind residual, one device layout and one upload for the four unary kinds on the poses
-// (ba_kernels.hpp: DevicePoseGroups), the host-side validation, sorting and read-back, and one interface (ba_kernels.hpp: DeviceFactors;
-// ba_solver.hpp: the handle's table of its sets).  A new kind brings a residual, a Jacobian, a setter with its widths and nouns, and its
-// entry there.
+// (ba_kernels.hpp: DevicePoseGroups), and the same for the binary kinds (DevicePosePairs): the two of them are ONE path -- one sort, one
+// upload, one gather kernel over a per-kind pair of terms, one launch helper -- with a linearisation kernel and a record layout each (90
+// numbers of finished sums for an edge, 14 numbers {J_i, J_j, w Omega, w Omega r} for a range: not worth forcing into one); the host-side
+// validation, sorting and read-back, and one interface (ba_kernels.hpp: DeviceFactors; ba_solver.hpp: the handle's table of its sets, and
+// of the binary ones in launch order).  A new kind brings a residual, a Jacobian, a setter with its widths and nouns, and its entry there;
+// a new binary kind also its record, block_term and pose_term.
 //
 //   prior_linearize_kernel     lane = free pose with priors: its priors in the caller's order, J^T Omega J / J^T Omega r summed in
 //                              registers, then added to the pose's diagonal block (upper triangle), bp and (mode 1) bsc -- one writer per
@@ -66,11 +64,6 @@
 //   relpose_linearize_kernel   lane = edge: r, J_i, J_j and the edge's record {J_i^T Omega J_i, J_j^T Omega J_j (upper triangles),
 //                              the cross term laid out as the block (min, max) of the internal pose pair stores it, J_i^T Omega r,
 //                              J_j^T Omega r}
-//   relpose_gather_kernel      lane = one number of the reduced system: an entry of an off-diagonal block with relative edges (the sum of
-//                              its edges' cross terms, added to what the Schur pass stored, or stored whole when the block has no products),
-//                              or an entry of a pose's diagonal block (upper triangle) / of bp and (mode 1) bsc, summed over the pose's
-//                              edges in the caller's order -- one writer per number, fixed order, no atomics; behind the Schur pass and the
-//                              priors' launch
 //   position_linearize_kernel  lane = free pose with position factors: the rotation matrix once, then the pose's factors in the caller's order,
 //                              J^T (Omega J) (21 numbers) and J^T Omega r (6) summed in registers, one read-modify-write of the diagonal
 //                              block's upper triangle, bp and (mode 1) bsc -- one writer per number; behind the priors' launch, ahead of the
@@ -81,14 +74,15 @@
 //                              launch behind the edges' gather
 //   range_linearize_kernel     lane = free pose with range factors: the rotation matrix once, then the pose's factors in the caller's order,
 //                              w Omega J^T J (21 numbers, rank 1 per factor) and w Omega r J^T (6) summed in registers, one read-modify-write of
-//                              the diagonal block's upper triangle, bp and (mode 1) bsc -- one writer per number; the last launch, behind the
+//                              the diagonal block's upper triangle, bp and (mode 1) bsc -- one writer per number; the launch behind the
 //                              direction factors'
 //   pose_range_linearize_kernel lane = range factor between poses with a free end: the record {J_i, J_j, w Omega, w Omega r}, 14 numbers
-//   pose_range_gather_kernel   lane = one number of the reduced system, as relpose_gather_kernel: an entry of an off-diagonal block with such
-//                              factors (mode 1: J_min[r] w Omega J_max[c] summed over the block's factors; stored whole where the block has
-//                              neither Schur products nor a relative-pose edge, added to what those stored otherwise), or an entry of a
-//                              pose's diagonal block (upper triangle) / of bp and (mode 1) bsc, summed over the pose's factors in the
-//                              caller's order -- one writer per number, fixed order, no atomics; the last two launches
+//   pair_gather_kernel<Kind>   lane = one number of the reduced system, for either binary kind: an entry of an off-diagonal block with such
+//                              factors (mode 1: the sum of block_term over the block's factors -- an edge's stored cross term, a range's
+//                              J_min[r] w Omega J_max[c]; stored whole where the block has neither Schur products nor a binary kind launched
+//                              earlier, added to what those stored otherwise), or an entry of a pose's diagonal block (upper triangle) / of bp
+//                              and (mode 1) bsc, the sum of pose_term over the pose's factors in the caller's order -- one writer per number,
+//                              fixed order, no atomics; the launch behind the kind's records
 //   factor_chi2_kernel         lane = factor of one kind: r^T Omega r at the current estimate (factor_chi, an overload per kind) into the per-factor
 //                              output and (rho of it) into per-workgroup partials that the caller sums together with the reprojection
 //                              edges' partials (fixed order, no atomics)
@@ -107,18 +101,16 @@ constexpr int POS_LIN_BLOCK = 64;
 constexpr int DIR_LIN_BLOCK = 64;
 constexpr int RNG_LIN_BLOCK = 64;
 constexpr int REL_LIN_BLOCK = 64;
-constexpr int REL_GATHER_BLOCK = 256;
+constexpr int PRNG_LIN_BLOCK = 64;          // (tiny, latency-bound launches: the siblings' block size)
+constexpr int PAIR_GATHER_BLOCK = 256;
 constexpr int CHI_BLOCK = 256;
 constexpr int CHI_MAX_GROUPS = 64;     // a chi2 launch's partials (a grid-stride loop beyond): they join the reprojection edges' partials
+constexpr int POSE_NUMBERS = 27;       // what a factor adds to per free end: 21 entries of the diagonal block (upper triangle) + 6 of bp / bsc
 // record of an edge: [0, 21) J_i^T Omega J_i, [21, 42) J_j^T Omega J_j (upper triangles, entry c (c + 1) / 2 + r), [42, 78) the cross block
 // (column-major, rows = the pose of smaller internal index), [78, 84) J_i^T Omega r, [84, 90) J_j^T Omega r
 constexpr int REL_HII = 0, REL_HJJ = 21, REL_HX = 42, REL_GI = 78, REL_GJ = 84;
 static_assert(REL_GJ + 6 == REL_REC, "record layout");
-constexpr int REL_POSE_NUMBERS = 27;        // 21 entries of a diagonal block + 6 of bp / bsc
-// the range factors between two poses run as the edges do (tiny, latency-bound launches: the siblings' block sizes)
-constexpr int PRNG_LIN_BLOCK = 64;
-constexpr int PRNG_GATHER_BLOCK = 256;
-// record of such a factor: [0, 6) J_i, [6, 12) J_j, w Omega, w Omega r
+// record of a range factor between two poses: [0, 6) J_i, [6, 12) J_j, w Omega, w Omega r
 constexpr int PRNG_JI = 0, PRNG_JJ = 6, PRNG_W = 12, PRNG_WR = 13;
 static_assert(PRNG_WR + 1 == PRNG_REC, "record layout");
 
@@ -206,6 +198,10 @@ __device__ __forceinline__ void add_pose_sums(const DeviceStructure& st, const D
 	}
 }
 
+// number `el` of the record of factor k of a binary kind: the records are stored number-major (all factors' number 0, then number 1, ...),
+// so that the lanes of the linearisation -- consecutive factors -- store to consecutive addresses
+__device__ __forceinline__ Scalar& pair_rec(const DevicePosePairs& f, int k, int el) { return f.rec[(size_t)el * f.n + k]; }
+
 // ---- pose priors ------------------------------------------------------------------------------------------------------------------
 
 template <bool ROBUST>
@@ -282,10 +278,6 @@ __device__ __forceinline__ Scalar factor_chi(const DeviceGraph& g, const DeviceP
 }
 
 // ---- relative-pose edges ----------------------------------------------------------------------------------------------------------
-
-// number `el` of the record of edge k: the records are stored number-major (all edges' number 0, then number 1, ...), so that the lanes of
-// the linearisation -- consecutive edges -- store to consecutive addresses
-__device__ __forceinline__ Scalar& rel_rec(const DeviceRelPoses& rp, int k, int el) { return rp.rec[(size_t)el * rp.n + k]; }
 
 // Hamilton product of (x, y, z, w) quaternions
 __device__ __forceinline__ void quat_mul(const Scalar a[4], const Scalar b[4], Scalar o[4])
@@ -375,8 +367,8 @@ __global__ __launch_bounds__(REL_LIN_BLOCK) void relpose_linearize_kernel(Device
 #pragma unroll
 			for (int a = 0; a < 6; a++) { sii += Ji[a][rr] * oi[a]; sjj += Jj[a][rr] * oj[a]; sx += Ji[a][rr] * oj[a]; }
 			if constexpr (ROBUST) { sii *= w; sjj *= w; sx *= w; }
-			if (rr <= c) { rel_rec(rp, k, REL_HII + c * (c + 1) / 2 + rr) = sii; rel_rec(rp, k, REL_HJJ + c * (c + 1) / 2 + rr) = sjj; }
-			rel_rec(rp, k, REL_HX + (flip ? rr * 6 + c : c * 6 + rr)) = sx;
+			if (rr <= c) { pair_rec(rp, k, REL_HII + c * (c + 1) / 2 + rr) = sii; pair_rec(rp, k, REL_HJJ + c * (c + 1) / 2 + rr) = sjj; }
+			pair_rec(rp, k, REL_HX + (flip ? rr * 6 + c : c * 6 + rr)) = sx;
 		}
 	}
 	if constexpr (!ROBUST) (void)info_times(O, r, Or);
@@ -387,50 +379,16 @@ __global__ __launch_bounds__(REL_LIN_BLOCK) void relpose_linearize_kernel(Device
 #pragma unroll
 		for (int a = 0; a < 6; a++) { si += Ji[a][c] * Or[a]; sj += Jj[a][c] * Or[a]; }
 		if constexpr (ROBUST) { si *= w; sj *= w; }
-		rel_rec(rp, k, REL_GI + c) = si; rel_rec(rp, k, REL_GJ + c) = sj;
+		pair_rec(rp, k, REL_GI + c) = si; pair_rec(rp, k, REL_GJ + c) = sj;
 	}
 }
 
-__global__ __launch_bounds__(REL_GATHER_BLOCK) void relpose_gather_kernel(DeviceStructure st, DeviceSystem sys, DeviceRelPoses rp, int mode)
+// what pair_gather_kernel sums: entry el (column-major) of the cross block of edge k as the pattern stores it, and entry el of what the
+// edge adds to the pose at its end `side` (el < 21: the diagonal block's packed upper triangle, else bp / bsc) -- stored numbers both
+__device__ __forceinline__ Scalar block_term(const DeviceRelPoses& rp, int k, int el) { return pair_rec(rp, k, REL_HX + el); }
+__device__ __forceinline__ Scalar pose_term(const DeviceRelPoses& rp, int k, int side, int el, int, int)
 {
-	const int x = blockIdx.x * REL_GATHER_BLOCK + threadIdx.x;
-	const int nBlkNumbers = mode == 1 ? 36 * rp.nBlocks : 0;
-	if (x < nBlkNumbers)
-	{
-		const int b = x / 36, el = x - 36 * b;
-		const int blk = rp.blk_id[b];
-		Scalar s = 0;
-		const int k1 = rp.blk_ptr[b + 1];
-		for (int k = rp.blk_ptr[b]; k < k1; k++) s += rel_rec(rp, k, REL_HX + el);
-		Scalar* dst = sys.hsc + 36 * (size_t)blk + el;
-		// (a block with products was stored by the Schur pass of this linearisation; one without has no other writer)
-		*dst = st.prod_end[blk] > st.prod_beg[blk] ? *dst + s : s;
-		return;
-	}
-	const int y = x - nBlkNumbers;
-	const int p = y / REL_POSE_NUMBERS, el = y - REL_POSE_NUMBERS * p;
-	if (p >= rp.nPoses) return;
-	const int ip = rp.pose_id[p];
-	Scalar s = 0;
-	const int k1 = rp.pose_ptr[p + 1];
-	for (int k = rp.pose_ptr[p]; k < k1; k++)
-	{
-		const int item = rp.pose_item[k], side = item & 1;
-		s += rel_rec(rp, item >> 1, el < 21 ? (side ? REL_HJJ : REL_HII) + el : (side ? REL_GJ : REL_GI) + (el - 21));
-	}
-	if (el < 21)
-	{
-		// packed upper-triangle index -> (r, c)
-		int c = 0;
-		while ((c + 1) * (c + 2) / 2 <= el) c++;
-		const int rr = el - c * (c + 1) / 2;
-		sys.hsc[36 * (size_t)st.hsc_rowptr[ip] + c * 6 + rr] += s;
-	}
-	else
-	{
-		sys.bp[6 * (size_t)ip + (el - 21)] -= s;
-		if (mode == 1) sys.bsc[6 * (size_t)ip + (el - 21)] -= s;
-	}
+	return pair_rec(rp, k, el < 21 ? (side ? REL_HJJ : REL_HII) + el : (side ? REL_GJ : REL_GI) + (el - 21));
 }
 
 // r^T Omega r of edge k at the current estimate (factor_chi2_kernel)
@@ -681,9 +639,6 @@ __device__ __forceinline__ Scalar factor_chi(const DeviceGraph& g, const DeviceR
 
 // ---- range factors between two poses ----------------------------------------------------------------------------------------------
 
-// number `el` of the record of factor k: number-major as rel_rec, so that the lanes of the linearisation store to consecutive addresses
-__device__ __forceinline__ Scalar& prng_rec(const DevicePoseRanges& pr, int k, int el) { return pr.rec[(size_t)el * pr.n + k]; }
-
 // w_i = R_i^T (a_i - t_i), the world position of the point on pose i; u = (a_j - t_j) - R_j w_i: the unary range factor on pose j with the
 // anchor w_i; rho = |u|, r = rho - rbar, mj = u / rho (frame j) and mi = -R_i R_j^T mj (frame i) -- from the ONE computed u, so that rho
 // and the rule at rho = 0 (range_residual: mi = mj = 0, e = info rbar^2) are the same for both ends.  Returns e = info r^2
@@ -729,38 +684,63 @@ __global__ __launch_bounds__(PRNG_LIN_BLOCK) void pose_range_linearize_kernel(De
 	const Scalar J[12] = { mi[1] * ai[2] - mi[2] * ai[1], mi[2] * ai[0] - mi[0] * ai[2], mi[0] * ai[1] - mi[1] * ai[0], -mi[0], -mi[1], -mi[2],
 		mj[1] * aj[2] - mj[2] * aj[1], mj[2] * aj[0] - mj[0] * aj[2], mj[0] * aj[1] - mj[1] * aj[0], -mj[0], -mj[1], -mj[2] };
 #pragma unroll
-	for (int c = 0; c < 12; c++) prng_rec(pr, k, PRNG_JI + c) = J[c];
-	prng_rec(pr, k, PRNG_W) = w;
-	prng_rec(pr, k, PRNG_WR) = w * r;
+	for (int c = 0; c < 12; c++) pair_rec(pr, k, PRNG_JI + c) = J[c];
+	pair_rec(pr, k, PRNG_W) = w;
+	pair_rec(pr, k, PRNG_WR) = w * r;
 }
 
-__global__ __launch_bounds__(PRNG_GATHER_BLOCK) void pose_range_gather_kernel(DeviceStructure st, DeviceSystem sys, DevicePoseRanges pr, int mode)
+// what pair_gather_kernel sums: entry el = (rr, c), column-major, of the block (min, max) of the internal pair, J_min[rr] w Omega J_max[c],
+// and entry el of what the factor adds to the pose at its end `side`: J[rr] w Omega J[c] (el < 21: (rr, c) of the upper triangle), else
+// J[c] w Omega r -- products of the record's numbers
+__device__ __forceinline__ Scalar block_term(const DevicePoseRanges& pr, int k, int el)
 {
-	const int x = blockIdx.x * PRNG_GATHER_BLOCK + threadIdx.x;
-	const int nBlkNumbers = mode == 1 ? 36 * pr.nBlocks : 0;
+	const int c = el / 6, rr = el - 6 * c;
+	const bool flip = pr.pose_i[k] > pr.pose_j[k];
+	return pair_rec(pr, k, (flip ? PRNG_JJ : PRNG_JI) + rr) * (pair_rec(pr, k, PRNG_W) * pair_rec(pr, k, (flip ? PRNG_JI : PRNG_JJ) + c));
+}
+__device__ __forceinline__ Scalar pose_term(const DevicePoseRanges& pr, int k, int side, int el, int rr, int c)
+{
+	const int J = side ? PRNG_JJ : PRNG_JI;
+	if (el < 21) return pair_rec(pr, k, J + rr) * (pair_rec(pr, k, PRNG_W) * pair_rec(pr, k, J + c));
+	return pair_rec(pr, k, J + c) * pair_rec(pr, k, PRNG_WR);
+}
+
+// info r^2 of factor k at the current estimate (factor_chi2_kernel)
+__device__ __forceinline__ Scalar factor_chi(const DeviceGraph& g, const DevicePoseRanges& pr, int k)
+{
+	if (k >= pr.nActive) return 0;
+	Scalar mi[3], mj[3], r;
+	return pose_range_residual(g, pr, k, mi, mj, r);
+}
+
+// ---- the binary kinds' gather -----------------------------------------------------------------------------------------------------
+
+// The sums of a binary kind's records into the reduced system: lane = one number of it -- in mode 1 first the 36 entries of every
+// off-diagonal block with such factors (block_term over the block's factors), then POSE_NUMBERS per free pose with such factors: the upper
+// triangle of its diagonal block, bp and (mode 1) bsc (pose_term over the pose's items, in the caller's order).  One writer per number,
+// fixed order, no atomics.  block_term / pose_term: an overload per kind next to its record layout
+template <class Kind>
+__global__ __launch_bounds__(PAIR_GATHER_BLOCK) void pair_gather_kernel(DeviceStructure st, DeviceSystem sys, Kind f, int mode)
+{
+	const int x = blockIdx.x * PAIR_GATHER_BLOCK + threadIdx.x;
+	const int nBlkNumbers = mode == 1 ? 36 * f.nBlocks : 0;
 	if (x < nBlkNumbers)
 	{
-		// entry (rr, c) of the block (min, max) of the internal pair, column-major: J_min[rr] w Omega J_max[c]
 		const int b = x / 36, el = x - 36 * b;
-		const int c = el / 6, rr = el - 6 * c;
-		const int blk = pr.blk_id[b];
+		const int blk = f.blk_id[b];
 		Scalar s = 0;
-		const int k1 = pr.blk_ptr[b + 1];
-		for (int k = pr.blk_ptr[b]; k < k1; k++)
-		{
-			const bool flip = pr.pose_i[k] > pr.pose_j[k];
-			s += prng_rec(pr, k, (flip ? PRNG_JJ : PRNG_JI) + rr) * (prng_rec(pr, k, PRNG_W) * prng_rec(pr, k, (flip ? PRNG_JI : PRNG_JJ) + c));
-		}
+		const int k1 = f.blk_ptr[b + 1];
+		for (int k = f.blk_ptr[b]; k < k1; k++) s += block_term(f, k, el);
 		Scalar* dst = sys.hsc + 36 * (size_t)blk + el;
-		// (a block with products was stored by the Schur pass of this linearisation, one with a relative-pose edge by relpose_gather_kernel;
-		// a block with neither has no other writer)
-		*dst = st.prod_end[blk] > st.prod_beg[blk] || pr.blk_rel[b] ? *dst + s : s;
+		// (a block with products was stored by the Schur pass of this linearisation, a shared one by an earlier binary kind's gather; a block
+		// with neither has no other writer and is cleared by no one: store)
+		*dst = st.prod_end[blk] > st.prod_beg[blk] || f.blk_shared[b] ? *dst + s : s;
 		return;
 	}
 	const int y = x - nBlkNumbers;
-	const int p = y / REL_POSE_NUMBERS, el = y - REL_POSE_NUMBERS * p;
-	if (p >= pr.nPoses) return;
-	const int ip = pr.pose_id[p];
+	const int p = y / POSE_NUMBERS, el = y - POSE_NUMBERS * p;
+	if (p >= f.nPoses) return;
+	const int ip = f.pose_id[p];
 	// packed upper-triangle index -> (rr, c); el >= 21: entry c of bp / bsc
 	int c = el - 21, rr = 0;
 	if (el < 21)
@@ -770,12 +750,11 @@ __global__ __launch_bounds__(PRNG_GATHER_BLOCK) void pose_range_gather_kernel(De
 		rr = el - c * (c + 1) / 2;
 	}
 	Scalar s = 0;
-	const int k1 = pr.pose_ptr[p + 1];
-	for (int k = pr.pose_ptr[p]; k < k1; k++)
+	const int k1 = f.pose_ptr[p + 1];
+	for (int k = f.pose_ptr[p]; k < k1; k++)
 	{
-		const int item = pr.pose_item[k], f = item >> 1, J = item & 1 ? PRNG_JJ : PRNG_JI;
-		if (el < 21) s += prng_rec(pr, f, J + rr) * (prng_rec(pr, f, PRNG_W) * prng_rec(pr, f, J + c));
-		else s += prng_rec(pr, f, J + c) * prng_rec(pr, f, PRNG_WR);
+		const int item = f.pose_item[k];
+		s += pose_term(f, item >> 1, item & 1, el, rr, c);
 	}
 	if (el < 21) sys.hsc[36 * (size_t)st.hsc_rowptr[ip] + c * 6 + rr] += s;
 	else
@@ -783,14 +762,6 @@ __global__ __launch_bounds__(PRNG_GATHER_BLOCK) void pose_range_gather_kernel(De
 		sys.bp[6 * (size_t)ip + c] -= s;
 		if (mode == 1) sys.bsc[6 * (size_t)ip + c] -= s;
 	}
-}
-
-// info r^2 of factor k at the current estimate (factor_chi2_kernel)
-__device__ __forceinline__ Scalar factor_chi(const DeviceGraph& g, const DevicePoseRanges& pr, int k)
-{
-	if (k >= pr.nActive) return 0;
-	Scalar mi[3], mj[3], r;
-	return pose_range_residual(g, pr, k, mi, mj, r);
 }
 
 // ---- chi2 -------------------------------------------------------------------------------------------------------------------------
@@ -845,54 +816,41 @@ void launch_factor_chi2(const DeviceGraph& g, const DeviceFactors& pf, Scalar* p
 	});
 }
 
+// a unary kind's launch: lane = free pose with such factors; `plain` / `robust`: the kind's kernel without / with robust kernels
+template <class Kind>
+using UnaryKernel = void (*)(DeviceGraph, DeviceStructure, DeviceSystem, Kind, int);
+template <class Kind>
+static void launch_unary(UnaryKernel<Kind> plain, UnaryKernel<Kind> robust, int block, const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const Kind& f,
+	int mode, hipStream_t s)
+{
+	if (f.nPoses <= 0) return;
+	const UnaryKernel<Kind> kernel = f.rk_kind ? robust : plain;
+	hipLaunchKernelGGL(kernel, dim3((f.nPoses + block - 1) / block), dim3(block), 0, s, g, st, sys, f, mode);
+}
+
+// a binary kind's two launches: the records (lane = factor with a free end), then their gather
+template <class Kind>
+using BinaryKernel = void (*)(DeviceGraph, Kind);
+template <class Kind>
+static void launch_binary(BinaryKernel<Kind> plain, BinaryKernel<Kind> robust, int block, const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const Kind& f,
+	int mode, hipStream_t s)
+{
+	if (f.nActive <= 0) return;
+	const BinaryKernel<Kind> kernel = f.rk_kind ? robust : plain;
+	hipLaunchKernelGGL(kernel, dim3((f.nActive + block - 1) / block), dim3(block), 0, s, g, f);
+	const size_t numbers = (mode == 1 ? (size_t)36 * f.nBlocks : 0) + (size_t)POSE_NUMBERS * f.nPoses;
+	hipLaunchKernelGGL(pair_gather_kernel<Kind>, dim3((unsigned)((numbers + PAIR_GATHER_BLOCK - 1) / PAIR_GATHER_BLOCK)), dim3(PAIR_GATHER_BLOCK), 0, s, st, sys, f, mode);
+}
+
+// (the order and the rule for a new kind: ba_kernels.hpp, at this function's declaration)
 void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DeviceFactors& pf, int mode, hipStream_t s)
 {
-	const DevicePriors& pr = pf.priors;
-	if (pr.nPoses > 0)
-	{
-		const dim3 grid((pr.nPoses + PRIOR_LIN_BLOCK - 1) / PRIOR_LIN_BLOCK);
-		if (pr.rk_kind) hipLaunchKernelGGL(prior_linearize_kernel<true>, grid, dim3(PRIOR_LIN_BLOCK), 0, s, g, st, sys, pr, mode);
-		else hipLaunchKernelGGL(prior_linearize_kernel<false>, grid, dim3(PRIOR_LIN_BLOCK), 0, s, g, st, sys, pr, mode);
-	}
-	const DevicePositionFactors& pp = pf.pos;
-	if (pp.nPoses > 0)
-	{
-		const dim3 grid((pp.nPoses + POS_LIN_BLOCK - 1) / POS_LIN_BLOCK);
-		if (pp.rk_kind) hipLaunchKernelGGL(position_linearize_kernel<true>, grid, dim3(POS_LIN_BLOCK), 0, s, g, st, sys, pp, mode);
-		else hipLaunchKernelGGL(position_linearize_kernel<false>, grid, dim3(POS_LIN_BLOCK), 0, s, g, st, sys, pp, mode);
-	}
-	const DeviceRelPoses& rp = pf.rel;
-	if (rp.nActive > 0)
-	{
-		const dim3 linGrid((rp.nActive + REL_LIN_BLOCK - 1) / REL_LIN_BLOCK);
-		if (rp.rk_kind) hipLaunchKernelGGL(relpose_linearize_kernel<true>, linGrid, dim3(REL_LIN_BLOCK), 0, s, g, rp);
-		else hipLaunchKernelGGL(relpose_linearize_kernel<false>, linGrid, dim3(REL_LIN_BLOCK), 0, s, g, rp);
-		const size_t numbers = (mode == 1 ? (size_t)36 * rp.nBlocks : 0) + (size_t)REL_POSE_NUMBERS * rp.nPoses;
-		hipLaunchKernelGGL(relpose_gather_kernel, dim3((unsigned)((numbers + REL_GATHER_BLOCK - 1) / REL_GATHER_BLOCK)), dim3(REL_GATHER_BLOCK), 0, s, st, sys, rp, mode);
-	}
-	const DeviceDirectionFactors& df = pf.dir;
-	if (df.nPoses > 0)
-	{
-		const dim3 grid((df.nPoses + DIR_LIN_BLOCK - 1) / DIR_LIN_BLOCK);
-		if (df.rk_kind) hipLaunchKernelGGL(direction_linearize_kernel<true>, grid, dim3(DIR_LIN_BLOCK), 0, s, g, st, sys, df, mode);
-		else hipLaunchKernelGGL(direction_linearize_kernel<false>, grid, dim3(DIR_LIN_BLOCK), 0, s, g, st, sys, df, mode);
-	}
-	const DeviceRangeFactors& rf = pf.rng;
-	if (rf.nPoses > 0)
-	{
-		const dim3 grid((rf.nPoses + RNG_LIN_BLOCK - 1) / RNG_LIN_BLOCK);
-		if (rf.rk_kind) hipLaunchKernelGGL(range_linearize_kernel<true>, grid, dim3(RNG_LIN_BLOCK), 0, s, g, st, sys, rf, mode);
-		else hipLaunchKernelGGL(range_linearize_kernel<false>, grid, dim3(RNG_LIN_BLOCK), 0, s, g, st, sys, rf, mode);
-	}
-	const DevicePoseRanges& pg = pf.prng;
-	if (pg.nActive > 0)
-	{
-		const dim3 linGrid((pg.nActive + PRNG_LIN_BLOCK - 1) / PRNG_LIN_BLOCK);
-		if (pg.rk_kind) hipLaunchKernelGGL(pose_range_linearize_kernel<true>, linGrid, dim3(PRNG_LIN_BLOCK), 0, s, g, pg);
-		else hipLaunchKernelGGL(pose_range_linearize_kernel<false>, linGrid, dim3(PRNG_LIN_BLOCK), 0, s, g, pg);
-		const size_t numbers = (mode == 1 ? (size_t)36 * pg.nBlocks : 0) + (size_t)REL_POSE_NUMBERS * pg.nPoses;
-		hipLaunchKernelGGL(pose_range_gather_kernel, dim3((unsigned)((numbers + PRNG_GATHER_BLOCK - 1) / PRNG_GATHER_BLOCK)), dim3(PRNG_GATHER_BLOCK), 0, s, st, sys, pg, mode);
-	}
+	launch_unary(prior_linearize_kernel<false>, prior_linearize_kernel<true>, PRIOR_LIN_BLOCK, g, st, sys, pf.priors, mode, s);
+	launch_unary(position_linearize_kernel<false>, position_linearize_kernel<true>, POS_LIN_BLOCK, g, st, sys, pf.pos, mode, s);
+	launch_binary(relpose_linearize_kernel<false>, relpose_linearize_kernel<true>, REL_LIN_BLOCK, g, st, sys, pf.rel, mode, s);
+	launch_unary(direction_linearize_kernel<false>, direction_linearize_kernel<true>, DIR_LIN_BLOCK, g, st, sys, pf.dir, mode, s);
+	launch_unary(range_linearize_kernel<false>, range_linearize_kernel<true>, RNG_LIN_BLOCK, g, st, sys, pf.rng, mode, s);
+	launch_binary(pose_range_linearize_kernel<false>, pose_range_linearize_kernel<true>, PRNG_LIN_BLOCK, g, st, sys, pf.prng, mode, s);
 }
 
 }  // namespace cubahip
@@ -1015,41 +973,61 @@ void cuba_hip_solver::setPosePriors(int n, const int32_t* pose, const double* q,
 	adopt_unary_pose_factors(*this, priorSet, v);
 }
 
+// the two ends of a binary factor: distinct pose indices within [0, limit)
+static void check_pose_pair(int i, int j, int limit, const std::string& noun)
+{
+	if (i < 0 || i >= limit || j < 0 || j >= limit) throw ArgError{ noun + ": pose index out of range" };
+	if (i == j) throw ArgError{ noun + " between a pose and itself" };
+}
+
+// a validated binary set replaces the handle's (adopt_unary_pose_factors' counterpart; vals: the kind's value arrays in the set's order).
+// The pairs are part of the topology; a binary kind launched later stores or adds into a block by whether this one writes it, so the
+// later sets' device copies are due again; the covariance blocks describe the factors -- and the block pattern -- they were computed on
+static void adopt_binary_pose_factors(cuba_hip_solver& s, BinaryPoseFactorSet& set, std::vector<int>& vi, std::vector<int>& vj, std::initializer_list<std::vector<double>*> vals,
+	std::vector<int>& kind, std::vector<double>& delta)
+{
+	set.pi.swap(vi); set.pj.swap(vj); set.kind.swap(kind); set.delta.swap(delta);
+	size_t a = 0;
+	for (std::vector<double>* v : vals) set.vals[a++].host.swap(*v);
+	s.collectBinaryPairs();
+	forget_factor_memories(s, set);
+	set.dev = DevicePosePairs();
+	bool later = false;
+	for (BinaryPoseFactorSet* other : s.binarySets)
+	{
+		if (later) other->uploaded = false;
+		later = later || other == &set;
+	}
+	s.covBlocksValid = false;
+}
+
 void cuba_hip_solver::setRelativePoseEdges(int n, const int32_t* pi, const int32_t* pj, const double* q, const double* t, const double* info)
 {
 	check_factor_call(*this, relSet, n, pi && pj && q && t && info, nullptr, nullptr, "reprojection edges");
-	std::vector<int> vi((size_t)n), vj((size_t)n);
-	std::vector<double> vq((size_t)4 * n), vt((size_t)3 * n), vinfo((size_t)36 * n);
+	std::vector<int> vi((size_t)n), vj((size_t)n), vk;
+	std::vector<double> vq((size_t)4 * n), vt((size_t)3 * n), vinfo((size_t)36 * n), vd;
 	for (int k = 0; k < n; k++)
 	{
-		if (pi[k] < 0 || pi[k] >= Pt || pj[k] < 0 || pj[k] >= Pt) throw ArgError{ "relative-pose edge: pose index out of range" };
-		if (pi[k] == pj[k]) throw ArgError{ "relative-pose edge between a pose and itself" };
+		check_pose_pair(pi[k], pj[k], Pt, relSet.noun);
 		vi[k] = pi[k]; vj[k] = pj[k];
 		take_factor_values(vq.data(), vt.data(), vinfo.data(), k, q, t, info, "relative", "relative-pose");
 	}
 	// (the replaced set is a new set: the robust kernels of the previous one go with it)
-	relSet.pi.swap(vi); relSet.pj.swap(vj); relSet.q.swap(vq); relSet.t.swap(vt); relSet.info.swap(vinfo);
-	relSet.kind.clear(); relSet.delta.clear();
-	collectBinaryPairs();
-	forget_factor_memories(*this, relSet);
-	pf.rel = DeviceRelPoses();
-	// (the range factors between poses store or add into a block by whether these edges write it: their device copy is due again)
-	prngSet.uploaded = false;
-	covBlocksValid = false;          // (the covariance blocks describe the edge set -- and the block pattern -- they were computed on)
+	adopt_binary_pose_factors(*this, relSet, vi, vj, { &vq, &vt, &vinfo }, vk, vd);
 }
 
-// the distinct free-free pairs of both binary kinds (caller's numbering, smaller index first): part of the topology -- need() rebuilds the
-// structure when they differ from the pairs the current one was seeded with.  Either kind's setter recomputes the union, so that setting or
-// clearing one kind keeps the other's pairs
+// the distinct free-free pairs of the binary kinds (caller's numbering, smaller index first): part of the topology -- need() rebuilds the
+// structure when they differ from the pairs the current one was seeded with.  Every binary setter recomputes the union, so that setting or
+// clearing one kind keeps the others' pairs
 void cuba_hip_solver::collectBinaryPairs()
 {
 	std::vector<uint64_t> pairs;
-	const auto take = [&](const std::vector<int>& vi, const std::vector<int>& vj) {
-		for (size_t k = 0; k < vi.size(); k++)
-			if (vi[k] < Pf && vj[k] < Pf) pairs.push_back(((uint64_t)(uint32_t)std::min(vi[k], vj[k]) << 32) | (uint32_t)std::max(vi[k], vj[k]));
-	};
-	take(relSet.pi, relSet.pj);
-	take(prngSet.pi, prngSet.pj);
+	for (const BinaryPoseFactorSet* set : binarySets)
+		for (size_t k = 0; k < set->pi.size(); k++)
+		{
+			const int i = set->pi[k], j = set->pj[k];
+			if (i < Pf && j < Pf) pairs.push_back(((uint64_t)(uint32_t)std::min(i, j) << 32) | (uint32_t)std::max(i, j));
+		}
 	std::sort(pairs.begin(), pairs.end());
 	pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
 	h_relPairs.swap(pairs);
@@ -1117,9 +1095,26 @@ void cuba_hip_solver::setDirectionFactors(int n, const int32_t* pose, const doub
 	covBlocksValid = false;
 }
 
+// what the two scalar kinds check of factor k: the 3-vectors of `vecs` finite (component by component, each vector where given), the range
+// and the information finite and not negative (0: no factor), the kernel a known one.  Returns whether the factor has a real kernel
+struct Vec3Arg { const double* v; const char* what; };
+static bool check_range_factor(const FactorSet& set, int k, std::initializer_list<Vec3Arg> vecs, const double* range, const double* info, const int32_t* kind, const double* delta)
+{
+	const std::string noun = set.noun;
+	for (int i = 0; i < 3; i++)
+		for (const Vec3Arg& a : vecs)
+			if (a.v && !std::isfinite(a.v[3 * (size_t)k + i])) throw ArgError{ "non-finite " + noun + " " + a.what };
+	if (!std::isfinite(range[k])) throw ArgError{ "non-finite " + noun + " range" };
+	if (range[k] < 0) throw ArgError{ "negative " + noun + " range" };
+	if (!std::isfinite(info[k])) throw ArgError{ "non-finite " + noun + " information" };
+	if (info[k] < 0) throw ArgError{ "negative " + noun + " information" };
+	if (!kind) return false;
+	check_factor_kernel(kind[k], delta[k], set.noun);
+	return kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE;
+}
+
 // a caller's set of range factors, factor by factor (the scalar kind's counterpart of take_factors3): the pose index within [0, limit), the
-// anchor, the lever arm (where given; zero otherwise) and the range finite, the range and the information not negative (0: no factor), the
-// kernel a known one.  a: {anchor, range} (width 4), b: the arm.  kind / delta as take_factors3
+// rest by check_range_factor.  a: {anchor, range} (width 4), b: the arm (zero where none is given).  kind / delta as take_factors3
 static TakenFactors take_range_factors(const FactorSet& set, int n, const int32_t* pose, int limit, const double* anchor, const double* range, const double* arm,
 	const double* info, const int32_t* kind, const double* delta)
 {
@@ -1131,25 +1126,14 @@ static TakenFactors take_range_factors(const FactorSet& set, int n, const int32_
 	{
 		if (pose[k] < 0 || pose[k] >= limit) throw ArgError{ noun + ": pose index out of range" };
 		v.idx[k] = pose[k];
+		any = check_range_factor(set, k, { { anchor, "anchor" }, { arm, "lever arm" } }, range, info, kind, delta) || any;
 		for (int i = 0; i < 3; i++)
 		{
-			if (!std::isfinite(anchor[3 * (size_t)k + i])) throw ArgError{ "non-finite " + noun + " anchor" };
 			v.a[4 * (size_t)k + i] = anchor[3 * (size_t)k + i];
-			if (!arm) continue;
-			if (!std::isfinite(arm[3 * (size_t)k + i])) throw ArgError{ "non-finite " + noun + " lever arm" };
-			v.b[3 * (size_t)k + i] = arm[3 * (size_t)k + i];
+			if (arm) v.b[3 * (size_t)k + i] = arm[3 * (size_t)k + i];
 		}
-		if (!std::isfinite(range[k])) throw ArgError{ "non-finite " + noun + " range" };
-		if (range[k] < 0) throw ArgError{ "negative " + noun + " range" };
 		v.a[4 * (size_t)k + 3] = range[k];
-		if (!std::isfinite(info[k])) throw ArgError{ "non-finite " + noun + " information" };
-		if (info[k] < 0) throw ArgError{ "negative " + noun + " information" };
 		v.info[k] = info[k];
-		if (kind)
-		{
-			check_factor_kernel(kind[k], delta[k], set.noun);
-			any = any || kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE;
-		}
 	}
 	if (any) { v.kind.assign(kind, kind + n); v.delta.assign(delta, delta + n); }
 	return v;
@@ -1168,40 +1152,23 @@ void cuba_hip_solver::setPoseRangeFactors(int n, const int32_t* pi, const int32_
 	const int32_t* kind, const double* delta)
 {
 	check_factor_call(*this, prngSet, n, pi && pj && range && info, kind, delta, "reprojection edges");
-	const std::string noun = prngSet.noun;
 	std::vector<int> vi((size_t)n), vj((size_t)n), vk;
 	std::vector<double> vai((size_t)3 * n, 0.0), vaj((size_t)3 * n, 0.0), vr((size_t)n), vinfo((size_t)n), vd;
 	bool any = false;
 	for (int k = 0; k < n; k++)
 	{
-		if (pi[k] < 0 || pi[k] >= Pt || pj[k] < 0 || pj[k] >= Pt) throw ArgError{ noun + ": pose index out of range" };
-		if (pi[k] == pj[k]) throw ArgError{ noun + " between a pose and itself" };
+		check_pose_pair(pi[k], pj[k], Pt, prngSet.noun);
 		vi[k] = pi[k]; vj[k] = pj[k];
+		any = check_range_factor(prngSet, k, { { armI, "lever arm" }, { armJ, "lever arm" } }, range, info, kind, delta) || any;
 		for (size_t x = 3 * (size_t)k; x < 3 * (size_t)k + 3; x++)
 		{
-			if ((armI && !std::isfinite(armI[x])) || (armJ && !std::isfinite(armJ[x]))) throw ArgError{ "non-finite " + noun + " lever arm" };
 			if (armI) vai[x] = armI[x];
 			if (armJ) vaj[x] = armJ[x];
 		}
-		if (!std::isfinite(range[k])) throw ArgError{ "non-finite " + noun + " range" };
-		if (range[k] < 0) throw ArgError{ "negative " + noun + " range" };
-		vr[k] = range[k];
-		if (!std::isfinite(info[k])) throw ArgError{ "non-finite " + noun + " information" };
-		if (info[k] < 0) throw ArgError{ "negative " + noun + " information" };
-		vinfo[k] = info[k];
-		if (kind)
-		{
-			check_factor_kernel(kind[k], delta[k], prngSet.noun);
-			any = any || kind[k] != cubahip::POSE_FACTOR_KERNEL_NONE;
-		}
+		vr[k] = range[k]; vinfo[k] = info[k];
 	}
 	if (any) { vk.assign(kind, kind + n); vd.assign(delta, delta + n); }
-	prngSet.pi.swap(vi); prngSet.pj.swap(vj); prngSet.ai.swap(vai); prngSet.aj.swap(vaj); prngSet.range.swap(vr); prngSet.info.swap(vinfo);
-	prngSet.kind.swap(vk); prngSet.delta.swap(vd);
-	collectBinaryPairs();
-	forget_factor_memories(*this, prngSet);
-	pf.prng = DevicePoseRanges();
-	covBlocksValid = false;          // (the covariance blocks describe the factors -- and the block pattern -- they were computed on)
+	adopt_binary_pose_factors(*this, prngSet, vi, vj, { &vai, &vaj, &vr, &vinfo }, vk, vd);
 }
 
 std::vector<uint64_t> cuba_hip_solver::relSeedKeys() const
@@ -1223,35 +1190,6 @@ static void sort_factors(FactorSet& set, const std::vector<uint64_t>& key)
 	set.order.resize(key.size());
 	std::iota(set.order.begin(), set.order.end(), 0);
 	std::stable_sort(set.order.begin(), set.order.end(), [&](int a, int b) { return key[a] < key[b]; });
-}
-
-// the edges' index arrays (`ints`, laid out by the caller) and their values q | t | information in the sorted order -> device; the device
-// pointers of the values and of the per-factor chi2 come back through q, t, info, chi.  A set with robust kernels: their kinds follow the
-// index arrays, their deltas the values, by the same permutation (rk_kind, rk_delta; null without)
-static void upload_factor_arrays(cuba_hip_solver& s, RelPoseSet& set, std::vector<int> ints, const Scalar*& q, const Scalar*& t, const Scalar*& info, Scalar*& chi,
-	const int*& rk_kind, const Scalar*& rk_delta)
-{
-	const size_t n = set.order.size();
-	const bool robust = !set.kind.empty();
-	const size_t nInts = ints.size();
-	std::vector<Scalar> vals((robust ? 44 : 43) * n);
-	Scalar* vq = vals.data(); Scalar* vt = vq + 4 * n; Scalar* vi = vt + 3 * n;
-	for (size_t p = 0; p < n; p++)
-	{
-		const size_t k = (size_t)set.order[p];
-		for (int i = 0; i < 4; i++) vq[4 * p + i] = (Scalar)set.q[4 * k + i];
-		for (int i = 0; i < 3; i++) vt[3 * p + i] = (Scalar)set.t[3 * k + i];
-		for (int i = 0; i < 36; i++) vi[36 * p + i] = (Scalar)set.info[36 * k + i];
-		if (robust) { ints.push_back(set.kind[k]); vi[36 * n + p] = (Scalar)set.delta[k]; }
-	}
-	set.d_ints.upload(ints, s.stream);
-	set.d_vals.upload(vals, s.stream);
-	set.d_chi.resize(std::max(n, (size_t)1));
-	q = set.d_vals.data(); t = q + 4 * n; info = t + 3 * n;
-	chi = set.d_chi.data();
-	rk_kind = robust ? set.d_ints.data() + nInts : nullptr; rk_delta = robust ? info + 36 * n : nullptr;
-	s.sync();          // (the staging vectors go out of scope)
-	set.uploaded = true;
 }
 
 static std::vector<int> concat(std::initializer_list<const std::vector<int>*> parts)
@@ -1306,9 +1244,9 @@ void UnaryPoseFactorSet::upload(cuba_hip_solver& s)
 	uploaded = true;
 }
 
-// the caller's edges -> device, in the internal pose order: free-free edges first, stable by the block (min, max) of the internal pair -- a
-// block's edges contiguous and in the caller's order --, then the edges with one fixed end, then (inactive) those with two
-// (shared by the two binary kinds: sets set.order; blkKey: the (min << 32 | max) key of every block of blkId, ascending)
+// a binary kind's factors in the internal pose order: free-free factors first, stable by the block (min, max) of the internal pair -- a
+// block's factors contiguous and in the caller's order --, then the factors with one fixed end, then (inactive) those with two
+// (sets set.order; blkKey: the (min << 32 | max) key of every block of blkId, ascending)
 struct BinaryLayout { std::vector<int> si, sj, blkPtr, blkId, posePtr, poseId, poseItem; std::vector<uint64_t> blkKey; int nActive = 0; };
 static BinaryLayout sort_binary_factors(cuba_hip_solver& s, FactorSet& set, const std::vector<int>& pi, const std::vector<int>& pj)
 {
@@ -1363,70 +1301,53 @@ static BinaryLayout sort_binary_factors(cuba_hip_solver& s, FactorSet& set, cons
 	return lay;
 }
 
-void RelPoseSet::upload(cuba_hip_solver& s)
-{
-	RelPoseSet& set = *this;
-	const int n = set.n();
-	const BinaryLayout lay = sort_binary_factors(s, set, set.pi, set.pj);
-	const int nActive = lay.nActive, nb = (int)lay.blkId.size(), np = (int)lay.poseId.size();
-	DeviceRelPoses rp;
-	upload_factor_arrays(s, set, concat({ &lay.si, &lay.sj, &lay.blkPtr, &lay.blkId, &lay.posePtr, &lay.poseId, &lay.poseItem }), rp.q, rp.t, rp.info, rp.chi, rp.rk_kind,
-		rp.rk_delta);
-	s.d_relRec.resize((size_t)cubahip::REL_REC * std::max(n, 1));
-	rp.n = n; rp.nActive = nActive; rp.nBlocks = nb; rp.nPoses = np;
-	rp.pose_i = set.d_ints.data(); rp.pose_j = rp.pose_i + n;
-	rp.blk_ptr = rp.pose_j + n; rp.blk_id = rp.blk_ptr + (nb + 1);
-	rp.pose_ptr = rp.blk_id + nb; rp.pose_id = rp.pose_ptr + (np + 1); rp.pose_item = rp.pose_id + np;
-	rp.rec = s.d_relRec.data();
-	s.pf.rel = rp;
-	set.structure = s.cntStructureBuilds;
-}
-
-// the caller's range factors between two poses -> device, sorted as the relative-pose edges.  blk_rel: the blocks that the relative-pose
-// edges' gather writes too (it stores a block without Schur products, so this kind's gather, which runs behind it, adds there) -- this
-// device copy depends on the structure AND on the relative-pose set: setRelativePoseEdges marks it due again.
-// ints: pose_i [n] | pose_j [n] | blk_ptr [nb + 1] | blk_id [nb] | blk_rel [nb] | pose_ptr [np + 1] | pose_id [np] | pose_item | kind [n, robust]
-// values: arm_i [3 n] | arm_j [3 n] | range [n] | info [n] | delta [n, robust]
-void PoseRangeSet::upload(cuba_hip_solver& s)
+// a binary kind's factors -> device, sorted by sort_binary_factors.  blk_shared: the blocks that the gather of a binary kind launched
+// EARLIER writes too (binarySets is in launch order; that gather stores a block without Schur products, so this kind's adds there) -- the
+// device copy depends on the structure AND on the earlier binary sets: their setters mark it due again.  The same layout for the kinds:
+// ints: pose_i [n] | pose_j [n] | blk_ptr [nb + 1] | blk_id [nb] | blk_shared [nb] | pose_ptr [np + 1] | pose_id [np] | pose_item | kind [n, robust]
+// values: the kind's arrays in the order of vals, [width n] each, the information last | delta [n, robust]
+void BinaryPoseFactorSet::upload(cuba_hip_solver& s)
 {
 	const size_t N = (size_t)n();
 	const bool robust = !kind.empty();
 	const BinaryLayout lay = sort_binary_factors(s, *this, pi, pj);
-	std::vector<uint64_t> relKeys;
-	for (int k = 0; k < s.relSet.n(); k++)
+	std::vector<uint64_t> earlier;
+	for (const BinaryPoseFactorSet* set : s.binarySets)
 	{
-		const int a = s.internalPose(s.relSet.pi[k]), b = s.internalPose(s.relSet.pj[k]);
-		if (a < s.Pf && b < s.Pf) relKeys.push_back(((uint64_t)(uint32_t)std::min(a, b) << 32) | (uint32_t)std::max(a, b));
+		if (set == this) break;
+		for (int k = 0; k < set->n(); k++)
+		{
+			const int a = s.internalPose(set->pi[k]), b = s.internalPose(set->pj[k]);
+			if (a < s.Pf && b < s.Pf) earlier.push_back(((uint64_t)(uint32_t)std::min(a, b) << 32) | (uint32_t)std::max(a, b));
+		}
 	}
-	std::sort(relKeys.begin(), relKeys.end());
+	std::sort(earlier.begin(), earlier.end());
 	const int nb = (int)lay.blkId.size(), np = (int)lay.poseId.size();
-	std::vector<int> blkRel((size_t)nb);
-	for (int b = 0; b < nb; b++) blkRel[b] = std::binary_search(relKeys.begin(), relKeys.end(), lay.blkKey[b]) ? 1 : 0;
-	std::vector<int> ints = concat({ &lay.si, &lay.sj, &lay.blkPtr, &lay.blkId, &blkRel, &lay.posePtr, &lay.poseId, &lay.poseItem });
+	std::vector<int> blkShared((size_t)nb);
+	for (int b = 0; b < nb; b++) blkShared[b] = std::binary_search(earlier.begin(), earlier.end(), lay.blkKey[b]) ? 1 : 0;
+	std::vector<int> ints = concat({ &lay.si, &lay.sj, &lay.blkPtr, &lay.blkId, &blkShared, &lay.posePtr, &lay.poseId, &lay.poseItem });
 	const size_t nInts = ints.size();
-	std::vector<Scalar> vals((robust ? 9 : 8) * N);
-	Scalar* vai = vals.data(); Scalar* vaj = vai + 3 * N; Scalar* vr = vaj + 3 * N; Scalar* vi = vr + N;
-	for (size_t p = 0; p < N; p++)
-	{
-		const size_t k = (size_t)order[p];
-		for (int i = 0; i < 3; i++) { vai[3 * p + i] = (Scalar)ai[3 * k + i]; vaj[3 * p + i] = (Scalar)aj[3 * k + i]; }
-		vr[p] = (Scalar)range[k]; vi[p] = (Scalar)info[k];
-		if (robust) { ints.push_back(kind[k]); vi[N + p] = (Scalar)delta[k]; }
-	}
+	size_t width = 0;
+	for (const Values& v : vals) width += (size_t)v.width;
+	std::vector<Scalar> staged((width + (robust ? 1 : 0)) * N);
+	Scalar* out = staged.data();
+	for (const Values& v : vals)
+		for (size_t p = 0; p < N; p++)
+			for (int i = 0; i < v.width; i++) *out++ = (Scalar)v.host[(size_t)v.width * order[p] + i];
+	for (size_t p = 0; robust && p < N; p++) { ints.push_back(kind[order[p]]); *out++ = (Scalar)delta[order[p]]; }
 	d_ints.upload(ints, s.stream);
-	d_vals.upload(vals, s.stream);
+	d_vals.upload(staged, s.stream);
 	d_chi.resize(std::max(N, (size_t)1));
-	d_rec.resize((size_t)cubahip::PRNG_REC * std::max(N, (size_t)1));
+	d_rec.resize((size_t)recSize * std::max(N, (size_t)1));
 	s.sync();          // (the staging vectors go out of scope)
-	DevicePoseRanges pr;
-	pr.n = (int)N; pr.nActive = lay.nActive; pr.nBlocks = nb; pr.nPoses = np;
-	pr.pose_i = d_ints.data(); pr.pose_j = pr.pose_i + N;
-	pr.blk_ptr = pr.pose_j + N; pr.blk_id = pr.blk_ptr + (nb + 1); pr.blk_rel = pr.blk_id + nb;
-	pr.pose_ptr = pr.blk_rel + nb; pr.pose_id = pr.pose_ptr + (np + 1); pr.pose_item = pr.pose_id + np;
-	pr.arm_i = d_vals.data(); pr.arm_j = pr.arm_i + 3 * N; pr.range = pr.arm_j + 3 * N; pr.info = pr.range + N;
-	pr.rec = d_rec.data(); pr.chi = d_chi.data();
-	pr.rk_kind = robust ? d_ints.data() + nInts : nullptr; pr.rk_delta = robust ? pr.info + N : nullptr;
-	s.pf.prng = pr;
+	dev.n = (int)N; dev.nActive = lay.nActive; dev.nBlocks = nb; dev.nPoses = np;
+	dev.pose_i = d_ints.data(); dev.pose_j = dev.pose_i + N;
+	dev.blk_ptr = dev.pose_j + N; dev.blk_id = dev.blk_ptr + (nb + 1); dev.blk_shared = dev.blk_id + nb;
+	dev.pose_ptr = dev.blk_shared + nb; dev.pose_id = dev.pose_ptr + (np + 1); dev.pose_item = dev.pose_id + np;
+	const Scalar* d = d_vals.data();
+	for (const Values& v : vals) { v.dev = d; d += (size_t)v.width * N; }
+	dev.rec = d_rec.data(); dev.chi = d_chi.data();
+	dev.rk_kind = robust ? d_ints.data() + nInts : nullptr; dev.rk_delta = robust ? d : nullptr;
 	uploaded = true; structure = s.cntStructureBuilds;
 }
 

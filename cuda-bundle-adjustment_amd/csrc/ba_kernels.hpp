@@ -169,37 +169,14 @@ struct DeviceDirectionFactors : DevicePoseGroups { const Scalar *d = nullptr, *m
 // (info: the scalar 1 / sigma^2).  At a computed distance of exactly 0 the direction is undefined: the factor then has J = 0 (ba_factor.hip)
 struct DeviceRangeFactors : DevicePoseGroups { const Scalar *br = nullptr, *arm = nullptr; };    // [4 n] {anchor, measured range}, [3 n] lever arms
 
-// SE(3) relative-pose edges (ba_factor.hip): rho(r^T Omega r), r = log(T_j T_i^-1 Zbar^-1), between two poses.  Sorted: the edges between two
-// free poses first, stable by the block (min, max) of the internal pose pair (a block's edges contiguous, in the caller's order), then the
-// edges with one fixed end (they act on the free end only), then those with two (ignored).
-constexpr int REL_REC = 90;        // numbers of an edge's linearisation record (layout: ba_factor.hip)
-struct DeviceRelPoses
-{
-	int n = 0;                     // edges
-	int nActive = 0;               // the first nActive have a free end
-	int nBlocks = 0;               // off-diagonal blocks of hsc with such edges
-	int nPoses = 0;                // free poses with such edges
-	const int *pose_i = nullptr, *pose_j = nullptr;   // [n] internal poses of every edge (>= Pf: a fixed pose)
-	const int* blk_ptr = nullptr;  // [nBlocks + 1] range of every such block in the sorted list
-	const int* blk_id = nullptr;   // [nBlocks] its block of hsc
-	const int* pose_ptr = nullptr; // [nPoses + 1] range of every such pose in pose_item
-	const int* pose_id = nullptr;  // [nPoses] its internal pose index
-	const int* pose_item = nullptr;// the pose's edges in the caller's order: 2 * sorted edge + (0: the pose is the edge's i, 1: its j)
-	const Scalar *q = nullptr, *t = nullptr;          // [4 n] unit quaternions, [3 n]: the measurements Zbar
-	const Scalar* info = nullptr;  // [36 n] column-major
-	Scalar* rec = nullptr;         // [REL_REC n] linearisation records, number-major (number el of edge k at el n + k)
-	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 with both ends fixed)
-	const int* rk_kind = nullptr;  // [n] robust kernel of every edge, sorted as the values; null: no edge has one (the kernels' ROBUST = false)
-	const Scalar* rk_delta = nullptr;   // [n]
-};
-
-// Range factors between two poses (peer UWB, odometer distances, rig baselines; ba_factor.hip): rho(Omega r^2), r = |u| - rbar with
-// u = a_j - (R_j w_i + t_j), w_i = R_i^T (a_i - t_i): the distance of the point a_i of camera frame i from the point a_j of camera frame j
-// against a measured range; info the scalar 1 / sigma^2.  The first binary kind with a low-rank term: J_i and J_j are 1 x 6 each.  Sorted as
-// the relative-pose edges: the factors between two free poses first, stable by the block (min, max) of the internal pose pair, then those
-// with one fixed end (they act on the free end only), then those with two (ignored).  At a computed distance of exactly 0 both J are 0.
-constexpr int PRNG_REC = 14;       // numbers of a factor's linearisation record: J_i [6] | J_j [6] | w Omega | w Omega r
-struct DevicePoseRanges
+// The binary kinds of factor on the poses (ba_factor.hip) -- SE(3) relative-pose edges and range factors between two poses -- share their
+// device layout and everything that works on it but the linearisation of a factor.  Sorted: the factors between two free poses first, stable
+// by the block (min, max) of the internal pose pair (a block's factors contiguous, in the caller's order), then the factors with one fixed
+// end (they act on the free end only), then those with two (ignored).  A kind adds its measurement arrays and the layout of its record.
+// Every free-free pair owns an off-diagonal block of hsc; the kinds' gathers run one behind the other (launch_pose_factor_linearize), and a
+// block without Schur products is cleared by no one, so the first gather to reach such a block STORES its sum and every later one adds:
+// blk_shared says per block whether a binary kind launched earlier writes it too (all zero for the kind launched first).
+struct DevicePosePairs
 {
 	int n = 0;                     // factors
 	int nActive = 0;               // the first nActive have a free end
@@ -208,17 +185,27 @@ struct DevicePoseRanges
 	const int *pose_i = nullptr, *pose_j = nullptr;   // [n] internal poses of every factor (>= Pf: a fixed pose)
 	const int* blk_ptr = nullptr;  // [nBlocks + 1] range of every such block in the sorted list
 	const int* blk_id = nullptr;   // [nBlocks] its block of hsc
-	const int* blk_rel = nullptr;  // [nBlocks] 1: the block has a relative-pose edge too (relpose_gather_kernel wrote it in this linearisation)
+	const int* blk_shared = nullptr;    // [nBlocks] 1: the gather of a binary kind launched earlier wrote the block in this linearisation
 	const int* pose_ptr = nullptr; // [nPoses + 1] range of every such pose in pose_item
 	const int* pose_id = nullptr;  // [nPoses] its internal pose index
 	const int* pose_item = nullptr;// the pose's factors in the caller's order: 2 * sorted factor + (0: the pose is the factor's i, 1: its j)
-	const Scalar *arm_i = nullptr, *arm_j = nullptr;  // [3 n] lever arms in the two camera frames
-	const Scalar* range = nullptr; // [n] measured distances
-	const Scalar* info = nullptr;  // [n]
-	Scalar* rec = nullptr;         // [PRNG_REC n] linearisation records, number-major (number el of factor k at el n + k)
-	Scalar* chi = nullptr;         // [n] Omega r^2 of the last chi2 launch (0 with both ends fixed)
+	const Scalar* info = nullptr;  // [D D n] column-major, D the dimension of r
+	Scalar* rec = nullptr;         // [record size x n] linearisation records, number-major (number el of factor k at el n + k)
+	Scalar* chi = nullptr;         // [n] r^T Omega r of the last chi2 launch (0 with both ends fixed)
 	const int* rk_kind = nullptr;  // [n] robust kernel of every factor, sorted as the values; null: no factor has one (the kernels' ROBUST = false)
 	const Scalar* rk_delta = nullptr;   // [n]
+};
+// SE(3) relative-pose edges: r = log(T_j T_i^-1 Zbar^-1), D = 6
+constexpr int REL_REC = 90;        // numbers of an edge's linearisation record (layout: ba_factor.hip)
+struct DeviceRelPoses : DevicePosePairs { const Scalar *q = nullptr, *t = nullptr; };       // [4 n] unit quaternions, [3 n]: the measurements Zbar
+// Range factors between two poses (peer UWB, odometer distances, rig baselines): r = |u| - rbar with u = a_j - (R_j w_i + t_j),
+// w_i = R_i^T (a_i - t_i): the distance of the point a_i of camera frame i from the point a_j of camera frame j against a measured range,
+// D = 1 (info: the scalar 1 / sigma^2).  A low-rank term: J_i and J_j are 1 x 6 each.  At a computed distance of exactly 0 both J are 0.
+constexpr int PRNG_REC = 14;       // numbers of a factor's linearisation record: J_i [6] | J_j [6] | w Omega | w Omega r
+struct DevicePoseRanges : DevicePosePairs
+{
+	const Scalar *arm_i = nullptr, *arm_j = nullptr;  // [3 n] lever arms in the two camera frames
+	const Scalar* range = nullptr; // [n] measured distances
 };
 
 // Landmark position priors (ba_factor.hip): rho(r^T Omega r), r = X - Xbar, Omega a symmetric 3 x 3 information.  Sorted by internal landmark
@@ -247,15 +234,20 @@ struct DeviceFactors
 	DevicePoseRanges prng;
 	template <class F> void each(F&& f) const { f(priors); f(rel); f(lmp); f(pos); f(dir); f(rng); f(prng); }      // every kind's device struct, in that order
 };
-// behind the Schur pass, the priors first (Omega: w Omega of a factor with a robust kernel): J^T Omega J into the diagonal blocks of hsc (upper triangle), -J^T Omega r into bp and (mode 1)
-// bsc, J = J_l(r)^-1; then the position factors the same way in a launch of their own, J = [R^T [a]x | -R^T]; then the edges in two
-// launches: per-edge records, then their sums into hsc (diagonal blocks: upper triangle; mode 1: the off-diagonal blocks of the pairs,
-// stored whole where a block has no Schur products), bp and (mode 1) bsc; then the direction factors in a launch of their own, J =
-// [-[R d]x | 0]: the rotation 3 x 3 of the diagonal block and the first three entries of bp / bsc only; then the range factors in a launch
-// of their own, J = [(m x a)^T | -m^T] (1 x 6, m the unit vector from the anchor to the antenna in the camera frame); last the range factors
-// between two poses in two launches as the edges: per-factor records {J_i, J_j, w Omega, w Omega r}, then their sums into hsc (mode 1: the
-// off-diagonal blocks of the pairs, stored whole where a block has neither Schur products nor a relative-pose edge), bp and (mode 1) bsc.
-// All six add to the same diagonal blocks: the order of the launches is part of the result
+// The factors' linearisation behind the Schur pass, every kind in launches of its own in one stream.  THE ORDER (it exists here only):
+//   1. pose priors            J = J_l(r)^-1 (6 x 6)
+//   2. position factors       J = [R^T [a]x | -R^T] (3 x 6)
+//   3. relative-pose edges    per-edge records, then their gather
+//   4. direction factors      J = [-[R d]x | 0] (3 x 6): the rotation 3 x 3 of the diagonal block and the first three entries of bp / bsc only
+//   5. range factors          J = [(m x a)^T | -m^T] (1 x 6, m the unit vector from the anchor to the antenna in the camera frame)
+//   6. range factors between two poses    per-factor records {J_i, J_j, w Omega, w Omega r}, then their gather
+// A unary kind adds J^T Omega J to the diagonal block of its pose in hsc (upper triangle) and -J^T Omega r to bp and (mode 1) bsc, Omega: w Omega
+// of a factor with a robust kernel.  A binary kind's gather adds the same for either end and (mode 1) its cross terms to the pairs'
+// off-diagonal blocks -- stored whole where a block has neither Schur products nor an earlier binary kind (DevicePosePairs: blk_shared).
+// All six kinds on the poses (the seventh, the landmark priors, is the landmark pass's) add to the same diagonal blocks, bp and bsc by read-modify-write, and floating-point sums do not
+// commute: the order of the launches is part of the result, a handle's bits depend on it.  THE RULE: a new kind goes BEHIND the ones a
+// handle may already combine, never between two of them.  (The position factors sit between the priors and the edges because no handle
+// could hold them before they came, so no existing sum changed; every kind since went last.)
 void launch_pose_factor_linearize(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const DeviceFactors& pf, int mode, hipStream_t s);
 // per-factor chi2 (the plain r^T Omega r) into every kind's chi, per-workgroup partial sums of rho(chi2) into
 // parts[0 .. factor_chi2_parts(&pf)), kind behind kind in the order of FACTOR_*.  only >= 0: that kind alone, its partials at parts[0]

@@ -163,24 +163,22 @@ struct UnaryPoseFactorSet : FactorSet
 	void clear() override { pose.clear(); a.clear(); b.clear(); info.clear(); FactorSet::clear(); }
 	void upload(cuba_hip_solver& s) override;
 };
-// relative-pose edges; kind / delta empty: no edge has a kernel
-struct RelPoseSet : FactorSet
+// the binary kinds on the poses -- relative-pose edges (q, t, information: widths 4, 3, 36; a record of REL_REC numbers), range factors
+// between two poses (lever arms i and j -- zero where the caller gave none --, measured distance, scalar information: 3, 3, 1, 1; PRNG_REC)
+// --: kind / delta empty: no factor has a kernel.  vals: the kind's value arrays in the order of the device copy, the information last, each
+// with its width and its pointer in the kind's device struct; dev: the part of that struct that the kinds share; d_rec: the linearisation records
+struct BinaryPoseFactorSet : FactorSet
 {
-	std::vector<int> pi, pj; std::vector<double> q, t, info;     // [n], [n], [4 n], [3 n], [36 n]
-	RelPoseSet() : FactorSet("relative-pose edge", "relative-pose edges", true) {}
-	int n() const override { return (int)pi.size(); }
-	void clear() override { pi.clear(); pj.clear(); q.clear(); t.clear(); info.clear(); FactorSet::clear(); }
-	void upload(cuba_hip_solver& s) override;
-};
-// range factors between two poses: lever arms (zero where the caller gave none), measured distance, scalar information; kind / delta empty:
-// no factor has a kernel.  d_rec: the linearisation records
-struct PoseRangeSet : FactorSet
-{
-	std::vector<int> pi, pj; std::vector<double> ai, aj, range, info;      // [n], [n], [3 n], [3 n], [n], [n]
+	struct Values { int width; const Scalar*& dev; std::vector<double> host; };
+	const int recSize;
+	DevicePosePairs& dev;
+	std::vector<Values> vals;
+	std::vector<int> pi, pj;         // [n] the two poses of every factor
 	DevBuf<Scalar> d_rec;
-	PoseRangeSet() : FactorSet("pose-range factor", "pose-range factors", true) {}
+	BinaryPoseFactorSet(const char* noun, const char* plural, int recSize, DevicePosePairs& dev, std::initializer_list<Values> vals)
+		: FactorSet(noun, plural, true), recSize(recSize), dev(dev), vals(vals) {}
 	int n() const override { return (int)pi.size(); }
-	void clear() override { pi.clear(); pj.clear(); ai.clear(); aj.clear(); range.clear(); info.clear(); FactorSet::clear(); }
+	void clear() override { pi.clear(); pj.clear(); for (Values& v : vals) v.host.clear(); FactorSet::clear(); }
 	void upload(cuba_hip_solver& s) override;
 };
 // landmark position priors: the information as its symmetrised upper triangle, every prior with a kernel (kind 0, delta 1: none)
@@ -639,21 +637,25 @@ struct cuba_hip_solver
 	// The factors besides the reprojection edges (ba_factor.hip): seven kinds, each a set kept as the caller gave it, in the caller's numbering
 	// (quaternions normalised, information symmetrised), with a device copy (pf) in the internal order that need() makes -- uploadFactors():
 	// once that order is known, again when it changes (the unary kinds on the poses: with the pose order; the two binary kinds, whose
-	// blocks are looked up in the pattern, and the landmark priors: with every structure; the range factors between poses also with the
-	// relative-pose set), and again after a setter or
+	// blocks are looked up in the pattern, and the landmark priors: with every structure; a binary kind also with the sets of
+	// the binary kinds launched before it), and again after a setter or
 	// cuba_hip_set_pose_factor_robust_kernels, whose kinds and deltas travel with the values.  The landmark pass linearises the landmark
 	// priors -- linearize() hands pf.lmp to it --, the chi2 sums take them as one more kind.
 	// No factors of any kind: factors() is null, nothing of it is launched, no extra seed enters the pattern build, and every launch and kernel argument is as
 	// without this feature.
 	DeviceFactors pf;
 	UnaryPoseFactorSet priorSet{ "prior", "pose priors", 4, 3, 36, pf.priors, pf.priors.qbar, pf.priors.tbar };
-	RelPoseSet relSet;
+	BinaryPoseFactorSet relSet{ "relative-pose edge", "relative-pose edges", REL_REC, pf.rel, { { 4, pf.rel.q, {} }, { 3, pf.rel.t, {} }, { 36, pf.rel.info, {} } } };
 	LandmarkPriorSet lmPriorSet;
 	UnaryPoseFactorSet posSet{ "position factor", "position factors", 3, 3, 9, pf.pos, pf.pos.z, pf.pos.arm };
 	UnaryPoseFactorSet dirSet{ "direction factor", "direction factors", 3, 3, 9, pf.dir, pf.dir.d, pf.dir.m };
 	UnaryPoseFactorSet rngSet{ "range factor", "range factors", 4, 3, 1, pf.rng, pf.rng.br, pf.rng.arm };
-	PoseRangeSet prngSet;
+	BinaryPoseFactorSet prngSet{ "pose-range factor", "pose-range factors", PRNG_REC, pf.prng,
+		{ { 3, pf.prng.arm_i, {} }, { 3, pf.prng.arm_j, {} }, { 1, pf.prng.range, {} }, { 1, pf.prng.info, {} } } };
 	FactorSet* const factorSets[FACTOR_KINDS] = { &priorSet, &relSet, &lmPriorSet, &posSet, &dirSet, &rngSet, &prngSet };      // in the order of FACTOR_* (ba_kernels.hpp)
+	// the binary kinds in the order of their launches (launch_pose_factor_linearize): a kind's gather adds to the blocks that an earlier one
+	// stored, so a set's device copy depends on the pairs of the sets before it here
+	BinaryPoseFactorSet* const binarySets[2] = { &relSet, &prngSet };
 	const DeviceFactors* factors() const
 	{
 		for (const FactorSet* set : factorSets) if (set->n() > 0) return &pf;
@@ -682,7 +684,7 @@ struct cuba_hip_solver
 		const double* delta);
 	void setPoseRangeFactors(int n, const int32_t* pi, const int32_t* pj, const double* range, const double* armI, const double* armJ, const double* info,
 		const int32_t* kind, const double* delta);
-	void collectBinaryPairs();       // h_relPairs from the two binary kinds' sets
+	void collectBinaryPairs();       // h_relPairs from the binary kinds' sets (binarySets)
 	void factorChiSquares(int kind, double* out);      // r^T Omega r of every factor of the kind (FACTOR_*), in the caller's order
 	// the distinct free-free pairs of the two binary kinds, the relative-pose edges and the range factors between poses (their union; sorted
 	// keys i << 32 | j, i < j, caller's numbering) and the pairs the current structure was seeded
@@ -690,7 +692,7 @@ struct cuba_hip_solver
 	std::vector<uint64_t> h_relPairs, structRelPairs;
 	int64_t cntStructureBuilds = 0;      // structures published on this handle (never reset)
 	std::vector<uint64_t> h_relSeeds;    // the pairs as the last pattern build took them
-	DevBuf<int> d_relSeedFlag, d_relSeedScan; DevBuf<uint64_t> d_relSeeds; DevBuf<Scalar> d_relRec;
+	DevBuf<int> d_relSeedFlag, d_relSeedScan; DevBuf<uint64_t> d_relSeeds;
 	// the pairs as (row, column) keys of the pattern in the internal pose order, sorted
 	std::vector<uint64_t> relSeedKeys() const;
 

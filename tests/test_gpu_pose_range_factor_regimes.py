@@ -1,4 +1,4 @@
-"""The kernels of the range factors between two poses (csrc/ba_factor.hip: pose_range_linearize_kernel, pose_range_gather_kernel,
+"""The kernels of the range factors between two poses (csrc/ba_factor.hip: pose_range_linearize_kernel, pair_gather_kernel<DevicePoseRanges>,
 factor_chi2_kernel<DevicePoseRanges>) against the 60-digit reference recorded in tests/golden/pose_range_cases.npz
 (tests/golden/make_golden_pose_range_cases.py), by the method of tests/test_gpu_range_factor_regimes.py: relative rotations of 1e-8
 (nearly identical orientations), 1 and pi - 1e-6 and a negated quaternion x distances rho of 1e-9 ("near"), 1 ("unit") and 1e6 ("far")
