@@ -102,7 +102,7 @@ struct DeviceSystem
 	Scalar *rz = nullptr, *pq = nullptr;
 	int rzStride = 0, pqStride = 0;        // entries per ring slot
 	int nrz0 = 0, nrz = 0, npq = 0;        // number of partials in slot 0 / in the ring slots of rz (nrz0 <= nrz) / in pq slots
-	int* done = nullptr;                   // set once the stop test fails: later queued launches return at once
+	int* done = nullptr;                   // set once the solve is over (1: the stop test fired, 2: the iteration limit): later queued launches return at once
 	int* iters = nullptr;      // device iteration counter
 	int* host_flags = nullptr; // device-mapped host ints: {fail, iterations done, stop flag, ticket}, refreshed by the last node of every
 	                           // iteration graph and by launch_pcg_report

@@ -596,7 +596,7 @@ bool cuba_hip_solver::solveReducedOnce()
 		}
 		waitReport();
 		if (sc.hInts[0] != 0) return solveBrokeDown(sc);
-		if (sc.hInts[2] != 0 || sc.hInts[1] < std::min(k0, maxIter)) converged = true;   // the device-side stop test fired
+		if (sc.hInts[2] == 1 || sc.hInts[1] < std::min(k0, maxIter)) converged = true;   // the device-side stop test fired (2 = stopped at the iteration limit: pcg_raise_done)
 		target = k0 + ((looks == 0 && k0 <= 96) ? 4 : std::max(8, k0 / 8 / 4 * 4));   // (a batch sized from the run's own history misses by a few iterations at most)
 		looks++; cntPcgLooks++; cntHostLooks++;
 	}
@@ -914,6 +914,9 @@ static int cuba_hip_optimize_batch_full(cuba_hip_solver** hs, int n, int niter, 
 	auto upload = [&](int k, int m) { HIP_TRY(hipMemcpyAsync(const_cast<BatchEntry*>(dTab[k]), hTab[k], sizeof(BatchEntry) * m, hipMemcpyHostToDevice, bs)); };
 	for (int i = 0; i < n; i++) hs[i]->lmRunBegin(runs[i], niter, chi2 ? chi2 + (size_t)i * niter : nullptr);
 	const bool mixed = hs[0]->st.mixed != 0;
+	// the kernel class the call's handles agreed on.  A handle can leave it in the middle of the call (retryWithFp64Inverse drops the fp32
+	// copy of its coarse inverse for the rest of its run): from then on it solves alone, see phase B
+	const int cls0 = batch_kernel_class(lead->g, lead->sys);
 	std::vector<int> act;
 	std::vector<char> okv((size_t)n), inPcg((size_t)n);
 	int batchSolves = 0;
@@ -923,6 +926,7 @@ static int cuba_hip_optimize_batch_full(cuba_hip_solver** hs, int n, int niter, 
 		for (int i = 0; i < n; i++) if (hs[i]->lmBeforeTrial(runs[i])) act.push_back(i);
 		if (act.empty()) break;
 		const int m = (int)act.size();
+		lead->cntBatchFullTrials++;
 		// ---- phase A: linearise + Schur (the state backup rides in the landmark pass's launch)
 		unsigned lmMax = 0, schurMax = 0;
 		for (int a = 0; a < m; a++)
@@ -940,6 +944,7 @@ static int cuba_hip_optimize_batch_full(cuba_hip_solver** hs, int n, int niter, 
 		// ---- phase B: front half of the reduced solves
 		unsigned setupMax = 0; int gridSpmvMax = 0, ncMax = 0; size_t ldsMax = 0; int target = 4, budgetMax = 0, nPcg = 0, nFused = 0;
 		Scalar tol2 = 0;
+		const cuba_hip_solver* kh = nullptr;      // the first graph in the PCG: the batched kernels are chosen from it (every graph in the PCG is of class cls0)
 		for (int a = 0; a < m; a++)
 		{
 			const int i = act[a];
@@ -947,10 +952,19 @@ static int cuba_hip_optimize_batch_full(cuba_hip_solver** hs, int n, int niter, 
 			ctx[i] = cuba_hip_solver::SolveCtx(); ctx[i].batched = true; ctx[i].deferCoarse = &coarseJobs; ctx[i].deferLaunch = true;
 			BatchEntry& e = hTab[1][a];
 			e = BatchEntry();
+			if (batch_kernel_class(h->g, h->sys) != cls0)
+			{
+				// the graph has left the batch's kernel class (its coarse inverse is stored in fp64 now: the instantiation the others run would
+				// read the wrong buffer): it solves alone, on the common stream, and sits the batched launches out (gridSpmv = 0, no set-up grid)
+				okv[i] = h->solveReduced(); inPcg[i] = 0;
+				e.g = h->g; e.st = h->st; e.sys = h->sys;
+				continue;
+			}
 			const bool finished = h->solveBegin(ctx[i]);
 			e.g = h->g; e.st = h->st; e.sys = h->sys;
 			if (finished) { okv[i] = ctx[i].result; inPcg[i] = 0; continue; }      // (an exact solve at once: the graph sits the batched launches out)
 			inPcg[i] = 1; nPcg++;
+			if (!kh) kh = h;
 			tol2 = ctx[i].tol2;
 			e.maxIter = ctx[i].maxIter;
 			e.gridSpmv = (h->g.Pf + h->sys.spmv_rows - 1) / h->sys.spmv_rows;
@@ -965,7 +979,7 @@ static int cuba_hip_optimize_batch_full(cuba_hip_solver** hs, int n, int niter, 
 			if (nFused > 0) launch_batch_setup(dTab[1], m, setupMax, bs);
 			HIP_TRY(hipEventRecord(lead->evSetup, bs));
 			lead->launchCoarseJobs(coarseJobs, lead->evSetup);
-			if (nFused > 0) launch_batch_first_precond(dTab[1], m, lead->sys, ncMax, ldsMax, tol2, bs);
+			if (nFused > 0) launch_batch_first_precond(dTab[1], m, kh->sys, ncMax, ldsMax, tol2, bs);
 			// ---- the iterations of all graphs
 			int k0 = 0, looks = 0;
 			std::vector<char> conv((size_t)n, 0), broke((size_t)n, 0);
@@ -976,7 +990,7 @@ static int cuba_hip_optimize_batch_full(cuba_hip_solver** hs, int n, int niter, 
 				while (todo > 0)
 				{
 					const int c = todo;
-					for (int k = 0; k < c; k++) launch_pcg_batch_iteration(dTab[1], m, lead->g, lead->sys, gridSpmvMax, ncMax, ldsMax, k, tol2, bs);
+					for (int k = 0; k < c; k++) launch_pcg_batch_iteration(dTab[1], m, kh->g, kh->sys, gridSpmvMax, ncMax, ldsMax, k, tol2, bs);
 					launch_pcg_batch_advance(dTab[1], m, c, bs, tol2);
 					for (int i : act) if (inPcg[i]) hs[i]->noteReport();
 					k0 += c; todo -= c;
@@ -989,7 +1003,7 @@ static int cuba_hip_optimize_batch_full(cuba_hip_solver** hs, int n, int niter, 
 					h->waitReport();
 					const volatile int* f = ctx[i].hInts;
 					if (f[0] != 0) broke[i] = 1;
-					else if (f[2] != 0 || f[1] < std::min(k0, ctx[i].maxIter)) conv[i] = 1;
+					else if (f[2] == 1 || f[1] < std::min(k0, ctx[i].maxIter)) conv[i] = 1;
 					if (!broke[i] && !conv[i] && k0 < ctx[i].budget) all = false;
 					h->cntPcgLooks++; h->cntHostLooks++;
 				}
@@ -1077,6 +1091,7 @@ int cuba_hip_optimize_batch_impl(cuba_hip_solver** hs, int n, int niter, double*
 	lead->ensureOverlapObjects();
 	std::vector<cuba_hip_solver::CoarseJob> coarseJobs;
 	for (int i = 0; i < n; i++) hs[i]->lmRunBegin(runs[i], niter, chi2 ? chi2 + (size_t)i * niter : nullptr);
+	const int cls0 = batch_kernel_class(lead->g, lead->sys);      // (a handle that leaves this class during the call solves alone: see cuba_hip_optimize_batch_full)
 	std::vector<int> act, inPcg;
 	std::vector<char> okv((size_t)n);
 	int batchSolves = 0;
@@ -1085,12 +1100,14 @@ int cuba_hip_optimize_batch_impl(cuba_hip_solver** hs, int n, int niter, double*
 		act.clear();
 		for (int i = 0; i < n; i++) if (hs[i]->lmBeforeTrial(runs[i])) act.push_back(i);
 		if (act.empty()) break;
+		lead->cntBatchIterTrials++;
 		// linearise + Schur and the front half of the reduced solve, each graph on its own stream
 		inPcg.clear();
 		for (int i : act)
 		{
 			hs[i]->schur(true);
 			ctx[i] = cuba_hip_solver::SolveCtx(); ctx[i].batched = true; ctx[i].deferCoarse = &coarseJobs;
+			if (batch_kernel_class(hs[i]->g, hs[i]->sys) != cls0) { okv[i] = hs[i]->solveReduced(); continue; }      // (alone, on its own stream)
 			if (hs[i]->solveBegin(ctx[i])) okv[i] = ctx[i].result; else inPcg.push_back(i);
 		}
 		lead->launchCoarseJobs(coarseJobs);
@@ -1110,6 +1127,7 @@ int cuba_hip_optimize_batch_impl(cuba_hip_solver** hs, int n, int niter, double*
 			}
 			HIP_TRY(hipMemcpyAsync(lead->d_batchTab.data(), hTab, sizeof(BatchEntry) * m, hipMemcpyHostToDevice, bs));
 			const Scalar tol2 = ctx[inPcg[0]].tol2;
+			const cuba_hip_solver* kh = hs[inPcg[0]];      // (every graph in the PCG is of class cls0: the kernels are chosen from the first)
 			int k0 = 0, looks = 0;
 			std::vector<char> conv((size_t)m, 0), broke((size_t)m, 0);
 			bool all = false;
@@ -1120,7 +1138,7 @@ int cuba_hip_optimize_batch_impl(cuba_hip_solver** hs, int n, int niter, double*
 				{
 					const int c = todo;
 					// chunk-local iteration numbers + the advance / stop test / report launch, as a lone handle enqueues its batches
-					for (int k = 0; k < c; k++) launch_pcg_batch_iteration(dTab, m, lead->g, lead->sys, gridSpmvMax, ncMax, ldsMax, k, tol2, bs);
+					for (int k = 0; k < c; k++) launch_pcg_batch_iteration(dTab, m, kh->g, kh->sys, gridSpmvMax, ncMax, ldsMax, k, tol2, bs);
 					launch_pcg_batch_advance(dTab, m, c, bs, tol2);
 					for (int a = 0; a < m; a++) hs[inPcg[a]]->noteReport();
 					k0 += c; todo -= c;
@@ -1132,7 +1150,7 @@ int cuba_hip_optimize_batch_impl(cuba_hip_solver** hs, int n, int niter, double*
 					h->waitReport();
 					const volatile int* f = ctx[inPcg[a]].hInts;
 					if (f[0] != 0) broke[a] = 1;
-					else if (f[2] != 0 || f[1] < std::min(k0, ctx[inPcg[a]].maxIter)) conv[a] = 1;
+					else if (f[2] == 1 || f[1] < std::min(k0, ctx[inPcg[a]].maxIter)) conv[a] = 1;
 					if (!broke[a] && !conv[a] && k0 < ctx[inPcg[a]].budget) all = false;
 					h->cntPcgLooks++; h->cntHostLooks++;
 				}

@@ -97,13 +97,23 @@ void launch_pcg_setup(const DeviceGraph& g, const DeviceStructure& st, const Dev
 	if (g.Pf > 0) hipLaunchKernelGGL(pcg_setup_kernel, dim3((g.Pf + PCG_SETUP_POSES - 1) / PCG_SETUP_POSES), dim3(256), 0, s, g, st, sys, lambda);
 }
 
+// The launch that finds the solve over raises `done`: 1 = the stop test fired (or the solve failed), 2 = the iteration limit was reached with
+// the stop test unsatisfied so far.  The host counts only 1 as convergence: a solve that hits its limit is an unconverged solve however many
+// launches were enqueued past the limit (a batch enqueues for its longest graph; a lone handle rounds its last chunk up to 4).  A raised
+// flag is never overwritten here; the advance node's stop test may still turn a 2 into a 1 (convergence at the very last iteration).
+__device__ __forceinline__ void pcg_raise_done(const DeviceSystem& sys, bool atLimit, Scalar rzk)
+{
+	if (*sys.done == 0) *sys.done = atLimit ? 2 : 1;
+	if (!(rzk == rzk)) *sys.fail = 3;   // NaN: a failed solve, not a converged one
+}
+
 __device__ __forceinline__ bool pcg_active(const DeviceSystem& sys, int k, int maxIter, Scalar tol2, int lane, Scalar& rzk)
 {
 	if (*sys.done) return false;
 	rzk = wave_sum(load_parts(rz_slot(sys, k), rz_count(sys, k), lane));
 	const Scalar rz0 = wave_sum(load_parts(sys.rz, sys.nrz0, lane));
 	const bool on = k < maxIter && *sys.fail == 0 && rzk > tol2 * rz0 && rzk == rzk;
-	if (!on && blockIdx.x == 0 && threadIdx.x == 0) { *sys.done = 1; if (!(rzk == rzk)) *sys.fail = 3; }   // NaN: a failed solve, not a converged one
+	if (!on && blockIdx.x == 0 && threadIdx.x == 0) pcg_raise_done(sys, k >= maxIter, rzk);   // NaN: a failed solve, not a converged one
 	return on;
 }
 
@@ -301,7 +311,7 @@ __device__ __forceinline__ void pcg_spmv_body(const DeviceGraph& g, const Device
 	const Scalar rzk = to_uniform(wave_sum(s_k)), rz0 = to_uniform(wave_sum(s_0)), rzm = to_uniform(wave_sum(s_m));
 	if (!(k < maxIter && failed == 0 && rzk > tol2 * rz0 && rzk == rzk))   // uniform over the grid
 	{
-		if (blockIdx.x == 0 && threadIdx.x == 0) { *sys.done = 1; if (!(rzk == rzk)) *sys.fail = 3; }   // NaN: reported as a failed solve
+		if (blockIdx.x == 0 && threadIdx.x == 0) pcg_raise_done(sys, k >= maxIter, rzk);   // NaN: reported as a failed solve
 		return;
 	}
 	const Scalar beta = k > 0 ? rzk / rzm : Scalar(0);
@@ -452,7 +462,7 @@ __global__ __launch_bounds__(64 * ROWS, 5) void pcg_spmv_row_kernel(DeviceGraph 
 	const Scalar rzk = to_uniform(wave_sum(s_k)), rz0 = to_uniform(wave_sum(s_0)), rzm = to_uniform(wave_sum(s_m));
 	if (!(k < maxIter && failed == 0 && rzk > tol2 * rz0 && rzk == rzk))   // uniform over the grid
 	{
-		if (blockIdx.x == 0 && threadIdx.x == 0) { *sys.done = 1; if (!(rzk == rzk)) *sys.fail = 3; }   // NaN: reported as a failed solve
+		if (blockIdx.x == 0 && threadIdx.x == 0) pcg_raise_done(sys, k >= maxIter, rzk);   // NaN: reported as a failed solve
 		return;
 	}
 	const Scalar beta = k > 0 ? rzk / rzm : Scalar(0);
@@ -771,7 +781,7 @@ __device__ __forceinline__ void pcg2_fused_body(const DeviceGraph& g, const Devi
 		for (int w = 0; w < PCG2_T / 64; w++) { rzk += wsum[w]; rz0 += wsum[8 + w]; pqk += wsum[16 + w]; }
 		if (!(kabs < maxIter && failed == 0 && rzk > tol2 * rz0 && rzk == rzk))
 		{
-			if (blockIdx.x == 0 && threadIdx.x == 0) { *sys.done = 1; if (!(rzk == rzk)) *sys.fail = 3; }
+			if (blockIdx.x == 0 && threadIdx.x == 0) pcg_raise_done(sys, kabs >= maxIter, rzk);
 			return;
 		}
 		if (!PRE)
@@ -1035,7 +1045,7 @@ __global__ __launch_bounds__(64 * UPPER_WAVES, 4) void pcg_spmv_upper_kernel(Dev
 	const Scalar rzk = to_uniform(wave_sum(s_k)), rz0 = to_uniform(wave_sum(s_0)), rzm = to_uniform(wave_sum(s_m));
 	if (!(k < maxIter && failed == 0 && rzk > tol2 * rz0 && rzk == rzk))   // uniform over the grid
 	{
-		if (blockIdx.x == 0 && threadIdx.x == 0) { *sys.done = 1; if (!(rzk == rzk)) *sys.fail = 3; }   // NaN: reported as a failed solve
+		if (blockIdx.x == 0 && threadIdx.x == 0) pcg_raise_done(sys, k >= maxIter, rzk);   // NaN: reported as a failed solve
 		return;
 	}
 	const Scalar beta = k > 0 ? rzk / rzm : Scalar(0);
@@ -1155,7 +1165,7 @@ __global__ __launch_bounds__(ROWS_T) void pcg_rows_kernel(DeviceGraph g, DeviceS
 	for (int w = 0; w < ROWS_T / 64; w++) { rzk += wsum[w]; rz0 += wsum[8 + w]; pqk += wsum[16 + w]; }
 	if (!(kabs < maxIter && failed == 0 && rzk > tol2 * rz0 && rzk == rzk))
 	{
-		if (blockIdx.x == 0 && threadIdx.x == 0) { *sys.done = 1; if (!(rzk == rzk)) *sys.fail = 3; }
+		if (blockIdx.x == 0 && threadIdx.x == 0) pcg_raise_done(sys, kabs >= maxIter, rzk);
 		return;
 	}
 	if (!(pqk > 0))
@@ -1278,7 +1288,7 @@ __device__ __forceinline__ void pcg_advance_body(const DeviceSystem& sys, int n,
 	{
 		const int lane = threadIdx.x;
 		const Scalar rzk = wave_sum(load_parts(rz_slot(sys, 0), sys.nrz, lane)), rz0 = wave_sum(load_parts(sys.rz, sys.nrz0, lane));
-		if (lane == 0 && *sys.done == 0 && *sys.fail == 0 && !(rzk > tol2 * rz0))
+		if (lane == 0 && *sys.done != 1 && *sys.fail == 0 && !(rzk > tol2 * rz0))
 		{
 			*sys.done = 1;
 			if (!(rzk == rzk)) *sys.fail = 3;

@@ -266,6 +266,7 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 	for (double& v : prof) v = 0;
 	cntPcgIters = cntTrials = cntCoarseRefresh = cntPcgLooks = cntPcgEnqueued = cntPcgUnconverged = 0;
 	cntCoarseInline = cntFp32Fallbacks = 0;
+	cntBatchFullTrials = cntBatchIterTrials = 0;
 	pcgHistory.clear();
 	cntUploads++;
 	prof[0] += std::chrono::duration<double>(Clock::now() - t0).count();

@@ -380,6 +380,8 @@ int cuba_hip_get_counter(cuba_hip_solver* s, const char* name, int64_t* value)
 		else if (k == "pcg_graph_instantiations") *value = s->gb.builds.load();
 		else if (k == "precond_fp32_fallbacks") *value = s->cntFp32Fallbacks;
 		else if (k == "pcg_iterations_plain_launches") *value = s->cntPcgPlain;
+		else if (k == "batch_full_trials") *value = s->cntBatchFullTrials;
+		else if (k == "batch_iteration_trials") *value = s->cntBatchIterTrials;
 		else if (k == "host_looks") *value = s->cntHostLooks;
 		else if (k == "exact_solve_fallbacks") *value = s->cntDirect;
 		else if (k == "exact_solve_failures") *value = s->cntDirectFailed;

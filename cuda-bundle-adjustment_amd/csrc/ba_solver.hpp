@@ -421,6 +421,7 @@ struct cuba_hip_solver
 	int64_t cntPcgPlain = 0;          // PCG iterations enqueued as plain launches while hipGraphs were switched on (graph not built yet, or another handle active)
 	int64_t cntCoarseInline = 0;      // coarse inversions that ran on the WORK stream (in front of a solve), a subset of cntCoarseRefresh
 	int64_t cntFp32Fallbacks = 0;     // solves repeated with the fp64 coarse inverse after the fp32-stored one broke the PCG down
+	int64_t cntBatchFullTrials = 0, cntBatchIterTrials = 0;   // as hs[0] of cuba_hip_optimize_batch: trial rounds issued with every launch batched / with the PCG iterations batched only
 	int64_t cntUploads = 0;           // successful cuba_hip_set_graph calls on this handle (never reset: identifies what the device holds)
 	bool acceptUnconverged = false;   // true: a solve that hits max_iter hands back its best iterate as a success (inexact LM step)
 	std::vector<int> pcgHistory;      // PCG iterations of every reduced solve since set_graph (negative = stopped at max_iter)

@@ -302,7 +302,9 @@ int cuba_hip_get_counters(cuba_hip_solver* s, int64_t counters[8]);
    coarse inverse after the fp32-stored one broke the PCG down), "exact_solve_fallbacks" (reduced solves that went to the exact
    solver, see "direct_fallback"; 0 on well-conditioned graphs), "exact_solve_failures" (of these, the ones that met a non-positive pivot), "host_looks" (times the host waited for a device report:
    PCG batches + the LM decisions it had to see), "pcg_iterations_plain_launches" (iterations enqueued as plain launches although graphs
-   are on: graph not instantiated yet), "graph_uploads" (successful cuba_hip_set_graph[_begin] calls in the
+   are on: graph not instantiated yet), "batch_full_trials" / "batch_iteration_trials" (on handles[0] of cuba_hip_optimize_batch calls:
+   rounds of LM trials it issued with every launch of the trial batched / with the PCG iterations batched only; a call that fell back
+   to one handle after the other counts in neither), "graph_uploads" (successful cuba_hip_set_graph[_begin] calls in the
    life of the handle, never reset: a caller that keeps state about "what the device holds" -- the promises of cuba_hip_hint_unchanged --
    stores this number with it and distrusts its state when the two differ), "value_bytes_uploaded" (bytes of measurements and
    information that crossed PCIe in the life of the handle: 32 per edge and full upload, 36 per OWNED edge for cuba_hip_set_graph_partition),
