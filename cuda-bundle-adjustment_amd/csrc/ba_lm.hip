@@ -383,8 +383,7 @@ bool cuba_hip_solver::solveBegin(SolveCtx& sc)
 		launch_pcg_setup(g, st, sys, lambda, stream);
 		failDirty = true;
 		coarseValid = false;
-		if (pcgHistory.size() >= 65536) pcgHistory.erase(pcgHistory.begin(), pcgHistory.begin() + 32768);
-		pcgHistory.push_back(0);
+		notePcgHistory(0);
 		sc.result = solveDirect();
 		return true;
 	}
@@ -519,19 +518,27 @@ bool cuba_hip_solver::solveBegin(SolveCtx& sc)
 // preconditioner application and the first chunk of iterations first, so that the main stream never waits for the host.
 void cuba_hip_solver::enqueueCoarseSide(int first)
 {
-	const size_t invBytes = sizeof(Scalar) * (size_t)36 * sys.cl * sys.cl * sys.nc * sys.nc;
 	HIP_TRY(hipStreamWaitEvent(gjStream, evSetup, 0));
 	(void)launch_coarse_setup(g, st, sys, d_coarse[first].data(), d_coarse[1 - first].data(), gjStream, evAssembled);
-	if (fp32Inverse()) launch_coarse_to_fp32(d_coarse[0].data(), d_coarse32[1].data(), 6 * sys.cl * sys.nc, gjStream);   // (staging: the iteration graphs read [0])
-	else launch_coarse_finish(d_coarse[0].data(), d_coarse[0].data(), 6 * sys.cl * sys.nc, gjStream);                     // (the sweep leaves -inverse in the upper triangle)
-	if (firstInvPending)
+	enqueueInversionTail(gjStream, firstInvPending);
+	if (firstInvPending) { firstInvPending = false; firstInvValid = true; }
+}
+
+// What follows the sweep of an overlapped coarse inversion on stream `side` (this handle's second stream, or the lead's in a batch): the
+// sweep of Nc / 32 steps started in d_coarse[first] with first = steps & 1, so its result is in d_coarse[0].  Conversion, the copy for the
+// next run's first solve (+ evFirstInv), evInverse.
+void cuba_hip_solver::enqueueInversionTail(hipStream_t side, bool firstInvCopy)
+{
+	const int Nc = 6 * sys.cl * sys.nc;
+	if (fp32Inverse()) launch_coarse_to_fp32(d_coarse[0].data(), d_coarse32[1].data(), Nc, side);   // (staging: the iteration graphs read [0])
+	else launch_coarse_finish(d_coarse[0].data(), d_coarse[0].data(), Nc, side);                     // (the sweep leaves -inverse in the upper triangle)
+	if (firstInvCopy)
 	{
-		if (fp32Inverse()) HIP_TRY(hipMemcpyAsync(d_firstInv32.data(), d_coarse32[1].data(), inv32Count() * sizeof(float), hipMemcpyDeviceToDevice, gjStream));
-		else HIP_TRY(hipMemcpyAsync(d_firstInv.data(), d_coarse[0].data(), invBytes, hipMemcpyDeviceToDevice, gjStream));
-		HIP_TRY(hipEventRecord(evFirstInv, gjStream));
-		firstInvPending = false; firstInvValid = true;
+		if (fp32Inverse()) HIP_TRY(hipMemcpyAsync(d_firstInv32.data(), d_coarse32[1].data(), inv32Count() * sizeof(float), hipMemcpyDeviceToDevice, side));
+		else HIP_TRY(hipMemcpyAsync(d_firstInv.data(), d_coarse[0].data(), sizeof(Scalar) * (size_t)Nc * Nc, hipMemcpyDeviceToDevice, side));
+		HIP_TRY(hipEventRecord(evFirstInv, side));
 	}
-	HIP_TRY(hipEventRecord(evInverse, gjStream));
+	HIP_TRY(hipEventRecord(evInverse, side));
 }
 
 bool cuba_hip_solver::solveBrokeDown(SolveCtx& sc)
@@ -542,13 +549,21 @@ bool cuba_hip_solver::solveBrokeDown(SolveCtx& sc)
 	// fp32-stored inverse is first repeated with fp64 storage by solveReduced)
 	if (sc.direct && lastFailCode != 1 && !(lastFailCode == 2 && fp32Inverse() && sc.twoLevel))
 	{
-		if (pcgHistory.size() >= 65536) pcgHistory.erase(pcgHistory.begin(), pcgHistory.begin() + 32768);
-		pcgHistory.push_back(-sc.hInts[1]);
+		notePcgHistory(-sc.hInts[1]);
 		d_fail.zero(stream); failDirty = false;
 		return solveDirect();
 	}
 	return false;
 }
+
+// The look schedule of a reduced solve: how many iterations are enqueued before the host looks at the device's stop flag.  One place for
+// the lone handle (solveReducedOnce) and for a batch (BatchPcg), whose handles are bit-identical to solo runs only while the two agree.
+// The first batch is sized from the prediction (solveBegin); a batch sized from the run's own history misses by a few iterations at most,
+// so the first continuation is short, later ones an eighth of what has run; lengths are multiples of 4 (the kernels address their
+// reduction slots by the chunk-local k & 3).
+static int pcgFirstTarget(int predicted) { return (predicted + 3) / 4 * 4; }
+static int pcgNextTarget(int k0, int looks) { return k0 + ((looks == 0 && k0 <= 96) ? 4 : std::max(8, k0 / 8 / 4 * 4)); }
+static int pcgBatchLength(int target, int budget, int k0) { return std::max(4, std::min(target, budget) - k0); }
 
 bool cuba_hip_solver::solveReducedOnce()
 {
@@ -563,10 +578,10 @@ bool cuba_hip_solver::solveReducedOnce()
 	// host round trip, so the first batch is sized from the previous solve of this run.
 	bool converged = false;
 	int k0 = 0, looks = 0, eagerIters = 0;
-	int target = (predicted + 3) / 4 * 4;
+	int target = pcgFirstTarget(predicted);
 	while (k0 < sc.budget && !converged)
 	{
-		int todo = std::max(4, std::min(target, sc.budget) - k0);
+		int todo = pcgBatchLength(target, sc.budget, k0);
 		while (todo > 0)
 		{
 			// without hipGraphs (the default): the whole batch as one chunk of plain launches -- chunk-local iteration numbers, then the
@@ -597,7 +612,7 @@ bool cuba_hip_solver::solveReducedOnce()
 		waitReport();
 		if (sc.hInts[0] != 0) return solveBrokeDown(sc);
 		if (sc.hInts[2] == 1 || sc.hInts[1] < std::min(k0, maxIter)) converged = true;   // the device-side stop test fired (2 = stopped at the iteration limit: pcg_raise_done)
-		target = k0 + ((looks == 0 && k0 <= 96) ? 4 : std::max(8, k0 / 8 / 4 * 4));   // (a batch sized from the run's own history misses by a few iterations at most)
+		target = pcgNextTarget(k0, looks);
 		looks++; cntPcgLooks++; cntHostLooks++;
 	}
 	sc.converged = converged; sc.k0 = k0; sc.looks = looks; sc.eagerIters = eagerIters;
@@ -623,8 +638,7 @@ bool cuba_hip_solver::solveEnd(SolveCtx& sc)
 	cntPcgIters += itersDone; cntPcgEnqueued += k0;
 	if (runIters.empty()) firstSolveIters = itersDone;
 	runIters.push_back(itersDone);
-	if (pcgHistory.size() >= 65536) pcgHistory.erase(pcgHistory.begin(), pcgHistory.begin() + 32768);   // drivers that never call set_graph again: keep the latest
-	pcgHistory.push_back(converged ? itersDone : -itersDone);
+	notePcgHistory(converged ? itersDone : -itersDone);
 	if (!converged)
 	{
 		// max_iter reached with the stop test still unsatisfied: never silent.  Reported like the reference's
@@ -863,32 +877,124 @@ void cuba_hip_solver::launchCoarseJobs(std::vector<CoarseJob>& jobs, hipEvent_t 
 	HIP_TRY(hipMemcpyAsync(d_gjTab.data(), h_gjTab, sizeof(GjJob) * m, hipMemcpyHostToDevice, side));
 	HIP_TRY(hipEventRecord(evGjTab, side));
 	launch_dense_inverse_batch(reinterpret_cast<const GjJob*>(d_gjTab.data()), m, nMax, side);
-	for (int a = 0; a < m; a++)
-	{
-		cuba_hip_solver* h = jobs[a].h;
-		const int Nc = 6 * h->sys.cl * h->sys.nc;
-		const size_t invBytes = sizeof(Scalar) * (size_t)Nc * Nc;
-		// (the sweep of Nc / 32 steps started in d_coarse[first] with first = steps & 1: its result is in d_coarse[0])
-		if (h->fp32Inverse()) launch_coarse_to_fp32(h->d_coarse[0].data(), h->d_coarse32[1].data(), Nc, side);
-		else launch_coarse_finish(h->d_coarse[0].data(), h->d_coarse[0].data(), Nc, side);
-		if (jobs[a].firstInvCopy)
-		{
-			if (h->fp32Inverse()) HIP_TRY(hipMemcpyAsync(h->d_firstInv32.data(), h->d_coarse32[1].data(), h->inv32Count() * sizeof(float), hipMemcpyDeviceToDevice, side));
-			else HIP_TRY(hipMemcpyAsync(h->d_firstInv.data(), h->d_coarse[0].data(), invBytes, hipMemcpyDeviceToDevice, side));
-			HIP_TRY(hipEventRecord(h->evFirstInv, side));
-		}
-		HIP_TRY(hipEventRecord(h->evInverse, side));
-	}
+	for (int a = 0; a < m; a++) jobs[a].h->enqueueInversionTail(side, jobs[a].firstInvCopy);
 	jobs.clear();
 }
 
-// cuba_hip_optimize_batch, every launch of a trial batched: all graphs share the first handle's stream for the duration of the call, and
-// per trial the host issues -- for ALL graphs together -- landmark pass + Schur pass, the PCG set-up launch, the first preconditioner
-// application, the iterations, the trial tail + sums / decision / report + conditional restore, and on the side stream one sweep of all
-// coarse matrices that are due.  What stays per graph: host bookkeeping, the first solve of a run (a copy or an in-line inversion sits
-// between its set-up launch and its first preconditioner application), exact solves, failed solves.
-static int cuba_hip_optimize_batch_full(cuba_hip_solver** hs, int n, int niter, double* chi2, int* nDone)
+void cuba_hip_solver::ensureBatchTables()
 {
+	// three tables (pinned host + device), one per phase of a trial: a phase's copy has long executed when the next trial rewrites it
+	// (the host waits for the PCG reports of every trial in between)
+	if (!h_batchTab) HIP_TRY(hipHostMalloc((void**)&h_batchTab, sizeof(BatchEntry) * CUBA_HIP_BATCH_MAX * 3, hipHostMallocDefault));
+	d_batchTab.resize(sizeof(BatchEntry) * CUBA_HIP_BATCH_MAX * 3);
+}
+
+// The PCG iterations of one trial of a batch: the graphs whose reduced solve goes through them (`who`), the maxima that size the batched
+// launches (the kernel instantiation comes from the first graph, the grid and the LDS bytes from the largest), the iteration loop and the
+// per-graph epilogue.  Both modes of the driver below run it; they differ in the device table they hand it (see there).
+namespace {
+struct BatchPcg
+{
+	typedef cuba_hip_solver::SolveCtx SolveCtx;
+	cuba_hip_solver** hs; std::vector<SolveCtx>& ctx; hipStream_t bs;
+	std::vector<int> who;                     // handle numbers, in the order of their table entries
+	std::vector<char> conv, broke;            // (per entry of `who`)
+	const cuba_hip_solver* kh = nullptr;      // the first graph in the PCG: the batched kernels are chosen from it (every graph in the PCG is of class cls0)
+	int gridSpmvMax = 0, ncMax = 0; size_t ldsMax = 0; Scalar tol2 = 0;
+	int target = 4, budgetMax = 0, k0 = 0, looks = 0;
+
+	BatchPcg(cuba_hip_solver** h, std::vector<SolveCtx>& c, hipStream_t s) : hs(h), ctx(c), bs(s) {}
+	int count() const { return (int)who.size(); }
+
+	// handle i, whose solveBegin has just left the iterations to do, and its table entry
+	void add(int i, BatchEntry& e)
+	{
+		const cuba_hip_solver* h = hs[i];
+		const SolveCtx& sc = ctx[i];
+		if (!kh) { kh = h; tol2 = sc.tol2; }      // (one pcg_tol for all: cuba_hip_optimize_batch_impl)
+		who.push_back(i);
+		e = BatchEntry();
+		e.g = h->g; e.st = h->st; e.sys = h->sys; e.maxIter = sc.maxIter;
+		e.gridSpmv = (h->g.Pf + h->sys.spmv_rows - 1) / h->sys.spmv_rows;
+		gridSpmvMax = std::max(gridSpmvMax, e.gridSpmv); ncMax = std::max(ncMax, h->sys.nc); ldsMax = std::max(ldsMax, batch_pcg2_lds_bytes(h->sys));
+		target = std::max(target, pcgFirstTarget(sc.predicted)); budgetMax = std::max(budgetMax, sc.budget);
+	}
+
+	// Batches of iterations for the mTab graphs of the device table -- chunk-local iteration numbers + the advance / stop test / report
+	// launch, as a lone handle enqueues its batches -- and after each a look at every participant's report, until each of them has
+	// converged, broken down or used up its budget
+	void iterate(const BatchEntry* dTab, int mTab)
+	{
+		conv.assign(who.size(), 0); broke.assign(who.size(), 0);
+		bool all = false;
+		while (k0 < budgetMax && !all)
+		{
+			const int c = pcgBatchLength(target, budgetMax, k0);
+			for (int k = 0; k < c; k++) launch_pcg_batch_iteration(dTab, mTab, kh->g, kh->sys, gridSpmvMax, ncMax, ldsMax, k, tol2, bs);
+			launch_pcg_batch_advance(dTab, mTab, c, bs, tol2);
+			for (int i : who) hs[i]->noteReport();
+			k0 += c;
+			all = true;
+			for (size_t p = 0; p < who.size(); p++)
+			{
+				cuba_hip_solver* h = hs[who[p]];
+				const SolveCtx& sc = ctx[who[p]];
+				h->waitReport();
+				const volatile int* f = sc.hInts;
+				if (f[0] != 0) broke[p] = 1;
+				else if (f[2] == 1 || f[1] < std::min(k0, sc.maxIter)) conv[p] = 1;
+				if (!broke[p] && !conv[p] && k0 < sc.budget) all = false;
+				h->cntPcgLooks++; h->cntHostLooks++;
+			}
+			target = pcgNextTarget(k0, looks);
+			looks++;
+		}
+	}
+
+	// the back half of every participant's solve -> okv.  A graph on a stream of its own goes back to it first: `fork` follows the iterations
+	void finish(std::vector<char>& okv, hipEvent_t fork)
+	{
+		for (size_t p = 0; p < who.size(); p++)
+		{
+			const int i = who[p];
+			cuba_hip_solver* h = hs[i];
+			if (fork && h->stream != bs) HIP_TRY(hipStreamWaitEvent(h->stream, fork, 0));
+			SolveCtx& sc = ctx[i];
+			sc.k0 = std::min(k0, std::max(sc.budget, 4)); sc.looks = looks; sc.eagerIters = 0;
+			// (a graph alone stops at ITS iteration budget and hands the solve over; in a batch its iterations run on while the others
+			// need them -- harmless, the exact solve replaces the iterate -- but convergence counts only within the budget)
+			sc.converged = conv[p] != 0 && sc.hInts[1] <= sc.budget;
+			if (!sc.converged && !broke[p]) sc.itersDone = std::min((int)sc.hInts[1], sc.budget);
+			okv[i] = h->retryWithFp64Inverse(broke[p] ? h->solveBrokeDown(sc) : h->solveEnd(sc));
+		}
+	}
+};
+}
+
+// The trial loop of cuba_hip_optimize_batch.  Every handle runs ITS OWN Levenberg-Marquardt loop -- decisions on the device, per graph --;
+// per trial round the host takes the graphs whose run goes on (`act`), linearises them (phase A), runs the front half of their reduced
+// solves, the PCG iterations of all of them as ONE chain of batched launches (blockIdx.y = graph, kernel arguments from a device table)
+// and the back halves (phase B), then the trial tails and decisions (phase C).  What stays per graph in either mode: host bookkeeping, the
+// first solve of a run (a copy or an in-line inversion sits between its set-up launch and its first preconditioner application), exact
+// solves, failed solves, and the solves of a graph that has left the batch's kernel class.
+//
+// Two modes.  full: every launch of a trial is batched, for the standard launch sequence only (fullyBatchable()).  Otherwise only the
+// iterations are: the rest of a trial overlaps across the graphs' own streams.  The modes differ in four places and nowhere else:
+//   streams      full: all graphs share the first handle's stream `bs` for the duration of the call (StreamGuard).  Else: each graph keeps
+//                its stream; bs waits for a join event of every graph in the PCG before the iterations, the graphs' streams wait for a
+//                fork event behind them.
+//   phase A      full: launch_batch_linearize from table 0 (landmark pass with the state backup + Schur pass of all graphs).  Else:
+//                schur(true) per handle.
+//   set-up       full: solveBegin leaves the set-up launch and the first preconditioner application to the driver (SolveCtx::deferLaunch),
+//                which issues them for all graphs from the PCG's table -- one entry per active graph, a graph outside the PCG sits the
+//                launches out with gridSpmv = 0 and no set-up grid -- and hands launchCoarseJobs the one event behind the batched set-up
+//                launch.  Else: solveBegin launches both, launchCoarseJobs waits for each graph's own evSetup, and the PCG's table is
+//                compact (one entry per graph in the PCG).
+//   phase C      full: launch_batch_tail from table 2 (trial tail, sums + decision + report, conditional restore).  Else: lmAfterSolve per
+//                handle.
+static int optimizeBatch(cuba_hip_solver** hs, int n, int niter, double* chi2, int* nDone, bool full)
+{
+	typedef cuba_hip_solver::SolveCtx SolveCtx;
 	cuba_hip_solver* lead = hs[0];
 	hipStream_t bs = lead->stream;
 	struct StreamGuard
@@ -899,26 +1005,26 @@ static int cuba_hip_optimize_batch_full(cuba_hip_solver** hs, int n, int niter, 
 			for (int i = 0; i < n; i++) { own[i] = hs[i]->stream; (void)hipStreamSynchronize(own[i]); hs[i]->stream = s; }
 		}
 		~StreamGuard() { if (n > 0) (void)hipStreamSynchronize(hs[0]->stream); for (int i = 0; i < n; i++) hs[i]->stream = own[i]; }
-	} streamGuard(hs, n, bs);
-	std::vector<cuba_hip_solver::LmRun> runs((size_t)n);
-	std::vector<cuba_hip_solver::SolveCtx> ctx((size_t)n);
+	} streamGuard(hs, full ? n : 0, bs);
+	std::vector<hipEvent_t>& evJoin = lead->batchEvents;
+	while (!full && (int)evJoin.size() < n + 1) { hipEvent_t e; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); evJoin.push_back(e); }
+	const hipEvent_t evFork = full ? nullptr : evJoin[n];
+	lead->ensureBatchTables();
 	lead->ensureOverlapObjects();
-	std::vector<cuba_hip_solver::CoarseJob> coarseJobs;
-	// three tables (pinned host + device), one per phase of a trial: a phase's copy has long executed when the next trial rewrites it
-	// (the host waits for the PCG reports of every trial in between)
-	if (lead->h_batchTab && lead->batchTabEntries < 3 * CUBA_HIP_BATCH_MAX) { (void)hipHostFree(lead->h_batchTab); lead->h_batchTab = nullptr; }
-	if (!lead->h_batchTab) { HIP_TRY(hipHostMalloc((void**)&lead->h_batchTab, sizeof(BatchEntry) * CUBA_HIP_BATCH_MAX * 3, hipHostMallocDefault)); lead->batchTabEntries = 3 * CUBA_HIP_BATCH_MAX; }
-	lead->d_batchTab.resize(sizeof(BatchEntry) * CUBA_HIP_BATCH_MAX * 3);
 	BatchEntry* hTab[3]; const BatchEntry* dTab[3];
 	for (int k = 0; k < 3; k++) { hTab[k] = lead->h_batchTab + (size_t)k * CUBA_HIP_BATCH_MAX; dTab[k] = reinterpret_cast<const BatchEntry*>(lead->d_batchTab.data()) + (size_t)k * CUBA_HIP_BATCH_MAX; }
 	auto upload = [&](int k, int m) { HIP_TRY(hipMemcpyAsync(const_cast<BatchEntry*>(dTab[k]), hTab[k], sizeof(BatchEntry) * m, hipMemcpyHostToDevice, bs)); };
+	const int pcgTab = full ? 1 : 0;
+	std::vector<cuba_hip_solver::LmRun> runs((size_t)n);
+	std::vector<SolveCtx> ctx((size_t)n);
+	std::vector<cuba_hip_solver::CoarseJob> coarseJobs;
 	for (int i = 0; i < n; i++) hs[i]->lmRunBegin(runs[i], niter, chi2 ? chi2 + (size_t)i * niter : nullptr);
-	const bool mixed = hs[0]->st.mixed != 0;
+	const bool mixed = lead->st.mixed != 0;
 	// the kernel class the call's handles agreed on.  A handle can leave it in the middle of the call (retryWithFp64Inverse drops the fp32
 	// copy of its coarse inverse for the rest of its run): from then on it solves alone, see phase B
 	const int cls0 = batch_kernel_class(lead->g, lead->sys);
 	std::vector<int> act;
-	std::vector<char> okv((size_t)n), inPcg((size_t)n);
+	std::vector<char> okv((size_t)n);
 	int batchSolves = 0;
 	for (;;)
 	{
@@ -926,142 +1032,114 @@ static int cuba_hip_optimize_batch_full(cuba_hip_solver** hs, int n, int niter, 
 		for (int i = 0; i < n; i++) if (hs[i]->lmBeforeTrial(runs[i])) act.push_back(i);
 		if (act.empty()) break;
 		const int m = (int)act.size();
-		lead->cntBatchFullTrials++;
+		(full ? lead->cntBatchFullTrials : lead->cntBatchIterTrials)++;
 		// ---- phase A: linearise + Schur (the state backup rides in the landmark pass's launch)
-		unsigned lmMax = 0, schurMax = 0;
-		for (int a = 0; a < m; a++)
+		if (full)
 		{
-			cuba_hip_solver* h = hs[act[a]];
-			h->zeroReduced();
-			BatchEntry& e = hTab[0][a];
-			e = BatchEntry();
-			e.g = h->g; e.st = h->st; e.sys = h->sys;
-			batch_fill_linearize(h->g, h->st, h->d_state.data(), h->d_backup.data(), h->d_state.size(), e.t);
-			lmMax = std::max(lmMax, e.t.lmGrid); schurMax = std::max(schurMax, e.t.schurGrid);
+			unsigned lmMax = 0, schurMax = 0;
+			for (int a = 0; a < m; a++)
+			{
+				cuba_hip_solver* h = hs[act[a]];
+				h->zeroReduced();
+				BatchEntry& e = hTab[0][a];
+				e = BatchEntry();
+				e.g = h->g; e.st = h->st; e.sys = h->sys;
+				batch_fill_linearize(h->g, h->st, h->d_state.data(), h->d_backup.data(), h->d_state.size(), e.t);
+				lmMax = std::max(lmMax, e.t.lmGrid); schurMax = std::max(schurMax, e.t.schurGrid);
+			}
+			upload(0, m);
+			launch_batch_linearize(dTab[0], m, lmMax, schurMax, mixed, bs);
 		}
-		upload(0, m);
-		launch_batch_linearize(dTab[0], m, lmMax, schurMax, mixed, bs);
-		// ---- phase B: front half of the reduced solves
-		unsigned setupMax = 0; int gridSpmvMax = 0, ncMax = 0; size_t ldsMax = 0; int target = 4, budgetMax = 0, nPcg = 0, nFused = 0;
-		Scalar tol2 = 0;
-		const cuba_hip_solver* kh = nullptr;      // the first graph in the PCG: the batched kernels are chosen from it (every graph in the PCG is of class cls0)
+		// ---- phase B: the reduced solves.  Front half per graph (behind its own phase A where that is per graph)
+		BatchPcg pcg(hs, ctx, bs);
+		unsigned setupMax = 0; int nFused = 0;
 		for (int a = 0; a < m; a++)
 		{
 			const int i = act[a];
 			cuba_hip_solver* h = hs[i];
-			ctx[i] = cuba_hip_solver::SolveCtx(); ctx[i].batched = true; ctx[i].deferCoarse = &coarseJobs; ctx[i].deferLaunch = true;
-			BatchEntry& e = hTab[1][a];
-			e = BatchEntry();
-			if (batch_kernel_class(h->g, h->sys) != cls0)
+			if (!full) h->schur(true);
+			ctx[i] = SolveCtx(); ctx[i].batched = true; ctx[i].deferCoarse = &coarseJobs; ctx[i].deferLaunch = full;
+			// a graph that has left the batch's kernel class (its coarse inverse is stored in fp64 now: the instantiation the others run would
+			// read the wrong buffer) solves alone, on the stream it is on; so does, at once, a graph whose solve is an exact one
+			const bool alone = batch_kernel_class(h->g, h->sys) != cls0;
+			const bool finished = alone || h->solveBegin(ctx[i]);
+			if (finished) okv[i] = alone ? h->solveReduced() : ctx[i].result;
+			BatchEntry& e = hTab[pcgTab][full ? a : pcg.count()];
+			if (!finished)
 			{
-				// the graph has left the batch's kernel class (its coarse inverse is stored in fp64 now: the instantiation the others run would
-				// read the wrong buffer): it solves alone, on the common stream, and sits the batched launches out (gridSpmv = 0, no set-up grid)
-				okv[i] = h->solveReduced(); inPcg[i] = 0;
-				e.g = h->g; e.st = h->st; e.sys = h->sys;
-				continue;
+				pcg.add(i, e);
+				if (ctx[i].deferred) { batch_fill_setup(h->g, h->st, h->sys, ctx[i].copySrc, ctx[i].copyDst, ctx[i].copyCount, e.t); e.t.fusedOn = 1; nFused++; }
+				setupMax = std::max(setupMax, e.t.setupGrid);
 			}
-			const bool finished = h->solveBegin(ctx[i]);
-			e.g = h->g; e.st = h->st; e.sys = h->sys;
-			if (finished) { okv[i] = ctx[i].result; inPcg[i] = 0; continue; }      // (an exact solve at once: the graph sits the batched launches out)
-			inPcg[i] = 1; nPcg++;
-			if (!kh) kh = h;
-			tol2 = ctx[i].tol2;
-			e.maxIter = ctx[i].maxIter;
-			e.gridSpmv = (h->g.Pf + h->sys.spmv_rows - 1) / h->sys.spmv_rows;
-			if (ctx[i].deferred) { batch_fill_setup(h->g, h->st, h->sys, ctx[i].copySrc, ctx[i].copyDst, ctx[i].copyCount, e.t); e.t.fusedOn = 1; nFused++; }
-			setupMax = std::max(setupMax, e.t.setupGrid);
-			gridSpmvMax = std::max(gridSpmvMax, e.gridSpmv); ncMax = std::max(ncMax, h->sys.nc); ldsMax = std::max(ldsMax, batch_pcg2_lds_bytes(h->sys));
-			target = std::max(target, (ctx[i].predicted + 3) / 4 * 4); budgetMax = std::max(budgetMax, ctx[i].budget);
+			else if (full) { e = BatchEntry(); e.g = h->g; e.st = h->st; e.sys = h->sys; }      // (sits the batched launches out)
 		}
-		if (nPcg > 0)
+		if (!full || pcg.count() == 0) lead->launchCoarseJobs(coarseJobs);      // (full mode with graphs in the PCG: behind the batched set-up launch)
+		if (pcg.count() > 0)
 		{
-			upload(1, m);
-			if (nFused > 0) launch_batch_setup(dTab[1], m, setupMax, bs);
-			HIP_TRY(hipEventRecord(lead->evSetup, bs));
-			lead->launchCoarseJobs(coarseJobs, lead->evSetup);
-			if (nFused > 0) launch_batch_first_precond(dTab[1], m, kh->sys, ncMax, ldsMax, tol2, bs);
-			// ---- the iterations of all graphs
-			int k0 = 0, looks = 0;
-			std::vector<char> conv((size_t)n, 0), broke((size_t)n, 0);
-			bool all = false;
-			while (k0 < budgetMax && !all)
+			const int mTab = full ? m : pcg.count();
+			if (full)
 			{
-				int todo = std::max(4, std::min(target, budgetMax) - k0);
-				while (todo > 0)
-				{
-					const int c = todo;
-					for (int k = 0; k < c; k++) launch_pcg_batch_iteration(dTab[1], m, kh->g, kh->sys, gridSpmvMax, ncMax, ldsMax, k, tol2, bs);
-					launch_pcg_batch_advance(dTab[1], m, c, bs, tol2);
-					for (int i : act) if (inPcg[i]) hs[i]->noteReport();
-					k0 += c; todo -= c;
-				}
-				all = true;
-				for (int i : act)
-				{
-					if (!inPcg[i]) continue;
-					cuba_hip_solver* h = hs[i];
-					h->waitReport();
-					const volatile int* f = ctx[i].hInts;
-					if (f[0] != 0) broke[i] = 1;
-					else if (f[2] == 1 || f[1] < std::min(k0, ctx[i].maxIter)) conv[i] = 1;
-					if (!broke[i] && !conv[i] && k0 < ctx[i].budget) all = false;
-					h->cntPcgLooks++; h->cntHostLooks++;
-				}
-				target = k0 + ((looks == 0 && k0 <= 96) ? 4 : std::max(8, k0 / 8 / 4 * 4));
-				looks++;
+				upload(1, m);
+				if (nFused > 0) launch_batch_setup(dTab[1], m, setupMax, bs);
+				HIP_TRY(hipEventRecord(lead->evSetup, bs));
+				lead->launchCoarseJobs(coarseJobs, lead->evSetup);
+				if (nFused > 0) launch_batch_first_precond(dTab[1], m, pcg.kh->sys, pcg.ncMax, pcg.ldsMax, pcg.tol2, bs);
 			}
-			for (int i : act)
+			else
 			{
-				if (!inPcg[i]) continue;
-				cuba_hip_solver::SolveCtx& sc = ctx[i];
-				sc.k0 = std::min(k0, std::max(sc.budget, 4)); sc.looks = looks; sc.eagerIters = 0;
-				// (a graph alone stops at ITS iteration budget and hands the solve over; in a batch its iterations run on while the others
-				// need them -- harmless, the exact solve replaces the iterate -- but convergence counts only within the budget)
-				sc.converged = conv[i] != 0 && sc.hInts[1] <= sc.budget;
-				if (!sc.converged && !broke[i]) sc.itersDone = std::min((int)sc.hInts[1], sc.budget);
-				okv[i] = hs[i]->retryWithFp64Inverse(broke[i] ? hs[i]->solveBrokeDown(sc) : hs[i]->solveEnd(sc));
+				for (int a = 0; a < mTab; a++)
+				{
+					cuba_hip_solver* h = hs[pcg.who[a]];
+					if (h != lead) { HIP_TRY(hipEventRecord(evJoin[a], h->stream)); HIP_TRY(hipStreamWaitEvent(bs, evJoin[a], 0)); }
+				}
+				upload(0, mTab);
 			}
+			pcg.iterate(dTab[pcgTab], mTab);
+			if (!full) HIP_TRY(hipEventRecord(evFork, bs));      // back to the graphs' own streams
+			pcg.finish(okv, evFork);
 			batchSolves++;
 		}
-		else lead->launchCoarseJobs(coarseJobs, nullptr);
 		// ---- phase C: trial tails, decisions, reports, conditional restores
-		unsigned tailMax = 0, restoreMax = 0;
-		for (int a = 0; a < m; a++)
+		if (full)
 		{
-			const int i = act[a];
-			cuba_hip_solver* h = hs[i];
-			BatchEntry& e = hTab[2][a];
-			e = BatchEntry();
-			e.g = h->g; e.st = h->st; e.sys = h->sys;
-			if (!h->lmAfterSolveHost(runs[i])) continue;          // (the run has ended: nothing of this trial is launched)
-			batch_fill_tail(h->g, h->st, h->sys, h->d_backup.data(), runs[i].lm, h->d_state.data(), h->d_state.size(), e.t);
-			e.t.backupDst = h->d_backup.data();
-			if (!okv[i])
+			unsigned tailMax = 0, restoreMax = 0;
+			for (int a = 0; a < m; a++)
 			{
-				// (a failed reduced solve: the decision alone, at once; the batched restore launch follows it in the stream)
-				launch_lm_decide_failed(h->sys, runs[i].lm, bs);
-				e.t.tailGrid = 0; e.t.reportOn = 0;
+				const int i = act[a];
+				cuba_hip_solver* h = hs[i];
+				BatchEntry& e = hTab[2][a];
+				e = BatchEntry();
+				e.g = h->g; e.st = h->st; e.sys = h->sys;
+				if (!h->lmAfterSolveHost(runs[i])) continue;          // (the run has ended: nothing of this trial is launched)
+				batch_fill_tail(h->g, h->st, h->sys, h->d_backup.data(), runs[i].lm, h->d_state.data(), h->d_state.size(), e.t);
+				e.t.backupDst = h->d_backup.data();
+				if (!okv[i])
+				{
+					// (a failed reduced solve: the decision alone, at once; the batched restore launch follows it in the stream)
+					launch_lm_decide_failed(h->sys, runs[i].lm, bs);
+					e.t.tailGrid = 0; e.t.reportOn = 0;
+				}
+				tailMax = std::max(tailMax, e.t.tailGrid); restoreMax = std::max(restoreMax, e.t.restoreGrid);
+				h->noteReport();
+				runs[i].enq++;
 			}
-			tailMax = std::max(tailMax, e.t.tailGrid); restoreMax = std::max(restoreMax, e.t.restoreGrid);
-			h->noteReport();
-			runs[i].enq++;
+			upload(2, m);
+			launch_batch_tail(dTab[2], m, tailMax, restoreMax, bs);
+			(void)hipStreamQuery(bs);
 		}
-		upload(2, m);
-		launch_batch_tail(dTab[2], m, tailMax, restoreMax, bs);
-		(void)hipStreamQuery(bs);
+		else for (int i : act) (void)hs[i]->lmAfterSolve(runs[i], okv[i] != 0);
 	}
 	for (int i = 0; i < n; i++) nDone[i] = hs[i]->lmRunEnd(runs[i]);
 	return batchSolves;
 }
 
-// Several graphs, one launch chain (include/cuba_hip.h: cuba_hip_optimize_batch).  Every handle runs ITS OWN Levenberg-Marquardt loop --
-// decisions on the device, per graph -- and everything of a trial but the PCG iterations on its own stream (linearise + Schur, set-up
-// launch, coarse inverse, trial tail: they overlap across the streams); the iterations of all graphs go out as ONE chain of batched
-// launches (blockIdx.y = graph, kernel arguments from a device table) on the first handle's stream, joined and forked by events.  Per
-// graph the kernels, their arguments and their order are those of cuba_hip_optimize: results are bit-identical to the solo runs.  A graph
-// whose solve has converged returns at once from the iterations the others still need (its device-side stop flag), a graph whose run has
-// ended leaves the batch.  The host issues 2 launches per iteration for the whole batch instead of 2 per graph -- it is the host's launch
-// rate, not the GPU, that bounds several handles driven side by side.
+// Several graphs, one launch chain (include/cuba_hip.h: cuba_hip_optimize_batch): handles that can share batched launches go to
+// optimizeBatch above -- with every launch of a trial batched where all of them run the standard launch sequence, with the PCG iterations
+// batched otherwise --, any others run one after the other.  Per graph the kernels, their arguments and their order are those of
+// cuba_hip_optimize: results are bit-identical to the solo runs.  A graph whose solve has converged returns at once from the iterations
+// the others still need (its device-side stop flag), a graph whose run has ended leaves the batch.  The host issues 2 launches per
+// iteration for the whole batch instead of 2 per graph -- it is the host's launch rate, not the GPU, that bounds several handles driven
+// side by side.
 int cuba_hip_optimize_batch_impl(cuba_hip_solver** hs, int n, int niter, double* chi2, int* nDone)
 {
 	bool together = n > 1;
@@ -1076,108 +1154,7 @@ int cuba_hip_optimize_batch_impl(cuba_hip_solver** hs, int n, int niter, double*
 	}
 	bool full = true;
 	for (int i = 0; i < n && full; i++) full = hs[i]->fullyBatchable() && hs[i]->st.mixed == hs[0]->st.mixed;
-	if (full) return cuba_hip_optimize_batch_full(hs, n, niter, chi2, nDone);
-	cuba_hip_solver* lead = hs[0];
-	hipStream_t bs = lead->stream;
-	std::vector<cuba_hip_solver::LmRun> runs((size_t)n);
-	std::vector<cuba_hip_solver::SolveCtx> ctx((size_t)n);
-	std::vector<hipEvent_t>& evJoin = lead->batchEvents;
-	while ((int)evJoin.size() < n + 1) { hipEvent_t e; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); evJoin.push_back(e); }
-	hipEvent_t evFork = evJoin[n];
-	if (!lead->h_batchTab) { HIP_TRY(hipHostMalloc((void**)&lead->h_batchTab, sizeof(BatchEntry) * CUBA_HIP_BATCH_MAX * 3, hipHostMallocDefault)); lead->batchTabEntries = 3 * CUBA_HIP_BATCH_MAX; }
-	lead->d_batchTab.resize(sizeof(BatchEntry) * CUBA_HIP_BATCH_MAX * 3);
-	BatchEntry* hTab = lead->h_batchTab;
-	const BatchEntry* dTab = reinterpret_cast<const BatchEntry*>(lead->d_batchTab.data());
-	lead->ensureOverlapObjects();
-	std::vector<cuba_hip_solver::CoarseJob> coarseJobs;
-	for (int i = 0; i < n; i++) hs[i]->lmRunBegin(runs[i], niter, chi2 ? chi2 + (size_t)i * niter : nullptr);
-	const int cls0 = batch_kernel_class(lead->g, lead->sys);      // (a handle that leaves this class during the call solves alone: see cuba_hip_optimize_batch_full)
-	std::vector<int> act, inPcg;
-	std::vector<char> okv((size_t)n);
-	int batchSolves = 0;
-	for (;;)
-	{
-		act.clear();
-		for (int i = 0; i < n; i++) if (hs[i]->lmBeforeTrial(runs[i])) act.push_back(i);
-		if (act.empty()) break;
-		lead->cntBatchIterTrials++;
-		// linearise + Schur and the front half of the reduced solve, each graph on its own stream
-		inPcg.clear();
-		for (int i : act)
-		{
-			hs[i]->schur(true);
-			ctx[i] = cuba_hip_solver::SolveCtx(); ctx[i].batched = true; ctx[i].deferCoarse = &coarseJobs;
-			if (batch_kernel_class(hs[i]->g, hs[i]->sys) != cls0) { okv[i] = hs[i]->solveReduced(); continue; }      // (alone, on its own stream)
-			if (hs[i]->solveBegin(ctx[i])) okv[i] = ctx[i].result; else inPcg.push_back(i);
-		}
-		lead->launchCoarseJobs(coarseJobs);
-		if (!inPcg.empty())
-		{
-			const int m = (int)inPcg.size();
-			int gridSpmvMax = 0, ncMax = 0; size_t ldsMax = 0; int target = 4, budgetMax = 0;
-			for (int a = 0; a < m; a++)
-			{
-				cuba_hip_solver* h = hs[inPcg[a]];
-				BatchEntry& e = hTab[a];
-				e.g = h->g; e.st = h->st; e.sys = h->sys; e.maxIter = ctx[inPcg[a]].maxIter;
-				e.gridSpmv = (h->g.Pf + h->sys.spmv_rows - 1) / h->sys.spmv_rows;
-				gridSpmvMax = std::max(gridSpmvMax, e.gridSpmv); ncMax = std::max(ncMax, h->sys.nc); ldsMax = std::max(ldsMax, batch_pcg2_lds_bytes(h->sys));
-				target = std::max(target, (ctx[inPcg[a]].predicted + 3) / 4 * 4); budgetMax = std::max(budgetMax, ctx[inPcg[a]].budget);
-				if (h != lead) { HIP_TRY(hipEventRecord(evJoin[a], h->stream)); HIP_TRY(hipStreamWaitEvent(bs, evJoin[a], 0)); }
-			}
-			HIP_TRY(hipMemcpyAsync(lead->d_batchTab.data(), hTab, sizeof(BatchEntry) * m, hipMemcpyHostToDevice, bs));
-			const Scalar tol2 = ctx[inPcg[0]].tol2;
-			const cuba_hip_solver* kh = hs[inPcg[0]];      // (every graph in the PCG is of class cls0: the kernels are chosen from the first)
-			int k0 = 0, looks = 0;
-			std::vector<char> conv((size_t)m, 0), broke((size_t)m, 0);
-			bool all = false;
-			while (k0 < budgetMax && !all)
-			{
-				int todo = std::max(4, std::min(target, budgetMax) - k0);
-				while (todo > 0)
-				{
-					const int c = todo;
-					// chunk-local iteration numbers + the advance / stop test / report launch, as a lone handle enqueues its batches
-					for (int k = 0; k < c; k++) launch_pcg_batch_iteration(dTab, m, kh->g, kh->sys, gridSpmvMax, ncMax, ldsMax, k, tol2, bs);
-					launch_pcg_batch_advance(dTab, m, c, bs, tol2);
-					for (int a = 0; a < m; a++) hs[inPcg[a]]->noteReport();
-					k0 += c; todo -= c;
-				}
-				all = true;
-				for (int a = 0; a < m; a++)
-				{
-					cuba_hip_solver* h = hs[inPcg[a]];
-					h->waitReport();
-					const volatile int* f = ctx[inPcg[a]].hInts;
-					if (f[0] != 0) broke[a] = 1;
-					else if (f[2] == 1 || f[1] < std::min(k0, ctx[inPcg[a]].maxIter)) conv[a] = 1;
-					if (!broke[a] && !conv[a] && k0 < ctx[inPcg[a]].budget) all = false;
-					h->cntPcgLooks++; h->cntHostLooks++;
-				}
-				target = k0 + ((looks == 0 && k0 <= 96) ? 4 : std::max(8, k0 / 8 / 4 * 4));
-				looks++;
-			}
-			// back to the graphs' own streams
-			HIP_TRY(hipEventRecord(evFork, bs));
-			for (int a = 0; a < m; a++)
-			{
-				const int i = inPcg[a];
-				cuba_hip_solver* h = hs[i];
-				if (h != lead) HIP_TRY(hipStreamWaitEvent(h->stream, evFork, 0));
-				cuba_hip_solver::SolveCtx& sc = ctx[i];
-				sc.k0 = std::min(k0, std::max(sc.budget, 4)); sc.looks = looks; sc.eagerIters = 0;
-				// (a graph alone stops at ITS iteration budget and hands the solve over; in a batch its iterations run on while the others
-				// need them -- harmless, the exact solve replaces the iterate -- but convergence counts only within the budget)
-				sc.converged = conv[a] != 0 && sc.hInts[1] <= sc.budget;
-				if (!sc.converged && !broke[a]) sc.itersDone = std::min((int)sc.hInts[1], sc.budget);
-				okv[i] = h->retryWithFp64Inverse(broke[a] ? h->solveBrokeDown(sc) : h->solveEnd(sc));
-			}
-			batchSolves++;
-		}
-		for (int i : act) (void)hs[i]->lmAfterSolve(runs[i], okv[i] != 0);
-	}
-	for (int i = 0; i < n; i++) nDone[i] = hs[i]->lmRunEnd(runs[i]);
-	return batchSolves;
+	return optimizeBatch(hs, n, niter, chi2, nDone, full);
 }
 
 int cuba_hip_solver::optimize(int niter, double* chi2Out)

@@ -425,6 +425,11 @@ struct cuba_hip_solver
 	int64_t cntUploads = 0;           // successful cuba_hip_set_graph calls on this handle (never reset: identifies what the device holds)
 	bool acceptUnconverged = false;   // true: a solve that hits max_iter hands back its best iterate as a success (inexact LM step)
 	std::vector<int> pcgHistory;      // PCG iterations of every reduced solve since set_graph (negative = stopped at max_iter)
+	void notePcgHistory(int iterations)
+	{
+		if (pcgHistory.size() >= 65536) pcgHistory.erase(pcgHistory.begin(), pcgHistory.begin() + 32768);   // drivers that never call set_graph again: keep the latest
+		pcgHistory.push_back(iterations);
+	}
 	double prof[CUBA_HIP_PROFILE_ITEMS] = { 0, 0, 0, 0, 0, 0, 0, 0 };
 
 	~cuba_hip_solver()
@@ -811,6 +816,7 @@ struct cuba_hip_solver
 	};
 	bool solveBegin(SolveCtx& sc);
 	void enqueueCoarseSide(int first);
+	void enqueueInversionTail(hipStream_t side, bool firstInvCopy);
 	bool coarseSideLater = false;           // set around the reduced solves of cuba_hip_optimize: SolveCtx::sideLater
 	bool solveBrokeDown(SolveCtx& sc);
 	bool solveEnd(SolveCtx& sc);
@@ -859,8 +865,9 @@ struct cuba_hip_solver
 	int lmRunEnd(LmRun& r);
 	bool batchable() const;
 	std::vector<hipEvent_t> batchEvents;        // (the lead handle of a batch owns the join / fork events and the device table)
-	BatchEntry* h_batchTab = nullptr; int batchTabEntries = 0;
+	BatchEntry* h_batchTab = nullptr;
 	DevBuf<unsigned char> d_batchTab;
+	void ensureBatchTables();
 	DevBuf<double> d_lmState; DevBuf<Scalar> d_lamS;
 	double* h_lmRing = nullptr; double* lmRingDev = nullptr; uint64_t lmRunNonce = 0; int64_t cntLateRecords = 0;
 	int64_t cntHostLooks = 0;           // waits of the host for a device report (PCG looks + LM decisions it had to see)

@@ -10,7 +10,7 @@ Reference of every handle of every batch: a fresh solo handle with the same grap
 sequence of calls.  Compared with np.array_equal: chi2 per iteration, state(), the "lm_trials" counter, pcg_history()[0] (and the
 increment array("xp") in the iterate cases).  Bit-identity to solo is correctness because tests/test_gpu_pcg.py holds the SOLO wrapper of
 each class to the fp64 emulator iterate by iterate; so each case asserts from pcg_config() which class it ran, and from the lead's
-"batch_full_trials" / "batch_iteration_trials" counters which of the two batch loops ran.  Wherever a case runs the fp64 library at the
+"batch_full_trials" / "batch_iteration_trials" counters which of the batch driver's two modes ran.  Wherever a case runs the fp64 library at the
 default tolerance the batched chi2 per iteration is also held to OracleSolver within CHI2_TOL of tests/test_gpu_configs.py.
 
 Cases: 1 every (storage, Nc bucket, cl) class with the smallest and with the largest graph as hs[0]; 2 both SpMV instantiations (the
@@ -18,7 +18,7 @@ Cases: 1 every (storage, Nc bucket, cl) class with the smallest and with the lar
 handles: full path; one of two: iterations-only path); 5 a run that ends inside the batch (table index != handle index); 6 failing
 reduced solves inside a batch; 7 the limits of the call (64, 65, 1 handle, two tolerances, one stream, one handle twice); 8 a second call
 on the same handles, bitwise; 9 fixed vertices and internal renumbering; 10 a handle that leaves its class in the middle of the call
-(fp32-stored coarse inverse dropped after a PCG breakdown).  DESIGN.md section 5."""
+(fp32-stored coarse inverse dropped after a PCG breakdown), on the full and on the iterations-only path.  DESIGN.md section 5."""
 import os
 import sys
 
@@ -153,7 +153,7 @@ def same(a, b):
 
 
 def run_batch(label, specs, plan, path, xp=False, oracle=True, want_class=None):
-    """the batch against its solo references.  path: "full" (cuba_hip_optimize_batch_full: every launch of a trial batched),
+    """the batch against its solo references.  path: "full" (the batch driver's full mode: every launch of a trial batched),
     "iterations" (the PCG iterations only), "fallback" (one handle after the other, batched == 0).  Returns what it ran."""
     hs = [make(sp) for sp in specs]
     cfgs = [h.pcg_config() for h in hs]
@@ -389,8 +389,8 @@ CLASS_CHANGE = {"kept": (dict(direct_fallback=0), {}), "restored": (dict(pcg_agg
 @pytest.mark.parametrize("variant", list(CLASS_CHANGE))
 def test_a_handle_that_leaves_its_class_solves_alone(variant, position):
     """retryWithFp64Inverse (csrc/ba_lm.hip) sets sys.acinv32 = nullptr for the rest of the run: the handle is then of an fp64-storage
-    class and must not sit in the others' W = 4 launches (nor they in its W = 2 ones).  Both batch loops check the class before every
-    trial's solves, let such a handle solve alone, and choose the kernels from the first graph still in the PCG -- position 0 is the
+    class and must not sit in the others' W = 4 launches (nor they in its W = 2 ones).  The batch driver checks the class before every
+    trial's solves, lets such a handle solve alone, and chooses the kernels from the first graph still in the PCG -- position 0 is the
     lead itself changing class"""
     n_it = 40
     opts, other_opts = CLASS_CHANGE[variant]
@@ -402,4 +402,23 @@ def test_a_handle_that_leaves_its_class_solves_alone(variant, position):
     others = [spec("small", **other_opts), spec("mid", **other_opts)]
     specs = others[:position] + [fb] + others[position:]
     got, _ = run_batch(f"class change ({variant}), position {position}", specs, (n_it,), "full", oracle=False, want_class="f32:<=768:cl2")
+    assert got[position]["fallbacks"] == want["fallbacks"]
+
+
+def class_change_iterations_only(position):
+    """the "kept" handle beside a plain and a mixed-precision one: the batch that keeps everything but the PCG iterations per stream"""
+    fb = spec("gaugefree", robust_none=1, direct_fallback=0)
+    others = [spec("small"), spec("mid", mixed_precision=1)]
+    return fb, others[:position] + [fb] + others[position:]
+
+
+@pytest.mark.parametrize("position", [0, 1])
+def test_a_handle_that_leaves_its_class_solves_alone_on_the_iterations_only_path(position):
+    """the same with the trial's other launches on the handles' own streams: the handle that left the class solves alone on ITS stream,
+    is no entry of the compact table, and the join / fork events go round it"""
+    n_it = 40
+    fb, specs = class_change_iterations_only(position)
+    want = solo(fb, (n_it,))
+    assert want["fallbacks"] >= 1 and want["coarse_fp32"] == 0, (want["fallbacks"], want["coarse_fp32"])
+    got, _ = run_batch(f"class change (kept), iterations only, position {position}", specs, (n_it,), "iterations", oracle=False, want_class="f32:<=768:cl2")
     assert got[position]["fallbacks"] == want["fallbacks"]
