@@ -177,6 +177,43 @@ def _d(a):
     return a.ctypes.data_as(_dp) if a is not None else None
 
 
+def _i(a):
+    return a.ctypes.data_as(_ip) if a is not None else None
+
+
+# ---- the factor setters' arguments as the C ABI takes them ------------------------------------------
+def _index(a):
+    """int32[n]: vertices in the solver numbering"""
+    return np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+
+
+def _rows(a, n, width=3):
+    """float64[n, width], or None"""
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(n, width)
+
+
+def _information(a, n, d):
+    """float64[n, d, d], every block column-major: the transpose of the row-major reading (symmetric matrices: the two agree up to the
+    symmetrisation the library applies)"""
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(n, d, d).transpose(0, 2, 1))
+
+
+def _scalars(a, n):
+    """float64[n], a scalar broadcast"""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (n,)))
+
+
+def _kernels(kind, delta, n):
+    """(int32[n], float64[n]) of a set of n factors, scalars broadcast; either may be None (the library wants both or neither)"""
+    if kind is not None:
+        kind = np.ascontiguousarray(np.full(n, kind) if np.ndim(kind) == 0 else kind, dtype=np.int32).reshape(-1)
+    if delta is not None:
+        delta = np.ascontiguousarray(np.full(n, delta) if np.ndim(delta) == 0 else delta, dtype=np.float64).reshape(-1)
+    if (kind is not None and kind.size != n) or (delta is not None and delta.size != n):
+        raise ValueError("kind / delta differ in length from the set")
+    return kind, delta
+
+
 def dense_inverse(A, precision="f64", device=0):
     """The library's blocked Gauss-Jordan inversion (coarse level of the preconditioner) applied to an SPD matrix: test hook."""
     A = np.asfortranarray(A, dtype=np.float64)
@@ -497,29 +534,22 @@ class HipSolver:
     def set_pose_priors(self, pose, q, t, info):
         """SE(3) pose priors (cuba_hip_set_pose_priors), replacing the handle's set: pose[n] in the solver numbering, q[n, 4] (x, y, z, w),
         t[n, 3], info[n, 6, 6] in the [omega, upsilon] order of the pose update (symmetric).  An empty pose list clears the set."""
-        pose = np.ascontiguousarray(pose, dtype=np.int32).reshape(-1)
+        pose = _index(pose)
         n = len(pose)
-        q = np.ascontiguousarray(q, dtype=np.float64).reshape(n, 4)
-        t = np.ascontiguousarray(t, dtype=np.float64).reshape(n, 3)
-        # (column-major 6 x 6 blocks: the transpose of the row-major reading)
-        info = np.ascontiguousarray(np.asarray(info, dtype=np.float64).reshape(n, 6, 6).transpose(0, 2, 1))
-        self._ck(self.lib.cuba_hip_set_pose_priors(self.h, n, pose.ctypes.data_as(_ip), _d(q), _d(t), _d(info)))
+        q, t, info = _rows(q, n, 4), _rows(t, n), _information(info, n, 6)
+        self._ck(self.lib.cuba_hip_set_pose_priors(self.h, n, _i(pose), _d(q), _d(t), _d(info)))
         self._n_factors["prior"] = n
 
     def set_relative_pose_edges(self, pose_i, pose_j, q, t, info):
         """SE(3) relative-pose edges (cuba_hip_set_relative_pose_edges), replacing the handle's set: pose_i[n], pose_j[n] in the solver
         numbering, the measured T_j T_i^-1 as q[n, 4] (x, y, z, w) and t[n, 3], info[n, 6, 6] symmetric in [omega, upsilon] order;
         n = 0 clears."""
-        pose_i = np.ascontiguousarray(pose_i, dtype=np.int32).reshape(-1)
-        pose_j = np.ascontiguousarray(pose_j, dtype=np.int32).reshape(-1)
+        pose_i, pose_j = _index(pose_i), _index(pose_j)
         n = int(pose_i.size)
-        q = np.ascontiguousarray(q, dtype=np.float64).reshape(n, 4)
-        t = np.ascontiguousarray(t, dtype=np.float64).reshape(n, 3)
-        # (symmetric matrices: row- and column-major agree up to the symmetrisation the library applies)
-        info = np.ascontiguousarray(np.asarray(info, dtype=np.float64).reshape(n, 6, 6).transpose(0, 2, 1))
+        q, t, info = _rows(q, n, 4), _rows(t, n), _information(info, n, 6)
         if pose_j.size != n:
             raise ValueError("pose_i and pose_j differ in length")
-        self._ck(self.lib.cuba_hip_set_relative_pose_edges(self.h, n, pose_i.ctypes.data_as(_ip), pose_j.ctypes.data_as(_ip), _d(q), _d(t), _d(info)))
+        self._ck(self.lib.cuba_hip_set_relative_pose_edges(self.h, n, _i(pose_i), _i(pose_j), _d(q), _d(t), _d(info)))
         self._n_factors["relative_pose"] = n
 
     def set_pose_factor_robust_kernels(self, factor_type, kind, delta):
@@ -556,19 +586,11 @@ class HipSolver:
         """Landmark position priors (cuba_hip_set_landmark_priors), replacing the handle's set: landmark[n] in the solver numbering,
         xyz[n, 3], info[n, 3, 3] symmetric; kind[n] (0 none, 1 Huber, 2 Tukey, 3 Cauchy) and delta[n] together or not at all (scalars
         broadcast).  An empty landmark list clears the set."""
-        landmark = np.ascontiguousarray(landmark, dtype=np.int32).reshape(-1)
+        landmark = _index(landmark)
         n = int(landmark.size)
-        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(n, 3)
-        # (column-major 3 x 3 blocks: the transpose of the row-major reading)
-        info = np.ascontiguousarray(np.asarray(info, dtype=np.float64).reshape(n, 3, 3).transpose(0, 2, 1))
-        if kind is not None:
-            kind = np.ascontiguousarray(np.full(n, kind) if np.ndim(kind) == 0 else kind, dtype=np.int32).reshape(-1)
-        if delta is not None:
-            delta = np.ascontiguousarray(np.full(n, delta) if np.ndim(delta) == 0 else delta, dtype=np.float64).reshape(-1)
-        if (kind is not None and kind.size != n) or (delta is not None and delta.size != n):
-            raise ValueError("kind / delta differ in length from the set")
-        self._ck(self.lib.cuba_hip_set_landmark_priors(self.h, n, landmark.ctypes.data_as(_ip), _d(xyz), _d(info),
-                                                       kind.ctypes.data_as(_ip) if kind is not None else None, _d(delta)))
+        xyz, info = _rows(xyz, n), _information(info, n, 3)
+        kind, delta = _kernels(kind, delta, n)
+        self._ck(self.lib.cuba_hip_set_landmark_priors(self.h, n, _i(landmark), _d(xyz), _d(info), _i(kind), _d(delta)))
         self._n_factors["landmark_prior"] = n
 
     def landmark_prior_chi_squares(self):
@@ -580,21 +602,11 @@ class HipSolver:
         solver numbering, the measured world positions position[n, 3], info[n, 3, 3] symmetric, lever_arm[n, 3] (the measured point in
         the camera frame; None: the camera centre); kind[n] (0 none, 1 Huber, 2 Tukey, 3 Cauchy) and delta[n] together or not at all
         (scalars broadcast).  An empty pose list clears the set."""
-        pose = np.ascontiguousarray(pose, dtype=np.int32).reshape(-1)
+        pose = _index(pose)
         n = int(pose.size)
-        position = np.ascontiguousarray(position, dtype=np.float64).reshape(n, 3)
-        # (column-major 3 x 3 blocks: the transpose of the row-major reading)
-        info = np.ascontiguousarray(np.asarray(info, dtype=np.float64).reshape(n, 3, 3).transpose(0, 2, 1))
-        if lever_arm is not None:
-            lever_arm = np.ascontiguousarray(lever_arm, dtype=np.float64).reshape(n, 3)
-        if kind is not None:
-            kind = np.ascontiguousarray(np.full(n, kind) if np.ndim(kind) == 0 else kind, dtype=np.int32).reshape(-1)
-        if delta is not None:
-            delta = np.ascontiguousarray(np.full(n, delta) if np.ndim(delta) == 0 else delta, dtype=np.float64).reshape(-1)
-        if (kind is not None and kind.size != n) or (delta is not None and delta.size != n):
-            raise ValueError("kind / delta differ in length from the set")
-        self._ck(self.lib.cuba_hip_set_position_factors(self.h, n, pose.ctypes.data_as(_ip), _d(position), _d(lever_arm), _d(info),
-                                                        kind.ctypes.data_as(_ip) if kind is not None else None, _d(delta)))
+        position, info, lever_arm = _rows(position, n), _information(info, n, 3), _rows(lever_arm, n)
+        kind, delta = _kernels(kind, delta, n)
+        self._ck(self.lib.cuba_hip_set_position_factors(self.h, n, _i(pose), _d(position), _d(lever_arm), _d(info), _i(kind), _d(delta)))
         self._n_factors["position_factor"] = n
 
     def position_factor_chi_squares(self):
@@ -606,20 +618,11 @@ class HipSolver:
         set: pose[n] in the solver numbering, the world vectors world_dir[n, 3], the same vectors as measured in the camera frame
         measured_dir[n, 3] (neither is normalised), info[n, 3, 3] symmetric; kind[n] (0 none, 1 Huber, 2 Tukey, 3 Cauchy) and delta[n]
         together or not at all (scalars broadcast).  An empty pose list clears the set."""
-        pose = np.ascontiguousarray(pose, dtype=np.int32).reshape(-1)
+        pose = _index(pose)
         n = int(pose.size)
-        world_dir = np.ascontiguousarray(world_dir, dtype=np.float64).reshape(n, 3)
-        measured_dir = np.ascontiguousarray(measured_dir, dtype=np.float64).reshape(n, 3)
-        # (column-major 3 x 3 blocks: the transpose of the row-major reading)
-        info = np.ascontiguousarray(np.asarray(info, dtype=np.float64).reshape(n, 3, 3).transpose(0, 2, 1))
-        if kind is not None:
-            kind = np.ascontiguousarray(np.full(n, kind) if np.ndim(kind) == 0 else kind, dtype=np.int32).reshape(-1)
-        if delta is not None:
-            delta = np.ascontiguousarray(np.full(n, delta) if np.ndim(delta) == 0 else delta, dtype=np.float64).reshape(-1)
-        if (kind is not None and kind.size != n) or (delta is not None and delta.size != n):
-            raise ValueError("kind / delta differ in length from the set")
-        self._ck(self.lib.cuba_hip_set_direction_factors(self.h, n, pose.ctypes.data_as(_ip), _d(world_dir), _d(measured_dir), _d(info),
-                                                         kind.ctypes.data_as(_ip) if kind is not None else None, _d(delta)))
+        world_dir, measured_dir, info = _rows(world_dir, n), _rows(measured_dir, n), _information(info, n, 3)
+        kind, delta = _kernels(kind, delta, n)
+        self._ck(self.lib.cuba_hip_set_direction_factors(self.h, n, _i(pose), _d(world_dir), _d(measured_dir), _d(info), _i(kind), _d(delta)))
         self._n_factors["direction_factor"] = n
 
     def direction_factor_chi_squares(self):
@@ -632,21 +635,11 @@ class HipSolver:
         informations info[n] (1 / sigma^2, >= 0), lever_arm[n, 3] (the ranging antenna in the camera frame; None: the camera centre);
         kind[n] (0 none, 1 Huber, 2 Tukey, 3 Cauchy) and delta[n] together or not at all (scalars broadcast).  An empty pose list clears
         the set."""
-        pose = np.ascontiguousarray(pose, dtype=np.int32).reshape(-1)
+        pose = _index(pose)
         n = int(pose.size)
-        anchor = np.ascontiguousarray(anchor, dtype=np.float64).reshape(n, 3)
-        range = np.ascontiguousarray(np.broadcast_to(np.asarray(range, dtype=np.float64), (n,)))
-        info = np.ascontiguousarray(np.broadcast_to(np.asarray(info, dtype=np.float64), (n,)))
-        if lever_arm is not None:
-            lever_arm = np.ascontiguousarray(lever_arm, dtype=np.float64).reshape(n, 3)
-        if kind is not None:
-            kind = np.ascontiguousarray(np.full(n, kind) if np.ndim(kind) == 0 else kind, dtype=np.int32).reshape(-1)
-        if delta is not None:
-            delta = np.ascontiguousarray(np.full(n, delta) if np.ndim(delta) == 0 else delta, dtype=np.float64).reshape(-1)
-        if (kind is not None and kind.size != n) or (delta is not None and delta.size != n):
-            raise ValueError("kind / delta differ in length from the set")
-        self._ck(self.lib.cuba_hip_set_range_factors(self.h, n, pose.ctypes.data_as(_ip), _d(anchor), _d(range), _d(lever_arm), _d(info),
-                                                     kind.ctypes.data_as(_ip) if kind is not None else None, _d(delta)))
+        anchor, range, info, lever_arm = _rows(anchor, n), _scalars(range, n), _scalars(info, n), _rows(lever_arm, n)
+        kind, delta = _kernels(kind, delta, n)
+        self._ck(self.lib.cuba_hip_set_range_factors(self.h, n, _i(pose), _d(anchor), _d(range), _d(lever_arm), _d(info), _i(kind), _d(delta)))
         self._n_factors["range_factor"] = n
 
     def range_factor_chi_squares(self):
@@ -659,25 +652,14 @@ class HipSolver:
         informations info[n] (1 / sigma^2, >= 0), lever_arm_i[n, 3] and lever_arm_j[n, 3] (the two points in their camera frames; None:
         the camera centre); kind[n] (0 none, 1 Huber, 2 Tukey, 3 Cauchy) and delta[n] together or not at all (scalars broadcast).  An
         empty pose list clears the set.  The free-free pairs are part of the topology, as the relative-pose edges'."""
-        pose_i = np.ascontiguousarray(pose_i, dtype=np.int32).reshape(-1)
-        pose_j = np.ascontiguousarray(pose_j, dtype=np.int32).reshape(-1)
+        pose_i, pose_j = _index(pose_i), _index(pose_j)
         n = int(pose_i.size)
         if pose_j.size != n:
             raise ValueError("pose_i / pose_j differ in length")
-        range = np.ascontiguousarray(np.broadcast_to(np.asarray(range, dtype=np.float64), (n,)))
-        info = np.ascontiguousarray(np.broadcast_to(np.asarray(info, dtype=np.float64), (n,)))
-        if lever_arm_i is not None:
-            lever_arm_i = np.ascontiguousarray(lever_arm_i, dtype=np.float64).reshape(n, 3)
-        if lever_arm_j is not None:
-            lever_arm_j = np.ascontiguousarray(lever_arm_j, dtype=np.float64).reshape(n, 3)
-        if kind is not None:
-            kind = np.ascontiguousarray(np.full(n, kind) if np.ndim(kind) == 0 else kind, dtype=np.int32).reshape(-1)
-        if delta is not None:
-            delta = np.ascontiguousarray(np.full(n, delta) if np.ndim(delta) == 0 else delta, dtype=np.float64).reshape(-1)
-        if (kind is not None and kind.size != n) or (delta is not None and delta.size != n):
-            raise ValueError("kind / delta differ in length from the set")
-        self._ck(self.lib.cuba_hip_set_pose_range_factors(self.h, n, pose_i.ctypes.data_as(_ip), pose_j.ctypes.data_as(_ip), _d(range), _d(lever_arm_i),
-                                                          _d(lever_arm_j), _d(info), kind.ctypes.data_as(_ip) if kind is not None else None, _d(delta)))
+        range, info, lever_arm_i, lever_arm_j = _scalars(range, n), _scalars(info, n), _rows(lever_arm_i, n), _rows(lever_arm_j, n)
+        kind, delta = _kernels(kind, delta, n)
+        self._ck(self.lib.cuba_hip_set_pose_range_factors(self.h, n, _i(pose_i), _i(pose_j), _d(range), _d(lever_arm_i), _d(lever_arm_j), _d(info),
+                                                          _i(kind), _d(delta)))
         self._n_factors["pose_range_factor"] = n
 
     def pose_range_factor_chi_squares(self):

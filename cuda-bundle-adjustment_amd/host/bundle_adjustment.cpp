@@ -13,6 +13,7 @@
 #include "cuda_bundle_adjustment.h"
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstring>
 #include <cstddef>
@@ -26,6 +27,8 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <tuple>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -91,10 +94,135 @@ private:
 	std::vector<T*> items_;
 };
 
-// one kind of factor (cuba::PosePrior, cuba::RelativePoseEdge, cuba::LandmarkPrior, cuba::PositionFactor, cuba::DirectionFactor, cuba::RangeFactor, cuba::PoseRangeFactor) as an object keeps it
+// ---- the factor kinds -------------------------------------------------------------------------------
+// Everything the host layer does with a factor exists once (HipBundleAdjustment: addFactor, upload, readChiSquares, dropFactorsOf,
+// clear; below the class: the three public functions of every kind); FactorKind<F> holds what is a kind's own:
+//   fn, noun, ofA   "cuba::addX", "a factor" / "an edge" / "a prior" and "a factor" / ..., for the messages
+//   kernelType      -1: kind | delta travel inside the setter (null | null when no factor has a kernel); otherwise the factor type
+//                   under which cuba_hip_set_pose_factor_robust_kernels takes them after the setter, and only when some factor has one
+//   inBlockPattern  its pose pairs are part of the reduced matrix's pattern: on a graph upload the set goes up again before
+//                   cuba_hip_build_structure
+//   set             fields -> flat arrays -> the C setter; setName, chiSquares, chiName: the setter's name and the chi2 reader
+// What a factor hangs on -- one pose, one landmark, two different poses -- is read off its struct (`vertex`, or `vertexI` and `vertexJ`).
+// A new kind: its struct in the header, its FactorKind and its place in FactorLists here, its three public functions at the end of the file.
+template <class F> struct FactorKind;
+
+template <class F> auto ends(const F& f) -> std::array<decltype(F::vertex), 1> { return { f.vertex }; }
+template <class F> auto ends(const F& f) -> std::array<decltype(F::vertexI), 2> { return { f.vertexI, f.vertexJ }; }
+template <class V, size_t N> bool distinctVertices(const std::array<V*, N>& e) { return e.front() && e.back() && (N == 1 || e.front() != e.back()); }
+inline const char* whatItNeeds(const std::array<PoseVertex*, 1>&) { return "a pose vertex"; }
+inline const char* whatItNeeds(const std::array<LandmarkVertex*, 1>&) { return "a landmark vertex"; }
+inline const char* whatItNeeds(const std::array<PoseVertex*, 2>&) { return "two different pose vertices"; }
+
+// one field of every factor of a set as the C ABI takes it, factor after factor
+struct Values { const double* p; size_t n; };
+template <size_t N> Values values(const std::array<double, N>& a) { return { a.data(), N }; }
+inline Values values(const double& x) { return { &x, 1 }; }
+inline Values values(const Array<double, 3>& v) { return { v.data(), 3 }; }
+inline Values values(const PoseVertex::Rotation& q) { return { q.coeffs().data(), 4 }; }       // (x, y, z, w)
+template <class F, class M> std::vector<double> column(const std::vector<F*>& factors, M F::* field)
+{
+	const size_t w = factors.empty() ? 0 : values(factors[0]->*field).n;
+	std::vector<double> a(w * factors.size());
+	for (size_t k = 0; k < factors.size(); k++) std::copy_n(values(factors[k]->*field).p, w, a.begin() + w * k);
+	return a;
+}
+
+template <> struct FactorKind<PosePrior>
+{
+	static constexpr const char* fn = "cuba::addPosePrior", *noun = "a prior", *ofA = "a prior";
+	static constexpr int kernelType = 0;
+	static constexpr bool inBlockPattern = false;
+	static constexpr const char* setName = "cuba_hip_set_pose_priors", *chiName = "cuba_hip_prior_chi_squares";
+	static constexpr auto chiSquares = cuba_hip_prior_chi_squares;
+	static int set(cuba_hip_solver* s, const std::vector<PosePrior*>& f, const int32_t* pose, const int32_t*, const int32_t*, const double*)
+	{
+		return cuba_hip_set_pose_priors(s, (int)f.size(), pose, column(f, &PosePrior::q).data(), column(f, &PosePrior::t).data(), column(f, &PosePrior::information).data());
+	}
+};
+template <> struct FactorKind<RelativePoseEdge>
+{
+	static constexpr const char* fn = "cuba::addRelativePoseEdge", *noun = "an edge", *ofA = "a relative-pose edge";
+	static constexpr int kernelType = 1;
+	static constexpr bool inBlockPattern = true;
+	static constexpr const char* setName = "cuba_hip_set_relative_pose_edges", *chiName = "cuba_hip_relative_pose_chi_squares";
+	static constexpr auto chiSquares = cuba_hip_relative_pose_chi_squares;
+	static int set(cuba_hip_solver* s, const std::vector<RelativePoseEdge*>& f, const int32_t* pi, const int32_t* pj, const int32_t*, const double*)
+	{
+		return cuba_hip_set_relative_pose_edges(s, (int)f.size(), pi, pj, column(f, &RelativePoseEdge::q).data(), column(f, &RelativePoseEdge::t).data(),
+			column(f, &RelativePoseEdge::information).data());
+	}
+};
+template <> struct FactorKind<LandmarkPrior>
+{
+	static constexpr const char* fn = "cuba::addLandmarkPrior", *noun = "a prior", *ofA = "a prior";
+	static constexpr int kernelType = -1;
+	static constexpr bool inBlockPattern = false;
+	static constexpr const char* setName = "cuba_hip_set_landmark_priors", *chiName = "cuba_hip_landmark_prior_chi_squares";
+	static constexpr auto chiSquares = cuba_hip_landmark_prior_chi_squares;
+	static int set(cuba_hip_solver* s, const std::vector<LandmarkPrior*>& f, const int32_t* lm, const int32_t*, const int32_t* kind, const double* delta)
+	{
+		return cuba_hip_set_landmark_priors(s, (int)f.size(), lm, column(f, &LandmarkPrior::position).data(), column(f, &LandmarkPrior::information).data(), kind, delta);
+	}
+};
+template <> struct FactorKind<PositionFactor>
+{
+	static constexpr const char* fn = "cuba::addPositionFactor", *noun = "a factor", *ofA = "a factor";
+	static constexpr int kernelType = -1;
+	static constexpr bool inBlockPattern = false;
+	static constexpr const char* setName = "cuba_hip_set_position_factors", *chiName = "cuba_hip_position_factor_chi_squares";
+	static constexpr auto chiSquares = cuba_hip_position_factor_chi_squares;
+	static int set(cuba_hip_solver* s, const std::vector<PositionFactor*>& f, const int32_t* pose, const int32_t*, const int32_t* kind, const double* delta)
+	{
+		return cuba_hip_set_position_factors(s, (int)f.size(), pose, column(f, &PositionFactor::position).data(), column(f, &PositionFactor::leverArm).data(),
+			column(f, &PositionFactor::information).data(), kind, delta);
+	}
+};
+template <> struct FactorKind<DirectionFactor>
+{
+	static constexpr const char* fn = "cuba::addDirectionFactor", *noun = "a factor", *ofA = "a factor";
+	static constexpr int kernelType = -1;
+	static constexpr bool inBlockPattern = false;
+	static constexpr const char* setName = "cuba_hip_set_direction_factors", *chiName = "cuba_hip_direction_factor_chi_squares";
+	static constexpr auto chiSquares = cuba_hip_direction_factor_chi_squares;
+	static int set(cuba_hip_solver* s, const std::vector<DirectionFactor*>& f, const int32_t* pose, const int32_t*, const int32_t* kind, const double* delta)
+	{
+		return cuba_hip_set_direction_factors(s, (int)f.size(), pose, column(f, &DirectionFactor::worldDirection).data(), column(f, &DirectionFactor::measurement).data(),
+			column(f, &DirectionFactor::information).data(), kind, delta);
+	}
+};
+template <> struct FactorKind<RangeFactor>
+{
+	static constexpr const char* fn = "cuba::addRangeFactor", *noun = "a factor", *ofA = "a factor";
+	static constexpr int kernelType = -1;
+	static constexpr bool inBlockPattern = false;
+	static constexpr const char* setName = "cuba_hip_set_range_factors", *chiName = "cuba_hip_range_factor_chi_squares";
+	static constexpr auto chiSquares = cuba_hip_range_factor_chi_squares;
+	static int set(cuba_hip_solver* s, const std::vector<RangeFactor*>& f, const int32_t* pose, const int32_t*, const int32_t* kind, const double* delta)
+	{
+		return cuba_hip_set_range_factors(s, (int)f.size(), pose, column(f, &RangeFactor::anchor).data(), column(f, &RangeFactor::range).data(),
+			column(f, &RangeFactor::leverArm).data(), column(f, &RangeFactor::information).data(), kind, delta);
+	}
+};
+template <> struct FactorKind<PoseRangeFactor>
+{
+	static constexpr const char* fn = "cuba::addPoseRangeFactor", *noun = "a factor", *ofA = "a factor";
+	static constexpr int kernelType = -1;
+	static constexpr bool inBlockPattern = true;
+	static constexpr const char* setName = "cuba_hip_set_pose_range_factors", *chiName = "cuba_hip_pose_range_factor_chi_squares";
+	static constexpr auto chiSquares = cuba_hip_pose_range_factor_chi_squares;
+	static int set(cuba_hip_solver* s, const std::vector<PoseRangeFactor*>& f, const int32_t* pi, const int32_t* pj, const int32_t* kind, const double* delta)
+	{
+		return cuba_hip_set_pose_range_factors(s, (int)f.size(), pi, pj, column(f, &PoseRangeFactor::range).data(), column(f, &PoseRangeFactor::leverArmI).data(),
+			column(f, &PoseRangeFactor::leverArmJ).data(), column(f, &PoseRangeFactor::information).data(), kind, delta);
+	}
+};
+
+// the factors of one kind as an object keeps them
 template <class F>
 struct FactorList
 {
+	using Kind = FactorKind<F>;
 	std::vector<F*> items, uploaded;      // in the caller's order; the set the last initialize() handed to the device
 	std::map<const F*, double> chi;       // per object of `uploaded`, from the last optimize()
 	bool onDevice = false, dirty = false;
@@ -126,6 +254,14 @@ struct FactorList
 		for (size_t k = 0; k < c.size(); k++) chi[uploaded[k]] = c[k];
 	}
 };
+
+// All kinds of an object.  The order of this tuple is the order of the C ABI calls, and part of the contract (tests/golden/host_factor_calls.txt):
+//   on a graph upload  the kinds in the block pattern -- relative-pose edges, range factors between poses -- before the structure build;
+//   before every solve all kinds: priors, relative-pose edges, landmark priors, position, direction, range, pose range (a set that went
+//                      up already, or is empty on both sides, sends nothing);
+//   after a solve      the chi2 of the kinds outside the block pattern, then of those in it.
+using FactorLists = std::tuple<FactorList<PosePrior>, FactorList<RelativePoseEdge>, FactorList<LandmarkPrior>, FactorList<PositionFactor>,
+	FactorList<DirectionFactor>, FactorList<RangeFactor>, FactorList<PoseRangeFactor>>;
 
 class HipBundleAdjustment final : public CudaBundleAdjustment
 {
@@ -162,12 +298,7 @@ public:
 		if (it == poses_.end()) return;
 		const std::vector<BaseEdge*> incident(it->second->edges.begin(), it->second->edges.end());
 		for (BaseEdge* e : incident) removeEdge(e);
-		priors_.removeIf([&](const PosePrior* p) { return p->vertex == it->second; });
-		posFactors_.removeIf([&](const PositionFactor* f) { return f->vertex == it->second; });
-		dirFactors_.removeIf([&](const DirectionFactor* f) { return f->vertex == it->second; });
-		rngFactors_.removeIf([&](const RangeFactor* f) { return f->vertex == it->second; });
-		relEdges_.removeIf([&](const RelativePoseEdge* e) { return e->vertexI == it->second || e->vertexJ == it->second; });
-		prngFactors_.removeIf([&](const PoseRangeFactor* f) { return f->vertexI == it->second || f->vertexJ == it->second; });
+		dropFactorsOf(it->second);
 		poses_.erase(it);
 		posesDirty_ = true;
 	}
@@ -178,7 +309,7 @@ public:
 		if (it == landmarks_.end()) return;
 		const std::vector<BaseEdge*> incident(it->second->edges.begin(), it->second->edges.end());
 		for (BaseEdge* e : incident) removeEdge(e);
-		lmPriors_.removeIf([&](const LandmarkPrior* p) { return p->vertex == it->second; });
+		dropFactorsOf(it->second);
 		landmarks_.erase(it);
 		landmarksDirty_ = true;
 	}
@@ -208,8 +339,8 @@ public:
 	void initialize() override
 	{
 		covPoseIndex_.clear(); covLmIndex_.clear();          // (marginal covariances describe the graph they were computed on)
-		priors_.dirty = relEdges_.dirty = lmPriors_.dirty = posFactors_.dirty = dirFactors_.dirty = rngFactors_.dirty = prngFactors_.dirty = true;      // (the factors as they stand now go to the device with the next solve)
-		poseIdx_.clear();                                    // (the factors' pose index: rebuilt below from the poses active now)
+		forEachKind([](auto& list) { list.dirty = true; });      // (the factors as they stand now go to the device with the next solve)
+		poseIdx_.clear(); landmarkIdx_.clear();              // (the factors' vertex indices: rebuilt from the vertices active now by the first factor that asks)
 		const auto t0 = std::chrono::steady_clock::now();
 		static const bool dbg = std::getenv("CUBA_HIP_DEBUG") != nullptr;
 		auto tl = t0;
@@ -392,60 +523,53 @@ public:
 				"cuba_hip_set_graph_begin");
 			// (an upload clears the handle's relative-pose edges and range factors between poses; their pose pairs are part of the block
 			// pattern, so they go up before the structure analysis: an unchanged pair set then keeps the structure of the previous initialize())
-			relEdges_.onDevice = false; relEdges_.dirty = true;
-			prngFactors_.onDevice = false; prngFactors_.dirty = true;
-			uploadRelativePoseEdges();
-			uploadPoseRangeFactors();
+			forEachKind([](auto& list) { if (inBlockPattern(list)) { list.onDevice = false; list.dirty = true; } });
+			forEachKind([this](auto& list) { if (inBlockPattern(list)) upload(list); });
 			check(cuba_hip_build_structure(solver_), "cuba_hip_build_structure");
 			check(cuba_hip_set_graph_end(solver_), "cuba_hip_set_graph_end");
 			graphDirty_ = false;
-			priors_.dirty = lmPriors_.dirty = posFactors_.dirty = dirFactors_.dirty = rngFactors_.dirty = true;          // (an upload clears the handle's priors, position, direction and range factors)
+			forEachKind([](auto& list) { if (!inBlockPattern(list)) list.dirty = true; });          // (an upload clears the handle's other factors too)
 			uploadedOnce_ = true; edgesChangedSinceUpload_ = valuesChangedSinceUpload_ = false;       // from here on the device holds exactly these edges and values
 			(void)cuba_hip_get_counter(solver_, "graph_uploads", &uploadGeneration_);
 		}
 		lap("create + set_graph");
-		uploadPriors();
-		uploadRelativePoseEdges();
-		uploadLandmarkPriors();
-		uploadPositionFactors();
-		uploadDirectionFactors();
-		uploadRangeFactors();
-		uploadPoseRangeFactors();
+		forEachKind([this](auto& list) { upload(list); });
 	}
 
-	// ---- factors (extensions: cuba::addPosePrior, cuba::addRelativePoseEdge, cuba::addLandmarkPrior, cuba::addPositionFactor, cuba::addDirectionFactor, cuba::addRangeFactor, cuba::addPoseRangeFactor) --
-	// (public: the extension functions below remove and look up through them)
-	FactorList<PosePrior> priors_;
-	FactorList<RelativePoseEdge> relEdges_;
-	FactorList<LandmarkPrior> lmPriors_;
-	FactorList<PositionFactor> posFactors_;
-	FactorList<DirectionFactor> dirFactors_;
-	FactorList<RangeFactor> rngFactors_;
-	FactorList<PoseRangeFactor> prngFactors_;
-	// index of a factor's vertex among the active poses (the map is built with the first factor of an initialize()); `refusal`: the message
-	// for a vertex that is not part of the graph
-	int32_t factorPose(const PoseVertex* v, const char* refusal)
+	// ---- factors (FactorKind, FactorLists above) -----------------------------------------------------
+	FactorLists factors_;
+	template <class Fn> void forEachKind(Fn&& fn) { std::apply([&](auto&... list) { (fn(list), ...); }, factors_); }
+	template <class F> static constexpr bool inBlockPattern(const FactorList<F>&) { return FactorKind<F>::inBlockPattern; }
+	// (public: the extension functions below remove and look up through it)
+	template <class F> FactorList<F>& list() { return std::get<FactorList<F>>(factors_); }
+	template <class F> const FactorList<F>& list() const { return std::get<FactorList<F>>(factors_); }
+
+	template <class F> void addFactor(F* f)
 	{
-		if (poseIdx_.empty())
-			for (size_t i = 0; i < activePoses_.size(); i++) poseIdx_[activePoses_[i]] = (int32_t)i;
-		const auto it = poseIdx_.find(v);
-		if (it == poseIdx_.end()) throw std::invalid_argument(refusal);
+		using K = FactorKind<F>;
+		using Ends = decltype(ends(*f));
+		if (!f || !distinctVertices(ends(*f))) throw std::invalid_argument(std::string(K::fn) + ": " + K::noun + " needs " + whatItNeeds(Ends()));
+		list<F>().add(f);
+	}
+	// a removed vertex takes its factors with it (initialize() would refuse them: their vertex is not part of the graph)
+	void dropFactorsOf(const void* vertex)
+	{
+		forEachKind([vertex](auto& list) {
+			list.removeIf([vertex](const auto* f) { for (const void* v : ends(*f)) if (v == vertex) return true; return false; });
+		});
+	}
+	// index of a factor's vertex among the active ones (each map is built with the first factor of an initialize() that asks);
+	// `refusal`: the message for a vertex that is not part of the graph
+	template <class V> static int32_t indexIn(std::map<const V*, int32_t>& index, const std::vector<V*>& active, const V* v, const std::string& refusal)
+	{
+		if (index.empty())
+			for (size_t i = 0; i < active.size(); i++) index[active[i]] = (int32_t)i;
+		const auto it = index.find(v);
+		if (it == index.end()) throw std::invalid_argument(refusal);
 		return it->second;
 	}
-	// q | t | information of a set of factors as the C ABI takes them
-	struct FactorArrays { std::vector<double> q, t, info; };
-	template <class F> static FactorArrays packFactors(const std::vector<F*>& factors)
-	{
-		const size_t n = factors.size();
-		FactorArrays a{ std::vector<double>(4 * n), std::vector<double>(3 * n), std::vector<double>(36 * n) };
-		for (size_t k = 0; k < n; k++)
-		{
-			for (int i = 0; i < 4; i++) a.q[4 * k + i] = factors[k]->q.coeffs().data()[i];
-			for (int i = 0; i < 3; i++) a.t[3 * k + i] = factors[k]->t.data()[i];
-			std::copy(factors[k]->information.begin(), factors[k]->information.end(), a.info.begin() + 36 * k);
-		}
-		return a;
-	}
+	int32_t vertexIndex(const PoseVertex* v, const std::string& refusal) { return indexIn(poseIdx_, activePoses_, v, refusal); }
+	int32_t vertexIndex(const LandmarkVertex* v, const std::string& refusal) { return indexIn(landmarkIdx_, activeLandmarks_, v, refusal); }
 	// kind | delta of a set of factors as the C ABI takes them; any: a factor has a kernel
 	struct FactorKernels { std::vector<int32_t> kind; std::vector<double> delta; bool any = false; };
 	template <class F> static FactorKernels packKernels(const std::vector<F*>& factors)
@@ -459,184 +583,37 @@ public:
 		}
 		return r;
 	}
-	// the pose factors' robust kernels follow the set they belong to (a set without any: nothing is sent, the handle has none after the upload)
-	template <class F> void uploadFactorKernels(int factorType, const std::vector<F*>& factors)
+	// the set as it stands goes to the device, if it changed since it last went (an empty set that replaces one: the clearing call)
+	template <class F> void upload(FactorList<F>& list)
 	{
-		const FactorKernels r = packKernels(factors);
-		if (r.any) check(cuba_hip_set_pose_factor_robust_kernels(solver_, factorType, (int)factors.size(), r.kind.data(), r.delta.data()), "cuba_hip_set_pose_factor_robust_kernels");
-	}
-
-	void addRelativePoseEdge(RelativePoseEdge* e)
-	{
-		if (!e || !e->vertexI || !e->vertexJ || e->vertexI == e->vertexJ) throw std::invalid_argument("cuba::addRelativePoseEdge: an edge needs two different pose vertices");
-		relEdges_.add(e);
-	}
-	void uploadRelativePoseEdges()
-	{
-		if (!relEdges_.beginUpload()) return;
-		const std::vector<RelativePoseEdge*>& edges = relEdges_.items;
-		const size_t n = edges.size();
-		std::vector<int32_t> pi(n), pj(n);
-		const char* refusal = "cuba::addRelativePoseEdge: a vertex of a relative-pose edge is not part of the graph";
-		for (size_t k = 0; k < n; k++) { pi[k] = factorPose(edges[k]->vertexI, refusal); pj[k] = factorPose(edges[k]->vertexJ, refusal); }
-		const FactorArrays a = packFactors(edges);
-		check(cuba_hip_set_relative_pose_edges(solver_, (int)n, pi.data(), pj.data(), a.q.data(), a.t.data(), a.info.data()), "cuba_hip_set_relative_pose_edges");
-		uploadFactorKernels(1, edges);
-		relEdges_.endUpload();
-	}
-
-	void addPosePrior(PosePrior* p)
-	{
-		if (!p || !p->vertex) throw std::invalid_argument("cuba::addPosePrior: a prior needs a pose vertex");
-		priors_.add(p);
-	}
-	void uploadPriors()
-	{
-		if (!priors_.beginUpload()) return;
-		const std::vector<PosePrior*>& priors = priors_.items;
-		const size_t n = priors.size();
-		std::vector<int32_t> pose(n);
-		for (size_t k = 0; k < n; k++) pose[k] = factorPose(priors[k]->vertex, "cuba::addPosePrior: the vertex of a prior is not part of the graph");
-		const FactorArrays a = packFactors(priors);
-		check(cuba_hip_set_pose_priors(solver_, (int)n, pose.data(), a.q.data(), a.t.data(), a.info.data()), "cuba_hip_set_pose_priors");
-		uploadFactorKernels(0, priors);
-		priors_.endUpload();
-	}
-
-	// ---- landmark position priors (extension: cuba::addLandmarkPrior) --------------------------------
-	void addLandmarkPrior(LandmarkPrior* p)
-	{
-		if (!p || !p->vertex) throw std::invalid_argument("cuba::addLandmarkPrior: a prior needs a landmark vertex");
-		lmPriors_.add(p);
-	}
-	void uploadLandmarkPriors()
-	{
-		if (!lmPriors_.beginUpload()) return;
-		const std::vector<LandmarkPrior*>& priors = lmPriors_.items;
-		const size_t n = priors.size();
-		std::map<const LandmarkVertex*, int32_t> lmIdx;
-		for (size_t i = 0; i < activeLandmarks_.size(); i++) lmIdx[activeLandmarks_[i]] = (int32_t)i;
-		std::vector<int32_t> lm(n);
-		std::vector<double> xyz(3 * n), info(9 * n);
-		for (size_t k = 0; k < n; k++)
-		{
-			const auto it = lmIdx.find(priors[k]->vertex);
-			if (it == lmIdx.end()) throw std::invalid_argument("cuba::addLandmarkPrior: the vertex of a prior is not part of the graph");
-			lm[k] = it->second;
-			for (int i = 0; i < 3; i++) xyz[3 * k + i] = priors[k]->position.data()[i];
-			std::copy(priors[k]->information.begin(), priors[k]->information.end(), info.begin() + 9 * k);
-		}
-		const FactorKernels r = packKernels(priors);
-		check(cuba_hip_set_landmark_priors(solver_, (int)n, lm.data(), xyz.data(), info.data(), r.any ? r.kind.data() : nullptr, r.any ? r.delta.data() : nullptr),
-			"cuba_hip_set_landmark_priors");
-		lmPriors_.endUpload();
-	}
-
-	// ---- position factors on the poses (extension: cuba::addPositionFactor) --------------------------
-	void addPositionFactor(PositionFactor* f)
-	{
-		if (!f || !f->vertex) throw std::invalid_argument("cuba::addPositionFactor: a factor needs a pose vertex");
-		posFactors_.add(f);
-	}
-	void uploadPositionFactors()
-	{
-		if (!posFactors_.beginUpload()) return;
-		const std::vector<PositionFactor*>& factors = posFactors_.items;
+		using K = FactorKind<F>;
+		if (!list.beginUpload()) return;
+		const std::vector<F*>& factors = list.items;
 		const size_t n = factors.size();
-		std::vector<int32_t> pose(n);
-		std::vector<double> z(3 * n), arm(3 * n), info(9 * n);
+		constexpr bool binary = std::tuple_size<decltype(ends(*factors[0]))>::value == 2;
+		std::vector<int32_t> vertex[2] = { std::vector<int32_t>(n), std::vector<int32_t>(binary ? n : 0) };
+		const std::string refusal = std::string(K::fn) + (binary ? ": a vertex of " : ": the vertex of ") + K::ofA + " is not part of the graph";
 		for (size_t k = 0; k < n; k++)
 		{
-			pose[k] = factorPose(factors[k]->vertex, "cuba::addPositionFactor: the vertex of a factor is not part of the graph");
-			std::copy(factors[k]->position.begin(), factors[k]->position.end(), z.begin() + 3 * k);
-			std::copy(factors[k]->leverArm.begin(), factors[k]->leverArm.end(), arm.begin() + 3 * k);
-			std::copy(factors[k]->information.begin(), factors[k]->information.end(), info.begin() + 9 * k);
+			const auto e = ends(*factors[k]);
+			for (size_t s = 0; s < e.size(); s++) vertex[s][k] = vertexIndex(e[s], refusal);
 		}
 		const FactorKernels r = packKernels(factors);
-		check(cuba_hip_set_position_factors(solver_, (int)n, pose.data(), z.data(), arm.data(), info.data(), r.any ? r.kind.data() : nullptr,
-			r.any ? r.delta.data() : nullptr), "cuba_hip_set_position_factors");
-		posFactors_.endUpload();
+		const bool inside = K::kernelType < 0 && r.any;
+		check(K::set(solver_, factors, vertex[0].data(), vertex[1].data(), inside ? r.kind.data() : nullptr, inside ? r.delta.data() : nullptr), K::setName);
+		// (the pose factors' kernels follow the set they belong to; a set without any sends nothing: the handle has none after the setter)
+		if (K::kernelType >= 0 && r.any)
+			check(cuba_hip_set_pose_factor_robust_kernels(solver_, K::kernelType, (int)n, r.kind.data(), r.delta.data()), "cuba_hip_set_pose_factor_robust_kernels");
+		list.endUpload();
 	}
-
-	// ---- direction factors on the poses (extension: cuba::addDirectionFactor) ------------------------
-	void addDirectionFactor(DirectionFactor* f)
+	// after a solve: the chi2 of the uploaded sets
+	void readChiSquares()
 	{
-		if (!f || !f->vertex) throw std::invalid_argument("cuba::addDirectionFactor: a factor needs a pose vertex");
-		dirFactors_.add(f);
-	}
-	void uploadDirectionFactors()
-	{
-		if (!dirFactors_.beginUpload()) return;
-		const std::vector<DirectionFactor*>& factors = dirFactors_.items;
-		const size_t n = factors.size();
-		std::vector<int32_t> pose(n);
-		std::vector<double> d(3 * n), m(3 * n), info(9 * n);
-		for (size_t k = 0; k < n; k++)
-		{
-			pose[k] = factorPose(factors[k]->vertex, "cuba::addDirectionFactor: the vertex of a factor is not part of the graph");
-			std::copy(factors[k]->worldDirection.begin(), factors[k]->worldDirection.end(), d.begin() + 3 * k);
-			std::copy(factors[k]->measurement.begin(), factors[k]->measurement.end(), m.begin() + 3 * k);
-			std::copy(factors[k]->information.begin(), factors[k]->information.end(), info.begin() + 9 * k);
-		}
-		const FactorKernels r = packKernels(factors);
-		check(cuba_hip_set_direction_factors(solver_, (int)n, pose.data(), d.data(), m.data(), info.data(), r.any ? r.kind.data() : nullptr,
-			r.any ? r.delta.data() : nullptr), "cuba_hip_set_direction_factors");
-		dirFactors_.endUpload();
-	}
-
-	// ---- range factors on the poses (extension: cuba::addRangeFactor) --------------------------------
-	void addRangeFactor(RangeFactor* f)
-	{
-		if (!f || !f->vertex) throw std::invalid_argument("cuba::addRangeFactor: a factor needs a pose vertex");
-		rngFactors_.add(f);
-	}
-	void uploadRangeFactors()
-	{
-		if (!rngFactors_.beginUpload()) return;
-		const std::vector<RangeFactor*>& factors = rngFactors_.items;
-		const size_t n = factors.size();
-		std::vector<int32_t> pose(n);
-		std::vector<double> anchor(3 * n), arm(3 * n), range(n), info(n);
-		for (size_t k = 0; k < n; k++)
-		{
-			pose[k] = factorPose(factors[k]->vertex, "cuba::addRangeFactor: the vertex of a factor is not part of the graph");
-			std::copy(factors[k]->anchor.begin(), factors[k]->anchor.end(), anchor.begin() + 3 * k);
-			std::copy(factors[k]->leverArm.begin(), factors[k]->leverArm.end(), arm.begin() + 3 * k);
-			range[k] = factors[k]->range;
-			info[k] = factors[k]->information;
-		}
-		const FactorKernels r = packKernels(factors);
-		check(cuba_hip_set_range_factors(solver_, (int)n, pose.data(), anchor.data(), range.data(), arm.data(), info.data(), r.any ? r.kind.data() : nullptr,
-			r.any ? r.delta.data() : nullptr), "cuba_hip_set_range_factors");
-		rngFactors_.endUpload();
-	}
-
-	// ---- range factors between two poses (extension: cuba::addPoseRangeFactor) ------------------------
-	void addPoseRangeFactor(PoseRangeFactor* f)
-	{
-		if (!f || !f->vertexI || !f->vertexJ || f->vertexI == f->vertexJ) throw std::invalid_argument("cuba::addPoseRangeFactor: a factor needs two different pose vertices");
-		prngFactors_.add(f);
-	}
-	void uploadPoseRangeFactors()
-	{
-		if (!prngFactors_.beginUpload()) return;
-		const std::vector<PoseRangeFactor*>& factors = prngFactors_.items;
-		const size_t n = factors.size();
-		std::vector<int32_t> pi(n), pj(n);
-		std::vector<double> armI(3 * n), armJ(3 * n), range(n), info(n);
-		const char* refusal = "cuba::addPoseRangeFactor: a vertex of a factor is not part of the graph";
-		for (size_t k = 0; k < n; k++)
-		{
-			pi[k] = factorPose(factors[k]->vertexI, refusal); pj[k] = factorPose(factors[k]->vertexJ, refusal);
-			std::copy(factors[k]->leverArmI.begin(), factors[k]->leverArmI.end(), armI.begin() + 3 * k);
-			std::copy(factors[k]->leverArmJ.begin(), factors[k]->leverArmJ.end(), armJ.begin() + 3 * k);
-			range[k] = factors[k]->range;
-			info[k] = factors[k]->information;
-		}
-		const FactorKernels r = packKernels(factors);
-		check(cuba_hip_set_pose_range_factors(solver_, (int)n, pi.data(), pj.data(), range.data(), armI.data(), armJ.data(), info.data(), r.any ? r.kind.data() : nullptr,
-			r.any ? r.delta.data() : nullptr), "cuba_hip_set_pose_range_factors");
-		prngFactors_.endUpload();
+		for (const bool pattern : { false, true })
+			forEachKind([&](auto& list) {
+				using K = typename std::decay_t<decltype(list)>::Kind;
+				if (K::inBlockPattern == pattern) list.readChi([&](double* c) { check(K::chiSquares(solver_, c), K::chiName); });
+			});
 	}
 
 	// (optimize() in three steps, so that cuba::optimizeBatch can run the middle one for several objects at once)
@@ -715,13 +692,7 @@ public:
 			tl = now;
 		};
 		for (int i = 0; i < done; i++) stats_.push_back({ i, chi2[i] });
-		priors_.readChi([&](double* c) { check(cuba_hip_prior_chi_squares(solver_, c), "cuba_hip_prior_chi_squares"); });
-		lmPriors_.readChi([&](double* c) { check(cuba_hip_landmark_prior_chi_squares(solver_, c), "cuba_hip_landmark_prior_chi_squares"); });
-		posFactors_.readChi([&](double* c) { check(cuba_hip_position_factor_chi_squares(solver_, c), "cuba_hip_position_factor_chi_squares"); });
-		dirFactors_.readChi([&](double* c) { check(cuba_hip_direction_factor_chi_squares(solver_, c), "cuba_hip_direction_factor_chi_squares"); });
-		rngFactors_.readChi([&](double* c) { check(cuba_hip_range_factor_chi_squares(solver_, c), "cuba_hip_range_factor_chi_squares"); });
-		relEdges_.readChi([&](double* c) { check(cuba_hip_relative_pose_chi_squares(solver_, c), "cuba_hip_relative_pose_chi_squares"); });
-		prngFactors_.readChi([&](double* c) { check(cuba_hip_pose_range_factor_chi_squares(solver_, c), "cuba_hip_pose_range_factor_chi_squares"); });
+		readChiSquares();
 
 		// finalize (ref :512-526): estimates back into the caller's vertices
 		check(cuba_hip_get_solution(solver_, q_.data(), t_.data(), Xw_.data()), "cuba_hip_get_solution");
@@ -767,13 +738,7 @@ public:
 	{
 		covPoseIndex_.clear(); covLmIndex_.clear();
 		poses_.clear(); landmarks_.clear(); mono_.clear(); stereo_.clear(); stats_.clear();
-		priors_.items.clear(); priors_.chi.clear();
-		relEdges_.items.clear(); relEdges_.chi.clear();
-		lmPriors_.items.clear(); lmPriors_.chi.clear();
-		posFactors_.items.clear(); posFactors_.chi.clear();
-		dirFactors_.items.clear(); dirFactors_.chi.clear();
-		rngFactors_.items.clear(); rngFactors_.chi.clear();
-		prngFactors_.items.clear(); prngFactors_.chi.clear();
+		forEachKind([](auto& list) { list.items.clear(); list.chi.clear(); });
 		posesDirty_ = landmarksDirty_ = edgesDirty_ = true;
 		initialized_ = false;
 	}
@@ -898,6 +863,7 @@ private:
 	std::vector<PoseVertex*> activePoses_;
 	std::map<const PoseVertex*, int32_t> poseIdx_;            // active pose -> solver index, for the factors of this initialize()
 	std::vector<LandmarkVertex*> activeLandmarks_;
+	std::map<const LandmarkVertex*, int32_t> landmarkIdx_;    // the same for the landmark priors
 	std::vector<BaseEdge*> activeEdges_;
 	int numFreePoses_ = 0, numFreeLandmarks_ = 0;
 	PinnedVector<double> q_, t_, cam_, Xw_, meas_, omega_;
@@ -996,147 +962,54 @@ bool landmarkCovariance(const CudaBundleAdjustment* object, const LandmarkVertex
 	return impl && impl->landmarkCovariance(v, cov);
 }
 
-// Extension (g2o's unary pose edges): SE(3) pose priors, effective at the next initialize() (cuba_hip_set_pose_priors)
-void addPosePrior(CudaBundleAdjustment* object, PosePrior* prior)
+// Extensions (the reference has no factors besides the reprojection edges): add / remove / chi2 of every factor kind, the same three
+// for all of them.  A factor takes effect at the next initialize(); an object of another library is refused by add and ignored by the
+// other two (remove: nothing to do, chi2: 0).
+namespace
+{
+template <class F> void addFactor(CudaBundleAdjustment* object, F* f)
 {
 	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (!impl) throw std::runtime_error("cuba::addPosePrior: not an object of this library");
-	impl->addPosePrior(prior);
+	if (!impl) throw std::runtime_error(std::string(FactorKind<F>::fn) + ": not an object of this library");
+	impl->addFactor(f);
 }
-
-void removePosePrior(CudaBundleAdjustment* object, PosePrior* prior)
+template <class F> void removeFactor(CudaBundleAdjustment* object, F* f)
 {
-	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (impl) impl->priors_.remove(prior);
+	if (auto* impl = dynamic_cast<HipBundleAdjustment*>(object)) impl->list<F>().remove(f);
 }
-
-double priorChiSquared(const CudaBundleAdjustment* object, const PosePrior* prior)
+template <class F> double factorChiSquared(const CudaBundleAdjustment* object, const F* f)
 {
 	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
-	return impl ? impl->priors_.chiSquared(prior) : 0.0;
+	return impl ? impl->list<F>().chiSquared(f) : 0.0;
 }
+}  // namespace
 
-// Extension (g2o's unary XYZ prior edge): landmark position priors, effective at the next initialize() (cuba_hip_set_landmark_priors)
-void addLandmarkPrior(CudaBundleAdjustment* object, LandmarkPrior* prior)
-{
-	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (!impl) throw std::runtime_error("cuba::addLandmarkPrior: not an object of this library");
-	impl->addLandmarkPrior(prior);
-}
+void addPosePrior(CudaBundleAdjustment* object, PosePrior* prior) { addFactor(object, prior); }
+void removePosePrior(CudaBundleAdjustment* object, PosePrior* prior) { removeFactor(object, prior); }
+double priorChiSquared(const CudaBundleAdjustment* object, const PosePrior* prior) { return factorChiSquared(object, prior); }
 
-void removeLandmarkPrior(CudaBundleAdjustment* object, LandmarkPrior* prior)
-{
-	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (impl) impl->lmPriors_.remove(prior);
-}
+void addRelativePoseEdge(CudaBundleAdjustment* object, RelativePoseEdge* edge) { addFactor(object, edge); }
+void removeRelativePoseEdge(CudaBundleAdjustment* object, RelativePoseEdge* edge) { removeFactor(object, edge); }
+double relativePoseChiSquared(const CudaBundleAdjustment* object, const RelativePoseEdge* edge) { return factorChiSquared(object, edge); }
 
-double landmarkPriorChiSquared(const CudaBundleAdjustment* object, const LandmarkPrior* prior)
-{
-	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
-	return impl ? impl->lmPriors_.chiSquared(prior) : 0.0;
-}
+void addLandmarkPrior(CudaBundleAdjustment* object, LandmarkPrior* prior) { addFactor(object, prior); }
+void removeLandmarkPrior(CudaBundleAdjustment* object, LandmarkPrior* prior) { removeFactor(object, prior); }
+double landmarkPriorChiSquared(const CudaBundleAdjustment* object, const LandmarkPrior* prior) { return factorChiSquared(object, prior); }
 
-// Extension (GNSS-style fixes): position factors on the poses, effective at the next initialize() (cuba_hip_set_position_factors)
-void addPositionFactor(CudaBundleAdjustment* object, PositionFactor* factor)
-{
-	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (!impl) throw std::runtime_error("cuba::addPositionFactor: not an object of this library");
-	impl->addPositionFactor(factor);
-}
+void addPositionFactor(CudaBundleAdjustment* object, PositionFactor* factor) { addFactor(object, factor); }
+void removePositionFactor(CudaBundleAdjustment* object, PositionFactor* factor) { removeFactor(object, factor); }
+double positionFactorChiSquared(const CudaBundleAdjustment* object, const PositionFactor* factor) { return factorChiSquared(object, factor); }
 
-void removePositionFactor(CudaBundleAdjustment* object, PositionFactor* factor)
-{
-	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (impl) impl->posFactors_.remove(factor);
-}
+void addDirectionFactor(CudaBundleAdjustment* object, DirectionFactor* factor) { addFactor(object, factor); }
+void removeDirectionFactor(CudaBundleAdjustment* object, DirectionFactor* factor) { removeFactor(object, factor); }
+double directionFactorChiSquared(const CudaBundleAdjustment* object, const DirectionFactor* factor) { return factorChiSquared(object, factor); }
 
-double positionFactorChiSquared(const CudaBundleAdjustment* object, const PositionFactor* factor)
-{
-	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
-	return impl ? impl->posFactors_.chiSquared(factor) : 0.0;
-}
+void addRangeFactor(CudaBundleAdjustment* object, RangeFactor* factor) { addFactor(object, factor); }
+void removeRangeFactor(CudaBundleAdjustment* object, RangeFactor* factor) { removeFactor(object, factor); }
+double rangeFactorChiSquared(const CudaBundleAdjustment* object, const RangeFactor* factor) { return factorChiSquared(object, factor); }
 
-// Extension (gravity, compass, vanishing directions): direction factors on the poses, effective at the next initialize()
-// (cuba_hip_set_direction_factors)
-void addDirectionFactor(CudaBundleAdjustment* object, DirectionFactor* factor)
-{
-	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (!impl) throw std::runtime_error("cuba::addDirectionFactor: not an object of this library");
-	impl->addDirectionFactor(factor);
-}
-
-void removeDirectionFactor(CudaBundleAdjustment* object, DirectionFactor* factor)
-{
-	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (impl) impl->dirFactors_.remove(factor);
-}
-
-double directionFactorChiSquared(const CudaBundleAdjustment* object, const DirectionFactor* factor)
-{
-	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
-	return impl ? impl->dirFactors_.chiSquared(factor) : 0.0;
-}
-
-// Extension (UWB-style distances to known anchors): range factors on the poses, effective at the next initialize()
-// (cuba_hip_set_range_factors)
-void addRangeFactor(CudaBundleAdjustment* object, RangeFactor* factor)
-{
-	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (!impl) throw std::runtime_error("cuba::addRangeFactor: not an object of this library");
-	impl->addRangeFactor(factor);
-}
-
-void removeRangeFactor(CudaBundleAdjustment* object, RangeFactor* factor)
-{
-	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (impl) impl->rngFactors_.remove(factor);
-}
-
-double rangeFactorChiSquared(const CudaBundleAdjustment* object, const RangeFactor* factor)
-{
-	auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
-	return impl ? impl->rngFactors_.chiSquared(factor) : 0.0;
-}
-
-// Extension (odometer distances, peer UWB ranging, rig baselines): range factors between two poses, effective at the next initialize()
-// (cuba_hip_set_pose_range_factors)
-void addPoseRangeFactor(CudaBundleAdjustment* object, PoseRangeFactor* factor)
-{
-	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (!impl) throw std::runtime_error("cuba::addPoseRangeFactor: not an object of this library");
-	impl->addPoseRangeFactor(factor);
-}
-
-void removePoseRangeFactor(CudaBundleAdjustment* object, PoseRangeFactor* factor)
-{
-	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (impl) impl->prngFactors_.remove(factor);
-}
-
-double poseRangeFactorChiSquared(const CudaBundleAdjustment* object, const PoseRangeFactor* factor)
-{
-	auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
-	return impl ? impl->prngFactors_.chiSquared(factor) : 0.0;
-}
-
-// Extension (g2o's binary SE(3) edge): relative-pose edges, effective at the next initialize() (cuba_hip_set_relative_pose_edges)
-void addRelativePoseEdge(CudaBundleAdjustment* object, RelativePoseEdge* edge)
-{
-	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (!impl) throw std::runtime_error("cuba::addRelativePoseEdge: not an object of this library");
-	impl->addRelativePoseEdge(edge);
-}
-
-void removeRelativePoseEdge(CudaBundleAdjustment* object, RelativePoseEdge* edge)
-{
-	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
-	if (impl) impl->relEdges_.remove(edge);
-}
-
-double relativePoseChiSquared(const CudaBundleAdjustment* object, const RelativePoseEdge* edge)
-{
-	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
-	return impl ? impl->relEdges_.chiSquared(edge) : 0.0;
-}
+void addPoseRangeFactor(CudaBundleAdjustment* object, PoseRangeFactor* factor) { addFactor(object, factor); }
+void removePoseRangeFactor(CudaBundleAdjustment* object, PoseRangeFactor* factor) { removeFactor(object, factor); }
+double poseRangeFactorChiSquared(const CudaBundleAdjustment* object, const PoseRangeFactor* factor) { return factorChiSquared(object, factor); }
 
 }  // namespace cuba
