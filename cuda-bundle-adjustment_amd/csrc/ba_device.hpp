@@ -1,6 +1,6 @@
 // ba_device.hpp -- device-side helpers shared by the kernel translation units (ba_edge.hip, ba_linearize.hip, ba_pcg.hip,
 // ba_coarse.hip): DPP wave reductions, flag loads on the vector path, the deterministic second-stage sums, loading +
-// linearising one edge, the factors' robust kernels, the landmark pass's prior hook.  Internal to csrc/ -- the launch interface is ba_kernels.hpp.
+// linearising one edge, the landmark sums' wave and workgroup forms, the factors' robust kernels, the landmark pass's prior hook.  Internal to csrc/ -- the launch interface is ba_kernels.hpp.
 #pragma once
 
 #include "ba_kernels.hpp"
@@ -203,44 +203,93 @@ static void launch_reduce_parts(const Scalar* parts, int n, Scalar* out, hipStre
 	hipLaunchKernelGGL(reduce_parts_kernel, dim3(1), dim3(1024), 0, s, parts, n, out);
 }
 
-// Everything a lane knows about its edge after loading + linearising it.
+// One reprojection edge at an estimate: what a lane knows of its edge after load_edge (first line of numbers) and load_edge_at (all).
 struct LaneEdge
 {
 	int ip, il;
 	bool stereo;
-	Scalar wr;       // omega * rho'(omega |r|^2)
-	EdgeLin lin;
+	Scalar q[4], t[3], cam[5], Xw[3], meas[3], w;   // pose and landmark at the estimate, measurement, information
+	Scalar Xc[3], chi, wr;                          // landmark in the camera frame, omega |r|^2, omega * rho'(omega |r|^2)
+	EdgeLin lin;                                    // residual and, on request, Jacobians
 };
 
-__device__ __forceinline__ void load_pose(const DeviceGraph& g, int ip, Scalar q[4], Scalar t[3], Scalar cam[5])
+// Edge e's indices, measurement and information from the graph; its pose and landmark from (q, t, Xw): the live state (g.q, g.t, g.Xw),
+// or the pre-update estimate `old` of a trial's tail.
+__device__ __forceinline__ void load_edge(const DeviceGraph& g, const Scalar* q, const Scalar* t, const Scalar* Xw, int e, LaneEdge& le)
 {
+	const int pe = g.e_pose[e];
+	le.stereo = (pe & STEREO_BIT) != 0;
+	le.ip = pe & ~STEREO_BIT;
+	le.il = g.e_lm[e];
 #pragma unroll
-	for (int i = 0; i < 4; i++) q[i] = g.q[4 * (size_t)ip + i];
+	for (int i = 0; i < 4; i++) le.q[i] = q[4 * (size_t)le.ip + i];
 #pragma unroll
-	for (int i = 0; i < 3; i++) t[i] = g.t[3 * (size_t)ip + i];
+	for (int i = 0; i < 3; i++) le.t[i] = t[3 * (size_t)le.ip + i];
 #pragma unroll
-	for (int i = 0; i < 5; i++) cam[i] = g.cam[5 * (size_t)ip + i];
+	for (int i = 0; i < 5; i++) le.cam[i] = g.cam[5 * (size_t)le.ip + i];
+#pragma unroll
+	for (int i = 0; i < 3; i++) le.Xw[i] = Xw[3 * (size_t)le.il + i];
+	le.meas[0] = g.e_mu[e]; le.meas[1] = g.e_mv[e]; le.meas[2] = g.e_mr[e];
+	le.w = g.e_w[e];
+}
+
+// load_edge, then residual, camera-frame point, omega |r|^2, IRLS weight and (JACOBIANS) the linearisation
+template <bool JACOBIANS>
+__device__ __forceinline__ void load_edge_at(const DeviceGraph& g, const Scalar* q, const Scalar* t, const Scalar* Xw, int e, LaneEdge& le)
+{
+	load_edge(g, q, t, Xw, e, le);
+	le.chi = le.w * edge_residual(le.q, le.t, le.cam, le.Xw, le.meas, le.stereo, le.lin.r, le.Xc);
+	const int kind = le.stereo ? g.rk[1].kind : g.rk[0].kind;
+	const Scalar delta = le.stereo ? g.rk[1].delta : g.rk[0].delta;
+	le.wr = le.w * robust_weight(kind, delta, le.chi);
+	if constexpr (JACOBIANS)
+	{
+		const Rot3 R = quat_to_rot(le.q[0], le.q[1], le.q[2], le.q[3]);
+		edge_jacobians(le.Xc, R, le.cam, le.stereo, le.lin);
+	}
 }
 
 // Load edge e and linearise it at the current estimate.
-__device__ __forceinline__ void linearize_edge(const DeviceGraph& g, int e, LaneEdge& out)
+__device__ __forceinline__ void linearize_edge(const DeviceGraph& g, int e, LaneEdge& le) { load_edge_at<true>(g, g.q, g.t, g.Xw, e, le); }
+
+// Wave form of a sum over a landmark's edges (lane = edge, the landmark's edges are lanes [seg0, seg1) of the wave): every lane puts its
+// N terms into the wave's LDS rows, the landmark's head lane (lane seg0) adds its segment front to back.
+template <int N>
+__device__ __forceinline__ void lanes_to_lds(Scalar* lds, int lane, const Scalar v[N])
 {
-	const int pe = g.e_pose[e];
-	out.stereo = (pe & STEREO_BIT) != 0;
-	out.ip = pe & ~STEREO_BIT;
-	out.il = g.e_lm[e];
-	Scalar q[4], t[3], cam[5], Xw[3], meas[3], Xc[3];
-	load_pose(g, out.ip, q, t, cam);
 #pragma unroll
-	for (int i = 0; i < 3; i++) Xw[i] = g.Xw[3 * (size_t)out.il + i];
-	meas[0] = g.e_mu[e]; meas[1] = g.e_mv[e]; meas[2] = g.e_mr[e];
-	const Scalar w = g.e_w[e];
-	const Scalar s = edge_residual(q, t, cam, Xw, meas, out.stereo, out.lin.r, Xc);
-	const int kind = out.stereo ? g.rk[1].kind : g.rk[0].kind;
-	const Scalar delta = out.stereo ? g.rk[1].delta : g.rk[0].delta;
-	out.wr = w * robust_weight(kind, delta, w * s);
-	const Rot3 R = quat_to_rot(q[0], q[1], q[2], q[3]);
-	edge_jacobians(Xc, R, cam, out.stereo, out.lin);
+	for (int k = 0; k < N; k++) lds[lane * N + k] = v[k];
+	wave_lds_sync();
+}
+
+template <int N>
+__device__ __forceinline__ void segment_sum(const Scalar* lds, int seg0, int seg1, Scalar s[N])
+{
+#pragma unroll
+	for (int k = 0; k < N; k++) s[k] = 0;
+	for (int j = seg0; j < seg1; j++)
+#pragma unroll
+		for (int k = 0; k < N; k++) s[k] += lds[j * N + k];
+}
+
+// Workgroup form (256 threads = four waves): each wave's sums of v[0..N) into red[wave], a barrier; then one thread adds the four --
+// left to right in the landmark sums, PAIRWISE in the chi2 partials of the trial tail, as each sum always was.
+template <int N>
+__device__ __forceinline__ void four_waves_to_lds(Scalar (&red)[4][N], Scalar (&v)[N])
+{
+#pragma unroll
+	for (int k = 0; k < N; k++) v[k] = wave_sum(v[k]);
+	if ((threadIdx.x & 63) == 0)
+#pragma unroll
+		for (int k = 0; k < N; k++) red[threadIdx.x >> 6][k] = v[k];
+	__syncthreads();
+}
+
+template <int N, bool PAIRWISE>
+__device__ __forceinline__ void four_wave_sum(const Scalar (&red)[4][N], Scalar s[N])
+{
+#pragma unroll
+	for (int k = 0; k < N; k++) s[k] = PAIRWISE ? (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]) : red[0][k] + red[1][k] + red[2][k] + red[3][k];
 }
 
 // rho(e) and rho'(e) of a factor's robust kernel (pose factors, landmark priors): Huber and Tukey as the reprojection edges have them, and Cauchy

@@ -16,29 +16,17 @@ namespace cubahip
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void residual_chi2_body(const DeviceGraph& g, Scalar* parts, Scalar* per_edge, int bid, int nb)
 {
-	Scalar acc = 0;
+	__shared__ Scalar part[4][1];
+	Scalar acc[1] = { 0 };
 	for (int e = g.e_begin + bid * 256 + threadIdx.x; e < g.e_end; e += nb * 256)
 	{
-		const int pe = g.e_pose[e];
-		const bool stereo = (pe & STEREO_BIT) != 0;
-		const int ip = pe & ~STEREO_BIT;
-		const int il = g.e_lm[e];
-		Scalar q[4], t[3], cam[5], Xw[3], meas[3], r[3], Xc[3];
-		load_pose(g, ip, q, t, cam);
-#pragma unroll
-		for (int i = 0; i < 3; i++) Xw[i] = g.Xw[3 * (size_t)il + i];
-		meas[0] = g.e_mu[e]; meas[1] = g.e_mv[e]; meas[2] = g.e_mr[e];
-		const Scalar ee = g.e_w[e] * edge_residual(q, t, cam, Xw, meas, stereo, r, Xc);
-		const int kind = stereo ? g.rk[1].kind : g.rk[0].kind;
-		const Scalar delta = stereo ? g.rk[1].delta : g.rk[0].delta;
-		acc += robust_rho(kind, delta, ee);
-		if (per_edge) per_edge[e] = ee;
+		LaneEdge le;
+		load_edge_at<false>(g, g.q, g.t, g.Xw, e, le);
+		acc[0] += robust_rho(le.stereo ? g.rk[1].kind : g.rk[0].kind, le.stereo ? g.rk[1].delta : g.rk[0].delta, le.chi);
+		if (per_edge) per_edge[e] = le.chi;
 	}
-	acc = wave_sum(acc);
-	__shared__ Scalar part[4];
-	if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-	__syncthreads();
-	if (threadIdx.x == 0) parts[bid] = part[0] + part[1] + part[2] + part[3];
+	four_waves_to_lds<1>(part, acc);
+	if (threadIdx.x == 0) four_wave_sum<1, false>(part, &parts[bid]);
 }
 
 __global__ __launch_bounds__(256) void residual_chi2_kernel(DeviceGraph g, Scalar* parts, Scalar* per_edge)
@@ -77,10 +65,11 @@ __device__ __forceinline__ void edge_hplT_x(const LaneEdge& le, const Scalar* xp
 	for (int k = 0; k < 3; k++) c[k] = L.JL[0][k] * v[0] + L.JL[1][k] * v[1] + L.JL[2][k] * v[2];
 }
 
-__device__ __forceinline__ Scalar finish_landmark(const DeviceSystem& sys, int il, const Scalar csum[3], Scalar lambda)
+// xl = inv (bl - csum) of free landmark il, stored; returns its term xl (lambda xl + bl) of the gain-ratio denominator
+__device__ __forceinline__ Scalar finish_landmark(const DeviceSystem& sys, int il, const Scalar csum[3], Scalar lambda, Scalar xl[3])
 {
 	const Scalar* ls = sys.lm_sys + 9 * (size_t)il;
-	Scalar inv[6], bl[3], cl[3], xl[3];
+	Scalar inv[6], bl[3], cl[3];
 #pragma unroll
 	for (int k = 0; k < 6; k++) inv[k] = ls[k];
 #pragma unroll
@@ -130,18 +119,13 @@ __global__ __launch_bounds__(LIN_BLOCK) void back_substitute_kernel(DeviceGraph 
 		}
 	}
 	const bool lmFree = valid && il < g.Lf;
-#pragma unroll
-	for (int k = 0; k < 3; k++) lds[lane * 3 + k] = c[k];
-	wave_lds_sync();
+	lanes_to_lds<3>(lds, lane, c);
 	Scalar sc = 0;
 	if (lmFree && lane == seg0)
 	{
-		Scalar cs[3] = { 0, 0, 0 };
-		for (int j = seg0; j < seg1; j++)
-		{
-			cs[0] += lds[j * 3 + 0]; cs[1] += lds[j * 3 + 1]; cs[2] += lds[j * 3 + 2];
-		}
-		sc = finish_landmark(sys, il, cs, lambda);
+		Scalar cs[3], xl[3];
+		segment_sum<3>(lds, seg0, seg1, cs);
+		sc = finish_landmark(sys, il, cs, lambda, xl);
 	}
 	sc = wave_sum(sc);
 	if (lane == 0) sys.parts[wave] = sc;     // one partial per wave, summed by reduce_parts_kernel
@@ -170,18 +154,12 @@ __global__ __launch_bounds__(256) void big_back_substitute_kernel(DeviceGraph g,
 		edge_hplT_x(le, xp, c);
 		acc[0] += c[0]; acc[1] += c[1]; acc[2] += c[2];
 	}
-#pragma unroll
-	for (int k = 0; k < 3; k++) acc[k] = wave_sum(acc[k]);
-	if ((threadIdx.x & 63) == 0)
-#pragma unroll
-		for (int k = 0; k < 3; k++) red[threadIdx.x >> 6][k] = acc[k];
-	__syncthreads();
+	four_waves_to_lds<3>(red, acc);
 	if (threadIdx.x == 0)
 	{
-		Scalar cs[3];
-#pragma unroll
-		for (int k = 0; k < 3; k++) cs[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-		sys.parts[st.nWaves + blockIdx.x] = finish_landmark(sys, il, cs, lambda);
+		Scalar cs[3], xl[3];
+		four_wave_sum<3, false>(red, cs);
+		sys.parts[st.nWaves + blockIdx.x] = finish_landmark(sys, il, cs, lambda, xl);
 	}
 }
 
@@ -376,25 +354,6 @@ void launch_update_state(const DeviceGraph& g, const DeviceSystem& sys, hipStrea
 // Roles by workgroup index: [0, nLmGroups) landmark waves, then poseBlocks pose-update workgroups, then nScale workgroups for the
 // pose part of the gain-ratio denominator.
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ Scalar finish_landmark_x(const DeviceSystem& sys, int il, const Scalar csum[3], Scalar lambda, Scalar xl[3])
-{
-	const Scalar* ls = sys.lm_sys + 9 * (size_t)il;
-	Scalar inv[6], bl[3], cl[3];
-#pragma unroll
-	for (int k = 0; k < 6; k++) inv[k] = ls[k];
-#pragma unroll
-	for (int k = 0; k < 3; k++) { bl[k] = ls[6 + k]; cl[k] = bl[k] - csum[k]; }
-	Scalar sc = 0;
-#pragma unroll
-	for (int i = 0; i < 3; i++)
-	{
-		xl[i] = inv[sym3_idx(i, 0)] * cl[0] + inv[sym3_idx(i, 1)] * cl[1] + inv[sym3_idx(i, 2)] * cl[2];
-		sys.xl[3 * (size_t)il + i] = xl[i];
-		sc += xl[i] * (lambda * xl[i] + bl[i]);
-	}
-	return sc;
-}
-
 // robust chi2 term of an edge at the UPDATED estimate: (q0, t0) is the pre-update pose, upd its increment (poseFree = false: fixed pose)
 __device__ __forceinline__ Scalar updated_edge_rho(const DeviceGraph& g, const Scalar q0[4], const Scalar t0[3], const Scalar cam[5], const Scalar upd[6], bool poseFree,
 	const Scalar Xn[3], const Scalar meas[3], Scalar w, bool stereo)
@@ -437,7 +396,7 @@ __device__ __forceinline__ void trial_tail_body(const DeviceGraph& g, const Devi
 		return;
 	}
 	__shared__ Scalar lds_all[(LIN_BLOCK / WAVE) * WAVE * 3];
-	__shared__ Scalar wpart[2][LIN_BLOCK / WAVE];
+	__shared__ Scalar wpart[LIN_BLOCK / WAVE][2];
 	const int lane = threadIdx.x & 63;
 	const int wv = threadIdx.x >> 6;
 	const int wave = blockIdx.x * (LIN_BLOCK / WAVE) + wv;
@@ -480,7 +439,10 @@ __device__ __forceinline__ void trial_tail_body(const DeviceGraph& g, const Devi
 			seg1 = g.lm_ptr[il + 1] - e0;
 			if (poseFree)
 			{
-				// Hpl^T xp at the linearisation point (the pre-update estimate), exactly as back_substitute_kernel forms it
+				// Hpl^T xp at the linearisation point (the pre-update estimate), exactly as back_substitute_kernel forms it through
+				// load_edge_at -- but written out: read through the loader (even its loads alone) the fp32 library's code of this kernel
+				// comes out with another mix of packed multiplies and fmas and the trial's chi2 moves in its last bits.
+				// tests/test_gpu_landmark_passes_bits.py pins both.
 				LaneEdge le;
 				Scalar Xc[3];
 				const Scalar ss = edge_residual(q, t, cam, Xw, meas, stereo, le.lin.r, Xc);
@@ -492,18 +454,13 @@ __device__ __forceinline__ void trial_tail_body(const DeviceGraph& g, const Devi
 		}
 	}
 	const bool lmFree = valid && il < g.Lf;
-#pragma unroll
-	for (int k = 0; k < 3; k++) lds[lane * 3 + k] = c[k];
-	wave_lds_sync();
+	lanes_to_lds<3>(lds, lane, c);
 	Scalar sc = 0, xl[3] = { 0, 0, 0 };
 	if (lmFree && lane == seg0)
 	{
-		Scalar cs[3] = { 0, 0, 0 };
-		for (int j = seg0; j < seg1; j++)
-		{
-			cs[0] += lds[j * 3 + 0]; cs[1] += lds[j * 3 + 1]; cs[2] += lds[j * 3 + 2];
-		}
-		sc = finish_landmark_x(sys, il, cs, lambda, xl);
+		Scalar cs[3];
+		segment_sum<3>(lds, seg0, seg1, cs);
+		sc = finish_landmark(sys, il, cs, lambda, xl);
 #pragma unroll
 		for (int k = 0; k < 3; k++) g.Xw[3 * (size_t)il + k] = Xw[k] + xl[k];     // (= update_landmarks: Xw += xl)
 	}
@@ -525,13 +482,12 @@ __device__ __forceinline__ void trial_tail_body(const DeviceGraph& g, const Devi
 		}
 		rho = updated_edge_rho(g, q, t, cam, xp, poseFree, Xn, meas, w, stereo);
 	}
-	sc = wave_sum(sc); rho = wave_sum(rho);
-	if (lane == 0) { wpart[0][wv] = sc; wpart[1][wv] = rho; }
-	__syncthreads();
+	Scalar part[2] = { sc, rho };
+	four_waves_to_lds<2>(wpart, part);
 	if (threadIdx.x == 0)
 	{
-		scParts[blockIdx.x] = (wpart[0][0] + wpart[0][1]) + (wpart[0][2] + wpart[0][3]);
-		chiParts[blockIdx.x] = (wpart[1][0] + wpart[1][1]) + (wpart[1][2] + wpart[1][3]);
+		four_wave_sum<2, true>(wpart, part);
+		scParts[blockIdx.x] = part[0]; chiParts[blockIdx.x] = part[1];
 	}
 }
 
@@ -556,10 +512,9 @@ __global__ __launch_bounds__(256) void big_trial_tail_kernel(DeviceGraph g, Devi
 {
 	__shared__ Scalar red[4][3];
 	__shared__ Scalar xsh[3];
-	__shared__ Scalar rsh[4];
+	__shared__ Scalar rsh[4][1];
 	lambda = launch_lambda(sys, lambda);
-	DeviceGraph go = g;                   // the pre-update estimate
-	go.q = const_cast<Scalar*>(old); go.t = go.q + 4 * (size_t)g.Pt; go.Xw = go.q + 7 * (size_t)g.Pt;
+	const Scalar* qo = old; const Scalar* to = old + 4 * (size_t)g.Pt; const Scalar* Xo = old + 7 * (size_t)g.Pt;     // the pre-update estimate
 	const int il = st.big_lm[blockIdx.x];
 	const int e0 = g.lm_ptr[il], e1 = g.lm_ptr[il + 1];
 	const bool lmFree = il < g.Lf;
@@ -571,7 +526,7 @@ __global__ __launch_bounds__(256) void big_trial_tail_kernel(DeviceGraph g, Devi
 			const int ip = g.e_pose[e] & ~STEREO_BIT;
 			if (ip >= g.Pf) continue;
 			LaneEdge le;
-			linearize_edge(go, e, le);
+			load_edge_at<true>(g, qo, to, Xo, e, le);
 			Scalar xp[6], c[3];
 #pragma unroll
 			for (int r = 0; r < 6; r++) xp[r] = sys.xp[6 * (size_t)ip + r];
@@ -579,23 +534,17 @@ __global__ __launch_bounds__(256) void big_trial_tail_kernel(DeviceGraph g, Devi
 			acc[0] += c[0]; acc[1] += c[1]; acc[2] += c[2];
 		}
 	}
-#pragma unroll
-	for (int k = 0; k < 3; k++) acc[k] = wave_sum(acc[k]);
-	if ((threadIdx.x & 63) == 0)
-#pragma unroll
-		for (int k = 0; k < 3; k++) red[threadIdx.x >> 6][k] = acc[k];
-	__syncthreads();
+	four_waves_to_lds<3>(red, acc);
 	if (threadIdx.x == 0)
 	{
 		Scalar xl[3] = { 0, 0, 0 }, sc = 0;
 		if (lmFree)
 		{
 			Scalar cs[3];
+			four_wave_sum<3, false>(red, cs);
+			sc = finish_landmark(sys, il, cs, lambda, xl);
 #pragma unroll
-			for (int k = 0; k < 3; k++) cs[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-			sc = finish_landmark_x(sys, il, cs, lambda, xl);
-#pragma unroll
-			for (int k = 0; k < 3; k++) g.Xw[3 * (size_t)il + k] = go.Xw[3 * (size_t)il + k] + xl[k];
+			for (int k = 0; k < 3; k++) g.Xw[3 * (size_t)il + k] = Xo[3 * (size_t)il + k] + xl[k];
 		}
 		scParts[blockIdx.x] = sc;
 #pragma unroll
@@ -604,65 +553,75 @@ __global__ __launch_bounds__(256) void big_trial_tail_kernel(DeviceGraph g, Devi
 	__syncthreads();
 	Scalar Xn[3];
 #pragma unroll
-	for (int k = 0; k < 3; k++) Xn[k] = go.Xw[3 * (size_t)il + k] + xsh[k];
-	Scalar rho = 0;
+	for (int k = 0; k < 3; k++) Xn[k] = Xo[3 * (size_t)il + k] + xsh[k];
+	Scalar rho[1] = { 0 };
 	for (int e = e0 + threadIdx.x; e < e1; e += 256)
 	{
-		const int pe = g.e_pose[e];
-		const bool stereo = (pe & STEREO_BIT) != 0;
-		const int ip = pe & ~STEREO_BIT;
-		Scalar q[4], t[3], cam[5], meas[3], xp[6];
-		load_pose(go, ip, q, t, cam);
-		meas[0] = g.e_mu[e]; meas[1] = g.e_mv[e]; meas[2] = g.e_mr[e];
-		const bool poseFree = ip < g.Pf;
+		LaneEdge le;
+		load_edge(g, qo, to, Xo, e, le);
+		const bool poseFree = le.ip < g.Pf;
+		Scalar xp[6];
 #pragma unroll
-		for (int r = 0; r < 6; r++) xp[r] = poseFree ? sys.xp[6 * (size_t)ip + r] : Scalar(0);
-		rho += updated_edge_rho(g, q, t, cam, xp, poseFree, Xn, meas, g.e_w[e], stereo);
+		for (int r = 0; r < 6; r++) xp[r] = poseFree ? sys.xp[6 * (size_t)le.ip + r] : Scalar(0);
+		rho[0] += updated_edge_rho(g, le.q, le.t, le.cam, xp, poseFree, Xn, le.meas, le.w, le.stereo);
 	}
-	rho = wave_sum(rho);
-	if ((threadIdx.x & 63) == 0) rsh[threadIdx.x >> 6] = rho;
-	__syncthreads();
-	if (threadIdx.x == 0) chiParts[blockIdx.x] = (rsh[0] + rsh[1]) + (rsh[2] + rsh[3]);
+	four_waves_to_lds<1>(rsh, rho);
+	if (threadIdx.x == 0) four_wave_sum<1, true>(rsh, &chiParts[blockIdx.x]);
 }
+
+// A trial's partial sums in sys.parts and the roles of the tail launch's workgroups.  Three groups, each starting on a multiple of 64:
+// scParts [0, nA), one per landmark workgroup and per big landmark; chiParts, the same nA followed by the factors' chi2 partials;
+// scaleParts, four per workgroup of the pose part of the denominator.
+struct TrialTailLayout
+{
+	int nLm, nA, poseBlocks, nScale;
+	size_t chiOff, scaleOff;
+	TrialTailLayout(const DeviceGraph& g, const DeviceStructure& st, int factorParts)
+	{
+		nLm = (st.nWaves + LIN_BLOCK / WAVE - 1) / (LIN_BLOCK / WAVE);
+		nA = nLm + st.nBig;
+		chiOff = ((size_t)nA + 63) / 64 * 64;
+		scaleOff = chiOff + ((size_t)nA + factorParts + 63) / 64 * 64;
+		poseBlocks = (g.Pf + LIN_BLOCK - 1) / LIN_BLOCK;
+		nScale = g.Pf > 0 ? min((g.Pf * 6 + 255) / 256, 256) : 0;
+	}
+	int grid() const { return nLm + poseBlocks + nScale; }
+	size_t size() const { return scaleOff + 4 * 256 + 64; }
+};
 
 size_t trial_tail_parts(const DeviceGraph& g, const DeviceStructure& st, int factorParts)
 {
-	const size_t a = (size_t)(st.nWaves + LIN_BLOCK / WAVE - 1) / (LIN_BLOCK / WAVE) + st.nBig;
-	const size_t nA = (a + 63) / 64 * 64;
-	return nA + (a + factorParts + 63) / 64 * 64 + 4 * 256 + 64;
+	return TrialTailLayout(g, st, factorParts).size();
 }
 
 void launch_trial_tail_fused(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, Scalar lambda, const Scalar* old, hipStream_t s,
 	const LmDevice* decide, const DeviceFactors* pf, int publish)
 {
-	const int nLm = (st.nWaves + LIN_BLOCK / WAVE - 1) / (LIN_BLOCK / WAVE);
-	const int nA = nLm + st.nBig;
 	const int nPf = factor_chi2_parts(pf);      // (the partials that follow the edges')
+	const TrialTailLayout L(g, st, nPf);
 	Scalar* scParts = sys.parts;
-	Scalar* chiParts = sys.parts + (size_t)(nA + 63) / 64 * 64;
-	Scalar* scaleParts = chiParts + (size_t)(nA + nPf + 63) / 64 * 64;
-	const int poseBlocks = (g.Pf + LIN_BLOCK - 1) / LIN_BLOCK;
-	const int nScale = g.Pf > 0 ? min((g.Pf * 6 + 255) / 256, 256) : 0;
-	if (nLm + poseBlocks + nScale > 0)
-		hipLaunchKernelGGL(trial_tail_kernel, dim3(nLm + poseBlocks + nScale), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, old, scParts, chiParts, nLm, poseBlocks, scaleParts, nScale);
-	if (st.nBig > 0) hipLaunchKernelGGL(big_trial_tail_kernel, dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, old, scParts + nLm, chiParts + nLm);
-	if (nPf > 0) launch_factor_chi2(g, *pf, chiParts + nA, s);          // (at the poses the edge pass has just updated)
-	hipLaunchKernelGGL(reduce_report_kernel, dim3(1), dim3(1024), 0, s, sys, scParts, nA, sys.slots + NSLOT, chiParts, nA + nPf, sys.slots, scaleParts, 4 * nScale, sys.slots + 3 * NSLOT,
+	Scalar* chiParts = sys.parts + L.chiOff;
+	Scalar* scaleParts = sys.parts + L.scaleOff;
+	if (L.grid() > 0)
+		hipLaunchKernelGGL(trial_tail_kernel, dim3(L.grid()), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, old, scParts, chiParts, L.nLm, L.poseBlocks, scaleParts, L.nScale);
+	if (st.nBig > 0) hipLaunchKernelGGL(big_trial_tail_kernel, dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, old, scParts + L.nLm, chiParts + L.nLm);
+	if (nPf > 0) launch_factor_chi2(g, *pf, chiParts + L.nA, s);          // (at the poses the edge pass has just updated)
+	hipLaunchKernelGGL(reduce_report_kernel, dim3(1), dim3(1024), 0, s, sys, scParts, L.nA, sys.slots + NSLOT, chiParts, L.nA + nPf, sys.slots, scaleParts, 4 * L.nScale, sys.slots + 3 * NSLOT,
 		decide ? decide->state : (double*)nullptr, decide ? decide->lam : (Scalar*)nullptr, decide ? decide->ring : (double*)nullptr, publish);
 }
 
 // launch_trial_tail_fused + launch_restore_if_rejected of one graph as entries of the batched launches (no landmark with more than 64 observations)
 void batch_fill_tail(const DeviceGraph& g, const DeviceStructure& st, const DeviceSystem& sys, const Scalar* old, const LmDevice& lm, Scalar* state, size_t stateCount, BatchTrial& t)
 {
-	const int nLm = (st.nWaves + LIN_BLOCK / WAVE - 1) / (LIN_BLOCK / WAVE);
-	const int nA = nLm + st.nBig;
+	// (no factor partials: a handle with factors, or with a big landmark, has no batched tail -- cuba_hip_solver::fullyBatchable)
+	const TrialTailLayout L(g, st, 0);
 	t.scParts = sys.parts;
-	t.chiParts = sys.parts + (size_t)(nA + 63) / 64 * 64;
-	t.scaleParts = t.chiParts + (size_t)(nA + 63) / 64 * 64;
-	t.poseBlocks = (g.Pf + LIN_BLOCK - 1) / LIN_BLOCK;
-	t.nScale = g.Pf > 0 ? min((g.Pf * 6 + 255) / 256, 256) : 0;
-	t.nLm = nLm; t.nA = nA; t.old = old;
-	t.tailGrid = (unsigned)(nLm + t.poseBlocks + t.nScale);
+	t.chiParts = sys.parts + L.chiOff;
+	t.scaleParts = sys.parts + L.scaleOff;
+	t.poseBlocks = L.poseBlocks;
+	t.nScale = L.nScale;
+	t.nLm = L.nLm; t.nA = L.nA; t.old = old;
+	t.tailGrid = (unsigned)L.grid();
 	t.lmState = lm.state; t.lmLam = lm.lam; t.lmRing = lm.ring; t.reportOn = 1;
 	t.state = state; t.stateCount = stateCount;
 	t.restoreGrid = (unsigned)std::min<size_t>(512, (stateCount + 255) / 256);

@@ -207,7 +207,11 @@ __global__ __launch_bounds__(LIN_BLOCK) void lm_pass_batch_kernel(const BatchEnt
 // behind the sum over its edges; the instantiations without it never touch lp (the launch passes an empty one).
 // One __global__ template, not two thin kernels around a shared __device__ body: inlined into a wrapper, the body's fp32 code comes out with
 // another mix of packed multiplies, adds and fmas -- other rounding -- while a template flag leaves every instantiation's code as it is, and
-// a handle without priors must compute what it computed before.
+// a handle without priors must compute what it computed before.  For the same reason this kernel and lm_pass_body share only what leaves
+// every instantiation's fp instructions alone: linearize_edge (here) and the four-wave sum.  The edge load of lm_pass_body, the nine
+// landmark terms, the segment sum over 9 numbers and the head's store / invert are written out in both: each of them, moved into a shared
+// helper, changed the fp32 library's instruction mix in at least one instantiation, and where that mix changes the bit fixtures
+// (tests/test_gpu_landmark_passes_bits.py, tests/test_gpu_landmark_prior_bits.py) move.  They are what says that the two agree.
 template <int MODE, typename ET, bool PRIOR>
 __global__ __launch_bounds__(256) void big_lm_pass_kernel(DeviceGraph g, DeviceStructure st, DeviceSystem sys, Scalar lambda, DeviceLandmarkPriors lp)
 {
@@ -220,13 +224,14 @@ __global__ __launch_bounds__(256) void big_lm_pass_kernel(DeviceGraph g, DeviceS
 	{
 		LaneEdge le;
 		linearize_edge(g, e, le);
-		// linearize_edge does not return Xc: recompute it for the record
-		Scalar q[4], t[3], cam[5], Xw[3], Xc[3];
-		load_pose(g, le.ip, q, t, cam);
+		// The record's Xc is formed once more, from the landmark read through the workgroup's own index, and not taken from le.Xc: with
+		// le.Xc the fp32 library's code comes out with another mix of packed multiplies, adds and fmas and lm_sys moves in its last bits
+		// (the fp64 library's stays).  The same holds for the nine landmark terms below, written out here and in lm_pass_body.
+		Scalar Xw[3], Xc[3];
 #pragma unroll
 		for (int i = 0; i < 3; i++) Xw[i] = g.Xw[3 * (size_t)il + i];
-		quat_rotate(q, Xw, Xc);
-		Xc[0] += t[0]; Xc[1] += t[1]; Xc[2] += t[2];
+		quat_rotate(le.q, Xw, Xc);
+		Xc[0] += le.t[0]; Xc[1] += le.t[1]; Xc[2] += le.t[2];
 		write_record<ET>(st.e_rec, (size_t)e, Xc, le.wr, le.lin.r, il, le.stereo);
 		if (il < g.Lf)
 		{
@@ -241,17 +246,11 @@ __global__ __launch_bounds__(256) void big_lm_pass_kernel(DeviceGraph g, DeviceS
 			}
 		}
 	}
-#pragma unroll
-	for (int k = 0; k < 9; k++) acc[k] = wave_sum(acc[k]);
-	if ((threadIdx.x & 63) == 0)
-#pragma unroll
-		for (int k = 0; k < 9; k++) red[threadIdx.x >> 6][k] = acc[k];
-	__syncthreads();
+	four_waves_to_lds<9>(red, acc);
 	if (threadIdx.x == 0 && il < g.Lf)
 	{
 		Scalar H[9];
-#pragma unroll
-		for (int k = 0; k < 9; k++) H[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
+		four_wave_sum<9, false>(red, H);
 		if constexpr (PRIOR)
 		{
 			const Scalar X[3] = { g.Xw[3 * (size_t)il], g.Xw[3 * (size_t)il + 1], g.Xw[3 * (size_t)il + 2] };
@@ -594,6 +593,16 @@ static DeviceStructure block_pass_view(const DeviceStructure& st, const BlockPas
 	return v;
 }
 
+// the landmark launch's grid: a workgroup per LIN_BLOCK / WAVE waves of landmarks, then (optimize() only) the state-copy workgroups
+struct LandmarkGrid
+{
+	unsigned groups, nCopy;
+	LandmarkGrid(const DeviceStructure& st, const Scalar* backupSrc, size_t backupCount)
+		: groups((st.nWaves + (LIN_BLOCK / WAVE) - 1) / (LIN_BLOCK / WAVE)),
+		nCopy(backupSrc ? (unsigned)std::min<size_t>(512, (backupCount + LIN_BLOCK - 1) / LIN_BLOCK) : 0) {}
+	unsigned grid() const { return groups + nCopy; }
+};
+
 template <typename ET>
 static void launch_linearize_dm_t(const DeviceGraph& g, const DeviceStructure& stAll, const DeviceSystem& sys, int mode, Scalar lambda, hipStream_t s,
 	Scalar* backupSrc, Scalar* backupDst, size_t backupCount, const BlockPassRange* range, const double* restoreFlag, const DeviceLandmarkPriors* lp)
@@ -602,21 +611,22 @@ static void launch_linearize_dm_t(const DeviceGraph& g, const DeviceStructure& s
 	const DeviceStructure st = range ? block_pass_view(stAll, *range) : stAll;
 	if (st.nWaves > 0)
 	{
-		const unsigned grid = (st.nWaves + (LIN_BLOCK / WAVE) - 1) / (LIN_BLOCK / WAVE);
-		const unsigned nCopy = backupSrc ? (unsigned)std::min<size_t>(512, (backupCount + LIN_BLOCK - 1) / LIN_BLOCK) : 0;
-		if (lp && mode == 0) hipLaunchKernelGGL((lm_pass_prior_kernel<0, ET>), dim3(grid + nCopy), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, grid, backupSrc, backupDst, backupCount, nCopy ? restoreFlag : nullptr, *lp);
-		else if (lp) hipLaunchKernelGGL((lm_pass_prior_kernel<1, ET>), dim3(grid + nCopy), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, grid, backupSrc, backupDst, backupCount, nCopy ? restoreFlag : nullptr, *lp);
-		else if (mode == 0) hipLaunchKernelGGL((lm_pass_kernel<0, ET>), dim3(grid + nCopy), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, grid, backupSrc, backupDst, backupCount, nCopy ? restoreFlag : nullptr);
-		else hipLaunchKernelGGL((lm_pass_kernel<1, ET>), dim3(grid + nCopy), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, grid, backupSrc, backupDst, backupCount, nCopy ? restoreFlag : nullptr);
+		const LandmarkGrid L(st, backupSrc, backupCount);
+		const double* flag = L.nCopy ? restoreFlag : nullptr;
+		if (lp)
+			hipLaunchKernelGGL((mode == 0 ? lm_pass_prior_kernel<0, ET> : lm_pass_prior_kernel<1, ET>), dim3(L.grid()), dim3(LIN_BLOCK), 0, s,
+				g, st, sys, lambda, L.groups, backupSrc, backupDst, backupCount, flag, *lp);
+		else
+			hipLaunchKernelGGL((mode == 0 ? lm_pass_kernel<0, ET> : lm_pass_kernel<1, ET>), dim3(L.grid()), dim3(LIN_BLOCK), 0, s,
+				g, st, sys, lambda, L.groups, backupSrc, backupDst, backupCount, flag);
 	}
 	else if (backupSrc && backupCount)
 		(void)hipMemcpyAsync(backupDst, backupSrc, backupCount * sizeof(Scalar), hipMemcpyDeviceToDevice, s);
 	if (st.nBig > 0)
 	{
-		if (lp && mode == 0) hipLaunchKernelGGL((big_lm_pass_kernel<0, ET, true>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, *lp);
-		else if (lp) hipLaunchKernelGGL((big_lm_pass_kernel<1, ET, true>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, *lp);
-		else if (mode == 0) hipLaunchKernelGGL((big_lm_pass_kernel<0, ET, false>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, DeviceLandmarkPriors());
-		else hipLaunchKernelGGL((big_lm_pass_kernel<1, ET, false>), dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, DeviceLandmarkPriors());
+		const auto big = lp ? (mode == 0 ? big_lm_pass_kernel<0, ET, true> : big_lm_pass_kernel<1, ET, true>)
+			: (mode == 0 ? big_lm_pass_kernel<0, ET, false> : big_lm_pass_kernel<1, ET, false>);
+		hipLaunchKernelGGL(big, dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, lp ? *lp : DeviceLandmarkPriors());
 	}
 	const int nbp = block_pass_groups(st.nOd, st.nHeavy);
 	if (mode == 1 && g.Pf > 0 && st.nOd > 0 && st.nDiagProd == 0)     // (duplicate observations: the block pass updates diagonal blocks after the pose pass)
@@ -646,9 +656,9 @@ void launch_linearize_dm(const DeviceGraph& g, const DeviceStructure& st, const 
 // graph, as grid sizes of the batched launches
 void batch_fill_linearize(const DeviceGraph& g, const DeviceStructure& st, const Scalar* backupSrc, Scalar* backupDst, size_t backupCount, BatchTrial& t)
 {
-	t.lmGroups = (st.nWaves + (LIN_BLOCK / WAVE) - 1) / (LIN_BLOCK / WAVE);
-	const unsigned nCopy = backupSrc ? (unsigned)std::min<size_t>(512, (backupCount + LIN_BLOCK - 1) / LIN_BLOCK) : 0;
-	t.lmGrid = t.lmGroups + nCopy;
+	const LandmarkGrid L(st, backupSrc, backupCount);
+	t.lmGroups = L.groups;
+	t.lmGrid = L.grid();
 	t.backupSrc = backupSrc; t.backupDst = backupDst; t.backupCount = backupCount;
 	t.poseGroups = (g.Pf + 3) / 4;
 	t.schurGrid = (unsigned)(t.poseGroups + block_pass_groups(st.nOd, st.nHeavy));
