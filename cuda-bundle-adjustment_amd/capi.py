@@ -165,6 +165,11 @@ def load_library(precision="f64"):
     lib.cuba_hip_debug_pair_plan.restype = C.c_int
     lib.cuba_hip_debug_pcg_config.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)]
     lib.cuba_hip_debug_pcg_config.restype = C.c_int
+    lib.cuba_hip_debug_lm_script.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, _dp, C.POINTER(C.c_uint64), C.c_double, C.c_double, C.c_int, C.c_int,
+                                             _ip, _dp, _ip, _dp, _ip, _dp, _ip, C.c_size_t, _dp, _dp]
+    lib.cuba_hip_debug_lm_script.restype = C.c_int
+    lib.cuba_hip_debug_lm_records.argtypes = [H, _dp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.cuba_hip_debug_lm_records.restype = C.c_int
     lib.cuba_hip_last_error.argtypes = [H]
     lib.cuba_hip_last_error.restype = C.c_char_p
     lib.cuba_hip_version.restype = C.c_char_p
@@ -222,6 +227,45 @@ def dense_inverse(A, precision="f64", device=0):
     if rc != 0:
         raise CubaHipError(f"cuba_hip_debug_dense_inverse failed with status {rc}")
     return np.array(out)
+
+
+LM_STATE = ("F", "lam", "nu", "halt", "trials", "accepted", "rej", "maxq", "tag_base")
+LM_RECORD = ("Fhat", "scale", "rho", "lam", "F", "accepted", "halt", "tag")
+
+
+def lm_script(trials, niter, F0=0.0, lam0=0.0, chi_slots=None, maxdiag_bits=None, tau=1e-5, tag_base=65536.0, scratch_count=1, precision="f64", device=0):
+    """The decision kernels of a device-decided run on scripted partial sums (cuba_hip_debug_lm_script): test hook.
+    trials: [(ok, a, b, c), ...] with a, b, c the partial-sum arrays of the landmark part of the denominator, of chi2 and of the pose part.
+    chi_slots (16 numbers) and maxdiag_bits (64 uint64) given: the run starts on the device (launch_lm_run_init) instead of from F0, lam0.
+    Returns (start, per_trial): start = dict(state, lam_scalar); per_trial = list of dict(state, record [dicts by name], lam_scalar,
+    sums (a, b, c) or None, slots_zero, restored, untouched, absorbed, done, stop, rej_run, chi2 (or None), host_lam, host_F)."""
+    n = len(trials)
+    ok = np.ascontiguousarray([1 if t[0] else 0 for t in trials], dtype=np.int32)
+    cols = []
+    for k in (1, 2, 3):
+        arrs = [np.asarray(t[k] if t[0] else [], dtype=np.float64).reshape(-1) for t in trials]
+        off = np.zeros(n + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(x) for x in arrs])
+        cols += [np.ascontiguousarray(np.concatenate(arrs + [np.zeros(1)])), off]
+    start, out = np.zeros(10), np.zeros((max(n, 1), 32))
+    on_device = chi_slots is not None
+    if on_device:
+        chi_slots = np.ascontiguousarray(chi_slots, dtype=np.float64).reshape(16)
+        maxdiag_bits = np.ascontiguousarray(maxdiag_bits, dtype=np.uint64).reshape(64)
+    rc = load_library(precision).cuba_hip_debug_lm_script(
+        int(device), 1 if on_device else 0, float(F0), float(lam0), _d(chi_slots), maxdiag_bits.ctypes.data_as(C.POINTER(C.c_uint64)) if on_device else None,
+        float(tau), float(tag_base), int(niter), n, _i(ok), _d(cols[0]), _i(cols[1]), _d(cols[2]), _i(cols[3]), _d(cols[4]), _i(cols[5]),
+        int(scratch_count), _d(start), _d(out))
+    if rc != 0:
+        raise CubaHipError(f"cuba_hip_debug_lm_script failed with status {rc}")
+    res = []
+    for t in range(n):
+        o = out[t]
+        res.append(dict(state=dict(zip(LM_STATE, o[0:9].tolist())), record=dict(zip(LM_RECORD, o[9:17].tolist())), lam_scalar=float(o[17]),
+                        sums=tuple(o[18:21].tolist()) if o[21] >= 0 else None, slots_zero=o[21] == 1, restored=o[22] == 1, untouched=o[23] == 1,
+                        absorbed=int(o[24]), done=int(o[25]), stop=o[26] == 1, rej_run=int(o[27]), chi2=float(o[29]) if o[28] == 1 else None,
+                        host_lam=float(o[30]), host_F=float(o[31])))
+    return dict(state=dict(zip(LM_STATE, start[0:9].tolist())), lam_scalar=float(start[9])), res
 
 
 _live = weakref.WeakSet()
@@ -710,6 +754,15 @@ class HipSolver:
         out = {k: int(v) for k, v in zip(keys, cfg)}
         out["pose_order"] = order[:n.value]
         return out
+
+    def lm_records(self):
+        """The ring of decision records of the last optimize() / optimize_batch() run (cuba_hip_debug_lm_records): [64, 8], record of
+        trial k in row k % 64, columns LM_RECORD."""
+        n = C.c_size_t()
+        self._ck(self.lib.cuba_hip_debug_lm_records(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value)
+        self._ck(self.lib.cuba_hip_debug_lm_records(self.h, _d(out), n.value, C.byref(n)))
+        return out.reshape(-1, len(LM_RECORD))
 
     def array(self, name):
         n = C.c_size_t()

@@ -589,6 +589,13 @@ struct TrialTailLayout
 	size_t size() const { return scaleOff + 4 * 256 + 64; }
 };
 
+void launch_reduce_report(const DeviceSystem& sys, const Scalar* pA, int nA, Scalar* oA, const Scalar* pB, int nB, Scalar* oB, const Scalar* pC, int nC, Scalar* oC,
+	const LmDevice* decide, int publish, hipStream_t s)
+{
+	hipLaunchKernelGGL(reduce_report_kernel, dim3(1), dim3(1024), 0, s, sys, pA, nA, oA, pB, nB, oB, pC, nC, oC,
+		decide ? decide->state : (double*)nullptr, decide ? decide->lam : (Scalar*)nullptr, decide ? decide->ring : (double*)nullptr, publish);
+}
+
 size_t trial_tail_parts(const DeviceGraph& g, const DeviceStructure& st, int factorParts)
 {
 	return TrialTailLayout(g, st, factorParts).size();
@@ -606,8 +613,7 @@ void launch_trial_tail_fused(const DeviceGraph& g, const DeviceStructure& st, co
 		hipLaunchKernelGGL(trial_tail_kernel, dim3(L.grid()), dim3(LIN_BLOCK), 0, s, g, st, sys, lambda, old, scParts, chiParts, L.nLm, L.poseBlocks, scaleParts, L.nScale);
 	if (st.nBig > 0) hipLaunchKernelGGL(big_trial_tail_kernel, dim3(st.nBig), dim3(256), 0, s, g, st, sys, lambda, old, scParts + L.nLm, chiParts + L.nLm);
 	if (nPf > 0) launch_factor_chi2(g, *pf, chiParts + L.nA, s);          // (at the poses the edge pass has just updated)
-	hipLaunchKernelGGL(reduce_report_kernel, dim3(1), dim3(1024), 0, s, sys, scParts, L.nA, sys.slots + NSLOT, chiParts, L.nA + nPf, sys.slots, scaleParts, 4 * L.nScale, sys.slots + 3 * NSLOT,
-		decide ? decide->state : (double*)nullptr, decide ? decide->lam : (Scalar*)nullptr, decide ? decide->ring : (double*)nullptr, publish);
+	launch_reduce_report(sys, scParts, L.nA, sys.slots + NSLOT, chiParts, L.nA + nPf, sys.slots, scaleParts, 4 * L.nScale, sys.slots + 3 * NSLOT, decide, publish, s);
 }
 
 // launch_trial_tail_fused + launch_restore_if_rejected of one graph as entries of the batched launches (no landmark with more than 64 observations)

@@ -307,6 +307,11 @@ struct LmDevice { double* state = nullptr; Scalar* lam = nullptr; double* ring =
 // 1, 0, maxq, tagBase}, lam = lambda0
 void launch_lm_run_init(const Scalar* chiSlots, const unsigned long long* maxdiag, const LmDevice& lm, double tau, double tagBase, int maxq, hipStream_t s);
 void launch_lm_decide_failed(const DeviceSystem& sys, const LmDevice& lm, hipStream_t s);
+// the sums' second stage of a trial on its own (what launch_trial_tail_fused ends with): partials pA[0, nA) -> oA[0..NSLOT) (total in oA[0], zeros
+// behind it), likewise B and C; with `decide` the decision of the trial from them (A = landmark part of the denominator, B = chi2, C = pose
+// part), with `publish` the report to the host
+void launch_reduce_report(const DeviceSystem& sys, const Scalar* pA, int nA, Scalar* oA, const Scalar* pB, int nB, Scalar* oB, const Scalar* pC, int nC, Scalar* oC,
+	const LmDevice* decide, int publish, hipStream_t s);
 void launch_restore_if_rejected(Scalar* state, const Scalar* backup, size_t count, const LmDevice& lm, hipStream_t s);
 // landmark-side part recomputed from xl and the stored bl (stage API; the fused path gets it from back_substitute)
 void launch_landmark_scale(const DeviceGraph& g, const DeviceSystem& sys, Scalar lambda, Scalar* slots, hipStream_t s);

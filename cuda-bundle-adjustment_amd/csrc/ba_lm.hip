@@ -739,33 +739,18 @@ void cuba_hip_solver::lmRunBegin(LmRun& r, int niter, double* chi2Out, bool chai
 void cuba_hip_solver::lmAbsorb(LmRun& r, int upto)
 {
 	std::atomic_thread_fence(std::memory_order_acquire);
-	for (; r.seen < upto && !r.stop; r.seen++)
+	while (r.seen < upto && !r.stop)
 	{
 		const volatile double* rec = h_lmRing + (size_t)(r.seen % LM_RING) * LM_REC;
 		// the record must be THIS run's record of THIS trial.  The ticket the caller waited for is stored after it by the same device thread
 		// behind a system-scope release (publish_report) -- and still, once in a few hundred short runs, a record had not landed when its
 		// ticket had (round 6: an iteration's chi2 came back as 0): whatever reorders the two on the way to host memory, a stream
 		// synchronisation ends it
-		const double tag = r.tagBase + (double)(r.seen + 1);
-		if (rec[7] != tag)
-		{
-			cntLateRecords++;
-			sync();
-			std::atomic_thread_fence(std::memory_order_acquire);
-			if (rec[7] != tag) throw StateError{ "the device's decision record of an LM trial never arrived" };
-		}
-		const bool acc = rec[5] != 0.0;
-		const double rho = rec[2];
-		r.lam = rec[3]; r.F = rec[4];
-		if (acc) r.rejRun = 0; else r.rejRun++;
-		// the reference's loops: an iteration ends with an accepted trial, with the maxq-th rejection, or with a rejected trial whose
-		// rho is not < 0; the run ends after niter iterations, or on `qn == maxq || rho <= 0 || !isfinite(lambda)` (:851)
-		const bool iterationEnds = acc || r.rejRun == LmRun::maxq || !(rho < 0);
-		if (!iterationEnds) continue;
-		if (r.chi2Out) r.chi2Out[r.done] = r.F;
-		r.done++;
-		if (r.done == r.niter || r.rejRun == LmRun::maxq || rho <= 0 || !std::isfinite(r.lam)) r.stop = true;
-		r.rejRun = 0;
+		if (r.absorb(rec)) continue;
+		cntLateRecords++;
+		sync();
+		std::atomic_thread_fence(std::memory_order_acquire);
+		if (!r.absorb(rec)) throw StateError{ "the device's decision record of an LM trial never arrived" };
 	}
 }
 

@@ -980,6 +980,160 @@ int cuba_hip_debug_pcg_config(cuba_hip_solver* s, int32_t cfg[9], int32_t* pose_
 	});
 }
 
+// The ring of decision records of the handle's last device-decided run (LM_RING x LM_REC doubles; zeros before its first run)
+int cuba_hip_debug_lm_records(cuba_hip_solver* s, double* out, size_t capacity, size_t* count)
+{
+	return guarded(s, [&] {
+		if (!count) throw ArgError{ "null output" };
+		*count = (size_t)LM_RING * LM_REC;
+		if (!out) return;
+		s->sync();
+		std::atomic_thread_fence(std::memory_order_acquire);
+		for (size_t i = 0; i < std::min(capacity, *count); i++) out[i] = s->h_lmRing ? ((const volatile double*)s->h_lmRing)[i] : 0.0;
+	});
+}
+
+// The decision kernels of a device-decided run on SCRIPTED sums, no handle and no graph: the start of a run (start_mode 0: the state as
+// lmRunBegin's host branch writes it, from F0 and lam0; 1: launch_lm_run_init over chi_slots[NSLOT] and maxdiag_bits[64] with tau), then per
+// trial t, in stream order, launch_reduce_report with a decision over the partial sums a[a_off[t], a_off[t + 1]) (landmark part of the
+// denominator), b (chi2), c (pose part) -- or launch_lm_decide_failed where ok[t] == 0 -- and launch_restore_if_rejected on a scratch
+// state / backup pair of scratch_count numbers.  Every trial is fed, whatever the host logic (LmRun::absorb, niter iterations) makes of
+// the records.  out_start[10]: the 9 state numbers and the damping as the kernels read it after the start.  out[32 t ..]: [0, 9) state,
+// [9, 17) the trial's ring record, 17 the damping as the kernels read it, 18..20 the three sums from their slot groups, 21 slots 1..NSLOT-1
+// of the three groups all zero (-1: a failed trial has no sums), 22 scratch state == backup, 23 scratch state as it was before the trial,
+// 24 the host absorbed the record (0: it had stopped before; -1: the record's tag was not the trial's), 25 done, 26 stop, 27 rejRun,
+// 28 a chi2 was written for this trial, 29 that chi2, 30 the host's damping, 31 the host's F
+int cuba_hip_debug_lm_script(int device, int start_mode, double F0, double lam0, const double* chi_slots, const uint64_t* maxdiag_bits, double tau, double tag_base,
+	int niter, int n_trials, const int32_t* ok, const double* a, const int32_t* a_off, const double* b, const int32_t* b_off, const double* c, const int32_t* c_off,
+	size_t scratch_count, double* out_start, double* out)
+{
+	constexpr int MAX_TRIALS = 512, MAX_PARTS = 1 << 16, GUARD = 64, STRIDE = 32;
+	constexpr size_t MAX_SCRATCH = (size_t)1 << 20;
+	if (start_mode < 0 || start_mode > 1 || n_trials < 0 || n_trials > MAX_TRIALS || niter < 0 || niter > MAX_TRIALS) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	if (!out_start || (n_trials > 0 && (!ok || !a_off || !b_off || !c_off || !out))) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	if (start_mode == 1 && (!chi_slots || !maxdiag_bits)) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	if (scratch_count > MAX_SCRATCH) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	if (!(tag_base >= 0 && tag_base <= 9e15)) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	const int32_t* offs[3] = { a_off, b_off, c_off };
+	const double* src[3] = { a, b, c };
+	for (int k = 0; k < 3 && n_trials > 0; k++)
+	{
+		if (offs[k][0] != 0) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+		for (int t = 0; t < n_trials; t++)
+			if (offs[k][t + 1] < offs[k][t] || offs[k][t + 1] - offs[k][t] > MAX_PARTS) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+		if (offs[k][n_trials] > 0 && !src[k]) return CUBA_HIP_ERR_INVALID_ARGUMENT;
+	}
+	if (hipSetDevice(device) != hipSuccess) return CUBA_HIP_ERR_NO_DEVICE;
+	double* ringHost = nullptr;
+	try
+	{
+		hipStream_t st = nullptr;
+		DevBuf<double> dState; dState.resize(16); dState.zero(st);
+		DevBuf<Scalar> dLam; dLam.resize(1); dLam.zero(st);
+		DevBuf<Scalar> dSlots; dSlots.resize(4 * NSLOT);
+		DevBuf<Scalar> dParts; dParts.resize(3 * (size_t)MAX_PARTS + 4 * GUARD);
+		DevBuf<Scalar> dScratch, dBackup;
+		HIP_TRY(hipHostMalloc((void**)&ringHost, sizeof(double) * LM_RING * LM_REC, hipHostMallocMapped | hipHostMallocCoherent));
+		std::memset(ringHost, 0, sizeof(double) * LM_RING * LM_REC);
+		LmDevice lm; lm.state = dState.data(); lm.lam = dLam.data();
+		HIP_TRY(hipHostGetDevicePointer((void**)&lm.ring, ringHost, 0));
+		const DeviceSystem sys{};                       // (host_flags null: nothing is published)
+		cuba_hip_solver::LmRun r;
+		r.niter = niter; r.stop = niter <= 0; r.tagBase = tag_base; r.lm = lm;
+		std::vector<double> chi2((size_t)std::max(niter, 1), 0.0);
+		r.chi2Out = chi2.data();
+		if (start_mode == 1)
+		{
+			std::vector<Scalar> hs(chi_slots, chi_slots + NSLOT);
+			DevBuf<Scalar> dChi; dChi.upload(hs, st);
+			DevBuf<unsigned long long> dMax; dMax.resize(64);
+			HIP_TRY(hipMemcpyAsync(dMax.data(), maxdiag_bits, sizeof(unsigned long long) * 64, hipMemcpyHostToDevice, st));
+			launch_lm_run_init(dChi.data(), dMax.data(), lm, tau, tag_base, cuba_hip_solver::LmRun::maxq, st);
+			HIP_TRY(hipStreamSynchronize(st));
+		}
+		else
+		{
+			const double st9[9] = { F0, lam0, 2.0, 0.0, 0.0, 1.0, 0.0, (double)cuba_hip_solver::LmRun::maxq, tag_base };
+			const Scalar l1 = (Scalar)lam0;
+			HIP_TRY(hipMemcpy(dState.data(), st9, sizeof st9, hipMemcpyHostToDevice));
+			HIP_TRY(hipMemcpy(dLam.data(), &l1, sizeof l1, hipMemcpyHostToDevice));
+			r.F = F0; r.lam = lam0;
+		}
+		{
+			Scalar l1 = 0;
+			HIP_TRY(hipMemcpy(out_start, dState.data(), sizeof(double) * 9, hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(&l1, dLam.data(), sizeof l1, hipMemcpyDeviceToHost));
+			out_start[9] = (double)l1;
+		}
+		std::vector<Scalar> hScratch(scratch_count), hBackup(scratch_count), hGot(scratch_count), hParts, hSlots(4 * NSLOT);
+		for (size_t i = 0; i < scratch_count; i++) { hScratch[i] = (Scalar)(1 + i % 251); hBackup[i] = -(Scalar)(1 + i % 127); }
+		dBackup.upload(hBackup, st);
+		for (int t = 0; t < n_trials; t++)
+		{
+			double* o = out + (size_t)STRIDE * t;
+			std::fill(o, o + STRIDE, 0.0);
+			dScratch.upload(hScratch, st);
+			if (ok[t])
+			{
+				// [guard | a | guard | b | guard | c | guard]: a read outside an array changes its total
+				const int n[3] = { a_off[t + 1] - a_off[t], b_off[t + 1] - b_off[t], c_off[t + 1] - c_off[t] };
+				hParts.assign((size_t)n[0] + n[1] + n[2] + 4 * GUARD, (Scalar)1048576);
+				size_t at[3], pos = GUARD;
+				for (int k = 0; k < 3; k++)
+				{
+					at[k] = pos;
+					for (int i = 0; i < n[k]; i++) hParts[pos + i] = (Scalar)src[k][offs[k][t] + i];
+					pos += (size_t)n[k] + GUARD;
+				}
+				HIP_TRY(hipMemcpyAsync(dParts.data(), hParts.data(), sizeof(Scalar) * hParts.size(), hipMemcpyHostToDevice, st));
+				std::fill(hSlots.begin(), hSlots.end(), (Scalar)77);
+				HIP_TRY(hipMemcpyAsync(dSlots.data(), hSlots.data(), sizeof(Scalar) * hSlots.size(), hipMemcpyHostToDevice, st));
+				launch_reduce_report(sys, dParts.data() + at[0], n[0], dSlots.data() + NSLOT, dParts.data() + at[1], n[1], dSlots.data(),
+					dParts.data() + at[2], n[2], dSlots.data() + 3 * NSLOT, &lm, 0, st);
+			}
+			else launch_lm_decide_failed(sys, lm, st);
+			launch_restore_if_rejected(dScratch.data(), dBackup.data(), scratch_count, lm, st);
+			HIP_TRY(hipStreamSynchronize(st));
+			HIP_TRY(hipMemcpy(o, dState.data(), sizeof(double) * 9, hipMemcpyDeviceToHost));
+			std::atomic_thread_fence(std::memory_order_acquire);
+			const volatile double* rec = ringHost + (size_t)(t % LM_RING) * LM_REC;
+			for (int i = 0; i < LM_REC; i++) o[9 + i] = rec[i];
+			Scalar l1 = 0;
+			HIP_TRY(hipMemcpy(&l1, dLam.data(), sizeof l1, hipMemcpyDeviceToHost));
+			o[17] = (double)l1;
+			if (ok[t])
+			{
+				HIP_TRY(hipMemcpy(hSlots.data(), dSlots.data(), sizeof(Scalar) * hSlots.size(), hipMemcpyDeviceToHost));
+				o[18] = (double)hSlots[NSLOT]; o[19] = (double)hSlots[0]; o[20] = (double)hSlots[3 * NSLOT];
+				bool zero = true;
+				for (int g = 0; g < 4; g++)
+					for (int i = 1; i < NSLOT; i++) if (g != 2 && hSlots[g * NSLOT + i] != Scalar(0)) zero = false;
+				o[21] = zero ? 1.0 : 0.0;
+			}
+			else o[21] = -1.0;
+			if (scratch_count) HIP_TRY(hipMemcpy(hGot.data(), dScratch.data(), sizeof(Scalar) * scratch_count, hipMemcpyDeviceToHost));
+			o[22] = hGot == hBackup ? 1.0 : 0.0;
+			o[23] = hGot == hScratch ? 1.0 : 0.0;
+			if (!r.stop && r.seen == t)
+			{
+				const int doneBefore = r.done;
+				if (!r.absorb(rec)) o[24] = -1.0;
+				else
+				{
+					o[24] = 1.0;
+					if (r.done > doneBefore) { o[28] = 1.0; o[29] = chi2[doneBefore]; }
+				}
+			}
+			o[25] = r.done; o[26] = r.stop ? 1.0 : 0.0; o[27] = r.rejRun; o[30] = r.lam; o[31] = r.F;
+		}
+		(void)hipHostFree(ringHost);
+		return CUBA_HIP_OK;
+	}
+	catch (const HipError&) { if (ringHost) (void)hipHostFree(ringHost); return CUBA_HIP_ERR_RUNTIME; }
+	catch (const std::exception&) { if (ringHost) (void)hipHostFree(ringHost); return CUBA_HIP_ERR_RUNTIME; }
+	catch (...) { if (ringHost) (void)hipHostFree(ringHost); return CUBA_HIP_ERR_RUNTIME; }
+}
+
 int cuba_hip_begin_run(cuba_hip_solver* s)
 {
 	return guarded(s, [&] { s->need(); s->coarseValid = false; s->startRunHistory(); });

@@ -854,6 +854,25 @@ struct cuba_hip_solver
 		double lam = 0, F = 0, tagBase = 0;
 		double* chi2Out = nullptr;
 		LmDevice lm;
+		// The record of trial `seen` (LM_REC numbers): false = it is not this run's record of that trial (nothing has changed).  Otherwise the
+		// reference's loops: an iteration ends with an accepted trial, with the maxq-th rejection, or with a rejected trial whose rho is not
+		// < 0; the run ends after niter iterations, or on `qn == maxq || rho <= 0 || !isfinite(lambda)` (:851)
+		bool absorb(const volatile double* rec)
+		{
+			if (rec[7] != tagBase + (double)(seen + 1)) return false;
+			const bool acc = rec[5] != 0.0;
+			const double rho = rec[2];
+			lam = rec[3]; F = rec[4];
+			seen++;
+			if (acc) rejRun = 0; else rejRun++;
+			const bool iterationEnds = acc || rejRun == maxq || !(rho < 0);
+			if (!iterationEnds) return true;
+			if (chi2Out) chi2Out[done] = F;
+			done++;
+			if (done == niter || rejRun == maxq || rho <= 0 || !std::isfinite(lam)) stop = true;
+			rejRun = 0;
+			return true;
+		}
 	};
 	void lmRunBegin(LmRun& r, int niter, double* chi2Out, bool chain = false);
 	const double* lmRestoreFlag = nullptr;      // set around the schur(true) of a trial whose landmark pass carries the conditional restore

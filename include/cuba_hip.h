@@ -726,6 +726,25 @@ int cuba_hip_debug_pair_plan(int n_poses, const int32_t* row_ptr, const int32_t*
    internal indices); *count = Pf, pose_order may be NULL. */
 int cuba_hip_debug_pcg_config(cuba_hip_solver* s, int32_t cfg[9], int32_t* pose_order, size_t capacity, size_t* count);
 
+/* Test hook: the decision kernels of a device-decided run (run start, the sums' second stage with the decision, the decision of a failed
+   solve, the conditional restore) on scripted partial sums, with the host's per-record logic beside them.  No solver handle involved.
+   start_mode 0: the decision state as the host writes it, from F0 and lam0; 1: formed on the device from chi_slots[16] (F0 = their sum) and
+   maxdiag_bits[64] (lam0 = tau * the largest bit pattern read as a double).  Trial t: ok[t] != 0 -> the partial sums a[a_off[t], a_off[t+1])
+   (landmark part of the gain ratio's denominator), b (chi2), c (pose part), at most 65536 each; ok[t] == 0 -> a failed solve.  Offsets
+   start at 0 and do not decrease.  At most 512 trials and iterations; scratch_count <= 2^20 numbers of scratch estimate and backup for
+   the restore.  out_start[10] = the 9 state numbers {F, lambda, nu, halt, trials, accepted, rejections in a row, max rejections, tag
+   base} and the damping as the kernels read it.  out[32 t + ..]: 0..8 state, 9..16 the trial's record {Fhat, denominator, rho, next
+   lambda, next F, accepted, halt, tag}, 17 kernels' damping, 18..20 the sums a, b, c as their slot groups hold them, 21 the groups' other
+   slots are zero (-1: no sums), 22 scratch == backup, 23 scratch untouched, 24 the host logic absorbed the record (0: it had stopped, -1:
+   tag mismatch), 25 iterations done, 26 stop, 27 rejections in a row, 28 / 29 a chi2 was written / its value, 30 / 31 the host's lambda / F.
+   Every trial is fed to the device whether or not the host logic has stopped. */
+int cuba_hip_debug_lm_script(int device, int start_mode, double F0, double lam0, const double* chi_slots, const uint64_t* maxdiag_bits, double tau, double tag_base,
+	int niter, int n_trials, const int32_t* ok, const double* a, const int32_t* a_off, const double* b, const int32_t* b_off, const double* c, const int32_t* c_off,
+	size_t scratch_count, double* out_start, double* out);
+/* Test hook, read-only: the 64 x 8 ring of decision records of the handle's last cuba_hip_optimize / cuba_hip_optimize_batch run (record of
+   trial k in slot k % 64, layout as above; zeros before the first run).  *count = 512; out may be NULL. */
+int cuba_hip_debug_lm_records(cuba_hip_solver* s, double* out, size_t capacity, size_t* count);
+
 /* A driver that runs the Levenberg-Marquardt loop itself through the stage calls announces the start of a run (a new lambda_0):
    the coarse inverse of the two-level preconditioner and the iteration-count predictions of the previous run are dropped, as
    cuba_hip_optimize does at its start; a hand-over to the exact reduced solve that an earlier run made (option "direct_fallback")

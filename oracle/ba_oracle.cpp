@@ -872,6 +872,7 @@ struct Problem
 			if (it == 0) lam = tau * maxDiagonal();
 			int qn = 0;
 			double rho = -1;
+			bool accepted = false;
 			for (; qn < maxq && rho < 0; qn++)
 			{
 				push();
@@ -887,6 +888,7 @@ struct Problem
 					lam *= std::max(1. / 3, std::min(a, 2. / 3));
 					nu = 2;
 					F = Fhat;
+					accepted = true;
 					break;
 				}
 				else
@@ -899,7 +901,7 @@ struct Problem
 			}
 			if (chi2Out) chi2Out[it] = F;
 			if (lambdaOut) lambdaOut[it] = lam;
-			if (trialsOut) trialsOut[it] = std::min(qn + 1, maxq);
+			if (trialsOut) trialsOut[it] = accepted ? qn + 1 : qn;      // (the break skips the loop's qn++; a loop that ends without it has counted every trial)
 			done = it + 1;
 			if (qn == maxq || rho <= 0 || !std::isfinite(lam)) break;
 		}
