@@ -137,6 +137,10 @@ def load_library(precision="f64"):
         "cuba_hip_range_factor_chi_squares": [H, _dp],
         "cuba_hip_set_pose_range_factors": [H, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _dp],
         "cuba_hip_pose_range_factor_chi_squares": [H, _dp],
+        "cuba_hip_gate_edges": [H, _dp, C.c_int, C.c_int, C.POINTER(C.c_int64), _dp],
+        "cuba_hip_set_edge_active": [H, _u8p],
+        "cuba_hip_get_edge_active": [H, _u8p],
+        "cuba_hip_landmark_active_edges": [H, _ip],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -573,6 +577,47 @@ class HipSolver:
     def chi_squares(self):
         out = np.zeros(self.fp.E)
         self._ck(self.lib.cuba_hip_chi_squares(self.h, _d(out)))
+        return out
+
+    # ---- edge gating (cuba_hip_gate_edges: g2o's setLevel / computeActiveErrors flow) ----------
+    GATE_MODES = {"reclassify": 0, "only_remove": 1, "dry_run": 2}
+    GATE_COUNTS = ("active_mono", "active_stereo", "gated_chi2_mono", "gated_chi2_stereo", "gated_depth", "changed")
+
+    def gate_edges(self, chi2_max=(5.991, 7.815), positive_depth=True, mode="reclassify", with_chi2=False):
+        """Classifies every reprojection edge on the device at the current estimate: active iff its omega |r|^2 (uploaded omega) is at most
+        chi2_max[stereo] and -- positive_depth -- its point lies in front of the camera.  mode: "reclassify", "only_remove", "dry_run" (or
+        the integer).  Returns the six counts by name; with_chi2: also "chi2", the ungated omega |r|^2 per edge in the caller's order."""
+        E = self.fp.E if self.fp is not None else 0
+        thr = np.ascontiguousarray(chi2_max, dtype=np.float64).reshape(2)
+        counts = (C.c_int64 * 6)()
+        chi = np.zeros(E) if with_chi2 else None
+        self._ck(self.lib.cuba_hip_gate_edges(self.h, _d(thr), int(bool(positive_depth)), int(self.GATE_MODES.get(mode, mode)), counts,
+                                              _d(chi) if with_chi2 else None))
+        out = {k: int(v) for k, v in zip(self.GATE_COUNTS, counts)}
+        if with_chi2:
+            out["chi2"] = chi
+        return out
+
+    def set_edge_active(self, mask):
+        """mask[E] in the caller's edge order (truthy = active); None: all edges active, the gate's storage is freed"""
+        if mask is None:
+            self._ck(self.lib.cuba_hip_set_edge_active(self.h, None))
+            return
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if self.fp is not None and m.shape != (self.fp.E,):
+            raise ValueError(f"mask: expected {self.fp.E} entries")
+        self._ck(self.lib.cuba_hip_set_edge_active(self.h, m.ctypes.data_as(_u8p)))
+
+    def edge_active(self):
+        """bool[E], caller's edge order; all True on a handle without a gate"""
+        out = np.zeros(self.fp.E if self.fp is not None else 0, dtype=np.uint8)
+        self._ck(self.lib.cuba_hip_get_edge_active(self.h, out.ctypes.data_as(_u8p)))
+        return out.astype(bool)
+
+    def landmark_active_edges(self):
+        """int32[Lt], caller's landmark order: active edges per landmark"""
+        out = np.zeros(self.fp.Lt if self.fp is not None else 0, dtype=np.int32)
+        self._ck(self.lib.cuba_hip_landmark_active_edges(self.h, out.ctypes.data_as(_ip)))
         return out
 
     def set_pose_priors(self, pose, q, t, info):

@@ -530,6 +530,31 @@ struct PairDev                    // device view of one chunk
 // out3 = {chi2 total, landmark scale part, pose scale part} gathered from the result slots of the kernels enqueued before
 void launch_collect_eval(const DeviceSystem& sys, Scalar* out3, hipStream_t s);
 
+// ---- edge gating (ba_gate.hip) ------------------------------------------------------------------------------------------------------
+enum { GATE_RECLASSIFY = 0, GATE_ONLY_REMOVE = 1, GATE_DRY_RUN = 2 };
+constexpr int GATE_COUNTS = 6;    // active mono, active stereo, gated by chi2 mono, gated by chi2 stereo, gated by depth, changed
+struct EdgeGateArgs
+{
+	DeviceGraph g;                     // e_w: the UPLOADED information
+	double chi2_mono = 0, chi2_stereo = 0;
+	int require_depth = 1, mode = GATE_RECLASSIFY;
+	const uint8_t* mask_in = nullptr;  // [E] sorted order; null: every edge is active
+	uint8_t* mask_out = nullptr;       // [E] sorted order    } not written by a dry run
+	Scalar* w_live = nullptr;          // [E] mask ? w0 : +0  }
+	Scalar* chi_out = nullptr;         // [E] omega |r|^2 with the uploaded omega, sorted order (optional)
+	long long* parts = nullptr;        // [GATE_COUNTS * edge_gate_grid(g)]
+};
+int edge_gate_grid(const DeviceGraph& g);
+// an edge stays active iff chi <= chi2_max[stereo] and (no depth test or Xc[2] > 0) -- a NaN fails both --; GATE_ONLY_REMOVE: and it was
+// active.  counts[GATE_COUNTS]: a depth failure counts as such whatever its chi2; `changed` compares with mask_in.
+void launch_edge_gate(const EdgeGateArgs& a, long long* counts, hipStream_t s);
+// the mask between the caller's edge order and the sorted one (perm[sorted position] = caller's index), with the live information
+void launch_gate_apply(const uint32_t* perm, const uint8_t* maskCaller, const Scalar* w0, int E, uint8_t* maskSorted, Scalar* w_live, hipStream_t s);
+void launch_gate_unsort(const uint32_t* perm, const uint8_t* maskSorted, int E, uint8_t* maskCaller, hipStream_t s);
+// out[l] = active edges of landmark l in the caller's numbering (newOfOld: the internal landmark order, or null; mask null: all active);
+// bigInternal[Lt]: scratch of the landmarks of big_lm (more than 64 edges: one workgroup each)
+void launch_landmark_active(const int* lm_ptr, const uint8_t* mask, const int* newOfOld, int Lt, const int* big_lm, int nBig, int* bigInternal, int* out, hipStream_t s);
+
 // copies {fail, iters, done} into sys.host_flags (what the last node of an iteration graph does anyway)
 void launch_pcg_report(const DeviceSystem& sys, hipStream_t s);
 

@@ -13,6 +13,7 @@ void cuba_hip_solver::finishValues()
 	topo::launch_gather_edges(d_perm.data(), d_rawEp.data(), d_rawEl.data(), d_rawDim.data(), d_rawMeas.data(), d_rawOmega.data(), E,
 		nullptr, nullptr, d_mu.data(), d_mv.data(), d_mr.data(), d_w.data(), stream);
 	sortedValuesValid = true;
+	valuesStamp++;          // (the permutation or the sorted values are new: an edge gate derives its copies again, refreshGate)
 }
 
 void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double* q, const double* t, const double* cam, const double* Xw,
@@ -60,6 +61,9 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 		if (bad == 2) throw ArgError{ "edge_dim must be 2 or 3" };
 		if (bad == 3) throw ArgError{ "edge with both ends fixed (must be dropped by the caller)" };
 	}
+	// an edge gate (ba_gate.hip) outlives a call whose edge arrays are the previous call's -- promised or found so above --: its mask is kept
+	// in the caller's edge order, and need() derives the live information from the newly uploaded one.  Other edges: all active again.
+	if (!sameInput) clearGate();
 	// from here on the old graph is being replaced: a failure below (allocation, upload) leaves NO graph
 	haveGraph = false;
 	haveStructure = false;
@@ -247,7 +251,7 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 	g.q = d_state.data(); g.t = d_state.data() + 4 * (size_t)Pt; g.Xw = d_state.data() + 7 * (size_t)Pt;
 	g.cam = d_cam.data();
 	g.e_pose = d_epose.data(); g.e_lm = d_elm.data(); g.lm_ptr = d_lmptr.data();
-	g.e_mu = d_mu.data(); g.e_mv = d_mv.data(); g.e_mr = d_mr.data(); g.e_w = d_w.data();
+	g.e_mu = d_mu.data(); g.e_mv = d_mv.data(); g.e_mr = d_mr.data(); g.e_w = liveInformation();
 	g.rk[0] = rk[0]; g.rk[1] = rk[1];
 	g.e_begin = 0; g.e_end = E;
 	partLo = ranged ? ownLo : 0; partHi = ranged ? ownHi : -1;
@@ -269,6 +273,7 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 	cntBatchFullTrials = cntBatchIterTrials = 0;
 	pcgHistory.clear();
 	cntUploads++;
+	valuesStamp++;          // (the permutation or the sorted values are new: an edge gate derives its copies again, refreshGate)
 	prof[0] += std::chrono::duration<double>(Clock::now() - t0).count();
 }
 
@@ -932,6 +937,7 @@ void cuba_hip_solver::runDeviceEdgeSort(bool withValues)
 		d_epose.data(), d_elm.data(), withValues ? d_mu.data() : nullptr, d_mv.data(), d_mr.data(), d_w.data(), stream);
 	topo::launch_segment_ptr(d_elm.data(), E, Lt, d_lmptr.data(), stream);
 	if (withValues) sortedValuesValid = true;
+	valuesStamp++;          // (the permutation or the sorted values are new: an edge gate derives its copies again, refreshGate)
 }
 
 std::vector<int> cuba_hip_solver::chainOrder(const std::vector<int>& rowptr, const std::vector<int>& colind, const std::vector<int>& prodPtr) const

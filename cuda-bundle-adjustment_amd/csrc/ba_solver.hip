@@ -352,6 +352,15 @@ int cuba_hip_chi_squares_end(cuba_hip_solver* s)
 	return guarded(s, [&] { s->sync(); });
 }
 
+int cuba_hip_gate_edges(cuba_hip_solver* s, const double chi2_max[2], int require_positive_depth, int mode, int64_t counts[6], double* chi2_per_edge)
+{
+	return guarded(s, [&] { s->gateEdges(chi2_max, require_positive_depth != 0, mode, counts, chi2_per_edge); });
+}
+
+int cuba_hip_set_edge_active(cuba_hip_solver* s, const uint8_t* active) { return guarded(s, [&] { s->setEdgeActive(active); }); }
+int cuba_hip_get_edge_active(cuba_hip_solver* s, uint8_t* active) { return guarded(s, [&] { s->getEdgeActive(active); }); }
+int cuba_hip_landmark_active_edges(cuba_hip_solver* s, int32_t* per_landmark) { return guarded(s, [&] { s->landmarkActiveEdges(per_landmark); }); }
+
 int cuba_hip_get_profile(cuba_hip_solver* s, double seconds[CUBA_HIP_PROFILE_ITEMS])
 {
 	return guarded(s, [&] { for (int i = 0; i < CUBA_HIP_PROFILE_ITEMS; i++) seconds[i] = s->prof[i]; });
@@ -588,6 +597,7 @@ int cuba_hip_set_partition(cuba_hip_solver* s, int landmark_begin, int landmark_
 			return;
 		}
 		if (landmark_begin < 0 || landmark_end > s->Lt || landmark_begin > landmark_end) throw ArgError{ "bad landmark range" };
+		if (s->gateActive) throw StateError{ "a landmark partition is not available on a handle with gated edges (cuba_hip_set_edge_active(s, NULL) first)" };
 		for (const FactorSet* set : s->factorSets)
 			if (set->n() > 0) throw StateError{ std::string("a landmark partition is not available on a handle with ") + set->plural };
 		if (s->partHi >= 0 && landmark_begin == s->partLo && landmark_end == s->partHi) return;      // (cuba_hip_set_graph_partition set it already)

@@ -638,7 +638,33 @@ struct cuba_hip_solver
 		if (haveStructure && h_relPairs != structRelPairs) haveStructure = false;      // (the relative-pose pairs are part of the topology)
 		buildStructure(); finishValues(); g.rk[0] = rk[0]; g.rk[1] = rk[1]; st.mixed = mixedPrecision ? 1 : 0;
 		uploadFactors();
+		refreshGate();
 	}
+
+	// Edge gating (ba_gate.hip; g2o's setLevel / computeActiveErrors): a gated reprojection edge is an edge of zero information.  d_w stays
+	// the UPLOADED information; the first gating call allocates the live array w_live = mask ? d_w : +0 and the mask (sorted order, and the
+	// caller's order: the copy that survives a new sort) and points g.e_w at w_live -- every kernel reads g.e_w afresh, batch tables are
+	// filled from g per call, and the captured PCG chain never reads it.  Clearing the gate points g.e_w back at d_w and frees all of it.
+	// A handle that never gates allocates and launches nothing of this.
+	bool gateActive = false;
+	int64_t valuesStamp = 0, gateStamp = -1;     // bumped when the sort permutation or d_w changed / the stamp the sorted copies were made at
+	DevBuf<Scalar> d_wLive;
+	DevBuf<uint8_t> d_gateMask, d_gateMaskCaller;
+	DevBuf<long long> d_gateCounts;
+	DevBuf<uint32_t> d_gatePerm;
+	DevBuf<int> d_gateLm;
+	std::vector<uint8_t> h_gateMask;
+	Scalar* liveInformation() const { return gateActive ? d_wLive.data() : d_w.data(); }
+	void requireGateable() const;
+	const uint32_t* permDevice();
+	void allocGate();
+	void gateChanged();
+	void refreshGate();
+	void clearGate();
+	void gateEdges(const double chi2Max[2], bool positiveDepth, int mode, int64_t counts[6], double* chi2PerEdge);
+	void setEdgeActive(const uint8_t* active);
+	void getEdgeActive(uint8_t* active);
+	void landmarkActiveEdges(int32_t* perLandmark);
 
 	// The factors besides the reprojection edges (ba_factor.hip): seven kinds, each a set kept as the caller gave it, in the caller's numbering
 	// (quaternions normalised, information symmetrised), with a device copy (pf) in the internal order that need() makes -- uploadFactors():

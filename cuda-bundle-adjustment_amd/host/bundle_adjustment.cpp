@@ -30,6 +30,7 @@
 #include <tuple>
 #include <type_traits>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "cuba_hip.h"
@@ -319,6 +320,7 @@ public:
 		if (PoseVertex* p = e->poseVertex()) p->edges.erase(e);
 		if (LandmarkVertex* l = e->landmarkVertex()) l->edges.erase(e);
 		edgesDirty_ = true;
+		if (inactiveEdges_.erase(e)) maskDirty_ = true;          // (the level leaves with the edge)
 		if (e->dim() == 2) mono_.erase(static_cast<MonoEdge*>(e));
 		else if (e->dim() == 3) stereo_.erase(static_cast<StereoEdge*>(e));
 	}
@@ -531,9 +533,65 @@ public:
 			forEachKind([](auto& list) { if (!inBlockPattern(list)) list.dirty = true; });          // (an upload clears the handle's other factors too)
 			uploadedOnce_ = true; edgesChangedSinceUpload_ = valuesChangedSinceUpload_ = false;       // from here on the device holds exactly these edges and values
 			(void)cuba_hip_get_counter(solver_, "graph_uploads", &uploadGeneration_);
+			maskDirty_ = true;          // (the edge order may be another, and the handle drops its mask with other edges)
 		}
 		lap("create + set_graph");
 		forEachKind([this](auto& list) { upload(list); });
+		sendEdgeMask();
+	}
+
+	// ---- edge gating (extension: cuba::gateEdges and friends) ----------------------------------------
+	// The levels are kept per edge OBJECT (inactiveEdges_: the edges at level 1), as the factor lists are kept per factor, and go to
+	// the handle as a mask over the active edges after every upload of the graph and after every change by hand.  An object that never
+	// gates sends nothing.
+	void sendEdgeMask()
+	{
+		if (!maskDirty_) return;
+		maskDirty_ = false;
+		if (inactiveEdges_.empty() && !deviceGated_) return;
+		bool any = false;
+		edgeMask_.assign(activeEdges_.size(), 1);
+		for (size_t o = 0; o < activeEdges_.size(); o++) if (inactiveEdges_.count(activeEdges_[o])) { edgeMask_[o] = 0; any = true; }
+		check(cuba_hip_set_edge_active(solver_, any ? edgeMask_.data() : nullptr), "cuba_hip_set_edge_active");
+		deviceGated_ = any;
+	}
+	EdgeGateResult gateEdges(const EdgeGate& gate)
+	{
+		prepareOptimize();            // (the graph and the levels set by hand go up first)
+		const double thr[2] = { gate.chi2Mono, gate.chi2Stereo };
+		int64_t c[6] = { 0, 0, 0, 0, 0, 0 };
+		gateChi_.assign(activeEdges_.size(), 0.0);
+		check(cuba_hip_gate_edges(solver_, thr, gate.positiveDepth ? 1 : 0, static_cast<int>(gate.mode), c, gateChi_.data()), "cuba_hip_gate_edges");
+		gateChiEdges_ = activeEdges_; gateChiIndex_.clear();          // (the edge -> value index is built by the first edgeGateChiSquared)
+		if (gate.mode != EdgeGateMode::DRY_RUN)
+		{
+			edgeMask_.assign(activeEdges_.size(), 1);
+			check(cuba_hip_get_edge_active(solver_, edgeMask_.data()), "cuba_hip_get_edge_active");
+			for (size_t o = 0; o < activeEdges_.size(); o++)
+				if (edgeMask_[o]) inactiveEdges_.erase(activeEdges_[o]); else inactiveEdges_.insert(activeEdges_[o]);
+			deviceGated_ = true;
+		}
+		return { c[0], c[1], c[2], c[3], c[4], c[5] };
+	}
+	void setEdgeActive(const BaseEdge* e, bool active)
+	{
+		if (!e) return;
+		if (active ? inactiveEdges_.erase(e) != 0 : inactiveEdges_.insert(e).second) maskDirty_ = true;
+	}
+	bool edgeActive(const BaseEdge* e) const { return inactiveEdges_.count(e) == 0; }
+	double edgeGateChiSquared(const BaseEdge* e) const
+	{
+		if (gateChiIndex_.empty()) for (size_t o = 0; o < gateChiEdges_.size(); o++) gateChiIndex_[gateChiEdges_[o]] = gateChi_[o];
+		const auto it = gateChiIndex_.find(e);
+		return it == gateChiIndex_.end() ? 0.0 : it->second;
+	}
+	int activeObservations(const LandmarkVertex* v) const
+	{
+		int n = 0;
+		if (v && landmarks_.count(v->id) && landmarks_.at(v->id) == v)
+			for (const BaseEdge* e : v->edges)
+				n += !(e->poseVertex()->fixed && v->fixed) && inactiveEdges_.count(e) == 0;
+		return n;
 	}
 
 	// ---- factors (FactorKind, FactorLists above) -----------------------------------------------------
@@ -739,6 +797,7 @@ public:
 		covPoseIndex_.clear(); covLmIndex_.clear();
 		poses_.clear(); landmarks_.clear(); mono_.clear(); stereo_.clear(); stats_.clear();
 		forEachKind([](auto& list) { list.items.clear(); list.chi.clear(); });
+		inactiveEdges_.clear(); maskDirty_ = true; gateChi_.clear(); gateChiEdges_.clear(); gateChiIndex_.clear();
 		posesDirty_ = landmarksDirty_ = edgesDirty_ = true;
 		initialized_ = false;
 	}
@@ -892,6 +951,13 @@ private:
 	mutable std::unordered_map<const BaseEdge*, double> chiSqs_;
 	mutable bool chiIndexBuilt_ = true;
 	mutable std::vector<BaseEdge*> chiEdges_;   // edge list the pending per-edge results refer to, once initialize() replaced activeEdges_
+
+	std::unordered_set<const BaseEdge*> inactiveEdges_;      // the edges switched off (level 1)
+	bool maskDirty_ = false, deviceGated_ = false;           // the handle's mask is not inactiveEdges_ / the handle holds a mask
+	std::vector<uint8_t> edgeMask_;
+	std::vector<double> gateChi_;                            // ungated chi2 of the last gateEdges, over gateChiEdges_
+	std::vector<BaseEdge*> gateChiEdges_;
+	mutable std::unordered_map<const BaseEdge*, double> gateChiIndex_;
 };
 
 }  // namespace
@@ -983,6 +1049,35 @@ template <class F> double factorChiSquared(const CudaBundleAdjustment* object, c
 	return impl ? impl->list<F>().chiSquared(f) : 0.0;
 }
 }  // namespace
+
+// Extension (g2o's setLevel / computeActiveErrors; the reference has none): edges switched off and on without a new topology.
+EdgeGateResult gateEdges(CudaBundleAdjustment* object, const EdgeGate& gate)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (!impl) throw std::runtime_error("cuba::gateEdges: not an object of this library");
+	return impl->gateEdges(gate);
+}
+void setEdgeActive(CudaBundleAdjustment* object, const BaseEdge* edge, bool active)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (!impl) throw std::runtime_error("cuba::setEdgeActive: not an object of this library");
+	impl->setEdgeActive(edge, active);
+}
+bool edgeActive(const CudaBundleAdjustment* object, const BaseEdge* edge)
+{
+	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
+	return !impl || impl->edgeActive(edge);
+}
+double edgeGateChiSquared(const CudaBundleAdjustment* object, const BaseEdge* edge)
+{
+	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
+	return impl ? impl->edgeGateChiSquared(edge) : 0.0;
+}
+int activeObservations(const CudaBundleAdjustment* object, const LandmarkVertex* v)
+{
+	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
+	return impl ? impl->activeObservations(v) : 0;
+}
 
 void addPosePrior(CudaBundleAdjustment* object, PosePrior* prior) { addFactor(object, prior); }
 void removePosePrior(CudaBundleAdjustment* object, PosePrior* prior) { removeFactor(object, prior); }

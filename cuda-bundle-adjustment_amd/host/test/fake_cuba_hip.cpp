@@ -208,4 +208,27 @@ int cuba_hip_compute_covariance_pairs(cuba_hip_solver*, int n, const int32_t* ki
 	return done();
 }
 
+// edge gating: the stand-in classifies nothing -- every edge is active, its ungated chi2 is its index
+int cuba_hip_gate_edges(cuba_hip_solver* s, const double chi2_max[2], int require_positive_depth, int mode, int64_t counts[6], double* chi2_per_edge)
+{
+	std::printf("cuba_hip_gate_edges %a %a %d %d", chi2_max[0], chi2_max[1], require_positive_depth, mode);
+	if (counts) for (int k = 0; k < 6; k++) counts[k] = k == 1 ? s->E : 0;
+	if (chi2_per_edge) for (int k = 0; k < s->E; k++) chi2_per_edge[k] = k;
+	return done();
+}
+int cuba_hip_set_edge_active(cuba_hip_solver* s, const uint8_t* active)
+{
+	int off = 0;
+	for (int k = 0; active && k < s->E; k++) off += active[k] == 0;
+	std::printf("cuba_hip_set_edge_active %s %d", active ? "mask" : "null", off);
+	return done();
+}
+int cuba_hip_get_edge_active(cuba_hip_solver* s, uint8_t* active)
+{
+	std::printf("cuba_hip_get_edge_active");
+	for (int k = 0; k < s->E; k++) active[k] = 1;
+	return done();
+}
+int cuba_hip_landmark_active_edges(cuba_hip_solver*, int32_t*) { std::printf("cuba_hip_landmark_active_edges"); return done(); }
+
 }  // extern "C"

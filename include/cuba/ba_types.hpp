@@ -119,6 +119,25 @@ struct BatchInfo
 using BatchStatistics = std::vector<BatchInfo>;
 using TimeProfile = std::map<std::string, double>;
 
+// ---- edge gating (extension: cuba::gateEdges, bundle_adjustment.hpp; the reference has no counterpart) ----------
+// RECLASSIFY judges every edge afresh (gated edges can come back), ONLY_REMOVE never re-admits one, DRY_RUN only counts.
+enum class EdgeGateMode { RECLASSIFY = 0, ONLY_REMOVE = 1, DRY_RUN = 2 };
+
+struct EdgeGate
+{
+	double chi2Mono = 5.991, chi2Stereo = 7.815;   // an edge stays active iff its omega |r|^2 is at most this (infinity: no chi2 test)
+	bool positiveDepth = true;                     // ... and its point lies in front of the camera
+	EdgeGateMode mode = EdgeGateMode::RECLASSIFY;
+};
+
+struct EdgeGateResult
+{
+	long long activeMono = 0, activeStereo = 0;
+	long long gatedChi2Mono = 0, gatedChi2Stereo = 0;   // in front of the camera, chi2 above the threshold
+	long long gatedDepth = 0;                           // not in front of the camera, whatever the chi2
+	long long changed = 0;                              // edges whose state changed (DRY_RUN: would change)
+};
+
 // short names used inside the reference's sources (types.h:242-245)
 using VertexP = PoseVertex;
 using VertexL = LandmarkVertex;

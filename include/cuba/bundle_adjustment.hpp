@@ -9,7 +9,8 @@
 //   * poseVertex(id) / landmarkVertex(id) throw std::out_of_range for unknown ids (ref .cpp:707-715);
 //   * initialize() must be called after the graph changed and before optimize();
 //   * optimize() may be called repeatedly (warm start); results are written back into the vertices;
-//   * chiSquared(e) is 0 for edges that were inactive (both ends fixed) or unknown (ref .cpp:878-881);
+//   * chiSquared(e) is 0 for edges that were inactive (both ends fixed, or switched off: cuba::gateEdges / cuba::setEdgeActive below)
+//     or unknown (ref .cpp:878-881);
 //   * timeProfile() uses the reference's eight key strings (ref .cpp:545-562).
 // Difference: device / numerical failures are reported by exceptions (std::runtime_error) from
 // initialize()/optimize() instead of being printed and ignored (ref src/macro.h:22-27).
@@ -107,6 +108,27 @@ struct CovarianceVertex
 };
 using CovariancePair = std::pair<CovarianceVertex, CovarianceVertex>;
 bool computeCrossCovariances(CudaBundleAdjustment* object, const std::vector<CovariancePair>& pairs, std::vector<std::array<double, 36>>& out);
+
+// Extension (g2o's OptimizableGraph::Edge::setLevel / computeActiveErrors, as ORB-SLAM's local bundle adjustment and pose optimisation
+// use them; the reference has no counterpart; include/cuba_hip.h, cuba_hip_gate_edges): reprojection edges are switched off and on
+// WITHOUT removeEdge + initialize() -- no new topology, structure or symbolic analysis.  An edge that is switched off takes no part in
+// optimize(), optimizeBatch(), the objective or the covariances, and its chiSquared() is 0.
+//   gateEdges          classifies every edge of the initialize()d graph on the device at the current estimate (EdgeGate, ba_types.hpp):
+//                      active iff omega |r|^2 <= chi2Mono / chi2Stereo and (positiveDepth) its point lies in front of the camera.
+//                      Returns the counts; unless the mode is DRY_RUN the edges' levels are those of the classification afterwards.
+//   edgeGateChiSquared the UNGATED omega |r|^2 of an edge at the last gateEdges (0 before one and for an edge it did not cover)
+//   setEdgeActive      one edge's level by hand (takes effect with the next optimize / gateEdges / covariance call; no initialize() needed)
+//   edgeActive         true unless the edge is switched off
+//   activeObservations a landmark's edges that are part of the graph and switched on (ORB-SLAM culls points left with fewer than two)
+// The levels belong to the edge objects: they survive initialize() after any change of the graph that keeps the edge, removeEdge /
+// removePoseVertex / removeLandmarkVertex drop the level of the edges that leave, clear() drops all.  The ORB-SLAM flow:
+//   ba->initialize(); ba->optimize(5); cuba::gateEdges(ba.get(), {}); ba->optimize(10);
+// Known limit: a switched-off edge whose point lies at depth exactly 0 in its camera still evaluates to 0 * inf.
+EdgeGateResult gateEdges(CudaBundleAdjustment* object, const EdgeGate& gate);
+void setEdgeActive(CudaBundleAdjustment* object, const BaseEdge* edge, bool active);
+bool edgeActive(const CudaBundleAdjustment* object, const BaseEdge* edge);
+double edgeGateChiSquared(const CudaBundleAdjustment* object, const BaseEdge* edge);
+int activeObservations(const CudaBundleAdjustment* object, const LandmarkVertex* v);
 
 // Robust kernel of a pose factor (PosePrior, RelativePoseEdge; include/cuba_hip.h, cuba_hip_set_pose_factor_robust_kernels): with
 // e = r^T Omega r the objective term becomes rho(e) and the linearisation takes rho'(e) Omega for Omega.  HUBER and TUKEY are the kernels of

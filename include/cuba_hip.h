@@ -278,13 +278,50 @@ int cuba_hip_get_solution(cuba_hip_solver* s, double* q, double* t, double* Xw);
 int cuba_hip_set_solution(cuba_hip_solver* s, const double* q, const double* t, const double* Xw);
 
 /* Replaces: CudaBlockSolver::getChiSqs -> gpu::computeChiSquares x2 (:528-543).
-   Non-robust omega*|r|^2 per edge, in the caller's edge order. */
+   Non-robust omega*|r|^2 per edge, in the caller's edge order.  omega is the information in force: 0 for an edge that is gated
+   (cuba_hip_gate_edges, below; g2o's rule for an inactive edge).  The ungated value comes from cuba_hip_gate_edges. */
 int cuba_hip_chi_squares(cuba_hip_solver* s, double* chi2_per_edge);
 /* The same in two steps, for a caller that has host work of its own to do meanwhile (the C++ layer copies the estimates back into the
    caller's vertices): _begin enqueues the evaluation and the copy into chi2_per_edge (page-locked memory from cuba_hip_host_alloc, or the
    copy is not asynchronous) and returns; cuba_hip_chi_squares_end waits for it.  No other call on the handle in between. */
 int cuba_hip_chi_squares_begin(cuba_hip_solver* s, double* chi2_per_edge);
 int cuba_hip_chi_squares_end(cuba_hip_solver* s);
+
+/* ---- edge gating ---------------------------------------------------------------------------------- */
+
+/* Replaces: nothing of the reference -- g2o's setLevel(1) / computeActiveErrors flow of ORB-SLAM's local bundle adjustment (optimize(5),
+   switch off every edge with chi2 > 5.991 / 7.815 or non-positive depth, optimize(10) on the rest) and pose optimisation (four rounds,
+   edges come back when they recover), which the reference lacks: there a caller reads cuba_hip_chi_squares back, re-flattens the graph
+   without the outliers and uploads a new topology.  Here a gated reprojection edge stays in the graph as an edge of zero information:
+   no new sort, structure, symbolic analysis or exact-solver plan.  cuba_hip_compute_errors, cuba_hip_optimize[_batch], the stage calls
+   and both covariance calls see the active edges only (g2o's activeChi2); cuba_hip_chi_squares reports 0 for a gated edge.
+
+   cuba_hip_gate_edges classifies every edge on the device at the current estimate with its UPLOADED information omega: it stays active
+   iff omega*|r|^2 <= chi2_max[stereo] and (require_positive_depth == 0 or its point's depth in the camera is > 0); a NaN fails both.
+   chi2_max[2] = {monocular, stereo}, +inf = no chi2 test, NaN = CUBA_HIP_ERR_INVALID_ARGUMENT (as is an unknown mode).
+   mode: CUBA_HIP_GATE_RECLASSIFY judges every edge afresh (gated edges can come back), CUBA_HIP_GATE_ONLY_REMOVE never re-admits a gated
+   edge, CUBA_HIP_GATE_DRY_RUN changes nothing and only reports.
+   counts[6] (optional): active monocular, active stereo, gated by chi2 monocular, gated by chi2 stereo, gated by depth (whatever its
+   chi2), edges whose state changed (would change: dry run).  With ONLY_REMOVE an edge that stays gated although it passes both tests is
+   in none of the first five.
+   chi2_per_edge (optional): the UNGATED omega*|r|^2, caller's edge order.
+
+   The mask outlives a cuba_hip_set_graph whose edge arrays (pose, landmark, dimension, count) are those of the previous call --
+   promised by cuba_hip_hint_unchanged or found by the library's own comparison --: the live information is rebuilt from the newly uploaded
+   one, and a same_values promise still means the uploaded information, never a gated zero.  Any other cuba_hip_set_graph drops the mask
+   (all edges active, storage freed).  None of these calls touches the estimates, the snapshot slots or the counters structure_builds,
+   graph_uploads, value_bytes_uploaded.  A handle that never calls them allocates and launches nothing for them.
+   CUBA_HIP_ERR_STATE before cuba_hip_set_graph and on a landmark-partitioned handle (cuba_hip_set_partition, cuba_hip_set_graph_partition;
+   a gated handle in turn refuses cuba_hip_set_partition).
+   Known limit: a GATED edge whose point lies at depth exactly 0.0 in its camera still yields 0 * inf = NaN in the evaluation kernels. */
+enum { CUBA_HIP_GATE_RECLASSIFY = 0, CUBA_HIP_GATE_ONLY_REMOVE = 1, CUBA_HIP_GATE_DRY_RUN = 2 };
+int cuba_hip_gate_edges(cuba_hip_solver* s, const double chi2_max[2], int require_positive_depth, int mode, int64_t counts[6], double* chi2_per_edge);
+/* g2o's setLevel per edge: active[E] in the caller's edge order, non-zero = active.  NULL: all active, the gate's storage is freed. */
+int cuba_hip_set_edge_active(cuba_hip_solver* s, const uint8_t* active);
+/* active[E] in the caller's edge order, 0 / 1; all 1 on a handle without a gate */
+int cuba_hip_get_edge_active(cuba_hip_solver* s, uint8_t* active);
+/* per_landmark[Lt] in the caller's landmark order: active edges of every landmark (ORB-SLAM culls map points left with fewer than two) */
+int cuba_hip_landmark_active_edges(cuba_hip_solver* s, int32_t* per_landmark);
 
 /* Replaces: CudaBlockSolver::getTimeProfile (:545-562). Seconds per bucket. */
 int cuba_hip_get_profile(cuba_hip_solver* s, double seconds[CUBA_HIP_PROFILE_ITEMS]);
