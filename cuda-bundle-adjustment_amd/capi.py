@@ -482,8 +482,6 @@ class HipSolver:
         measurements cross PCIe on a second stream while the structure analysis runs).
         landmark_range = (begin, end): cuba_hip_set_graph_partition -- the upload of one rank of a landmark partition, which sends the
         measurements and information of its own landmarks' edges only."""
-        self.fp = fp
-        self._n_factors = {}            # (every upload clears the pose priors, the relative-pose edges, the landmark priors, the position, the direction and both kinds of range factors)
         q, t, cam, Xw = (np.ascontiguousarray(a, dtype=np.float64) for a in (fp.q, fp.t, fp.cam, fp.Xw))
         eP = np.ascontiguousarray(fp.eP, dtype=np.int32)
         eL = np.ascontiguousarray(fp.eL, dtype=np.int32)
@@ -494,15 +492,22 @@ class HipSolver:
             self._ck(self.lib.cuba_hip_set_graph_partition(self.h, fp.Pt, fp.Pf, fp.Lt, fp.Lf, _d(q), _d(t), _d(cam), _d(Xw), len(eP),
                      eP.ctypes.data_as(_ip), eL.ctypes.data_as(_ip), eD.ctypes.data_as(_u8p), _d(meas), _d(om),
                      int(landmark_range[0]), int(landmark_range[1])))
+            self._uploaded(fp)
             return
         fn = self.lib.cuba_hip_set_graph_begin if two_step else self.lib.cuba_hip_set_graph
         self._ck(fn(self.h, fp.Pt, fp.Pf, fp.Lt, fp.Lf, _d(q), _d(t), _d(cam), _d(Xw), len(eP),
                     eP.ctypes.data_as(_ip), eL.ctypes.data_as(_ip), eD.ctypes.data_as(_u8p), _d(meas), _d(om)))
+        self._uploaded(fp)
         if two_step == "begin_only":                                 # (test hook: the arrays are kept alive by the caller of this method)
             self._pending_upload = (meas, om)
         elif two_step:
             self.build_structure()
             self._ck(self.lib.cuba_hip_set_graph_end(self.h))        # (meas / om stay referenced until here)
+
+    def _uploaded(self, fp):
+        """after a SUCCESSFUL upload (a refused one leaves the handle, and so the sizes of this object's output buffers, as they were)"""
+        self.fp = fp
+        self._n_factors = {}            # (every upload clears the pose priors, the relative-pose edges, the landmark priors, the position, the direction and both kinds of range factors)
 
     # ---- stages --------------------------------------------------------------------------------
     def build_structure(self): self._ck(self.lib.cuba_hip_build_structure(self.h))

@@ -20,6 +20,9 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 	int E_, const int32_t* ep, const int32_t* el, const uint8_t* edim, const double* meas, const double* omega, bool deferValues, int ownLo, int ownHi)
 {
 	const bool ranged = ownHi >= 0;
+	// (a promise covers one call, successful or not: it is gone before the first check that can refuse this one)
+	const bool hintEdges = hintSameEdges, hintValues = hintSameValues;
+	hintSameEdges = hintSameValues = false;
 	if (ranged && (ownLo < 0 || ownHi > Lt_ || ownLo > ownHi)) throw ArgError{ "bad landmark range" };
 	if (ranged) deferValues = false;
 	// (a begin without its end: the old upload must not outlive its arrays' replacement, and the sorted measurement / information arrays
@@ -32,7 +35,6 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 	if (sizeof(Scalar) == 4 && Lt_ >= (1 << 23)) throw ArgError{ "fp32 build: at most 2^23 - 1 landmarks" };
 	if ((Pt_ && (!q || !t || !cam)) || (Lt_ && !Xw) || (E_ && (!ep || !el || !edim || !meas || !omega))) throw ArgError{ "null array" };
 	const auto t0 = Clock::now();
-	clearFactors();           // (they name poses of the previous graph; need() rebuilds a kept structure unless the same pairs come back)
 	static const bool noCache = std::getenv("CUBA_HIP_NO_STRUCTURE_CACHE") != nullptr;   // A/B knob for set-up timings
 	const bool sameCounts = !noCache && !ranged && haveStructure && partHi < 0 && Pt == Pt_ && Pf == Pf_ && Lt == Lt_ && Lf == Lf_ && E == E_;
 	// the very same index arrays as in the previous call (re-initialisation of an unchanged graph): the sort, the
@@ -40,8 +42,7 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 	bool sameInput = !noCache && haveGraph && Pt == Pt_ && Pf == Pf_ && Lt == Lt_ && Lf == Lf_ && E == E_ && (int)h_inEp.size() == E_;
 	// (a ranged upload changes what the handle evaluates: nothing of the previous call is reused, and the sort runs in the caller's landmark order)
 	if (ranged) sameInput = false;
-	const bool promisedEdges = sameInput && hintSameEdges, promisedValues = promisedEdges && hintSameValues;
-	hintSameEdges = hintSameValues = false;          // (a promise covers one call)
+	const bool promisedEdges = sameInput && hintEdges, promisedValues = promisedEdges && hintValues;
 	if (sameInput && !promisedEdges)
 	{
 		std::atomic<int> diff{ 0 };
@@ -64,12 +65,14 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 	// an edge gate (ba_gate.hip) outlives a call whose edge arrays are the previous call's -- promised or found so above --: its mask is kept
 	// in the caller's edge order, and need() derives the live information from the newly uploaded one.  Other edges: all active again.
 	if (!sameInput) clearGate();
+	clearFactors();           // (they name poses of the previous graph; need() rebuilds a kept structure unless the same pairs come back)
 	// from here on the old graph is being replaced: a failure below (allocation, upload) leaves NO graph
 	haveGraph = false;
 	haveStructure = false;
 	covBlocksValid = false;
 	Pt = Pt_; Pf = Pf_; Lt = Lt_; Lf = Lf_; E = E_;
-	if (ranged) { partLo = ownLo; partHi = ownHi; }          // (before the sort: the internal landmark order is for whole-range handles)
+	// (before the sort: the internal landmark order is for whole-range handles -- and a whole upload is one, whatever range was in force)
+	partLo = ranged ? ownLo : 0; partHi = ranged ? ownHi : -1;
 	lap(nullptr);
 	// the estimates and cameras go up straight from the caller's arrays when they need neither a conversion (fp64 build) nor a
 	// row permutation (internal pose order): no staging copy, and page-locked caller memory (cuba_hip_host_alloc) moves by DMA
@@ -84,13 +87,18 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 	const DeviceGraph gOld = g;
 	bool sameTopology = false;
 	const bool useDev = deviceSetup && E > 0;
-	if (!useDev && (!hostTopoValid || reorderActive)) sameInput = false;      // the host-side sort of the previous call does not exist (device path)
+	// the host-side sort of the previous call does not exist (device path), or it was read back from a device sort in the internal landmark
+	// order, which the host pipeline leaves (below): its landmark indices do not name the rows this call uploads
+	if (!useDev && (!hostTopoValid || reorderActive || lmOrderActive)) sameInput = false;
 	if (useDev)
 	{
 		// ---- device path: raw arrays go up as they are; sort, gather and the landmark pointers are kernels -------------
-		// (an internal pose order found for this very topology is kept; otherwise it starts over as the identity)
-		const bool keepOrder = reorderActive && sameInput && devTopology && sameCounts;
-		const bool reuseSort = sameInput && devTopology && (keepOrder || !reorderActive);
+		// (an internal pose order found for this very topology is kept -- while "pose_reorder" is on --; otherwise it starts over as the identity)
+		// (the kept sort carries the landmark order it was made under: a changed "landmark_reorder", or a landmark partition in force until
+		// this call, takes effect here)
+		const bool lmOrderFits = lmOrderActive == landmarkOrderAllowed();
+		const bool keepOrder = reorderActive && poseReorder && sameInput && devTopology && sameCounts && lmOrderFits;
+		const bool reuseSort = sameInput && devTopology && (keepOrder || !reorderActive) && lmOrderFits;
 		if (!keepOrder) resetPoseOrder();
 		if (!reuseSort)
 		{

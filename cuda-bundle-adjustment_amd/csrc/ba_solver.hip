@@ -146,7 +146,7 @@ int cuba_hip_set_option(cuba_hip_solver* s, const char* key, double value)
 			if (value < 0 || value > (double)(1 << 30)) throw ArgError{ "covariance_workspace_mb must lie in 0 .. 2^30 (0 = automatic)" };
 			s->covWorkspaceMb = value;
 		}
-		else if (k == "landmark_reorder") s->lmReorder = value != 0;         // (takes effect with the next cuba_hip_set_graph)
+		else if (k == "landmark_reorder") s->lmReorder = value != 0;         // (takes effect with the next cuba_hip_set_graph: setGraph's lmOrderFits)
 		else if (k == "reduction_chunks")
 		{
 			if (value < 0 || value > 64) throw ArgError{ "reduction_chunks must lie in 0 .. 64" };

@@ -128,7 +128,8 @@ int cuba_hip_set_stream(cuba_hip_solver* s, void* hip_stream);
    block, row updates + P^T r per aggregate, preconditioner -- instead of two launches on a row-ordered copy of both triangles).
    "reduction_chunks" (default 0 = automatic; landmark partitions only: number of block-row ranges the reduced matrix is produced -- and,
    by the multi-GPU driver, summed -- in, see cuba_hip_schur_part),
-   "landmark_reorder" (default 1, takes effect with the next cuba_hip_set_graph: the free landmarks are renumbered internally by (first, last)
+   "landmark_reorder" (default 1, takes effect with the next cuba_hip_set_graph -- also one that uploads the previous call's index arrays
+   again, promised or not --: the free landmarks are renumbered internally by (first, last)
    observing pose of the internal pose order, so that landmark-major data inherit the trajectory's locality whatever the caller's ids are;
    every host-pointer entry point keeps the caller's landmark numbering; a landmark partition other than the whole range, and the host
    pipeline, use the caller's order),
@@ -141,10 +142,12 @@ int cuba_hip_set_stream(cuba_hip_solver* s, void* hip_stream);
    that has instantiated a hipGraph no longer overlaps the kernel chains of several handles; see cuba_hip_create),
    "device_setup" (default 1: the edge sort of
    cuba_hip_set_graph and the whole symbolic analysis of cuba_hip_build_structure run on the GPU; 0 = the host pipeline, the
-   independent cross-check of the tests), "pose_reorder" (default 1: when most blocks of the reduced matrix lie far off its diagonal
+   independent cross-check of the tests; on a handle that holds a graph the analysis follows the option at once, the edge sort and
+   with it the internal landmark order with the next cuba_hip_set_graph -- until then sums may differ from a fresh handle's in rounding), "pose_reorder" (default 1: when most blocks of the reduced matrix lie far off its diagonal
    in the caller's pose numbering -- arbitrary vertex ids --, the free poses are renumbered internally along the trajectory found by
    a strongest-neighbour walk over the co-visibility counts, which the aggregates of the preconditioner need; every host-pointer
-   entry point keeps the caller's numbering, only cuba_hip_device_pointer / cuba_hip_reduction_buffer expose the internal one),
+   entry point keeps the caller's numbering, only cuba_hip_device_pointer / cuba_hip_reduction_buffer expose the internal one; 0 takes
+   effect with the next cuba_hip_set_graph, which then starts from the caller's numbering also when it uploads the same index arrays),
    "profile" (0/1: per-stage synchronising wall-clock like the reference's get_time_point(), src/cuda_bundle_adjustment.cpp:43-47).
    Variants that were built, measured slower and removed again (first-generation Schur kernel with fp64 atomics, single-launch
    PCG iteration, speculative trial tail, in-line coarse refresh policy, CU-masked side stream, forcing term on the PCG tolerance)
@@ -158,7 +161,10 @@ int cuba_hip_set_option(cuba_hip_solver* s, const char* key, double value);
    q[4*Pt], t[3*Pt], cam[5*Pt] = (fx,fy,cx,cy,bf) per pose, Xw[3*Lt];
    edge_pose[E], edge_landmark[E] solver indices; edge_dim[E] in {2,3};
    meas[3*E] (third component ignored for monocular edges); omega[E] scalar information.
-   Edges whose two ends are both fixed must already be removed (as the reference does, :204-243). */
+   Edges whose two ends are both fixed must already be removed (as the reference does, :204-243).
+   A cuba_hip_set_graph[_begin / _partition] that is refused with CUBA_HIP_ERR_INVALID_ARGUMENT (bad counts, a null array, a bad landmark
+   range, an edge index or dimension out of range, an edge between two fixed vertices) leaves the handle as it was: the previous graph, its
+   factor sets, its mask and its snapshot slots stay in force; only a pending cuba_hip_hint_unchanged promise is consumed. */
 int cuba_hip_set_graph(cuba_hip_solver* s, int Pt, int Pf, int Lt, int Lf,
 	const double* q, const double* t, const double* cam, const double* Xw,
 	int E, const int32_t* edge_pose, const int32_t* edge_landmark, const uint8_t* edge_dim,
