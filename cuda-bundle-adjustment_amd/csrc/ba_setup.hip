@@ -10,61 +10,82 @@ void cuba_hip_solver::finishValues()
 	if (!valuesPending) return;
 	valuesPending = false;
 	HIP_TRY(hipStreamWaitEvent(stream, evValues, 0));
+	gatherSortedValues();
+	valuesStamp++;          // (the permutation or the sorted values are new: an edge gate derives its copies again, refreshGate)
+}
+
+void cuba_hip_solver::gatherSortedValues()
+{
+	sizeSortedValues();
 	topo::launch_gather_edges(d_perm.data(), d_rawEp.data(), d_rawEl.data(), d_rawDim.data(), d_rawMeas.data(), d_rawOmega.data(), E,
 		nullptr, nullptr, d_mu.data(), d_mv.data(), d_mr.data(), d_w.data(), stream);
 	sortedValuesValid = true;
-	valuesStamp++;          // (the permutation or the sorted values are new: an edge gate derives its copies again, refreshGate)
+}
+
+UploadFacts cuba_hip_solver::uploadFacts() const
+{
+	static const bool noCache = std::getenv("CUBA_HIP_NO_STRUCTURE_CACHE") != nullptr;   // A/B knob for set-up timings
+	UploadFacts f{};
+	f.haveGraph = haveGraph; f.haveStructure = haveStructure;
+	f.Pt = Pt; f.Pf = Pf; f.Lt = Lt; f.Lf = Lf; f.E = E;
+	f.partitioned = partHi >= 0;
+	f.devTopology = devTopology; f.hostTopoValid = hostTopoValid; f.reorderActive = reorderActive; f.lmOrderActive = lmOrderActive;
+	// (a begin without its end: the sorted measurement / information arrays it was going to fill were never gathered -- a "same values"
+	// promise for THIS call must not keep them: round-4 advisor)
+	f.sortedValuesValid = sortedValuesValid && !valuesPending;
+	f.valuesPartial = valuesPartial;
+	f.sortedValuesFit = d_mu.size() == (size_t)E && d_w.size() == (size_t)E;
+	f.edgesHeld = h_inEp.size() == (size_t)E;
+	f.deviceSetup = deviceSetup; f.poseReorder = poseReorder; f.lmReorder = lmReorder;
+	f.noCache = noCache;
+	return f;
+}
+
+// the caller's index arrays are the previous call's, entry by entry (read where needsEdgeCompare says so: the counts are equal then)
+bool cuba_hip_solver::sameEdgeArrays(const UploadArrays& in) const
+{
+	const int32_t* ep = in.ep; const int32_t* el = in.el; const uint8_t* edim = in.edim;
+	std::atomic<int> diff{ 0 };
+	parallelFor(E, [&](int e) { if (h_inEp[e] != ep[e] || h_inEl[e] != el[e] || h_inDim[e] != edim[e]) diff.store(1, std::memory_order_relaxed); });
+	return diff == 0;
+}
+
+static void validateEdges(const UploadCall& c, const cuba_hip_solver::UploadArrays& in)
+{
+	const int32_t* ep = in.ep; const int32_t* el = in.el; const uint8_t* edim = in.edim;
+	const int Pt = c.Pt, Pf = c.Pf, Lt = c.Lt, Lf = c.Lf;
+	std::atomic<int> bad{ 0 };
+	cuba_hip_solver::parallelFor(c.E, [&](int e) {
+		if (ep[e] < 0 || ep[e] >= Pt || el[e] < 0 || el[e] >= Lt) bad.store(1, std::memory_order_relaxed);
+		else if (edim[e] != 2 && edim[e] != 3) bad.store(2, std::memory_order_relaxed);
+		else if (ep[e] >= Pf && el[e] >= Lf) bad.store(3, std::memory_order_relaxed);
+	});
+	if (bad == 1) throw ArgError{ "edge index out of range" };
+	if (bad == 2) throw ArgError{ "edge_dim must be 2 or 3" };
+	if (bad == 3) throw ArgError{ "edge with both ends fixed (must be dropped by the caller)" };
 }
 
 void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double* q, const double* t, const double* cam, const double* Xw,
 	int E_, const int32_t* ep, const int32_t* el, const uint8_t* edim, const double* meas, const double* omega, bool deferValues, int ownLo, int ownHi)
 {
-	const bool ranged = ownHi >= 0;
 	// (a promise covers one call, successful or not: it is gone before the first check that can refuse this one)
-	const bool hintEdges = hintSameEdges, hintValues = hintSameValues;
+	const UploadCall call{ Pt_, Pf_, Lt_, Lf_, E_, ownLo, ownHi, deferValues, hintSameEdges, hintSameValues,
+		!q || !t || !cam, !Xw, !ep || !el || !edim || !meas || !omega, sizeof(Scalar) };
 	hintSameEdges = hintSameValues = false;
-	if (ranged && (ownLo < 0 || ownHi > Lt_ || ownLo > ownHi)) throw ArgError{ "bad landmark range" };
-	if (ranged) deferValues = false;
-	// (a begin without its end: the old upload must not outlive its arrays' replacement, and the sorted measurement / information arrays
-	// it was going to fill were never gathered -- a "same values" promise for THIS call must not keep them: round-4 advisor)
-	if (valuesPending) { HIP_TRY(hipStreamSynchronize(upStream)); valuesPending = false; sortedValuesValid = false; }
-	deferredUpload = false;
-	if (Pt_ < 0 || Lt_ < 0 || E_ < 0 || Pf_ < 0 || Pf_ > Pt_ || Lf_ < 0 || Lf_ > Lt_) throw ArgError{ "bad vertex counts" };
-	if (Pt_ >= STEREO_BIT) throw ArgError{ "too many poses" };
-	// the per-edge linearisation record carries 2*landmark+stereo in a Scalar slot: exact in fp32 only below 2^24
-	if (sizeof(Scalar) == 4 && Lt_ >= (1 << 23)) throw ArgError{ "fp32 build: at most 2^23 - 1 landmarks" };
-	if ((Pt_ && (!q || !t || !cam)) || (Lt_ && !Xw) || (E_ && (!ep || !el || !edim || !meas || !omega))) throw ArgError{ "null array" };
+	const UploadArrays in{ q, t, cam, Xw, ep, el, edim, meas, omega };
+	// ---- plan and refuse: nothing is touched yet, a rejected call must leave the previous graph fully usable ----
 	const auto t0 = Clock::now();
-	static const bool noCache = std::getenv("CUBA_HIP_NO_STRUCTURE_CACHE") != nullptr;   // A/B knob for set-up timings
-	const bool sameCounts = !noCache && !ranged && haveStructure && partHi < 0 && Pt == Pt_ && Pf == Pf_ && Lt == Lt_ && Lf == Lf_ && E == E_;
-	// the very same index arrays as in the previous call (re-initialisation of an unchanged graph): the sort, the
-	// permutation and the sorted index arrays on the host and on the device are all still valid
-	bool sameInput = !noCache && haveGraph && Pt == Pt_ && Pf == Pf_ && Lt == Lt_ && Lf == Lf_ && E == E_ && (int)h_inEp.size() == E_;
-	// (a ranged upload changes what the handle evaluates: nothing of the previous call is reused, and the sort runs in the caller's landmark order)
-	if (ranged) sameInput = false;
-	const bool promisedEdges = sameInput && hintEdges, promisedValues = promisedEdges && hintValues;
-	if (sameInput && !promisedEdges)
-	{
-		std::atomic<int> diff{ 0 };
-		parallelFor(E_, [&](int e) { if (h_inEp[e] != ep[e] || h_inEl[e] != el[e] || h_inDim[e] != edim[e]) diff.store(1, std::memory_order_relaxed); });
-		sameInput = diff == 0;
-	}
-	// validate BEFORE any member changes: a rejected call must leave the previous graph fully usable
-	if (!sameInput)
-	{
-		std::atomic<int> bad{ 0 };
-		parallelFor(E_, [&](int e) {
-			if (ep[e] < 0 || ep[e] >= Pt_ || el[e] < 0 || el[e] >= Lt_) bad.store(1, std::memory_order_relaxed);
-			else if (edim[e] != 2 && edim[e] != 3) bad.store(2, std::memory_order_relaxed);
-			else if (ep[e] >= Pf_ && el[e] >= Lf_) bad.store(3, std::memory_order_relaxed);
-		});
-		if (bad == 1) throw ArgError{ "edge index out of range" };
-		if (bad == 2) throw ArgError{ "edge_dim must be 2 or 3" };
-		if (bad == 3) throw ArgError{ "edge with both ends fixed (must be dropped by the caller)" };
-	}
+	const UploadFacts facts = uploadFacts();
+	const UploadPlan plan = planUpload(facts, call, needsEdgeCompare(facts, call) && sameEdgeArrays(in));
+	if (plan.refusal) throw ArgError{ plan.refusal };
+	if (!plan.sameEdges) validateEdges(call, in);
+	// ---- replace ----
+	// (a begin without its end: the old upload must not outlive its arrays' replacement.  Below every refusal: a refused call leaves the
+	// begun graph in force, and its values still arrive with the next need())
+	if (valuesPending) { HIP_TRY(hipStreamSynchronize(upStream)); valuesPending = false; sortedValuesValid = false; }
 	// an edge gate (ba_gate.hip) outlives a call whose edge arrays are the previous call's -- promised or found so above --: its mask is kept
 	// in the caller's edge order, and need() derives the live information from the newly uploaded one.  Other edges: all active again.
-	if (!sameInput) clearGate();
+	if (!plan.sameEdges) clearGate();
 	clearFactors();           // (they name poses of the previous graph; need() rebuilds a kept structure unless the same pairs come back)
 	// from here on the old graph is being replaced: a failure below (allocation, upload) leaves NO graph
 	haveGraph = false;
@@ -72,95 +93,85 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 	covBlocksValid = false;
 	Pt = Pt_; Pf = Pf_; Lt = Lt_; Lf = Lf_; E = E_;
 	// (before the sort: the internal landmark order is for whole-range handles -- and a whole upload is one, whatever range was in force)
-	partLo = ranged ? ownLo : 0; partHi = ranged ? ownHi : -1;
+	partLo = call.ranged() ? ownLo : 0; partHi = call.ranged() ? ownHi : -1;
 	lap(nullptr);
-	// the estimates and cameras go up straight from the caller's arrays when they need neither a conversion (fp64 build) nor a
-	// row permutation (internal pose order): no staging copy, and page-locked caller memory (cuba_hip_host_alloc) moves by DMA
-	std::vector<Scalar>&state = h_stage[4], &camv = h_stage[5];
-	auto stageState = [&] {
-		state.resize((size_t)7 * Pt + (size_t)3 * Lt);
-		for (size_t i = 0; i < (size_t)4 * Pt; i++) state[i] = (Scalar)q[i];
-		for (size_t i = 0; i < (size_t)3 * Pt; i++) state[4 * (size_t)Pt + i] = (Scalar)t[i];
-		for (size_t i = 0; i < (size_t)3 * Lt; i++) state[7 * (size_t)Pt + i] = (Scalar)Xw[i];
-		camv.assign(cam, cam + 5 * (size_t)Pt);
-	};
 	const DeviceGraph gOld = g;
-	bool sameTopology = false;
-	const bool useDev = deviceSetup && E > 0;
-	// the host-side sort of the previous call does not exist (device path), or it was read back from a device sort in the internal landmark
-	// order, which the host pipeline leaves (below): its landmark indices do not name the rows this call uploads
-	if (!useDev && (!hostTopoValid || reorderActive || lmOrderActive)) sameInput = false;
-	if (useDev)
+	const bool sameTopology = plan.useDev ? sortEdgesDevice(plan, in) : sortEdgesHost(plan, in);
+	uploadState(in);
+	allocRunBuffers();
+	// (enqueued LAST: the copy engine serves its queue in order, and the small uploads of this call must not wait behind 18 MB)
+	if (plan.deferValues) enqueueDeferredValues(in);
+	sync(); expectedTicket = 0; ((volatile int*)((char*)h_pinned + 1024))[3] = 0;
+	sync();   // host staging vectors go out of scope
+	lap("set_graph: alloc + upload + sync");
+	publishGraph(plan, gOld, sameTopology);
+	prof[0] += std::chrono::duration<double>(Clock::now() - t0).count();
+}
+
+// ---- device path: raw arrays go up as they are; sort, gather and the landmark pointers are kernels.  Returns: the structure stays. ----
+bool cuba_hip_solver::sortEdgesDevice(const UploadPlan& plan, const UploadArrays& in)
+{
+	const bool ranged = partHi >= 0;
+	if (!plan.keepPoseOrder) resetPoseOrder();
+	if (!plan.reuseSort)
 	{
-		// ---- device path: raw arrays go up as they are; sort, gather and the landmark pointers are kernels -------------
-		// (an internal pose order found for this very topology is kept -- while "pose_reorder" is on --; otherwise it starts over as the identity)
-		// (the kept sort carries the landmark order it was made under: a changed "landmark_reorder", or a landmark partition in force until
-		// this call, takes effect here)
-		const bool lmOrderFits = lmOrderActive == landmarkOrderAllowed();
-		const bool keepOrder = reorderActive && poseReorder && sameInput && devTopology && sameCounts && lmOrderFits;
-		const bool reuseSort = sameInput && devTopology && (keepOrder || !reorderActive) && lmOrderFits;
-		if (!keepOrder) resetPoseOrder();
-		if (!reuseSort)
-		{
-			if (!sameInput) { h_inEp.assign(ep, ep + E); h_inEl.assign(el, el + E); h_inDim.assign(edim, edim + E); }
-			d_rawEpCaller.uploadRaw(ep, E, stream); d_rawElCaller.uploadRaw(el, E, stream); d_rawDim.uploadRaw(edim, E, stream);
-			d_rawEp.resize(E);
-			HIP_TRY(hipMemcpyAsync(d_rawEp.data(), d_rawEpCaller.data(), sizeof(int) * (size_t)E, hipMemcpyDeviceToDevice, stream));
-			// internal landmark order from the pose numbering in force (the caller's here; applyPoseOrder renews it under a new one)
-			if (landmarkOrderAllowed()) computeLandmarkOrder(); else resetLandmarkOrder();
-		}
-		const bool keepValues = promisedValues && reuseSort && sortedValuesValid && !valuesPartial && d_mu.size() == (size_t)E && d_w.size() == (size_t)E;   // (sorted measurement / information arrays of the previous call)
-		const bool defer = deferValues && !keepValues && E > 0;
-		deferredUpload = defer;          // (enqueued LAST, below: the copy engine serves its queue in order, and the small uploads of this call must not wait behind 18 MB)
-		if (defer) { d_rawMeas.resize((size_t)3 * E); d_rawOmega.resize(E); }
-		else if (ranged)
-		{
-			// the values of the rank's own edges only: ids + {u, v, r, omega} packed by the host, spread into the caller-order arrays by a kernel
-			// (the other edges' slots read as zeros; no kernel of a partitioned handle looks at them)
-			h_ownIds.clear();
-			for (int e = 0; e < E; e++) if (el[e] >= ownLo && el[e] < ownHi) h_ownIds.push_back(e);
-			const int n = (int)h_ownIds.size();
-			h_ownVals.resize((size_t)4 * n);
-			parallelFor(n, [&](int i) {
-				const size_t e = (size_t)h_ownIds[i];
-				h_ownVals[4 * (size_t)i] = meas[3 * e]; h_ownVals[4 * (size_t)i + 1] = meas[3 * e + 1]; h_ownVals[4 * (size_t)i + 2] = meas[3 * e + 2];
-				h_ownVals[4 * (size_t)i + 3] = omega[e];
-			});
-			d_ownIds.upload(h_ownIds, stream); d_ownVals.upload(h_ownVals, stream);
-			d_rawMeas.resize((size_t)3 * E); d_rawOmega.resize(E);
-			d_rawMeas.zero(stream); d_rawOmega.zero(stream);
-			topo::launch_scatter_values(d_ownIds.data(), d_ownVals.data(), n, d_rawMeas.data(), d_rawOmega.data(), stream);
-			cntValueBytes += (int64_t)n * 36;
-		}
-		else if (!keepValues) { d_rawMeas.uploadRaw(meas, (size_t)3 * E, stream); d_rawOmega.uploadRaw(omega, E, stream); cntValueBytes += (int64_t)E * 32; }
-		lap("set_graph: raw uploads enqueued");
-		if (!keepValues) sortedValuesValid = false;
-		if (!reuseSort) runDeviceEdgeSort(!defer);
-		else if (!keepValues && !defer)
-		{
-			d_mu.resize(E); d_mv.resize(E); d_mr.resize(E); d_w.resize(E);
-			topo::launch_gather_edges(d_perm.data(), d_rawEp.data(), d_rawEl.data(), d_rawDim.data(), d_rawMeas.data(), d_rawOmega.data(), E,
-				nullptr, nullptr, d_mu.data(), d_mv.data(), d_mr.data(), d_w.data(), stream);
-			sortedValuesValid = true;
-		}
-		if (defer) { d_mu.resize(E); d_mv.resize(E); d_mr.resize(E); d_w.resize(E); valuesPending = true; }      // (finishValues gathers them and marks them valid)
-		sameTopology = sameCounts && reuseSort;
-		devTopology = true; hostTopoValid = false;
-		if (reorderActive) { stageState(); permuteStateRows(state, camv); }          // the caller's rows -> the internal pose order kept from the last call
-		lap("set_graph: device sort + gather enqueued");
+		if (!plan.sameEdges) { h_inEp.assign(in.ep, in.ep + E); h_inEl.assign(in.el, in.el + E); h_inDim.assign(in.edim, in.edim + E); }
+		d_rawEpCaller.uploadRaw(in.ep, E, stream); d_rawElCaller.uploadRaw(in.el, E, stream); d_rawDim.uploadRaw(in.edim, E, stream);
+		d_rawEp.resize(E);
+		HIP_TRY(hipMemcpyAsync(d_rawEp.data(), d_rawEpCaller.data(), sizeof(int) * (size_t)E, hipMemcpyDeviceToDevice, stream));
+		// internal landmark order from the pose numbering in force (the caller's here; applyPoseOrder renews it under a new one)
+		if (plan.lmOrderWanted) computeLandmarkOrder(); else resetLandmarkOrder();
 	}
-	else
+	if (plan.deferValues) { d_rawMeas.resize((size_t)3 * E); d_rawOmega.resize(E); }
+	else if (ranged)
 	{
+		// the values of the rank's own edges only: ids + {u, v, r, omega} packed by the host, spread into the caller-order arrays by a kernel
+		// (the other edges' slots read as zeros; no kernel of a partitioned handle looks at them)
+		const int32_t* el = in.el; const double* meas = in.meas; const double* omega = in.omega;
+		const int ownLo = partLo, ownHi = partHi;
+		h_ownIds.clear();
+		for (int e = 0; e < E; e++) if (el[e] >= ownLo && el[e] < ownHi) h_ownIds.push_back(e);
+		const int n = (int)h_ownIds.size();
+		h_ownVals.resize((size_t)4 * n);
+		parallelFor(n, [&](int i) {
+			const size_t e = (size_t)h_ownIds[i];
+			h_ownVals[4 * (size_t)i] = meas[3 * e]; h_ownVals[4 * (size_t)i + 1] = meas[3 * e + 1]; h_ownVals[4 * (size_t)i + 2] = meas[3 * e + 2];
+			h_ownVals[4 * (size_t)i + 3] = omega[e];
+		});
+		d_ownIds.upload(h_ownIds, stream); d_ownVals.upload(h_ownVals, stream);
+		d_rawMeas.resize((size_t)3 * E); d_rawOmega.resize(E);
+		d_rawMeas.zero(stream); d_rawOmega.zero(stream);
+		topo::launch_scatter_values(d_ownIds.data(), d_ownVals.data(), n, d_rawMeas.data(), d_rawOmega.data(), stream);
+		cntValueBytes += (int64_t)n * 36;
+	}
+	else if (!plan.keepValues) { d_rawMeas.uploadRaw(in.meas, (size_t)3 * E, stream); d_rawOmega.uploadRaw(in.omega, E, stream); cntValueBytes += (int64_t)E * 32; }
+	lap("set_graph: raw uploads enqueued");
+	if (!plan.keepValues) sortedValuesValid = false;
+	if (!plan.reuseSort) runDeviceEdgeSort(!plan.deferValues);
+	else if (!plan.keepValues && !plan.deferValues) gatherSortedValues();
+	if (plan.deferValues) { sizeSortedValues(); valuesPending = true; }      // (finishValues gathers them and marks them valid)
+	devTopology = true; hostTopoValid = false;
+	lap("set_graph: device sort + gather enqueued");
+	return plan.mayKeepStructure && plan.reuseSort;
+}
+
+// ---- host path (the independent cross-check pipeline, and graphs without edges): sort and gather here, upload the sorted arrays.  Runs
+// in the caller's pose and landmark order.  Returns: the structure stays. ----
+bool cuba_hip_solver::sortEdgesHost(const UploadPlan& plan, const UploadArrays& in)
+{
+	const int32_t* ep = in.ep; const int32_t* el = in.el; const uint8_t* edim = in.edim; const double* meas = in.meas; const double* omega = in.omega;
+	const bool reuse = plan.reuseHostSort;
 	resetPoseOrder();
-	if (!sameInput)
+	lmOrderActive = false;          // (uploadState leaves the landmark rows as the caller numbers them)
+	if (!reuse)
 	{
-	h_inEp.assign(ep, ep + E); h_inEl.assign(el, el + E); h_inDim.assign(edim, edim + E);
-	// sort edges by (landmark, pose, original index): counting sort on the landmark, small sorts inside
-	h_lmptr.assign(Lt + 1, 0);
-	for (int e = 0; e < E; e++) h_lmptr[el[e] + 1]++;
-	for (int l = 0; l < Lt; l++) h_lmptr[l + 1] += h_lmptr[l];
-	perm.assign(E, 0);
-	{
+		h_inEp.assign(ep, ep + E); h_inEl.assign(el, el + E); h_inDim.assign(edim, edim + E);
+		// sort edges by (landmark, pose, original index): counting sort on the landmark, small sorts inside
+		cntEdgeSorts++;
+		h_lmptr.assign(Lt + 1, 0);
+		for (int e = 0; e < E; e++) h_lmptr[el[e] + 1]++;
+		for (int l = 0; l < Lt; l++) h_lmptr[l + 1] += h_lmptr[l];
+		perm.assign(E, 0);
 		std::vector<int> cursor(h_lmptr.begin(), h_lmptr.end() - 1);
 		for (int e = 0; e < E; e++) perm[cursor[el[e]]++] = e;
 		std::vector<long long> byEdges(h_lmptr.begin(), h_lmptr.end());    // balance the small sorts by edge count
@@ -169,40 +180,43 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 				[&](int a, int b) { return ep[a] != ep[b] ? ep[a] < ep[b] : a < b; });
 		});
 	}
-	}
 	lap("set_graph: validate + sort edges");
-	std::vector<int>& sPose = h_spose[sameInput ? topoSlot : topoSlot ^ 1];   // the previous call's sorted index arrays stay in the other slot
-	std::vector<int>& sLm = h_slm[sameInput ? topoSlot : topoSlot ^ 1];
+	std::vector<int>& sPose = h_spose[reuse ? topoSlot : topoSlot ^ 1];   // the previous call's sorted index arrays stay in the other slot
+	std::vector<int>& sLm = h_slm[reuse ? topoSlot : topoSlot ^ 1];
 	sPose.resize(E); sLm.resize(E);
 	// staging buffers are members: a second set_graph of similar size touches no fresh pages
 	std::vector<Scalar>&mu = h_stage[0], &mv = h_stage[1], &mr = h_stage[2], &w = h_stage[3];
 	mu.resize(E); mv.resize(E); mr.resize(E); w.resize(E);
 	h_epose.resize(E);
-	{
-		parallelFor(E, [&](int i) {       // random gather through the sort permutation
-			const int e = perm[i];
-			if (!sameInput)
-			{
-				h_epose[i] = ep[e];
-				sPose[i] = ep[e] | (edim[e] == 3 ? STEREO_BIT : 0);
-				sLm[i] = el[e];
-			}
-			mu[i] = meas[3 * (size_t)e]; mv[i] = meas[3 * (size_t)e + 1];
-			mr[i] = edim[e] == 3 ? meas[3 * (size_t)e + 2] : 0.0;
-			w[i] = omega[e];
-		});
-	}
+	parallelFor(E, [&](int i) {       // random gather through the sort permutation
+		const int e = perm[i];
+		if (!reuse)
+		{
+			h_epose[i] = ep[e];
+			sPose[i] = ep[e] | (edim[e] == 3 ? STEREO_BIT : 0);
+			sLm[i] = el[e];
+		}
+		mu[i] = meas[3 * (size_t)e]; mv[i] = meas[3 * (size_t)e + 1];
+		mr[i] = edim[e] == 3 ? meas[3 * (size_t)e + 2] : 0.0;
+		w[i] = omega[e];
+	});
 	// Same vertices, same edges (in sorted order, same types) as last time: everything build_structure() derives from
 	// the topology is still valid on the device -- only the values are new (the samples' warm-up + timed protocol,
 	// repeated optimisation of one window).  Decided by comparing the sorted index arrays, 8 bytes per edge.
-	sameTopology = sameCounts && hostTopoValid && (sameInput || (sPose == h_spose[topoSlot] && sLm == h_slm[topoSlot]));
-	if (!sameInput) topoSlot ^= 1;
+	const bool sameTopology = plan.mayKeepStructure && hostTopoValid && (reuse || (sPose == h_spose[topoSlot] && sLm == h_slm[topoSlot]));
+	if (!reuse) topoSlot ^= 1;
 	lap("set_graph: gather sorted arrays");
-	if (!sameInput || devTopology) { d_epose.upload(sPose, stream); d_elm.upload(sLm, stream); d_lmptr.upload(h_lmptr, stream); }
+	if (!reuse || devTopology) { d_epose.upload(sPose, stream); d_elm.upload(sLm, stream); d_lmptr.upload(h_lmptr, stream); }
 	d_mu.upload(mu, stream); d_mv.upload(mv, stream); d_mr.upload(mr, stream); d_w.upload(w, stream);
 	cntValueBytes += (int64_t)E * 4 * (int64_t)sizeof(Scalar);
 	devTopology = false; hostTopoValid = true;
-	}
+	return sameTopology;
+}
+
+// the estimates and cameras go up straight from the caller's arrays when they need neither a conversion (fp64 build) nor a
+// row permutation (internal pose order): no staging copy, and page-locked caller memory (cuba_hip_host_alloc) moves by DMA
+void cuba_hip_solver::uploadState(const UploadArrays& in)
+{
 	const size_t nState = (size_t)7 * Pt + (size_t)3 * Lt;
 	if (sizeof(Scalar) == sizeof(double) && !reorderActive)
 	{
@@ -210,21 +224,30 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 		Scalar* ds = d_state.data();
 		if (Pt)
 		{
-			HIP_TRY(hipMemcpyAsync(ds, q, sizeof(double) * 4 * (size_t)Pt, hipMemcpyHostToDevice, stream));
-			HIP_TRY(hipMemcpyAsync(ds + 4 * (size_t)Pt, t, sizeof(double) * 3 * (size_t)Pt, hipMemcpyHostToDevice, stream));
-			HIP_TRY(hipMemcpyAsync(d_cam.data(), cam, sizeof(double) * 5 * (size_t)Pt, hipMemcpyHostToDevice, stream));
+			HIP_TRY(hipMemcpyAsync(ds, in.q, sizeof(double) * 4 * (size_t)Pt, hipMemcpyHostToDevice, stream));
+			HIP_TRY(hipMemcpyAsync(ds + 4 * (size_t)Pt, in.t, sizeof(double) * 3 * (size_t)Pt, hipMemcpyHostToDevice, stream));
+			HIP_TRY(hipMemcpyAsync(d_cam.data(), in.cam, sizeof(double) * 5 * (size_t)Pt, hipMemcpyHostToDevice, stream));
 		}
-		if (Lt) HIP_TRY(hipMemcpyAsync(ds + 7 * (size_t)Pt, Xw, sizeof(double) * 3 * (size_t)Lt, hipMemcpyHostToDevice, stream));
+		if (Lt) HIP_TRY(hipMemcpyAsync(ds + 7 * (size_t)Pt, in.Xw, sizeof(double) * 3 * (size_t)Lt, hipMemcpyHostToDevice, stream));
 	}
 	else
 	{
-		if (!reorderActive) stageState();
+		std::vector<Scalar>&state = h_stage[4], &camv = h_stage[5];
+		state.resize(nState);
+		for (size_t i = 0; i < (size_t)4 * Pt; i++) state[i] = (Scalar)in.q[i];
+		for (size_t i = 0; i < (size_t)3 * Pt; i++) state[4 * (size_t)Pt + i] = (Scalar)in.t[i];
+		for (size_t i = 0; i < (size_t)3 * Lt; i++) state[7 * (size_t)Pt + i] = (Scalar)in.Xw[i];
+		camv.assign(in.cam, in.cam + 5 * (size_t)Pt);
+		permuteStateRows(state, camv);          // the caller's rows -> the internal pose order kept from the last call (none: as they are)
 		d_state.upload(state, stream);
 		d_cam.upload(camv, stream);
 	}
-	if (!useDev && lmOrderActive) { lmOrderActive = false; }          // (host pipeline: the caller's landmark order)
 	if (lmOrderActive) landmarkRowsInPlace(d_state.data() + 7 * (size_t)Pt, Lt, 3, true);
-	d_backup.resize(nState);
+}
+
+void cuba_hip_solver::allocRunBuffers()
+{
+	d_backup.resize((size_t)7 * Pt + (size_t)3 * Lt);
 	dropSnapshots();
 	d_perEdge.resize(E);
 	if (!h_pinned)
@@ -239,21 +262,22 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 	}
 	d_parts.resize(8192 + (size_t)E + 64); d_maxdiag.resize(64); d_fail.resize(1); d_iters.resize(1); d_kbase.resize(1); d_done.resize(1); d_ticket.resize(1);
 	d_fail.zero(stream); d_iters.zero(stream); d_kbase.zero(stream); d_done.zero(stream); d_ticket.zero(stream);
-	if (deferredUpload)
-	{
-		if (!upStream) { HIP_TRY(hipStreamCreateWithFlags(&upStream, hipStreamNonBlocking)); HIP_TRY(hipEventCreateWithFlags(&evValues, hipEventDisableTiming)); }
-		// (the raw buffers may still be read by a gather of the previous call on the work stream)
-		HIP_TRY(hipEventRecord(evValues, stream)); HIP_TRY(hipStreamWaitEvent(upStream, evValues, 0));
-		HIP_TRY(hipMemcpyAsync(d_rawMeas.data(), meas, sizeof(double) * 3 * (size_t)E, hipMemcpyHostToDevice, upStream));
-		HIP_TRY(hipMemcpyAsync(d_rawOmega.data(), omega, sizeof(double) * (size_t)E, hipMemcpyHostToDevice, upStream));
-		HIP_TRY(hipEventRecord(evValues, upStream));
-		cntValueBytes += (int64_t)E * 32;
-		deferredUpload = false;
-	}
-	sync(); expectedTicket = 0; ((volatile int*)((char*)h_pinned + 1024))[3] = 0;
-	sync();   // host staging vectors go out of scope
+}
 
-	lap("set_graph: alloc + upload + sync");
+// deferValues (cuba_hip_set_graph_begin): meas / omega, 32 bytes per edge, cross on the second stream while the structure analysis runs
+void cuba_hip_solver::enqueueDeferredValues(const UploadArrays& in)
+{
+	if (!upStream) { HIP_TRY(hipStreamCreateWithFlags(&upStream, hipStreamNonBlocking)); HIP_TRY(hipEventCreateWithFlags(&evValues, hipEventDisableTiming)); }
+	// (the raw buffers may still be read by a gather of the previous call on the work stream)
+	HIP_TRY(hipEventRecord(evValues, stream)); HIP_TRY(hipStreamWaitEvent(upStream, evValues, 0));
+	HIP_TRY(hipMemcpyAsync(d_rawMeas.data(), in.meas, sizeof(double) * 3 * (size_t)E, hipMemcpyHostToDevice, upStream));
+	HIP_TRY(hipMemcpyAsync(d_rawOmega.data(), in.omega, sizeof(double) * (size_t)E, hipMemcpyHostToDevice, upStream));
+	HIP_TRY(hipEventRecord(evValues, upStream));
+	cntValueBytes += (int64_t)E * 32;
+}
+
+void cuba_hip_solver::publishGraph(const UploadPlan& plan, const DeviceGraph& gOld, bool sameTopology)
+{
 	g = DeviceGraph();
 	g.Pt = Pt; g.Pf = Pf; g.Lt = Lt; g.Lf = Lf; g.E = E;
 	g.q = d_state.data(); g.t = d_state.data() + 4 * (size_t)Pt; g.Xw = d_state.data() + 7 * (size_t)Pt;
@@ -262,8 +286,7 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 	g.e_mu = d_mu.data(); g.e_mv = d_mv.data(); g.e_mr = d_mr.data(); g.e_w = liveInformation();
 	g.rk[0] = rk[0]; g.rk[1] = rk[1];
 	g.e_begin = 0; g.e_end = E;
-	partLo = ranged ? ownLo : 0; partHi = ranged ? ownHi : -1;
-	valuesPartial = ranged && useDev;          // (the host pipeline reads the whole arrays)
+	valuesPartial = partHi >= 0 && plan.useDev;          // (a ranged upload; the host pipeline reads the whole arrays)
 	if (sameTopology)
 	{
 		// the captured PCG graphs carry the DeviceGraph by value: they stay usable only if no buffer moved
@@ -282,7 +305,6 @@ void cuba_hip_solver::setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double*
 	pcgHistory.clear();
 	cntUploads++;
 	valuesStamp++;          // (the permutation or the sorted values are new: an edge gate derives its copies again, refreshGate)
-	prof[0] += std::chrono::duration<double>(Clock::now() - t0).count();
 }
 
 void cuba_hip_solver::buildStructure()
@@ -933,7 +955,7 @@ void cuba_hip_solver::permuteStateRows(std::vector<Scalar>& state, std::vector<S
 void cuba_hip_solver::runDeviceEdgeSort(bool withValues)
 {
 	if (withValues && valuesPending) { valuesPending = false; HIP_TRY(hipStreamWaitEvent(stream, evValues, 0)); }     // (a re-sort under a new pose order: the values must have landed)
-	d_mu.resize(E); d_mv.resize(E); d_mr.resize(E); d_w.resize(E);
+	sizeSortedValues();
 	d_k64a.resize(E); d_k64b.resize(E); d_v32a.resize(E); d_perm.resize(E); d_counters.resize(topo::CNT_COUNT);
 	d_epose.resize(E); d_elm.resize(E); d_lmptr.resize((size_t)Lt + 1);
 	d_counters.zero(stream);
@@ -945,6 +967,7 @@ void cuba_hip_solver::runDeviceEdgeSort(bool withValues)
 		d_epose.data(), d_elm.data(), withValues ? d_mu.data() : nullptr, d_mv.data(), d_mr.data(), d_w.data(), stream);
 	topo::launch_segment_ptr(d_elm.data(), E, Lt, d_lmptr.data(), stream);
 	if (withValues) sortedValuesValid = true;
+	cntEdgeSorts++;
 	valuesStamp++;          // (the permutation or the sorted values are new: an edge gate derives its copies again, refreshGate)
 }
 

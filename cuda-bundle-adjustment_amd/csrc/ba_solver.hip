@@ -397,6 +397,7 @@ int cuba_hip_get_counter(cuba_hip_solver* s, const char* name, int64_t* value)
 		else if (k == "graph_uploads") *value = s->cntUploads;
 		else if (k == "structure_builds") *value = s->cntStructureBuilds;
 		else if (k == "value_bytes_uploaded") *value = s->cntValueBytes;
+		else if (k == "edge_sorts") *value = s->cntEdgeSorts;
 		else if (k == "late_decision_records") *value = s->cntLateRecords;
 		else if (k == "covariance_ns") *value = (int64_t)(1e9 * s->covSeconds);
 		else if (k == "covariance_pairs_ns") *value = (int64_t)(1e9 * s->covPairsSeconds);

@@ -33,8 +33,10 @@
 #include "ba_kernels.hpp"
 #include "host_pool.hpp"
 #include "ba_structure.hpp"
+#include "ba_upload_plan.hpp"
 
 using namespace cubahip;
+static_assert(UPLOAD_POSE_LIMIT == STEREO_BIT, "the upload plan refuses the poses a sorted edge cannot name");
 
 // (a named namespace: the handle is one type across the translation units that implement it, and an exception thrown in one of
 // them is caught by the C ABI in another)
@@ -211,8 +213,9 @@ struct cuba_hip_solver
 	// device-side set-up (ba_structure.hip): the edge sort and the whole symbolic structure are built on the GPU; the host
 	// pipeline below stays as the independent cross-check ("device_setup" = 0) and for graphs without edges
 	bool deviceSetup = true;
-	bool devTopology = false;    // the sorted edge arrays / permutation exist on the device only (host copies are stale)
-	bool hostTopoValid = false;  // perm / h_lmptr / h_epose / h_spose / h_slm describe the current graph
+	bool devTopology = false;    // the sort in force was made on the device (runDeviceEdgeSort); false: on the host, and uploaded
+	bool hostTopoValid = false;  // perm / h_lmptr / h_epose / h_spose / h_slm describe the sort in force: made on the host, or read back from
+	                             // the device (ensureHostTopology) -- then in the internal pose and landmark order of that moment
 	static int bitsFor(long long n) { int b = 1; while ((1LL << b) < n + 1) b++; return b; }
 	DevBuf<int> d_rawEp, d_rawEl, d_counters, d_tmpI0, d_tmpI1, d_adjRow, d_lowerPtr, d_chunk;
 	DevBuf<uint8_t> d_rawDim;
@@ -528,13 +531,26 @@ struct cuba_hip_solver
 	// deferValues (cuba_hip_set_graph_begin): the caller keeps meas / omega valid until cuba_hip_set_graph_end, so their 32 bytes per
 	// edge may still be crossing PCIe -- on a second stream -- while the structure analysis (which needs the index arrays only) runs
 	hipStream_t upStream = nullptr; hipEvent_t evValues = nullptr;
-	bool valuesPending = false, deferredUpload = false;
+	bool valuesPending = false;
 	bool sortedValuesValid = false;     // d_mu / d_mv / d_mr / d_w hold the gathered values of the last upload (false while a two-step upload is open or was abandoned)
 	int* h_tileStage = nullptr; size_t tileStageCap = 0; hipEvent_t evTileInputs = nullptr;     // page-locked staging of the tile-order inputs
 	void finishValues();
+	void sizeSortedValues() { d_mu.resize(E); d_mv.resize(E); d_mr.resize(E); d_w.resize(E); }
+	void gatherSortedValues();          // raw values -> d_mu / d_mv / d_mr / d_w through the sort permutation
 	void setGraph(int Pt_, int Pf_, int Lt_, int Lf_, const double* q, const double* t, const double* cam, const double* Xw,
 		int E_, const int32_t* ep, const int32_t* el, const uint8_t* edim, const double* meas, const double* omega, bool deferValues = false,
 		int ownLo = 0, int ownHi = -1);      // ownHi >= 0: the handle is restricted to the landmarks [ownLo, ownHi) and reads the values of their edges only
+	// setGraph decides nothing itself: what the call refuses and what it reuses of the previous upload is planUpload's answer
+	// (ba_upload_plan.hpp, checked on the CPU) to the facts below, and the steps act on that plan in the order they stand here
+	struct UploadArrays { const double *q, *t, *cam, *Xw; const int32_t *ep, *el; const uint8_t* edim; const double *meas, *omega; };
+	UploadFacts uploadFacts() const;    // every cached fact of the handle that a decision reads, taken before anything is touched
+	bool sameEdgeArrays(const UploadArrays& in) const;
+	bool sortEdgesDevice(const UploadPlan& plan, const UploadArrays& in);
+	bool sortEdgesHost(const UploadPlan& plan, const UploadArrays& in);
+	void uploadState(const UploadArrays& in);
+	void allocRunBuffers();
+	void enqueueDeferredValues(const UploadArrays& in);
+	void publishGraph(const UploadPlan& plan, const DeviceGraph& gOld, bool sameTopology);
 
 	// ---------------------------------------------------------------------------------------------
 	// Symbolic structure: Hsc pattern from landmark co-visibility (ref: HschurSparseBlockMatrix::
@@ -723,6 +739,7 @@ struct cuba_hip_solver
 	// with: every such pair owns a block of the reduced matrix, so need() rebuilds the structure exactly when the two sets differ
 	std::vector<uint64_t> h_relPairs, structRelPairs;
 	int64_t cntStructureBuilds = 0;      // structures published on this handle (never reset)
+	int64_t cntEdgeSorts = 0;            // edge sorts run on this handle, host and device (never reset)
 	std::vector<uint64_t> h_relSeeds;    // the pairs as the last pattern build took them
 	DevBuf<int> d_relSeedFlag, d_relSeedScan; DevBuf<uint64_t> d_relSeeds;
 	// the pairs as (row, column) keys of the pattern in the internal pose order, sorted

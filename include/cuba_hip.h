@@ -164,7 +164,8 @@ int cuba_hip_set_option(cuba_hip_solver* s, const char* key, double value);
    Edges whose two ends are both fixed must already be removed (as the reference does, :204-243).
    A cuba_hip_set_graph[_begin / _partition] that is refused with CUBA_HIP_ERR_INVALID_ARGUMENT (bad counts, a null array, a bad landmark
    range, an edge index or dimension out of range, an edge between two fixed vertices) leaves the handle as it was: the previous graph, its
-   factor sets, its mask and its snapshot slots stay in force; only a pending cuba_hip_hint_unchanged promise is consumed. */
+   factor sets, its mask and its snapshot slots stay in force; only a pending cuba_hip_hint_unchanged promise is consumed.  A previous
+   graph whose cuba_hip_set_graph_begin is still open stays open: its meas / omega must stay valid until its cuba_hip_set_graph_end. */
 int cuba_hip_set_graph(cuba_hip_solver* s, int Pt, int Pf, int Lt, int Lf,
 	const double* q, const double* t, const double* cam, const double* Xw,
 	int E, const int32_t* edge_pose, const int32_t* edge_landmark, const uint8_t* edge_dim,
@@ -351,6 +352,9 @@ int cuba_hip_get_counters(cuba_hip_solver* s, int64_t counters[8]);
    life of the handle, never reset: a caller that keeps state about "what the device holds" -- the promises of cuba_hip_hint_unchanged --
    stores this number with it and distrusts its state when the two differ), "value_bytes_uploaded" (bytes of measurements and
    information that crossed PCIe in the life of the handle: 32 per edge and full upload, 36 per OWNED edge for cuba_hip_set_graph_partition),
+   "edge_sorts" (edge sorts run in the life of the handle, on the host or on the device: one per upload that could not keep the previous
+   sort, one more whenever the library changes its internal pose or landmark order on a live graph; like "structure_builds" it shows
+   what an upload reused),
    "late_decision_records" (life of the handle: LM decision records that had not reached host memory when the report behind them had, and
    were fetched by a stream synchronisation instead; 0 in normal operation).
    Unknown name: CUBA_HIP_ERR_INVALID_ARGUMENT. */

@@ -331,6 +331,7 @@ TRANSITIONS = {
     "refused.upload.counts": "Pf > Pt", "refused.upload.range": "a bad landmark range", "refused.upload.edge_index": "an edge index out of range",
     "refused.upload.with_promise": "a promise was pending", "refused.upload.with_factors": "factor sets were in force",
     "refused.upload.with_mask": "a mask was set", "refused.upload.with_snapshot": "a slot was in use",
+    "refused.upload.after_begin_only": "a begin-only upload was the one in force: it stays, with ITS values",
     "refused.factors": "a factor set the library refuses", "refused.factors.partitioned": "a factor set on a partitioned handle",
     "refused.option": "a value or key cuba_hip_set_option refuses", "refused.restore": "an empty slot",
     "hint": "cuba_hip_hint_unchanged",
@@ -455,6 +456,7 @@ def _upload(step, spec, handle, refused_status=None):
         if spec.factors: _hit(spec, "refused.upload.with_factors")
         if spec.mask is not None: _hit(spec, "refused.upload.with_mask")
         if spec.snapshots: _hit(spec, "refused.upload.with_snapshot")
+        if spec.begun: _hit(spec, "refused.upload.after_begin_only")
         _expect_status(handle, ERR_ARGUMENT, call)
         if rules.refusal_consumes_promise:
             spec.promise = (False, False)

@@ -127,7 +127,8 @@ def windows():
 
 
 def windows_refusals():
-    """a promise followed by a refused upload followed by a valid upload of other edges with the same counts: the promise must be gone"""
+    """a promise followed by a refused upload followed by a valid upload of other edges with the same counts: the promise must be gone;
+    a begin without its end followed by a refused upload: the begun graph stays in force, with the values that were on their way"""
     A = problem("w40")
     A2, A3 = other_edges(A, 1), other_edges(A, 3)
     return [
@@ -136,6 +137,7 @@ def windows_refusals():
         Hint(True, False), Refused(Upload(A, "ranged", (5, A.Lt + 3)), ERR_ARGUMENT), Upload(A3, "two"), Check(3),
         Hint(True, True), Refused(Upload(broken(A3, "edge_index")), ERR_ARGUMENT), Upload(A), Check(2),
         Refused(Upload(broken(A, "edge_index")), ERR_ARGUMENT), start(A), Check(2),          # no promise: the graph in force stays
+        Upload(other_values(A, 11), "begin"), Refused(Upload(broken(A, "counts")), ERR_ARGUMENT), Check(2),          # ... a begun one too
     ]
 
 

@@ -40,6 +40,10 @@ What the scripts found on the MI355X (script, check, first quantity that differe
   partition         check 5  hsc in the last bits (4196 of 11700): a whole upload after a ranged one (or under a set partition) was
                              sorted while the old range was still in force and lost the internal landmark order.  The range is now
                              lifted before the sort.
+  windows_refusals  check 5  compute_errors 239926.68 against 240058.67 (read from the code, then shown by the twin): a _begin alone, then
+                             an upload refused for its counts, then a run.  The refused call had already closed the open two-step
+                             upload -- values no longer pending, never gathered -- so the begun graph ran on the sorted values of the
+                             upload before it.  The bookkeeping of an open upload now sits below every refusal of setGraph.
   factors_all                (the test's own plumbing) HipSolver.set_graph recorded a REFUSED problem as the one in force, so the next
                              chi_squares() handed the library a buffer one edge short.  It records the problem after a successful call.
   Not a defect, now written into the header: "device_setup" changed on a handle that holds a graph switches the analysis at once and the
