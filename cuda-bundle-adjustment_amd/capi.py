@@ -29,6 +29,8 @@ ARRAY_IDS = dict(bp=0, bsc=1, xp=2, xl=3, lm_sys=4, hsc=5, state=6)
 PROFILE_KEYS = (  # same strings as CudaBlockSolver::getTimeProfile (src/cuda_bundle_adjustment.cpp:545-562)
     "0: Initialize Optimizer", "1: Build Structure", "2: Compute Error", "3: Build System",
     "4: Schur Complement", "5: Symbolic Decomposition", "6: Numerical Decomposition", "7: Update Solution")
+TRI_STATUS_NAMES = (  # CUBA_HIP_TRI_* of include/cuba_hip.h, in the order the statuses are decided
+    "ok", "not_selected", "fixed", "few_observations", "low_parallax", "singular", "behind_camera", "chi2")
 
 
 class CubaHipError(RuntimeError):
@@ -141,6 +143,7 @@ def load_library(precision="f64"):
         "cuba_hip_set_edge_active": [H, _u8p],
         "cuba_hip_get_edge_active": [H, _u8p],
         "cuba_hip_landmark_active_edges": [H, _ip],
+        "cuba_hip_triangulate_landmarks": [H, _u8p, C.c_int, C.c_double, _dp, C.c_int, _ip, C.POINTER(C.c_int64), _dp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -623,6 +626,27 @@ class HipSolver:
         """int32[Lt], caller's landmark order: active edges per landmark"""
         out = np.zeros(self.fp.Lt if self.fp is not None else 0, dtype=np.int32)
         self._ck(self.lib.cuba_hip_landmark_active_edges(self.h, out.ctypes.data_as(_ip)))
+        return out
+
+    # ---- landmark triangulation (cuba_hip_triangulate_landmarks) --------------------------------
+    def triangulate_landmarks(self, select=None, refine_iterations=5, min_parallax_deg=1.0, chi2_max=(5.991, 7.815), dry_run=False):
+        """(Re-)triangulates the free landmarks on the device from their active reprojection edges and the current poses: a linear start,
+        refine_iterations Gauss-Newton steps per landmark, acceptance tests (include/cuba_hip.h).  select: truthy[Lt] in the caller's
+        landmark order, None = all.  Returns "status" (int32[Lt], indices into TRI_STATUS_NAMES), the eight counts by name, and "xyz"
+        ([Lt, 3]: the accepted position of every "ok" landmark, the unchanged one of every other)."""
+        Lt = self.fp.Lt if self.fp is not None else 0
+        sel = None
+        if select is not None:
+            sel = np.ascontiguousarray(np.asarray(select) != 0, dtype=np.uint8)
+            if sel.shape != (Lt,):
+                raise ValueError(f"select: expected {Lt} entries")
+        thr = np.ascontiguousarray(chi2_max, dtype=np.float64).reshape(2)
+        status, xyz = np.zeros(Lt, dtype=np.int32), np.zeros((Lt, 3))
+        counts = (C.c_int64 * len(TRI_STATUS_NAMES))()
+        self._ck(self.lib.cuba_hip_triangulate_landmarks(self.h, sel.ctypes.data_as(_u8p) if sel is not None else None, int(refine_iterations),
+                                                         float(min_parallax_deg), _d(thr), int(bool(dry_run)), status.ctypes.data_as(_ip), counts, _d(xyz)))
+        out = {k: int(v) for k, v in zip(TRI_STATUS_NAMES, counts)}
+        out["status"], out["xyz"] = status, xyz
         return out
 
     def set_pose_priors(self, pose, q, t, info):

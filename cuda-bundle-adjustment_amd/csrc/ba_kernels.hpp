@@ -555,6 +555,31 @@ void launch_gate_unsort(const uint32_t* perm, const uint8_t* maskSorted, int E, 
 // bigInternal[Lt]: scratch of the landmarks of big_lm (more than 64 edges: one workgroup each)
 void launch_landmark_active(const int* lm_ptr, const uint8_t* mask, const int* newOfOld, int Lt, const int* big_lm, int nBig, int* bigInternal, int* out, hipStream_t s);
 
+// ---- landmark triangulation (ba_triangulate.hip) ------------------------------------------------------------------------------------
+// the statuses in the order they are decided (include/cuba_hip.h: CUBA_HIP_TRI_*)
+enum { TRI_OK = 0, TRI_NOT_SELECTED, TRI_FIXED, TRI_FEW_OBSERVATIONS, TRI_LOW_PARALLAX, TRI_SINGULAR, TRI_BEHIND_CAMERA, TRI_CHI2, TRI_STATUSES };
+constexpr int TRI_MAX_ITERATIONS = 16;
+struct TriangulateArgs
+{
+	DeviceGraph g;                     // e_w: the LIVE information (a gated edge is out); rk: the handle's robust kernels
+	const int* wave_lm = nullptr; int nWaves = 0;      // the landmark pass's wave list ...
+	const int* big_lm = nullptr; int nBig = 0;         // ... and its landmarks of more than 64 edges
+	int iterations = 0;                // Gauss-Newton steps behind the linear start
+	int parallax_on = 0; double cos_half_parallax = 1; // LOW_PARALLAX: |sum of the unit rays| / n > cos(min_parallax / 2)
+	double chi2_mono = 0, chi2_stereo = 0;
+	int dry_run = 0;                   // 1: g.Xw is left alone
+	int* status = nullptr;             // [Lt] internal landmark order (between the launches also the internal "pending" mark)
+	double* xnew = nullptr;            // [3 Lt] internal order: the accepted position of an OK landmark as the state holds it (others: not written)
+};
+int triangulate_collect_grid(int Lt);
+// status[] = NOT_SELECTED / FIXED / "pending" per landmark (select[Lt], caller's numbering, or null: all; newOfOld: the internal order
+// or null), then the wave and workgroup kernels decide every pending landmark and (no dry run) store the OK ones into g.Xw
+void launch_triangulate(const TriangulateArgs& a, const uint8_t* select, const int* newOfOld, hipStream_t s);
+// into the caller's numbering: statusOut[Lt] (a landmark still pending -- it has no edge -- as FEW_OBSERVATIONS), xyzOut[3 Lt] (xnew of an
+// OK landmark, g.Xw of every other), counts[TRI_STATUSES] through
+// parts[TRI_STATUSES * triangulate_collect_grid(Lt)]
+void launch_triangulate_collect(const TriangulateArgs& a, const int* newOfOld, int* statusOut, double* xyzOut, long long* parts, long long* counts, hipStream_t s);
+
 // copies {fail, iters, done} into sys.host_flags (what the last node of an iteration graph does anyway)
 void launch_pcg_report(const DeviceSystem& sys, hipStream_t s);
 

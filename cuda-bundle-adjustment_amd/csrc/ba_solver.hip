@@ -361,6 +361,12 @@ int cuba_hip_set_edge_active(cuba_hip_solver* s, const uint8_t* active) { return
 int cuba_hip_get_edge_active(cuba_hip_solver* s, uint8_t* active) { return guarded(s, [&] { s->getEdgeActive(active); }); }
 int cuba_hip_landmark_active_edges(cuba_hip_solver* s, int32_t* per_landmark) { return guarded(s, [&] { s->landmarkActiveEdges(per_landmark); }); }
 
+int cuba_hip_triangulate_landmarks(cuba_hip_solver* s, const uint8_t* select, int refine_iterations, double min_parallax_deg,
+	const double chi2_max[2], int dry_run, int32_t* status, int64_t counts[CUBA_HIP_TRI_STATUSES], double* xyz)
+{
+	return guarded(s, [&] { s->triangulateLandmarks(select, refine_iterations, min_parallax_deg, chi2_max, dry_run != 0, status, counts, xyz); });
+}
+
 int cuba_hip_get_profile(cuba_hip_solver* s, double seconds[CUBA_HIP_PROFILE_ITEMS])
 {
 	return guarded(s, [&] { for (int i = 0; i < CUBA_HIP_PROFILE_ITEMS; i++) seconds[i] = s->prof[i]; });

@@ -682,6 +682,15 @@ struct cuba_hip_solver
 	void getEdgeActive(uint8_t* active);
 	void landmarkActiveEdges(int32_t* perLandmark);
 
+	// Landmark triangulation (ba_triangulate.hip): free landmarks from their active reprojection edges and the current poses.  Its buffers
+	// exist from the first call on; a handle that never calls it allocates and launches nothing of this.
+	DevBuf<int> d_triStatus;             // [2 Lt] statuses in the internal order | in the caller's
+	DevBuf<double> d_triX;               // [6 Lt] accepted positions in the internal order | positions in the caller's
+	DevBuf<uint8_t> d_triSelect;
+	DevBuf<long long> d_triCounts;
+	void triangulateLandmarks(const uint8_t* select, int refineIterations, double minParallaxDeg, const double chi2Max[2], bool dryRun,
+		int32_t* status, int64_t* counts, double* xyz);
+
 	// The factors besides the reprojection edges (ba_factor.hip): seven kinds, each a set kept as the caller gave it, in the caller's numbering
 	// (quaternions normalised, information symmetrised), with a device copy (pf) in the internal order that need() makes -- uploadFactors():
 	// once that order is known, again when it changes (the unary kinds on the poses: with the pose order; the two binary kinds, whose

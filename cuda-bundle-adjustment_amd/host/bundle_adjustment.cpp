@@ -585,6 +585,41 @@ public:
 		const auto it = gateChiIndex_.find(e);
 		return it == gateChiIndex_.end() ? 0.0 : it->second;
 	}
+	// ---- landmark triangulation (extension: cuba::triangulateLandmarks) --------------------------------
+	// One call behind the ABI.  The accepted positions go into the vertex objects (and the staging array of the next upload): the next
+	// initialize() reads the estimates from there, and the handle already holds them.
+	TriangulationResult triangulateLandmarks(const TriangulationOptions& o, const std::vector<LandmarkVertex*>* subset)
+	{
+		prepareOptimize();            // (the graph and the levels set by hand go up first)
+		const size_t nL = activeLandmarks_.size();
+		std::vector<uint8_t> select;
+		if (subset)
+		{
+			select.assign(nL, 0);
+			for (const LandmarkVertex* v : *subset)
+				if (v && v->iL >= 0 && static_cast<size_t>(v->iL) < nL && activeLandmarks_[v->iL] == v) select[v->iL] = 1;
+		}
+		const double thr[2] = { o.chi2Mono, o.chi2Stereo };
+		int64_t c[CUBA_HIP_TRI_STATUSES] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+		triStatus_.assign(nL, CUBA_HIP_TRI_NOT_SELECTED);
+		std::vector<double> xyz(3 * nL);
+		check(cuba_hip_triangulate_landmarks(solver_, subset ? select.data() : nullptr, o.refineIterations, o.minParallaxDeg, thr, o.dryRun ? 1 : 0,
+			triStatus_.data(), c, xyz.data()), "cuba_hip_triangulate_landmarks");
+		triLandmarks_ = activeLandmarks_; triIndex_.clear();          // (the vertex -> status index is built by the first triangulationStatus)
+		if (!o.dryRun)
+			for (size_t i = 0; i < nL; i++)
+				if (triStatus_[i] == CUBA_HIP_TRI_OK)
+					for (int k = 0; k < 3; k++) activeLandmarks_[i]->Xw.data()[k] = Xw_[3 * i + k] = xyz[3 * i + k];
+		TriangulationResult r;
+		for (int k = 0; k < CUBA_HIP_TRI_STATUSES; k++) r.counts[k] = c[k];
+		return r;
+	}
+	TriangulationStatus triangulationStatus(const LandmarkVertex* v) const
+	{
+		if (triIndex_.empty()) for (size_t i = 0; i < triLandmarks_.size(); i++) triIndex_[triLandmarks_[i]] = triStatus_[i];
+		const auto it = triIndex_.find(v);
+		return it == triIndex_.end() ? TriangulationStatus::NOT_SELECTED : static_cast<TriangulationStatus>(it->second);
+	}
 	int activeObservations(const LandmarkVertex* v) const
 	{
 		int n = 0;
@@ -798,6 +833,7 @@ public:
 		poses_.clear(); landmarks_.clear(); mono_.clear(); stereo_.clear(); stats_.clear();
 		forEachKind([](auto& list) { list.items.clear(); list.chi.clear(); });
 		inactiveEdges_.clear(); maskDirty_ = true; gateChi_.clear(); gateChiEdges_.clear(); gateChiIndex_.clear();
+		triStatus_.clear(); triLandmarks_.clear(); triIndex_.clear();
 		posesDirty_ = landmarksDirty_ = edgesDirty_ = true;
 		initialized_ = false;
 	}
@@ -958,6 +994,9 @@ private:
 	std::vector<double> gateChi_;                            // ungated chi2 of the last gateEdges, over gateChiEdges_
 	std::vector<BaseEdge*> gateChiEdges_;
 	mutable std::unordered_map<const BaseEdge*, double> gateChiIndex_;
+	std::vector<int32_t> triStatus_;                         // statuses of the last triangulateLandmarks, over triLandmarks_
+	std::vector<LandmarkVertex*> triLandmarks_;
+	mutable std::unordered_map<const LandmarkVertex*, int32_t> triIndex_;
 };
 
 }  // namespace
@@ -1077,6 +1116,19 @@ int activeObservations(const CudaBundleAdjustment* object, const LandmarkVertex*
 {
 	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
 	return impl ? impl->activeObservations(v) : 0;
+}
+
+// Extension (g2o's StructureOnlySolver<3> / ORB-SLAM's CreateNewMapPoints; the reference has none): landmarks from their edges and the poses.
+TriangulationResult triangulateLandmarks(CudaBundleAdjustment* object, const TriangulationOptions& options, const std::vector<LandmarkVertex*>* subset)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (!impl) throw std::runtime_error("cuba::triangulateLandmarks: not an object of this library");
+	return impl->triangulateLandmarks(options, subset);
+}
+TriangulationStatus triangulationStatus(const CudaBundleAdjustment* object, const LandmarkVertex* v)
+{
+	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
+	return impl ? impl->triangulationStatus(v) : TriangulationStatus::NOT_SELECTED;
 }
 
 void addPosePrior(CudaBundleAdjustment* object, PosePrior* prior) { addFactor(object, prior); }

@@ -138,6 +138,24 @@ struct EdgeGateResult
 	long long changed = 0;                              // edges whose state changed (DRY_RUN: would change)
 };
 
+// ---- landmark triangulation (extension: cuba::triangulateLandmarks, bundle_adjustment.hpp; the reference has no counterpart) ----------
+struct TriangulationOptions
+{
+	int refineIterations = 5;                      // Gauss-Newton steps per landmark behind the linear start (0 ... 16)
+	double minParallaxDeg = 1.0;                   // two views closer than this are LOW_PARALLAX (<= 0: no such test)
+	double chi2Mono = 5.991, chi2Stereo = 7.815;   // a landmark is accepted only if every active edge stays at or below this (infinity: no chi2 test)
+	bool dryRun = false;                           // only the statuses and counts: no position changes
+};
+
+// the statuses in the order they are decided (CUBA_HIP_TRI_* of cuba_hip.h)
+enum class TriangulationStatus { OK = 0, NOT_SELECTED, FIXED, FEW_OBSERVATIONS, LOW_PARALLAX, SINGULAR, BEHIND_CAMERA, CHI2 };
+
+struct TriangulationResult
+{
+	long long counts[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };      // landmarks per TriangulationStatus
+	long long count(TriangulationStatus s) const { return counts[static_cast<int>(s)]; }
+};
+
 // short names used inside the reference's sources (types.h:242-245)
 using VertexP = PoseVertex;
 using VertexL = LandmarkVertex;

@@ -130,6 +130,17 @@ bool edgeActive(const CudaBundleAdjustment* object, const BaseEdge* edge);
 double edgeGateChiSquared(const CudaBundleAdjustment* object, const BaseEdge* edge);
 int activeObservations(const CudaBundleAdjustment* object, const LandmarkVertex* v);
 
+// Extension (g2o's StructureOnlySolver<3>, ORB-SLAM's CreateNewMapPoints; the reference has no counterpart; include/cuba_hip.h,
+// cuba_hip_triangulate_landmarks): the free landmarks of the initialize()d graph -- or those of `subset` -- are (re-)triangulated on the
+// device from their switched-on reprojection edges and the current pose estimates: a linear start, refineIterations Gauss-Newton steps
+// per landmark with the poses held and the robust kernels in force, then the acceptance tests (TriangulationOptions, ba_types.hpp).  The
+// landmark's current Xw is never read.  Unless dryRun is set, the accepted positions are written into the LandmarkVertex::Xw of the OK
+// landmarks (and are what the next optimize() starts from); every other vertex keeps its Xw.  Landmark priors take no part.
+//   triangulationStatus   a landmark's status at the last triangulateLandmarks (NOT_SELECTED before one and for a vertex it did not cover)
+// New map points with any Xw at all:  ba->initialize(); cuba::triangulateLandmarks(ba.get(), {}, &newPoints); ba->optimize(10);
+TriangulationResult triangulateLandmarks(CudaBundleAdjustment* object, const TriangulationOptions& options, const std::vector<LandmarkVertex*>* subset = nullptr);
+TriangulationStatus triangulationStatus(const CudaBundleAdjustment* object, const LandmarkVertex* v);
+
 // Robust kernel of a pose factor (PosePrior, RelativePoseEdge; include/cuba_hip.h, cuba_hip_set_pose_factor_robust_kernels): with
 // e = r^T Omega r the objective term becomes rho(e) and the linearisation takes rho'(e) Omega for Omega.  HUBER and TUKEY are the kernels of
 // the reprojection edges; CAUCHY, rho = delta^2 log1p(e / delta^2), exists for the pose factors only -- the usual choice on loop closures,

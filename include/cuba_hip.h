@@ -330,6 +330,41 @@ int cuba_hip_get_edge_active(cuba_hip_solver* s, uint8_t* active);
 /* per_landmark[Lt] in the caller's landmark order: active edges of every landmark (ORB-SLAM culls map points left with fewer than two) */
 int cuba_hip_landmark_active_edges(cuba_hip_solver* s, int32_t* per_landmark);
 
+/* ---- landmark triangulation ---------------------------------------------------------------------- */
+
+/* Replaces: nothing of the reference -- g2o's StructureOnlySolver<3> / ORB-SLAM's CreateNewMapPoints: the position a landmark has
+   BEFORE it is optimised (new map points behind a keyframe, points whose edges were gated and came back, points behind a loop
+   closure that moved the poses).  Without it a caller reads the poses back, triangulates on the host and uploads the points again.
+   Here every free landmark is (re-)triangulated on the device from its ACTIVE reprojection edges (live information omega > 0: a gated
+   edge is out) and the current pose estimates, all arithmetic in double in both libraries.  Per landmark, the first rule that applies:
+     NOT_SELECTED       select given and select[l] == 0
+     FIXED              a fixed landmark
+     FEW_OBSERVATIONS   fewer than two active edges, none of them a stereo edge of positive disparity u - u_r
+     LOW_PARALLAX       (only without such a stereo edge, and min_parallax_deg > 0) the mean of the unit viewing rays in the world
+                        frame is longer than cos(min_parallax_deg / 2) -- two views: their angle is below min_parallax_deg
+     SINGULAR           the linear start (below) or a refinement step met a non-positive determinant or a non-finite number
+     BEHIND_CAMERA      at the final position an active edge has depth <= 0
+     CHI2               at the final position an active edge has omega |r|^2 > chi2_max[stereo] (+inf: no such test)
+     OK                 the landmark's position is replaced (dry_run != 0: nothing is written)
+   Linear start: the rows (fx R0 + (cx - u) R2) X = -(fx t0 + (cx - u) t2), the same in v and -- stereo -- in u_r with bf on the right,
+   weighted by omega, solved through the 3 x 3 normal equations; the landmark's current position is never read (it may be NaN).
+   Refinement: refine_iterations (0 ... 16) Gauss-Newton steps on the landmark's robustified reprojection cost with the handle's robust
+   kernels (cuba_hip_set_robust_kernel), the poses held.  Landmark priors (cuba_hip_set_landmark_priors) take NO part in any of this.
+   Known limit: SINGULAR is a test of a determinant's sign.  Where a Tukey kernel gives every edge of a landmark but ONE monocular edge
+   the weight 0, H has rank 2, its determinant is rounding noise (1e-16 of the diagonal's product) and whether such a landmark is reported
+   as SINGULAR or as what the huge step leads to (CHI2, BEHIND_CAMERA) is not determined; it is rejected either way.
+   select[Lt] (optional), status[Lt] (optional), xyz[3 Lt] (optional): the caller's landmark numbering; xyz receives the accepted position
+   of every OK landmark (as the estimate holds it) and the unchanged current position of every other one.
+   counts[CUBA_HIP_TRI_STATUSES] (optional): landmarks per status; they sum to Lt.
+   Poses, unselected, fixed and rejected landmarks, the gate, the snapshot slots and the counters stay as they are; a covariance computed
+   before is dropped when a position changed.  A handle that never calls this allocates and launches nothing for it.
+   CUBA_HIP_ERR_INVALID_ARGUMENT: refine_iterations outside 0 ... 16, a NaN min_parallax_deg or threshold, chi2_max NULL.
+   CUBA_HIP_ERR_STATE before cuba_hip_set_graph and on a landmark-partitioned handle. */
+enum { CUBA_HIP_TRI_OK = 0, CUBA_HIP_TRI_NOT_SELECTED, CUBA_HIP_TRI_FIXED, CUBA_HIP_TRI_FEW_OBSERVATIONS,
+       CUBA_HIP_TRI_LOW_PARALLAX, CUBA_HIP_TRI_SINGULAR, CUBA_HIP_TRI_BEHIND_CAMERA, CUBA_HIP_TRI_CHI2, CUBA_HIP_TRI_STATUSES };
+int cuba_hip_triangulate_landmarks(cuba_hip_solver* s, const uint8_t* select, int refine_iterations, double min_parallax_deg,
+	const double chi2_max[2], int dry_run, int32_t* status, int64_t counts[CUBA_HIP_TRI_STATUSES], double* xyz);
+
 /* Replaces: CudaBlockSolver::getTimeProfile (:545-562). Seconds per bucket. */
 int cuba_hip_get_profile(cuba_hip_solver* s, double seconds[CUBA_HIP_PROFILE_ITEMS]);
 
