@@ -31,6 +31,8 @@ PROFILE_KEYS = (  # same strings as CudaBlockSolver::getTimeProfile (src/cuda_bu
     "4: Schur Complement", "5: Symbolic Decomposition", "6: Numerical Decomposition", "7: Update Solution")
 TRI_STATUS_NAMES = (  # CUBA_HIP_TRI_* of include/cuba_hip.h, in the order the statuses are decided
     "ok", "not_selected", "fixed", "few_observations", "low_parallax", "singular", "behind_camera", "chi2")
+POSEREF_STATUS_NAMES = (  # CUBA_HIP_POSEREF_* of include/cuba_hip.h
+    "ok", "not_selected", "fixed", "few_observations", "singular", "few_inliers")
 
 
 class CubaHipError(RuntimeError):
@@ -144,6 +146,7 @@ def load_library(precision="f64"):
         "cuba_hip_get_edge_active": [H, _u8p],
         "cuba_hip_landmark_active_edges": [H, _ip],
         "cuba_hip_triangulate_landmarks": [H, _u8p, C.c_int, C.c_double, _dp, C.c_int, _ip, C.POINTER(C.c_int64), _dp],
+        "cuba_hip_refine_poses": [H, _u8p, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _ip, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp, _u8p],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -647,6 +650,30 @@ class HipSolver:
                                                          float(min_parallax_deg), _d(thr), int(bool(dry_run)), status.ctypes.data_as(_ip), counts, _d(xyz)))
         out = {k: int(v) for k, v in zip(TRI_STATUS_NAMES, counts)}
         out["status"], out["xyz"] = status, xyz
+        return out
+
+    # ---- pose refinement with the landmarks held (cuba_hip_refine_poses) -----------------------------
+    def refine_poses(self, select=None, rounds=4, iterations=10, robust_rounds=2, chi2_max=(5.991, 7.815), min_inliers=10, dry_run=False):
+        """Refines the free poses on the device from their active reprojection edges with every landmark held: `rounds` outlier rounds of
+        `iterations` Levenberg-Marquardt trials each, all inside one launch, the robust kernels in the first robust_rounds rounds
+        (include/cuba_hip.h).  select: truthy[Pt] in the caller's pose order, None = all.  Returns "status" (int32[Pt], indices into
+        POSEREF_STATUS_NAMES), the six counts by name, "inliers" (int32[Pt]), "chi2" ([Pt]), "q" ([Pt, 4]) and "t" ([Pt, 3]) (the refined
+        pose of every "ok" pose, the unchanged one of every other) and "edge_inlier" (bool[E], the caller's edge order)."""
+        Pt, E = (self.fp.Pt, self.fp.E) if self.fp is not None else (0, 0)
+        sel = None
+        if select is not None:
+            sel = np.ascontiguousarray(np.asarray(select) != 0, dtype=np.uint8)
+            if sel.shape != (Pt,):
+                raise ValueError(f"select: expected {Pt} entries")
+        thr = np.ascontiguousarray(chi2_max, dtype=np.float64).reshape(2)
+        status, inliers = np.zeros(Pt, dtype=np.int32), np.zeros(Pt, dtype=np.int32)
+        chi2, q, t, edge = np.zeros(Pt), np.zeros((Pt, 4)), np.zeros((Pt, 3)), np.zeros(E, dtype=np.uint8)
+        counts = (C.c_int64 * len(POSEREF_STATUS_NAMES))()
+        self._ck(self.lib.cuba_hip_refine_poses(self.h, sel.ctypes.data_as(_u8p) if sel is not None else None, int(rounds), int(iterations),
+                                                int(robust_rounds), _d(thr), int(min_inliers), int(bool(dry_run)), status.ctypes.data_as(_ip), counts,
+                                                inliers.ctypes.data_as(_ip), _d(chi2), _d(q), _d(t), edge.ctypes.data_as(_u8p)))
+        out = {k: int(v) for k, v in zip(POSEREF_STATUS_NAMES, counts)}
+        out.update(status=status, inliers=inliers, chi2=chi2, q=q, t=t, edge_inlier=edge.astype(bool))
         return out
 
     def set_pose_priors(self, pose, q, t, info):

@@ -580,6 +580,34 @@ void launch_triangulate(const TriangulateArgs& a, const uint8_t* select, const i
 // parts[TRI_STATUSES * triangulate_collect_grid(Lt)]
 void launch_triangulate_collect(const TriangulateArgs& a, const int* newOfOld, int* statusOut, double* xyzOut, long long* parts, long long* counts, hipStream_t s);
 
+// ---- pose refinement with the landmarks held (ba_pose_refine.hip) ---------------------------------------------------------------------
+// the statuses (include/cuba_hip.h: CUBA_HIP_POSEREF_*)
+enum { POSEREF_OK = 0, POSEREF_NOT_SELECTED, POSEREF_FIXED, POSEREF_FEW_OBSERVATIONS, POSEREF_SINGULAR, POSEREF_FEW_INLIERS, POSEREF_STATUSES };
+constexpr int POSEREF_MAX_ROUNDS = 4, POSEREF_MAX_ITERATIONS = 32;
+struct PoseRefineArgs
+{
+	DeviceGraph g;                     // e_w: the LIVE information (a gated edge is out); rk: the handle's robust kernels
+	const int *pe_beg = nullptr, *pe_end = nullptr, *pe_edge = nullptr;      // the pose pass's edge list per free pose
+	int rounds = 0, iterations = 0;    // outlier rounds, LM trials per round (a fixed count)
+	int robust_rounds = 0;             // the rounds below this one use g.rk, the later ones the identity kernel
+	int min_inliers = 0;
+	double chi2_mono = 0, chi2_stereo = 0;
+	int dry_run = 0;                   // 1: g.q / g.t are left alone
+	int* status = nullptr;             // [Pt] internal pose order (between the launches also the internal "pending" mark)
+	int* inliers = nullptr;            // [Pt] internal order: edges in at the pose's last classification
+	double* chi2 = nullptr;            // [Pt] internal order: sum omega |r|^2 over the final inliers (0 without a final classification)
+	double* qt = nullptr;              // [7 Pt] internal order: q | t of an OK pose as the state holds it (others: not written)
+	uint8_t* cls = nullptr;            // [E] sorted edges: this call's classification
+};
+int pose_refine_collect_grid(int Pt);
+// status[] = NOT_SELECTED / FIXED / "pending" per pose (select[Pt], caller's numbering, or null: all; newOfOld[Pf]: the internal order of
+// the free poses or null), cls[] = "live information > 0"; then one wave per pending pose runs all its rounds and (no dry run) stores it
+void launch_pose_refine(const PoseRefineArgs& a, const uint8_t* select, const int* newOfOld, hipStream_t s);
+// into the caller's numbering: statusOut[Pt], inliersOut[Pt], chi2Out[Pt], qOut[4 Pt] / tOut[3 Pt] (qt of an OK pose, g.q / g.t of every
+// other), counts[POSEREF_STATUSES] through parts[POSEREF_STATUSES * pose_refine_collect_grid(Pt)]
+void launch_pose_refine_collect(const PoseRefineArgs& a, const int* newOfOld, int* statusOut, int* inliersOut, double* chi2Out, double* qOut, double* tOut,
+	long long* parts, long long* counts, hipStream_t s);
+
 // copies {fail, iters, done} into sys.host_flags (what the last node of an iteration graph does anyway)
 void launch_pcg_report(const DeviceSystem& sys, hipStream_t s);
 

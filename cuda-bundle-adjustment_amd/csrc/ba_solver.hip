@@ -367,6 +367,13 @@ int cuba_hip_triangulate_landmarks(cuba_hip_solver* s, const uint8_t* select, in
 	return guarded(s, [&] { s->triangulateLandmarks(select, refine_iterations, min_parallax_deg, chi2_max, dry_run != 0, status, counts, xyz); });
 }
 
+int cuba_hip_refine_poses(cuba_hip_solver* s, const uint8_t* select, int rounds, int iterations, int robust_rounds, const double chi2_max[2],
+	int min_inliers, int dry_run, int32_t* status, int64_t counts[CUBA_HIP_POSEREF_STATUSES], int32_t* inliers, double* chi2, double* q, double* t,
+	uint8_t* edge_inlier)
+{
+	return guarded(s, [&] { s->refinePoses(select, rounds, iterations, robust_rounds, chi2_max, min_inliers, dry_run != 0, status, counts, inliers, chi2, q, t, edge_inlier); });
+}
+
 int cuba_hip_get_profile(cuba_hip_solver* s, double seconds[CUBA_HIP_PROFILE_ITEMS])
 {
 	return guarded(s, [&] { for (int i = 0; i < CUBA_HIP_PROFILE_ITEMS; i++) seconds[i] = s->prof[i]; });

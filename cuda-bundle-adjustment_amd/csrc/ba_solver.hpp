@@ -691,6 +691,15 @@ struct cuba_hip_solver
 	void triangulateLandmarks(const uint8_t* select, int refineIterations, double minParallaxDeg, const double chi2Max[2], bool dryRun,
 		int32_t* status, int64_t* counts, double* xyz);
 
+	// Pose refinement with the landmarks held (ba_pose_refine.hip): free poses from their active reprojection edges and the current landmarks.
+	// Its buffers exist from the first call on; a handle that never calls it allocates and launches nothing of this.
+	DevBuf<int> d_prInt;                 // [4 Pt] status | inliers in the internal order, then in the caller's
+	DevBuf<double> d_prReal;             // [16 Pt] chi2 | q t in the internal order, then chi2 | q | t in the caller's
+	DevBuf<uint8_t> d_prCls, d_prSelect; // [2 E] the call's classification per sorted edge | per caller's edge
+	DevBuf<long long> d_prCounts;
+	void refinePoses(const uint8_t* select, int rounds, int iterations, int robustRounds, const double chi2Max[2], int minInliers, bool dryRun,
+		int32_t* status, int64_t* counts, int32_t* inliers, double* chi2, double* q, double* t, uint8_t* edgeInlier);
+
 	// The factors besides the reprojection edges (ba_factor.hip): seven kinds, each a set kept as the caller gave it, in the caller's numbering
 	// (quaternions normalised, information symmetrised), with a device copy (pf) in the internal order that need() makes -- uploadFactors():
 	// once that order is known, again when it changes (the unary kinds on the poses: with the pose order; the two binary kinds, whose

@@ -620,6 +620,53 @@ public:
 		const auto it = triIndex_.find(v);
 		return it == triIndex_.end() ? TriangulationStatus::NOT_SELECTED : static_cast<TriangulationStatus>(it->second);
 	}
+	// ---- pose refinement with the landmarks held (extension: cuba::refinePoses) ---------------------------
+	// One call behind the ABI.  The refined poses go into the vertex objects (and the staging arrays of the next upload): the next
+	// initialize() reads the estimates from there, and the handle already holds them.
+	PoseRefinementResult refinePoses(const PoseRefinementOptions& o, const std::vector<PoseVertex*>* subset)
+	{
+		if (o.rounds < 1 || o.rounds > 4 || o.iterations < 1 || o.iterations > 32 || o.robustRounds < 0 || o.robustRounds > o.rounds || o.minInliers < 0 ||
+			std::isnan(o.chi2Mono) || std::isnan(o.chi2Stereo))
+			throw std::invalid_argument("cuba::refinePoses: rounds 1 ... 4, iterations 1 ... 32, robustRounds 0 ... rounds, minInliers >= 0, thresholds not NaN");
+		prepareOptimize();            // (the graph and the levels set by hand go up first)
+		const size_t nP = activePoses_.size();
+		std::vector<uint8_t> select;
+		if (subset)
+		{
+			select.assign(nP, 0);
+			for (const PoseVertex* v : *subset)
+				if (v && v->iP >= 0 && static_cast<size_t>(v->iP) < nP && activePoses_[v->iP] == v) select[v->iP] = 1;
+		}
+		const double thr[2] = { o.chi2Mono, o.chi2Stereo };
+		int64_t c[CUBA_HIP_POSEREF_STATUSES] = { 0, 0, 0, 0, 0, 0 };
+		refStatus_.assign(nP, CUBA_HIP_POSEREF_NOT_SELECTED);
+		std::vector<double> q(4 * nP), t(3 * nP);
+		check(cuba_hip_refine_poses(solver_, subset ? select.data() : nullptr, o.rounds, o.iterations, o.robustRounds, thr, o.minInliers, o.dryRun ? 1 : 0,
+			refStatus_.data(), c, nullptr, nullptr, q.data(), t.data(), nullptr), "cuba_hip_refine_poses");
+		refPoses_ = activePoses_; refIndex_.clear();          // (the vertex -> row index is built by the first poseRefinementStatus)
+		if (!o.dryRun)
+			for (size_t i = 0; i < nP; i++)
+				if (refStatus_[i] == CUBA_HIP_POSEREF_OK)
+				{
+					double* qc = activePoses_[i]->q.coeffs().data();
+					for (int k = 0; k < 4; k++) qc[k] = q_[4 * i + k] = q[4 * i + k];
+					for (int k = 0; k < 3; k++) activePoses_[i]->t.data()[k] = t_[3 * i + k] = t[3 * i + k];
+				}
+		PoseRefinementResult r;
+		for (int k = 0; k < CUBA_HIP_POSEREF_STATUSES; k++) r.counts[k] = c[k];
+		return r;
+	}
+	size_t refinementRow(const PoseVertex* v) const
+	{
+		if (refIndex_.empty()) for (size_t i = 0; i < refPoses_.size(); i++) refIndex_[refPoses_[i]] = i;
+		const auto it = refIndex_.find(v);
+		return it == refIndex_.end() ? refPoses_.size() : it->second;
+	}
+	PoseRefinementStatus poseRefinementStatus(const PoseVertex* v) const
+	{
+		const size_t i = refinementRow(v);
+		return i == refPoses_.size() ? PoseRefinementStatus::NOT_SELECTED : static_cast<PoseRefinementStatus>(refStatus_[i]);
+	}
 	int activeObservations(const LandmarkVertex* v) const
 	{
 		int n = 0;
@@ -834,6 +881,7 @@ public:
 		forEachKind([](auto& list) { list.items.clear(); list.chi.clear(); });
 		inactiveEdges_.clear(); maskDirty_ = true; gateChi_.clear(); gateChiEdges_.clear(); gateChiIndex_.clear();
 		triStatus_.clear(); triLandmarks_.clear(); triIndex_.clear();
+		refStatus_.clear(); refPoses_.clear(); refIndex_.clear();
 		posesDirty_ = landmarksDirty_ = edgesDirty_ = true;
 		initialized_ = false;
 	}
@@ -997,6 +1045,9 @@ private:
 	std::vector<int32_t> triStatus_;                         // statuses of the last triangulateLandmarks, over triLandmarks_
 	std::vector<LandmarkVertex*> triLandmarks_;
 	mutable std::unordered_map<const LandmarkVertex*, int32_t> triIndex_;
+	std::vector<int32_t> refStatus_;                         // statuses of the last refinePoses, over refPoses_
+	std::vector<PoseVertex*> refPoses_;
+	mutable std::unordered_map<const PoseVertex*, size_t> refIndex_;
 };
 
 }  // namespace
@@ -1129,6 +1180,19 @@ TriangulationStatus triangulationStatus(const CudaBundleAdjustment* object, cons
 {
 	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
 	return impl ? impl->triangulationStatus(v) : TriangulationStatus::NOT_SELECTED;
+}
+
+// Extension (g2o's motion-only bundle adjustment / ORB-SLAM's PoseOptimization; the reference has none): poses from their edges and the landmarks.
+PoseRefinementResult refinePoses(CudaBundleAdjustment* object, const PoseRefinementOptions& options, const std::vector<PoseVertex*>* subset)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (!impl) throw std::runtime_error("cuba::refinePoses: not an object of this library");
+	return impl->refinePoses(options, subset);
+}
+PoseRefinementStatus poseRefinementStatus(const CudaBundleAdjustment* object, const PoseVertex* v)
+{
+	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
+	return impl ? impl->poseRefinementStatus(v) : PoseRefinementStatus::NOT_SELECTED;
 }
 
 void addPosePrior(CudaBundleAdjustment* object, PosePrior* prior) { addFactor(object, prior); }

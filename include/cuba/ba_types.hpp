@@ -156,6 +156,26 @@ struct TriangulationResult
 	long long count(TriangulationStatus s) const { return counts[static_cast<int>(s)]; }
 };
 
+// ---- pose refinement with the landmarks held (extension: cuba::refinePoses, bundle_adjustment.hpp; the reference has no counterpart) ----
+struct PoseRefinementOptions
+{
+	int rounds = 4;                                // outlier rounds (1 ... 4): the edges are classified again at the start of each and once more at the end
+	int iterations = 10;                           // Levenberg-Marquardt trials per round (1 ... 32), a fixed count
+	int robustRounds = 2;                          // the rounds below this one use the robust kernels, the later ones none (0 ... rounds)
+	double chi2Mono = 5.991, chi2Stereo = 7.815;   // from round 1 on an edge is in only at or below this (infinity: no chi2 test)
+	int minInliers = 10;                           // a pose left with fewer edges (and always: fewer than 3) is FEW_INLIERS and keeps its value
+	bool dryRun = false;                           // only the statuses and counts: no pose changes
+};
+
+// the statuses (CUBA_HIP_POSEREF_* of cuba_hip.h)
+enum class PoseRefinementStatus { OK = 0, NOT_SELECTED, FIXED, FEW_OBSERVATIONS, SINGULAR, FEW_INLIERS };
+
+struct PoseRefinementResult
+{
+	long long counts[6] = { 0, 0, 0, 0, 0, 0 };      // poses per PoseRefinementStatus
+	long long count(PoseRefinementStatus s) const { return counts[static_cast<int>(s)]; }
+};
+
 // short names used inside the reference's sources (types.h:242-245)
 using VertexP = PoseVertex;
 using VertexL = LandmarkVertex;

@@ -141,6 +141,18 @@ int activeObservations(const CudaBundleAdjustment* object, const LandmarkVertex*
 TriangulationResult triangulateLandmarks(CudaBundleAdjustment* object, const TriangulationOptions& options, const std::vector<LandmarkVertex*>* subset = nullptr);
 TriangulationStatus triangulationStatus(const CudaBundleAdjustment* object, const LandmarkVertex* v);
 
+// Extension (g2o's motion-only bundle adjustment with EdgeSE3ProjectXYZOnlyPose, ORB-SLAM's Optimizer::PoseOptimization; the reference has
+// no counterpart; include/cuba_hip.h, cuba_hip_refine_poses): the free poses of the initialize()d graph -- or those of `subset` -- are
+// refined on the device from their switched-on reprojection edges with EVERY landmark held at its current estimate: `rounds` outlier
+// rounds of `iterations` Levenberg-Marquardt trials, each pose with a damping of its own, the robust kernels in force in the first
+// robustRounds rounds (PoseRefinementOptions, ba_types.hpp).  Unless dryRun is set, the refined poses are written into the PoseVertex::q / t
+// of the OK poses (and are what the next optimize() starts from); every other vertex keeps its value.  Pose priors, relative-pose edges,
+// position, direction and range factors take no part; the edge levels (setEdgeActive) are read, never written.
+//   poseRefinementStatus    a pose's status at the last refinePoses (NOT_SELECTED before one and for a vertex it did not cover)
+// New keyframes from a motion-model guess:  ba->initialize(); cuba::refinePoses(ba.get(), {}, &newKeyframes); ba->optimize(10);
+PoseRefinementResult refinePoses(CudaBundleAdjustment* object, const PoseRefinementOptions& options, const std::vector<PoseVertex*>* subset = nullptr);
+PoseRefinementStatus poseRefinementStatus(const CudaBundleAdjustment* object, const PoseVertex* v);
+
 // Robust kernel of a pose factor (PosePrior, RelativePoseEdge; include/cuba_hip.h, cuba_hip_set_pose_factor_robust_kernels): with
 // e = r^T Omega r the objective term becomes rho(e) and the linearisation takes rho'(e) Omega for Omega.  HUBER and TUKEY are the kernels of
 // the reprojection edges; CAUCHY, rho = delta^2 log1p(e / delta^2), exists for the pose factors only -- the usual choice on loop closures,

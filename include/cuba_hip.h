@@ -365,6 +365,58 @@ enum { CUBA_HIP_TRI_OK = 0, CUBA_HIP_TRI_NOT_SELECTED, CUBA_HIP_TRI_FIXED, CUBA_
 int cuba_hip_triangulate_landmarks(cuba_hip_solver* s, const uint8_t* select, int refine_iterations, double min_parallax_deg,
 	const double chi2_max[2], int dry_run, int32_t* status, int64_t counts[CUBA_HIP_TRI_STATUSES], double* xyz);
 
+/* ---- pose refinement with the landmarks held -------------------------------------------------------- */
+
+/* Replaces: nothing of the reference -- g2o's motion-only bundle adjustment with EdgeSE3ProjectXYZOnlyPose, ORB-SLAM's
+   Optimizer::PoseOptimization, the PnP refinement of a relocalisation candidate: the value a POSE gets from the current landmarks (poses
+   behind a loop closure or a map merge, new keyframes whose start is a motion-model guess, the poses of a window whose points were just
+   re-triangulated) -- the mirror image of cuba_hip_triangulate_landmarks and the flow "pose optimisation (four rounds, edges come back
+   when they recover)" of the gating section above.  Free and fixed landmarks are both HELD at their current estimate, so every free pose
+   is a 6-parameter problem of its own: all its Levenberg-Marquardt trials and all its outlier rounds run inside one launch, each pose
+   with a damping of its own, all arithmetic in double in both libraries.
+   The only terms are the pose's reprojection edges of live information omega > 0 (a gated edge is out).  Pose priors, relative-pose
+   edges, position, direction and range factors take NO part (as landmark priors take none in triangulation).
+   Classification, at the start of round k = 0 ... rounds - 1 and once more behind the last round, at the pose's then-current value:
+     round 0       an edge is in iff omega > 0 and its point's depth in the camera is > 0
+     later, final  it must also satisfy omega |r|^2 <= chi2_max[stereo] (chi2_max = {monocular, stereo}; +inf: no chi2 test; a NaN fails)
+   An edge that was out can come back (ORB-SLAM's rule).  The classification lives in a scratch byte per edge owned by this call: the
+   handle's gate is neither read for it (beyond omega > 0) nor written -- pass edge_inlier to cuba_hip_set_edge_active for that.
+   One round: lambda = 1e-5 max_k H_kk at the round's first linearisation, nu = 2, then `iterations` TRIALS, a fixed count without an
+   early exit.  A trial:
+     1. H = sum w' J^T J, b = sum w' J^T r, F = sum rho(omega |r|^2) over the round's edges; r = proj - meas, J the 2 x 6 or 3 x 6
+        Jacobian -d r / d [omega; upsilon] for the left-multiplicative update T <- exp([omega; upsilon]) T (the convention of the pose
+        update everywhere in this library), w' = omega rho'(omega |r|^2), rho the handle's robust kernels (cuba_hip_set_robust_kernel) in
+        the rounds below robust_rounds and the identity kernel in the later ones (ORB-SLAM drops Huber after two rounds)
+     2. (H + lambda I) d = b by a 6 x 6 LDL^T; a non-positive pivot or a non-finite number: SINGULAR
+     3. T' = exp(d) T; the trial is rejected if an edge of the round has depth <= 0 at T' or F' is not finite
+     4. otherwise gain = (F - F') / (d^T (lambda d + b)); gain > 0: accept, lambda <- lambda max(1/3, 1 - (2 gain - 1)^3), nu = 2;
+        else (also for a NaN gain and a denominator of exactly 0) lambda <- lambda nu, nu <- 2 nu
+   Per pose, the first rule that applies:
+     NOT_SELECTED       select given and select[p] == 0
+     FIXED              a fixed pose
+     FEW_OBSERVATIONS   fewer than 3 edges in at round 0
+     SINGULAR           step 2 of a trial
+     FEW_INLIERS        fewer than max(3, min_inliers) edges in at a later round's start or at the final classification
+     OK                 the pose is replaced (dry_run != 0: nothing is written)
+   rounds 1 ... 4, iterations 1 ... 32, robust_rounds 0 ... rounds, min_inliers >= 0.
+   select[Pt], status[Pt], inliers[Pt], chi2[Pt], q[4 Pt] (x, y, z, w), t[3 Pt]: the caller's pose numbering; edge_inlier[E]: the
+   caller's edge order.  Every array argument but chi2_max is optional (NULL).
+     q, t           the refined pose of every OK pose as the estimate holds it (also in a dry run), the unchanged current pose of every other
+     inliers[p]     the edges in at the pose's last classification: the final one for OK poses (and FEW_INLIERS decided there); 0 for a
+                    pose that is not selected or fixed
+     chi2[p]        sum omega |r|^2 (without the robust kernel) over the final inliers; 0 for a pose that did not reach the final classification
+     edge_inlier[e] the final classification for the edges of poses that reached it; for every other edge whether its live omega > 0
+     counts[CUBA_HIP_POSEREF_STATUSES]   poses per status; they sum to Pt
+   Landmarks, unselected, fixed and rejected poses, the gate, the snapshot slots, the handle's LM state and the counters stay as they
+   are; a covariance computed before is dropped when a pose changed.  A handle that never calls this allocates and launches nothing for it.
+   CUBA_HIP_ERR_INVALID_ARGUMENT: a count outside its range, a NaN threshold, chi2_max NULL.
+   CUBA_HIP_ERR_STATE before cuba_hip_set_graph and on a landmark-partitioned handle. */
+enum { CUBA_HIP_POSEREF_OK = 0, CUBA_HIP_POSEREF_NOT_SELECTED, CUBA_HIP_POSEREF_FIXED, CUBA_HIP_POSEREF_FEW_OBSERVATIONS,
+       CUBA_HIP_POSEREF_SINGULAR, CUBA_HIP_POSEREF_FEW_INLIERS, CUBA_HIP_POSEREF_STATUSES };
+int cuba_hip_refine_poses(cuba_hip_solver* s, const uint8_t* select, int rounds, int iterations, int robust_rounds, const double chi2_max[2],
+	int min_inliers, int dry_run, int32_t* status, int64_t counts[CUBA_HIP_POSEREF_STATUSES], int32_t* inliers, double* chi2, double* q, double* t,
+	uint8_t* edge_inlier);
+
 /* Replaces: CudaBlockSolver::getTimeProfile (:545-562). Seconds per bucket. */
 int cuba_hip_get_profile(cuba_hip_solver* s, double seconds[CUBA_HIP_PROFILE_ITEMS]);
 
