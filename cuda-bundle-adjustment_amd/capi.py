@@ -33,6 +33,8 @@ TRI_STATUS_NAMES = (  # CUBA_HIP_TRI_* of include/cuba_hip.h, in the order the s
     "ok", "not_selected", "fixed", "few_observations", "low_parallax", "singular", "behind_camera", "chi2")
 POSEREF_STATUS_NAMES = (  # CUBA_HIP_POSEREF_* of include/cuba_hip.h
     "ok", "not_selected", "fixed", "few_observations", "singular", "few_inliers")
+POSELOC_STATUS_NAMES = (  # CUBA_HIP_POSELOC_* of include/cuba_hip.h
+    "ok", "not_selected", "fixed", "few_observations", "no_solution", "few_inliers")
 
 
 class CubaHipError(RuntimeError):
@@ -147,6 +149,7 @@ def load_library(precision="f64"):
         "cuba_hip_landmark_active_edges": [H, _ip],
         "cuba_hip_triangulate_landmarks": [H, _u8p, C.c_int, C.c_double, _dp, C.c_int, _ip, C.POINTER(C.c_int64), _dp],
         "cuba_hip_refine_poses": [H, _u8p, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _ip, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp, _u8p],
+        "cuba_hip_localize_poses": [H, _u8p, C.c_int, C.c_uint64, _dp, C.c_int, C.c_int, _ip, C.POINTER(C.c_int64), _ip, _dp, _ip, _dp, _dp, _u8p],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -674,6 +677,32 @@ class HipSolver:
                                                 inliers.ctypes.data_as(_ip), _d(chi2), _d(q), _d(t), edge.ctypes.data_as(_u8p)))
         out = {k: int(v) for k, v in zip(POSEREF_STATUS_NAMES, counts)}
         out.update(status=status, inliers=inliers, chi2=chi2, q=q, t=t, edge_inlier=edge.astype(bool))
+        return out
+
+    # ---- pose localisation from scratch (cuba_hip_localize_poses) -------------------------------------------
+    def localize_poses(self, select=None, hypotheses=256, seed=0, chi2_max=(5.991, 7.815), min_inliers=10, dry_run=False):
+        """Gives the free poses a value on the device from their active reprojection edges and the current landmarks alone, by a
+        deterministic RANSAC of `hypotheses` three-point (P3P) samples per pose scored by MSAC; a pose's current value is never read (it may
+        be NaN) (include/cuba_hip.h).  select: truthy[Pt] in the caller's pose order, None = all.  Returns "status" (int32[Pt], indices into
+        POSELOC_STATUS_NAMES), the six counts by name, "inliers" (int32[Pt]), "cost" ([Pt], the winner's score), "winner" (int32[Pt],
+        4 h + root, -1 for a pose that is not ok), "q" ([Pt, 4]) and "t" ([Pt, 3]) (the new pose of every "ok" pose, the unchanged one of
+        every other) and "edge_inlier" (bool[E], the caller's edge order)."""
+        Pt, E = (self.fp.Pt, self.fp.E) if self.fp is not None else (0, 0)
+        sel = None
+        if select is not None:
+            sel = np.ascontiguousarray(np.asarray(select) != 0, dtype=np.uint8)
+            if sel.shape != (Pt,):
+                raise ValueError(f"select: expected {Pt} entries")
+        thr = np.ascontiguousarray(chi2_max, dtype=np.float64).reshape(2)
+        status, inliers, winner = np.zeros(Pt, dtype=np.int32), np.zeros(Pt, dtype=np.int32), np.zeros(Pt, dtype=np.int32)
+        cost, q, t, edge = np.zeros(Pt), np.zeros((Pt, 4)), np.zeros((Pt, 3)), np.zeros(E, dtype=np.uint8)
+        counts = (C.c_int64 * len(POSELOC_STATUS_NAMES))()
+        self._ck(self.lib.cuba_hip_localize_poses(self.h, sel.ctypes.data_as(_u8p) if sel is not None else None, int(hypotheses),
+                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, _d(thr), int(min_inliers), int(bool(dry_run)),
+                                                  status.ctypes.data_as(_ip), counts, inliers.ctypes.data_as(_ip), _d(cost),
+                                                  winner.ctypes.data_as(_ip), _d(q), _d(t), edge.ctypes.data_as(_u8p)))
+        out = {k: int(v) for k, v in zip(POSELOC_STATUS_NAMES, counts)}
+        out.update(status=status, inliers=inliers, cost=cost, winner=winner, q=q, t=t, edge_inlier=edge.astype(bool))
         return out
 
     def set_pose_priors(self, pose, q, t, info):

@@ -608,6 +608,37 @@ void launch_pose_refine(const PoseRefineArgs& a, const uint8_t* select, const in
 void launch_pose_refine_collect(const PoseRefineArgs& a, const int* newOfOld, int* statusOut, int* inliersOut, double* chi2Out, double* qOut, double* tOut,
 	long long* parts, long long* counts, hipStream_t s);
 
+// ---- pose localisation from scratch: P3P RANSAC per pose (ba_localize.hip) -------------------------------------------------------------
+// the statuses (include/cuba_hip.h: CUBA_HIP_POSELOC_*)
+enum { POSELOC_OK = 0, POSELOC_NOT_SELECTED, POSELOC_FIXED, POSELOC_FEW_OBSERVATIONS, POSELOC_NO_SOLUTION, POSELOC_FEW_INLIERS, POSELOC_STATUSES };
+constexpr int POSELOC_MAX_HYPOTHESES = 4096;
+struct PoseLocalizeArgs
+{
+	DeviceGraph g;                     // e_w: the LIVE information (a gated edge is out); g.q / g.t are written, never read
+	const int *pe_beg = nullptr, *pe_end = nullptr, *pe_edge = nullptr;      // the pose pass's edge list per free pose
+	const uint32_t* perm = nullptr;    // [E] the caller's index of a sorted edge
+	int hypotheses = 0;                // a fixed count
+	unsigned long long seed = 0;
+	int min_inliers = 0;
+	double chi2_mono = 0, chi2_stereo = 0;
+	int dry_run = 0;                   // 1: g.q / g.t are left alone
+	int* status = nullptr;             // [Pt] internal pose order (between the launches also the internal "pending" mark)
+	int* inliers = nullptr;            // [Pt] internal order
+	int* winner = nullptr;             // [Pt] internal order: 4 h + root of an OK pose, -1 of every other
+	unsigned long long* key = nullptr; // [Pt] internal order: the pose's seed word, hashed from (seed, the CALLER's pose index)
+	double* cost = nullptr;            // [Pt] internal order: the winner's MSAC score (0 without a winner)
+	double* qt = nullptr;              // [7 Pt] internal order: q | t of an OK pose as the state holds it (others: not written)
+	uint8_t* cls = nullptr;            // [E] sorted edges: this call's classification
+};
+int pose_localize_collect_grid(int Pt);
+// status[] = NOT_SELECTED / FIXED / "pending" and the seed word per pose (select[Pt], caller's numbering, or null: all; newOfOld[Pf]: the
+// internal order of the free poses or null), cls[] = "live information > 0"; then one workgroup per pending pose, thread = hypothesis
+void launch_pose_localize(const PoseLocalizeArgs& a, const uint8_t* select, const int* newOfOld, hipStream_t s);
+// into the caller's numbering: statusOut[Pt], inliersOut[Pt], winnerOut[Pt], costOut[Pt], qOut[4 Pt] / tOut[3 Pt] (qt of an OK pose,
+// g.q / g.t of every other), counts[POSELOC_STATUSES] through parts[POSELOC_STATUSES * pose_localize_collect_grid(Pt)]
+void launch_pose_localize_collect(const PoseLocalizeArgs& a, const int* newOfOld, int* statusOut, int* inliersOut, int* winnerOut, double* costOut,
+	double* qOut, double* tOut, long long* parts, long long* counts, hipStream_t s);
+
 // copies {fail, iters, done} into sys.host_flags (what the last node of an iteration graph does anyway)
 void launch_pcg_report(const DeviceSystem& sys, hipStream_t s);
 

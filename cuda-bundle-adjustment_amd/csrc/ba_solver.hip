@@ -374,6 +374,13 @@ int cuba_hip_refine_poses(cuba_hip_solver* s, const uint8_t* select, int rounds,
 	return guarded(s, [&] { s->refinePoses(select, rounds, iterations, robust_rounds, chi2_max, min_inliers, dry_run != 0, status, counts, inliers, chi2, q, t, edge_inlier); });
 }
 
+int cuba_hip_localize_poses(cuba_hip_solver* s, const uint8_t* select, int hypotheses, uint64_t seed, const double chi2_max[2], int min_inliers,
+	int dry_run, int32_t* status, int64_t counts[CUBA_HIP_POSELOC_STATUSES], int32_t* inliers, double* cost, int32_t* winner, double* q, double* t,
+	uint8_t* edge_inlier)
+{
+	return guarded(s, [&] { s->localizePoses(select, hypotheses, seed, chi2_max, min_inliers, dry_run != 0, status, counts, inliers, cost, winner, q, t, edge_inlier); });
+}
+
 int cuba_hip_get_profile(cuba_hip_solver* s, double seconds[CUBA_HIP_PROFILE_ITEMS])
 {
 	return guarded(s, [&] { for (int i = 0; i < CUBA_HIP_PROFILE_ITEMS; i++) seconds[i] = s->prof[i]; });

@@ -700,6 +700,17 @@ struct cuba_hip_solver
 	void refinePoses(const uint8_t* select, int rounds, int iterations, int robustRounds, const double chi2Max[2], int minInliers, bool dryRun,
 		int32_t* status, int64_t* counts, int32_t* inliers, double* chi2, double* q, double* t, uint8_t* edgeInlier);
 
+	// Pose localisation from scratch (ba_localize.hip): free poses from their active reprojection edges and the current landmarks by a P3P
+	// RANSAC; the pose's current value is never read.  Its buffers exist from the first call on; a handle that never calls it allocates and
+	// launches nothing of this.
+	DevBuf<int> d_plInt;                 // [6 Pt] status | inliers | winner in the internal order, then in the caller's
+	DevBuf<double> d_plReal;             // [16 Pt] cost | q t in the internal order, then cost | q | t in the caller's
+	DevBuf<unsigned long long> d_plKey;  // [Pt] the poses' seed words
+	DevBuf<uint8_t> d_plCls, d_plSelect; // [2 E] the call's classification per sorted edge | per caller's edge
+	DevBuf<long long> d_plCounts;
+	void localizePoses(const uint8_t* select, int hypotheses, uint64_t seed, const double chi2Max[2], int minInliers, bool dryRun,
+		int32_t* status, int64_t* counts, int32_t* inliers, double* cost, int32_t* winner, double* q, double* t, uint8_t* edgeInlier);
+
 	// The factors besides the reprojection edges (ba_factor.hip): seven kinds, each a set kept as the caller gave it, in the caller's numbering
 	// (quaternions normalised, information symmetrised), with a device copy (pf) in the internal order that need() makes -- uploadFactors():
 	// once that order is known, again when it changes (the unary kinds on the poses: with the pose order; the two binary kinds, whose

@@ -667,6 +667,47 @@ public:
 		const size_t i = refinementRow(v);
 		return i == refPoses_.size() ? PoseRefinementStatus::NOT_SELECTED : static_cast<PoseRefinementStatus>(refStatus_[i]);
 	}
+	// ---- pose localisation from scratch (extension: cuba::localizePoses) -----------------------------------
+	// One call behind the ABI.  The winners go into the vertex objects (and the staging arrays of the next upload), as refinePoses' do.
+	PoseLocalizationResult localizePoses(const PoseLocalizationOptions& o, const std::vector<PoseVertex*>* subset)
+	{
+		if (o.hypotheses < 1 || o.hypotheses > 4096 || o.minInliers < 0 || !std::isfinite(o.chi2Mono) || !std::isfinite(o.chi2Stereo) ||
+			!(o.chi2Mono > 0) || !(o.chi2Stereo > 0))
+			throw std::invalid_argument("cuba::localizePoses: hypotheses 1 ... 4096, minInliers >= 0, thresholds finite and positive");
+		prepareOptimize();            // (the graph and the levels set by hand go up first)
+		const size_t nP = activePoses_.size();
+		std::vector<uint8_t> select;
+		if (subset)
+		{
+			select.assign(nP, 0);
+			for (const PoseVertex* v : *subset)
+				if (v && v->iP >= 0 && static_cast<size_t>(v->iP) < nP && activePoses_[v->iP] == v) select[v->iP] = 1;
+		}
+		const double thr[2] = { o.chi2Mono, o.chi2Stereo };
+		int64_t c[CUBA_HIP_POSELOC_STATUSES] = { 0, 0, 0, 0, 0, 0 };
+		locStatus_.assign(nP, CUBA_HIP_POSELOC_NOT_SELECTED);
+		std::vector<double> q(4 * nP), t(3 * nP);
+		check(cuba_hip_localize_poses(solver_, subset ? select.data() : nullptr, o.hypotheses, static_cast<uint64_t>(o.seed), thr, o.minInliers, o.dryRun ? 1 : 0,
+			locStatus_.data(), c, nullptr, nullptr, nullptr, q.data(), t.data(), nullptr), "cuba_hip_localize_poses");
+		locPoses_ = activePoses_; locIndex_.clear();          // (the vertex -> row index is built by the first poseLocalizationStatus)
+		if (!o.dryRun)
+			for (size_t i = 0; i < nP; i++)
+				if (locStatus_[i] == CUBA_HIP_POSELOC_OK)
+				{
+					double* qc = activePoses_[i]->q.coeffs().data();
+					for (int k = 0; k < 4; k++) qc[k] = q_[4 * i + k] = q[4 * i + k];
+					for (int k = 0; k < 3; k++) activePoses_[i]->t.data()[k] = t_[3 * i + k] = t[3 * i + k];
+				}
+		PoseLocalizationResult r;
+		for (int k = 0; k < CUBA_HIP_POSELOC_STATUSES; k++) r.counts[k] = c[k];
+		return r;
+	}
+	PoseLocalizationStatus poseLocalizationStatus(const PoseVertex* v) const
+	{
+		if (locIndex_.empty()) for (size_t i = 0; i < locPoses_.size(); i++) locIndex_[locPoses_[i]] = i;
+		const auto it = locIndex_.find(v);
+		return it == locIndex_.end() ? PoseLocalizationStatus::NOT_SELECTED : static_cast<PoseLocalizationStatus>(locStatus_[it->second]);
+	}
 	int activeObservations(const LandmarkVertex* v) const
 	{
 		int n = 0;
@@ -882,6 +923,7 @@ public:
 		inactiveEdges_.clear(); maskDirty_ = true; gateChi_.clear(); gateChiEdges_.clear(); gateChiIndex_.clear();
 		triStatus_.clear(); triLandmarks_.clear(); triIndex_.clear();
 		refStatus_.clear(); refPoses_.clear(); refIndex_.clear();
+		locStatus_.clear(); locPoses_.clear(); locIndex_.clear();
 		posesDirty_ = landmarksDirty_ = edgesDirty_ = true;
 		initialized_ = false;
 	}
@@ -1048,6 +1090,9 @@ private:
 	std::vector<int32_t> refStatus_;                         // statuses of the last refinePoses, over refPoses_
 	std::vector<PoseVertex*> refPoses_;
 	mutable std::unordered_map<const PoseVertex*, size_t> refIndex_;
+	std::vector<int32_t> locStatus_;                         // statuses of the last localizePoses, over locPoses_
+	std::vector<PoseVertex*> locPoses_;
+	mutable std::unordered_map<const PoseVertex*, size_t> locIndex_;
 };
 
 }  // namespace
@@ -1193,6 +1238,19 @@ PoseRefinementStatus poseRefinementStatus(const CudaBundleAdjustment* object, co
 {
 	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
 	return impl ? impl->poseRefinementStatus(v) : PoseRefinementStatus::NOT_SELECTED;
+}
+
+// Extension (the PnP-RANSAC half of ORB-SLAM's relocalisation; the reference has none): poses from their edges and the landmarks alone.
+PoseLocalizationResult localizePoses(CudaBundleAdjustment* object, const PoseLocalizationOptions& options, const std::vector<PoseVertex*>* subset)
+{
+	auto* impl = dynamic_cast<HipBundleAdjustment*>(object);
+	if (!impl) throw std::runtime_error("cuba::localizePoses: not an object of this library");
+	return impl->localizePoses(options, subset);
+}
+PoseLocalizationStatus poseLocalizationStatus(const CudaBundleAdjustment* object, const PoseVertex* v)
+{
+	const auto* impl = dynamic_cast<const HipBundleAdjustment*>(object);
+	return impl ? impl->poseLocalizationStatus(v) : PoseLocalizationStatus::NOT_SELECTED;
 }
 
 void addPosePrior(CudaBundleAdjustment* object, PosePrior* prior) { addFactor(object, prior); }

@@ -176,6 +176,25 @@ struct PoseRefinementResult
 	long long count(PoseRefinementStatus s) const { return counts[static_cast<int>(s)]; }
 };
 
+// ---- pose localisation from scratch (extension: cuba::localizePoses, bundle_adjustment.hpp; the reference has no counterpart) ----
+struct PoseLocalizationOptions
+{
+	int hypotheses = 256;                          // three-point samples per pose (1 ... 4096), a fixed count
+	unsigned long long seed = 0;                   // the samples are a function of (seed, pose, hypothesis, edge) in the graph's own numbering
+	double chi2Mono = 5.991, chi2Stereo = 7.815;   // the cap of an edge's term in the score and the inlier threshold (finite, > 0)
+	int minInliers = 10;                           // a pose whose winner has fewer inliers (and always: fewer than 4) is FEW_INLIERS and keeps its value
+	bool dryRun = false;                           // only the statuses and counts: no pose changes
+};
+
+// the statuses (CUBA_HIP_POSELOC_* of cuba_hip.h)
+enum class PoseLocalizationStatus { OK = 0, NOT_SELECTED, FIXED, FEW_OBSERVATIONS, NO_SOLUTION, FEW_INLIERS };
+
+struct PoseLocalizationResult
+{
+	long long counts[6] = { 0, 0, 0, 0, 0, 0 };      // poses per PoseLocalizationStatus
+	long long count(PoseLocalizationStatus s) const { return counts[static_cast<int>(s)]; }
+};
+
 // short names used inside the reference's sources (types.h:242-245)
 using VertexP = PoseVertex;
 using VertexL = LandmarkVertex;

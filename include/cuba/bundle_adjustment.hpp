@@ -153,6 +153,18 @@ TriangulationStatus triangulationStatus(const CudaBundleAdjustment* object, cons
 PoseRefinementResult refinePoses(CudaBundleAdjustment* object, const PoseRefinementOptions& options, const std::vector<PoseVertex*>* subset = nullptr);
 PoseRefinementStatus poseRefinementStatus(const CudaBundleAdjustment* object, const PoseVertex* v);
 
+// Extension (the PnP-RANSAC half of ORB-SLAM's Tracking::Relocalization; the reference has no counterpart; include/cuba_hip.h,
+// cuba_hip_localize_poses): the free poses of the initialize()d graph -- or those of `subset` -- get a value on the device from their
+// switched-on reprojection edges and the current landmarks ALONE, by a deterministic RANSAC of `hypotheses` three-point (P3P) samples per
+// pose scored by MSAC (PoseLocalizationOptions, ba_types.hpp).  A vertex's q / t before the call is never read: it may be anything, NaN
+// included.  Unless dryRun is set, the winners are written into the PoseVertex::q / t of the OK poses (and are what the next refinePoses or
+// optimize() starts from); every other vertex keeps its value.  Pose factors, landmark priors and robust kernels take no part; the edge
+// levels (setEdgeActive) are read, never written.
+//   poseLocalizationStatus  a pose's status at the last localizePoses (NOT_SELECTED before one and for a vertex it did not cover)
+// A keyframe without a guess:  ba->initialize(); cuba::localizePoses(ba.get(), {}, &lost); cuba::refinePoses(ba.get(), {}, &lost); ba->optimize(10);
+PoseLocalizationResult localizePoses(CudaBundleAdjustment* object, const PoseLocalizationOptions& options, const std::vector<PoseVertex*>* subset = nullptr);
+PoseLocalizationStatus poseLocalizationStatus(const CudaBundleAdjustment* object, const PoseVertex* v);
+
 // Robust kernel of a pose factor (PosePrior, RelativePoseEdge; include/cuba_hip.h, cuba_hip_set_pose_factor_robust_kernels): with
 // e = r^T Omega r the objective term becomes rho(e) and the linearisation takes rho'(e) Omega for Omega.  HUBER and TUKEY are the kernels of
 // the reprojection edges; CAUCHY, rho = delta^2 log1p(e / delta^2), exists for the pose factors only -- the usual choice on loop closures,

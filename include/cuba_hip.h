@@ -417,6 +417,69 @@ int cuba_hip_refine_poses(cuba_hip_solver* s, const uint8_t* select, int rounds,
 	int min_inliers, int dry_run, int32_t* status, int64_t counts[CUBA_HIP_POSEREF_STATUSES], int32_t* inliers, double* chi2, double* q, double* t,
 	uint8_t* edge_inlier);
 
+/* ---- pose localisation from scratch: P3P RANSAC per pose ---------------------------------------------- */
+
+/* Replaces: nothing of the reference -- the first half of ORB-SLAM's Tracking::Relocalization (PnP-RANSAC; cuba_hip_refine_poses is
+   the second half, PoseOptimization): the value a POSE gets when there is no usable guess at all (a relocalisation after tracking loss,
+   a keyframe joined from another map, a pose behind a wrong loop closure, a camera with only 2-D - 3-D matches) -- the counterpart of the
+   triangulation's linear start.  An absolute pose per selected free pose from its active reprojection edges and the current landmarks
+   only, by a deterministic RANSAC over a minimal three-point solver; the intended flow is localize_poses -> refine_poses -> optimize.
+   All arithmetic in double in both libraries.  THE POSE'S CURRENT VALUE IS NEVER READ (it may be NaN).
+   1. Usable edges: the pose's reprojection edges of live information omega > 0 (a gated edge is out).  Free and fixed landmarks are both
+      held at their current estimate.  Pose factors, landmark priors and robust kernels take no part.  Fewer than 4: FEW_OBSERVATIONS.
+   2. Sampling: hypothesis h = 0 ... hypotheses - 1 takes the three usable edges of smallest key K(seed, p, h, e), p and e the CALLER's
+      pose and edge indices, a tie to the smaller e; the three enter the solver ordered by key (points 1, 2, 3).  With
+        mix(x):  x ^= x >> 30;  x *= 0xbf58476d1ce4e5b9;  x ^= x >> 27;  x *= 0x94d049bb133111eb;  x ^= x >> 31     (mod 2^64)
+        K = mix(mix(mix(mix(seed + 0x9e3779b97f4a7c15) + p) + h) + e)
+      so the sample does not depend on pose_reorder, landmark_reorder, device_setup or the internal sort.  A fixed count, no early exit.
+   3. Minimal solver (P3P, Grunert's law-of-cosines system reduced to a quartic in one depth ratio).  Every edge gives the unit bearing
+      f = (x, y, 1) / sqrt(x^2 + y^2 + 1), x = (u - cx) / fx, y = (v - cy) / fy (a stereo edge: its left measurement only).  With the
+      landmarks X_1, X_2, X_3:  a2 = |X_2 - X_3|^2, b2 = |X_1 - X_3|^2, c2 = |X_1 - X_2|^2, ca = f_2 . f_3, cb = f_1 . f_3, cg = f_1 . f_2,
+      K = (a2 - c2) / b2, C = c2 / b2, and the distances s_1, s_2 = u s_1, s_3 = v s_1 of the points from the centre:
+        N(v) = (K - 1) v^2 - 2 K cb v + (1 + K),   D(v) = 2 (cg - ca v),   W(v) = -C v^2 + 2 C cb v + (1 - C),    u = N / D
+        quartic  N^2 - 2 cg N D + D^2 W = A_4 v^4 + ... + A_0  (the coefficients by multiplying out), divided by A_4:  v^4 + B v^3 + C' v^2 + D' v + E
+        depressed with v = y - B / 4:  y^4 + p y^2 + q y + r;  resolvent  m^3 + p m^2 + (p^2 / 4 - r) m - q^2 / 8 = 0, its LARGEST real
+        root m in closed form (m = z - p / 3, z^3 + P z + Q: Cardano's cube roots for Q^2 / 4 + P^3 / 27 > 0, the cosine form otherwise), two
+        Newton steps on the resolvent;  s = sqrt(2 m);  the two quadratics  y^2 - s y + (p / 2 + m + q / (2 s))  and
+        y^2 + s y + (p / 2 + m - q / (2 s));  root index 0, 1: the first one's roots with + and - the square root of its discriminant, 2, 3:
+        the second one's; a negative discriminant: no such roots.  Each root v: two Newton steps on the normalised quartic, then
+        u = N(v) / D(v), s_1 = sqrt(b2 / (1 + v^2 - 2 v cb)), s_2 = u s_1, s_3 = v s_1, and two Newton steps (3 x 3, Cramer's rule) on
+        the law-of-cosines system  s_2^2 + s_3^2 - 2 s_2 s_3 ca = a2,  s_1^2 + s_3^2 - 2 s_1 s_3 cb = b2,  s_1^2 + s_2^2 - 2 s_1 s_2 cg = c2
+        itself: near a double root of the quartic the ratio N / D and the quartic's own polish lose digits that the system still holds.
+      [R | t] (world -> camera) from two orthonormal triads: Y_i = s_i f_i; e_1 = unit(Y_2 - Y_1), e_3 = unit(e_1 x (Y_3 - Y_1)),
+      e_2 = e_3 x e_1; g_1, g_2, g_3 likewise from X_1, X_2, X_3; R = e_1 g_1^T + e_2 g_2^T + e_3 g_3^T, t = Y_1 - R X_1.
+      A candidate is discarded if a number in it is not finite, if one of s_1, s_2, s_3 is <= 0, if a triad has no normal -- the three
+      points collinear or coincident to rounding, |e_1 x (Y_3 - Y_1)|^2 <= 1e-24 |Y_3 - Y_1|^2, likewise for X: what is left of such a
+      normal is rounding noise, and a pose that merely turns about the points' line reprojects all three -- or if one of its own three
+      edges has depth <= 0 or omega |r|^2 > chi2_max[dim] at [R | t] (r with 2 or 3 components, the edge's own): badly conditioned roots
+      go this way.
+   4. Score (MSAC): C = sum over ALL usable edges of min(omega |r_e|^2, chi2_max[dim_e]); an edge of depth <= 0 or with a chi2 that is not
+      finite counts chi2_max[dim_e].
+   5. Winner: the candidate of smallest C, a tie to the smaller 4 h + root.  None at all: NO_SOLUTION.  Fewer than max(4, min_inliers)
+      usable edges with depth > 0 and omega |r|^2 <= chi2_max at the winner (the classification, at the winner's [R | t]): FEW_INLIERS.
+      Otherwise OK: the winner's pose replaces the estimate, as a quaternion (Shepperd) normalised with w >= 0 and written once as the
+      library's scalar type (dry_run != 0: nothing is written).
+   Per pose, the first rule that applies: NOT_SELECTED (select given and select[p] == 0), FIXED, FEW_OBSERVATIONS, NO_SOLUTION,
+   FEW_INLIERS, OK.  hypotheses 1 ... 4096; chi2_max = {monocular, stereo}, both finite and > 0 (the score needs them); min_inliers >= 0.
+   select[Pt], status[Pt], inliers[Pt], cost[Pt], winner[Pt], q[4 Pt] (x, y, z, w), t[3 Pt]: the caller's pose numbering;
+   edge_inlier[E]: the caller's edge order.  Every array argument but chi2_max is optional (NULL).
+     q, t           the pose of every OK pose as the estimate holds it (also in a dry run), the unchanged current pose of every other
+     winner[p]      4 h + root of an OK pose, -1 of every other
+     inliers[p]     the classification's count at the winner (OK, FEW_INLIERS); the usable edges (FEW_OBSERVATIONS, NO_SOLUTION); 0 for a
+                    pose that is not selected or fixed
+     cost[p]        C of the winner (OK, FEW_INLIERS); 0 for every other pose
+     edge_inlier[e] the classification at the winner for the edges of OK and FEW_INLIERS poses; for every other edge whether its live omega > 0
+     counts[CUBA_HIP_POSELOC_STATUSES]   poses per status; they sum to Pt
+   Landmarks, other poses, the gate, the snapshot slots, the handle's LM state and the counters stay as they are; a covariance computed
+   before is dropped when a pose changed.  A handle that never calls this allocates and launches nothing for it.
+   CUBA_HIP_ERR_INVALID_ARGUMENT: a count outside its range, chi2_max NULL, not finite or not positive.
+   CUBA_HIP_ERR_STATE before cuba_hip_set_graph and on a landmark-partitioned handle. */
+enum { CUBA_HIP_POSELOC_OK = 0, CUBA_HIP_POSELOC_NOT_SELECTED, CUBA_HIP_POSELOC_FIXED, CUBA_HIP_POSELOC_FEW_OBSERVATIONS,
+       CUBA_HIP_POSELOC_NO_SOLUTION, CUBA_HIP_POSELOC_FEW_INLIERS, CUBA_HIP_POSELOC_STATUSES };
+int cuba_hip_localize_poses(cuba_hip_solver* s, const uint8_t* select, int hypotheses, uint64_t seed, const double chi2_max[2], int min_inliers,
+	int dry_run, int32_t* status, int64_t counts[CUBA_HIP_POSELOC_STATUSES], int32_t* inliers, double* cost, int32_t* winner, double* q, double* t,
+	uint8_t* edge_inlier);
+
 /* Replaces: CudaBlockSolver::getTimeProfile (:545-562). Seconds per bucket. */
 int cuba_hip_get_profile(cuba_hip_solver* s, double seconds[CUBA_HIP_PROFILE_ITEMS]);
 
